@@ -2,6 +2,7 @@
 """Headline benchmark: learner FPS of the deepq actor->replay->learner loop (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed to DIR/*.npy: see dump_outputs)
 
 One "step" is one Trainer iteration exactly as the reference times it (agent0/deepq/trainer.py:176-181):
 ``sample_steps`` (80) vectorized env steps on ``num_envs`` (256) envs — Q-network forward, epsilon-greedy, env step,
@@ -46,8 +47,13 @@ def parse():
                          "BASELINE configs[4] read as 'one game per GPU') — the ranks share only the barriers and the max-over-ranks clock")
     ap.add_argument("--self-launch", action="store_true",
                     help="start the ranks as a child torch.distributed.run even for --gpus 1 (what --gpus N > 1 does when no launcher environment is present)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("overrides", nargs="*", help="extra key=value config overrides")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -259,6 +265,48 @@ def throughput_fields(world: int, per_iter: int, learner_steps: int, steps: int,
             "updates_per_sec": round(world * learner_steps * steps / dt, 2)}
 
 
+DUMP_BYTES = 60_000_000          # data; the .npy headers (~128 bytes each) keep the files well under 64 MB
+
+
+def dump_outputs(out_dir: str, tr, last: dict, marks: tuple) -> dict:
+    """``--dump-outputs DIR``: what the LAST timed step computed, as DIR/<name>.npy, so that two builds can be compared output for output (every input of the run is
+    drawn from cfg.seed, so the same arguments give the same inputs).  Called after the clock has stopped, before anything else runs on the trainer.
+      result_<key>          the dict run_iteration returned (frames, loss, qmax, ...; not its wall-clock fps), float64 scalars
+      update_losses         the loss of every update of the step's block (update_fraction_losses: FQF's fraction loss), float64
+      rollout_qmax          max-Q per env step of the rollout the step consumed, float64
+      rollout_returns       returns of the episodes that rollout finished, float64 (may be empty)
+      online_params         the learner's flat parameters after the step's last Adam update, float32
+      target_params         the target network's flat parameters after the step, float32
+    An array that does not fit the 64 MB budget is replaced by a fixed sample of its elements (seeded, sorted indices; the same for the same sizes) and listed as
+    such in the returned summary."""
+    import numpy as np
+
+    nL, nFL, nQ, nR = marks
+    eng = tr.learner.engine
+    n = eng.L.n_params
+    arrays = {f"result_{k}": np.asarray(v, np.float64) for k, v in last.items() if k != "fps" and v is not None}
+    arrays["update_losses"] = np.asarray(tr.Ls[nL:], np.float64)
+    if len(tr.FLs) > nFL:
+        arrays["update_fraction_losses"] = np.asarray(tr.FLs[nFL:], np.float64)
+    arrays["rollout_qmax"] = np.asarray(tr.Qs[nQ:], np.float64)
+    arrays["rollout_returns"] = np.asarray(tr.Rs[nR:], np.float64)
+    arrays["online_params"] = eng.online.flat[:n].float().cpu().numpy()
+    arrays["target_params"] = eng.target.flat[:n].float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    summary, left = {}, DUMP_BYTES
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):        # smallest first: each takes at most an even share of what is left
+        cap = left // (len(arrays) - i) // a.itemsize
+        info = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+            info.update(shape=list(a.shape), sampled_from=info["shape"])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        summary[name] = info
+    return summary
+
+
 # ------------------------------------------------------------------------------------------------ roofline (SURVEY.md §8(d))
 PEAK_BF16, PEAK_FP32 = 2500.0, 157.3          # TFLOP/s dense MFMA, MI355X_MICROARCH.md
 ENC_F1, ENC_F2, ENC_F3 = 2.0 * 400 * 32 * 256, 2.0 * 81 * 64 * 512, 2.0 * 49 * 64 * 576       # conv1 / conv2 / conv3 FLOP per observation (model.py:93-105)
@@ -446,6 +494,7 @@ def main():
     t0 = time.time()
     last = None
     for _ in range(args.steps):
+        marks = len(tr.Ls), len(tr.FLs), len(tr.Qs), len(tr.Rs)         # where the last step's statistics start (--dump-outputs)
         last = tr.run_iteration(prefetch=ahead)
     torch.cuda.synchronize()
     dt_local = time.time() - t0          # this rank's own K steps, before it waits for the others: diagnoses a straggler from the one JSON line
@@ -455,6 +504,7 @@ def main():
     if dp:
         import torch.distributed as dist
         dt, per_rank = rank_clock(dist, dt, dt_local, rank, world, args.steps, "cuda")
+    dumped = dump_outputs(args.dump_outputs, tr, last, marks) if args.dump_outputs and rank == 0 else None
     # ---- roofline of the dominant kernel: the same iterations once more per candidate kernel family with the hipGraphs switched off, every launch of
     # the family carrying a HIP event pair on its stream (events cannot be read out of a replayed graph; single-kernel families take the dispatch's own begin / end
     # timestamps through hipExtLaunchKernelGGL — what rocprofv3's kernel trace reports).  The family with the largest share of the iteration is THE roofline kernel; the
@@ -585,6 +635,8 @@ def main():
     }
     out["roofline"] = roofline_object(probes, cfg, args, tr.ops.x9_products(), dt / args.steps)
     out["cpu_baseline"] = cpu_base
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     print(json.dumps(out))
     if dp:
         import torch.distributed as dist

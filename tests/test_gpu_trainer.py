@@ -412,7 +412,7 @@ def test_grouped_host_env_rollouts_match_the_device_env(algo, n_step, workers, g
 
 
 @pytest.mark.parametrize("algo,extra", [("dqn", []), ("c51", ["learner.noisy_net=true", "learner.n_step_q=3", "replay.policy=prioritize"])])
-def test_launch_mode_overlap_is_race_free(algo, extra):
+def test_launch_mode_overlap_is_race_free(algo, extra, tmp_path):
     """Trainer(use_lp=True) — the launch.py schedule: rollout k+1 with a weight snapshot runs on a second stream while the update block
     consumes rollout k.  Issuing the same work on ONE stream must give bit-identical parameters, replay contents and statistics."""
     from agent0_amd.deepq.config import parse_overrides
@@ -420,7 +420,7 @@ def test_launch_mode_overlap_is_race_free(algo, extra):
     res = []
     for overlap in (True, False):
         cfg = parse_overrides([f"learner.algo={algo}", "actor.num_envs=16", "actor.sample_steps=12", "learner.batch_size=32", "learner.learner_steps=3", "replay.size=500",
-                               "trainer.training_start_steps=100", "learner.target_update_freq=4", "wandb=false", "tb=false", "logdir=/tmp/a0_lp"] + extra)
+                               "trainer.training_start_steps=100", "learner.target_update_freq=4", "wandb=false", "tb=false", f"logdir={tmp_path}"] + extra)
         tr = Trainer(cfg, use_lp=True)
         tr.overlap = overlap
         out = [tr.run_iteration() for _ in range(7)]            # wraps the 500-slot ring, captures + replays the graphs
@@ -435,7 +435,7 @@ def test_launch_mode_overlap_is_race_free(algo, extra):
 
 
 @pytest.mark.parametrize("algo,extra,workers", [("dqn", [], 3), ("c51", ["learner.noisy_net=true", "learner.n_step_q=3", "replay.policy=prioritize"], 2)])
-def test_launch_mode_with_host_envs_trains_beside_the_rollout(algo, extra, workers):
+def test_launch_mode_with_host_envs_trains_beside_the_rollout(algo, extra, workers, tmp_path):
     """Round 4 (N1 x N2): with a HOST env the rollout occupies the Python thread (it waits for the worker processes), so ``run_iteration_lp`` enqueues the update block
     first and runs the rollout on the actor stream beside it — launch.py's actor processes stepping emulators while the learner trains (launch.py:44-63).  Parameters,
     replay contents and statistics must equal, bit for bit, the one-stream order (rollout, then block) on the host env AND the same schedule on the device-resident env."""
@@ -447,7 +447,7 @@ def test_launch_mode_with_host_envs_trains_beside_the_rollout(algo, extra, worke
     res = []
     for host, overlap in ((False, False), (True, True), (True, False)):
         cfg = parse_overrides([f"learner.algo={algo}", "actor.num_envs=16", "actor.sample_steps=12", "learner.batch_size=32", "learner.learner_steps=3", "replay.size=500",
-                               "trainer.training_start_steps=100", "learner.target_update_freq=4", "wandb=false", "tb=false", "logdir=/tmp/a0_lp"] + extra)
+                               "trainer.training_start_steps=100", "learner.target_update_freq=4", "wandb=false", "tb=false", f"logdir={tmp_path}"] + extra)
         tr = Trainer(cfg, use_lp=True)
         if host:
             tr.actors[1].close()
@@ -467,13 +467,13 @@ def test_launch_mode_with_host_envs_trains_beside_the_rollout(algo, extra, worke
     assert res[0][4][-1] is not None
 
 
-def test_launch_mode_uses_stale_weights_like_the_reference():
+def test_launch_mode_uses_stale_weights_like_the_reference(tmp_path):
     """launch.py:58-63 issues the next rollout BEFORE the update block: rollout k+1 acts with the weights after block k-1.  Check that the
     actor's snapshot equals the learner's parameters as they were when the rollout was issued."""
     from agent0_amd.deepq.config import parse_overrides
     from agent0_amd.deepq.trainer import Trainer
     cfg = parse_overrides(["actor.num_envs=16", "actor.sample_steps=12", "learner.batch_size=32", "learner.learner_steps=2", "replay.size=2000",
-                           "trainer.training_start_steps=100", "wandb=false", "tb=false", "logdir=/tmp/a0_lp"])
+                           "trainer.training_start_steps=100", "wandb=false", "tb=false", f"logdir={tmp_path}"])
     tr = Trainer(cfg, use_lp=True)
     for _ in range(3):
         tr.run_iteration()
@@ -484,7 +484,7 @@ def test_launch_mode_uses_stale_weights_like_the_reference():
     assert not torch.equal(tr.learner.engine.online.flat, before)
 
 
-def test_graphed_update_with_a_gradient_hook_matches_eager():
+def test_graphed_update_with_a_gradient_hook_matches_eager(tmp_path):
     """Data parallelism installs a grad_hook (RCCL all-reduce) between backward and Adam.  The learner then replays two hipGraphs around
     the eager hook; the result must equal the fully eager update bit for bit (the hook here scales the gradients, so skipping or
     misplacing it would show)."""
@@ -493,7 +493,7 @@ def test_graphed_update_with_a_gradient_hook_matches_eager():
     res = []
     for use_graph in (True, False):
         cfg = parse_overrides(["actor.num_envs=16", "actor.sample_steps=12", "learner.batch_size=32", "learner.learner_steps=3", "replay.size=1000",
-                               "trainer.training_start_steps=100", "wandb=false", "tb=false", "logdir=/tmp/a0_hook"])
+                               "trainer.training_start_steps=100", "wandb=false", "tb=false", f"logdir={tmp_path}"])
         tr = Trainer(cfg)
         tr.learner.use_graph = use_graph
         calls = []
