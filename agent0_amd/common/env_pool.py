@@ -108,7 +108,7 @@ class HostEnvPool:
         self._uploaded = torch.cuda.Event()
         # the step path's two PCIe legs as one library call each (a0_env_pool_upload / a0_env_pool_send): raw addresses, resolved once.  ``inline_upload``:
         # the upload is enqueued on the caller's stream (the encoder waits for it anyway), False: on the pool's copy stream, whose DMA can run beside another
-        # group's inference (HostEnvGroups, A0_ENV_GROUP_COPY_STREAMS=1).  A0_ENV_POOL_CALLS=0: the per-copy torch calls (same bytes; a tuning aid)
+        # group's inference.  A0_ENV_POOL_CALLS=0: the per-copy torch calls (same bytes; a tuning aid)
         self.library_calls = self.newest_frame and os.environ.get("A0_ENV_POOL_CALLS", "1") != "0"
         self.inline_upload = bool(inline_upload)
         self.wait_s = 0.0                     # host time spent waiting for the workers (the env's own cost as the step path sees it)
@@ -322,9 +322,8 @@ class HostEnvGroups:
         per = 0 if num_workers == 0 else max(1, int(num_workers) // groups)
         self.offsets = bounds[:-1]
         # every group's upload goes on the caller's stream: the Python thread bounds a grouped rollout, and a copy stream per group costs it three stream calls per
-        # group-step for a DMA overlap the GPU does not need (1.16 - 1.22 M env-frames/s against 0.94 - 1.00 M, profiles/r04_experiments.md).  A0_ENV_GROUP_COPY_STREAMS=1: copy streams
-        inline = os.environ.get("A0_ENV_GROUP_COPY_STREAMS", "0") != "1"
-        self.pools = [HostEnvPool(OffsetSlices(make_slice, bounds[i]), bounds[i + 1] - bounds[i], num_workers=per, ops=ops, inline_upload=inline, **kw) for i in range(groups)]
+        # group-step for a DMA overlap the GPU does not need (1.16 - 1.22 M env-frames/s against 0.94 - 1.00 M, profiles/r04_experiments.md)
+        self.pools = [HostEnvPool(OffsetSlices(make_slice, bounds[i]), bounds[i + 1] - bounds[i], num_workers=per, ops=ops, inline_upload=True, **kw) for i in range(groups)]
         p0 = self.pools[0]
         self.obs_shape, self.obs_bytes, self.action_dim = p0.obs_shape, p0.obs_bytes, p0.action_dim
         self.observation_space = _Space(shape=(self.E,) + self.obs_shape)

@@ -1,5 +1,5 @@
 // The scalar-head actor tail + the synthetic env's step as DEVICE functions, shared by the kernel that runs them alone (a0_actor_qhead_env_kernel, net.hip) and the
-// kernel that goes on to encode the NEXT observation in the same launch (a0_actor_step_enc_kernel, encoder_fused.hip: round 5).
+// kernel that goes on to encode the NEXT observation in the same launch (a0_actor_step_enc2_kernel, encoder_fused.hip: round 5).
 #pragma once
 #include "synth_env.h"
 // One wave finishes fc1 for env `er` from the GEMM's slabs (slab sum + bias + ReLU, in slab order: bit-identical to a0_reduce_bias_act_kernel),

@@ -150,22 +150,6 @@ struct EpiFwd {                 // y = relu(acc + bias[n]) -> LDS image [oh][ow]
         }
     }
 };
-template <int OW, int S>
-struct EpiBwd {                 // dx = mask > 0 ? acc : 0 at pixel (oh*S + ph, ow*S + pw) of a Wfull-wide NHWC image; optional padded LDS image
-    static constexpr bool PER_ELEM = true;
-    static constexpr bool TR = false;
-    static constexpr bool ROW4 = false;
-    A0_D void emit4(int, int, const a0_acc4&, float) const {}
-    const float* mask; float* dst; float* lds; int pitch, rp, Wfull, ph, pw, N;
-    A0_D unsigned gi(int m, int n) const { const int oh = m / OW, ow = m - oh * OW; return (unsigned)(((oh * S + ph) * Wfull + ow * S + pw) * N + n); }
-    A0_D float pre_col(int) const { return 0.f; }
-    A0_D float pre_elem(int m, int n) const { return mask[gi(m, n)]; }
-    A0_D void emit(int m, int n, float acc, float pre) const {
-        const float v = pre > 0.f ? acc : 0.f;
-        dst[gi(m, n)] = v;
-        if (lds) { const int oh = m / OW; lds[oh * rp + (m - oh * OW) * pitch + n] = v; }
-    }
-};
 
 // What a layer's epilogue needs from global memory, in the wave's tile layout.  Loaded well ahead of the layer (kernel start, or the
 // previous layer's `between` slot) so that its latency is never waited for on its own.
@@ -900,42 +884,15 @@ A0_D void a0_encoder_fused_x9_body(const a0_fused_args& P, int bid, int nblk) {
 // moves 4 MB takes 4.8 us; the PMC's wave lifetimes put ~17 us of waves inside the one-observation encoder's 25.7 us), and the actor's step crossed three of them:
 // encoder | fc1 GEMM | tail + env step.  The tail + env step of step t and the encoder of step t + 1 are both one workgroup of 512 threads PER ENV, and the encoder's
 // input is exactly what that workgroup has just written (the env's new observation): so the same workgroup goes on — tail, env step, barrier, encoder — and a step
-// is fc1 GEMM | tail + env step + next encoder.  Same device functions as the two kernels it replaces (a0_actor_qhead_env_body, a0_encoder_fused_x9_body): the same
-// bytes and the same features (tests/test_gpu_trainer.py); a rollout's first step still needs the encoder on its own, and its last step the tail without one.
+// is fc1 GEMM | tail + env step + next encoder.  Same device functions as the two kernels it replaces (a0_actor_qhead_env_body / a0_actor_dist_tail_env_body,
+// a0_encoder_fused_x9_body): the same bytes and the same features (tests/test_gpu_trainer.py); a rollout's first step still needs the encoder on its own, and its last
+// step the tail without one.
 #include "actor_tail.h"
 // (the encoder's arguments travel as five pointers: the 4 x 84 x 84 geometry is a compile-time constant here, and the two full argument structs together do not fit
 // the scalar registers)
 struct a0_step_enc_args { const float *wt, *b1, *b2, *b3; float* act3; };
-template <int ORD>
-__global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_actor_step_enc_kernel(a0_qenv_args Q, a0_step_enc_args N) {
-    __shared__ float raw[64];
-    __shared__ int s_chase_cell;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // the encoder's pointers wait in VECTOR registers while the tail runs (the tail's own uniform values fill the scalar file) and come back as scalars behind it
-    unsigned long long v_wt = (unsigned long long)N.wt, v_b1 = (unsigned long long)N.b1, v_b2 = (unsigned long long)N.b2, v_b3 = (unsigned long long)N.b3,
-                       v_a3 = (unsigned long long)N.act3, v_obs = (unsigned long long)Q.obs_out;
-    A0_TO_VGPR(v_wt); A0_TO_VGPR(v_b1); A0_TO_VGPR(v_b2); A0_TO_VGPR(v_b3); A0_TO_VGPR(v_a3); A0_TO_VGPR(v_obs);
-    int v_E = Q.E;
-    A0_TO_VGPR(v_E);
-    a0_actor_qhead_env_body(Q, raw, (float*)smem, &s_chase_cell);
-    __syncthreads();      // the frame waves' stores of obs_out[e] have been acknowledged (vmcnt(0) ahead of the barrier) and the tail's LDS is dead
-    auto uni = [](unsigned long long v) {
-        return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffull));
-    };
-    const float* wt = (const float*)uni(v_wt);
-    a0_fused_args P;
-    P.frames = (const uint8_t*)uni(v_obs); P.slot = nullptr; P.sample_stride = 4 * 84 * 84; P.chan_off = 0;
-    P.wt1 = wt; P.wt2 = wt + 48LL * 4 * 64; P.wt3 = P.wt2 + 64LL * 512;
-    P.wx2 = P.wt3 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256; P.wx3 = P.wx2 + 96LL * 512;
-    P.b1 = (const float*)uni(v_b1); P.b2 = (const float*)uni(v_b2); P.b3 = (const float*)uni(v_b3);
-    P.act1 = nullptr; P.act2 = nullptr; P.act3 = (float*)uni(v_a3); P.B = __builtin_amdgcn_readfirstlane(v_E);
-    P.C = 4; P.H = 84; P.W = 84; P.H1 = 20; P.W1 = 20; P.H2 = 9; P.W2 = 9; P.H3 = 7; P.W3 = 7;
-    P.off_act1 = 0; P.off_act2 = 0; P.off_end = 0; P.rp1 = 0; P.rp2 = 0;      // (the fp32-chain variants' LDS layout: not used by the split-operand body)
-    a0_encoder_fused_x9_body<ORD, 7, 3, 2, false>(P, (int)blockIdx.x, (int)gridDim.x);
-}
-
 // The distributional heads' step (c51 / qr): a0_actor_dist_tail_env_kernel's body (head slab sum, dueling, expectation or quantile mean, first maximum, epsilon-greedy,
-// env step, replay row), then the same encoder phase.
+// env step, replay row), a barrier, then the whole encoder.
 template <int ORD>
 __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_actor_dist_step_enc_kernel(a0_dtenv_args Q, a0_step_enc_args N) {
     __shared__ int s_chase_cell;
@@ -962,8 +919,8 @@ __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_actor_
     a0_encoder_fused_x9_body<ORD, 7, 3, 2, false>(P, (int)blockIdx.x, (int)gridDim.x);
 }
 
-// ---- Round 5, second form: the step's tail BESIDE conv1 (scalar heads).  In a0_actor_step_enc_kernel seven waves copy frames and then wait for wave 0's latency chain
-// (slab sums, head, Philox, n-step bookkeeping) before anyone touches the matrix pipe.  But three of the new observation's four channels are the OLD stack's frames
+// ---- Round 5, second form: the step's tail BESIDE conv1 (scalar heads).  In the first form (tail, barrier, whole encoder, as a0_actor_dist_step_enc_kernel) seven
+// waves copy frames and then wait for wave 0's latency chain (slab sums, head, Philox, n-step bookkeeping) before anyone touches the matrix pipe.  But three of the new observation's four channels are the OLD stack's frames
 // 1..3 — known when the kernel starts — and conv1's reduction runs channel by channel (MFMA steps 2c, 2c + 1 = channel c): so the frame waves put those channels
 // into the LDS image themselves (from the registers they copy the stack with) and run conv1's steps 0..5 while wave 0 is in the tail; behind the barrier that
 // publishes the action the workgroup adds the newest frame's steps 6, 7.  Same MFMAs on the same operands in the same k order per accumulator: bit-identical features.
@@ -1241,7 +1198,6 @@ int a0_actor_dist_step_enc_launch(const a0_dtenv_args& Q, size_t tail_lds, const
     a0_fused_args P;
     size_t lds = 0;
     if (!wt || !w || !w->b1 || !w->b2 || !w->b3 || !act3 || !a0_fused_layout(4, 84, 84, P, lds)) return a0_fail(A0_EINVAL, "a0_actor_dist_tail_env_step_enc: bad encoder argument");
-    if (getenv("A0_NO_X9") != nullptr) return a0_fail(A0_EINVAL, "a0_actor_dist_tail_env_step_enc: the split-operand encoder only");
     if (P.H1 != 20 || P.W1 != 20 || P.H2 != 9 || P.W2 != 9 || P.H3 != 7 || P.W3 != 7) return a0_fail(A0_EINVAL, "a0_actor_dist_tail_env_step_enc: geometry");
     const a0_step_enc_args N{wt, w->b1, w->b2, w->b3, act3};
     lds = A0_X9_LDS_BYTES > tail_lds ? (size_t)A0_X9_LDS_BYTES : tail_lds;
@@ -1263,14 +1219,12 @@ int a0_actor_step_enc_launch(const a0_qenv_args& Q, const float* wt, const a0_en
     a0_fused_args P;
     size_t lds = 0;
     if (!wt || !w || !w->b1 || !w->b2 || !w->b3 || !act3 || !a0_fused_layout(4, 84, 84, P, lds)) return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: bad encoder argument");
-    if (getenv("A0_NO_X9") != nullptr) return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: the split-operand encoder only");
     if (P.H1 != 20 || P.W1 != 20 || P.H2 != 9 || P.W2 != 9 || P.H3 != 7 || P.W3 != 7) return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: geometry");
     const a0_step_enc_args N{wt, w->b1, w->b2, w->b3, act3};
     const size_t tail_lds = (size_t)(Q.A + (Q.dueling ? 1 : 0)) * 512 * sizeof(float);
     lds = A0_X9_LDS_BYTES > tail_lds ? (size_t)A0_X9_LDS_BYTES : tail_lds;
-    static const int form = getenv("A0_STEP_ENC") ? atoi(getenv("A0_STEP_ENC")) : 2;      // tuning aid: 1 = tail, barrier, whole encoder (the first form); 2 = conv1's channels 0..2 beside the tail
     const int six = a0_x9_products_now() == 6;
-    auto kern = form != 1 ? (six ? a0_actor_step_enc2_kernel<2> : a0_actor_step_enc2_kernel<4>) : (six ? a0_actor_step_enc_kernel<2> : a0_actor_step_enc_kernel<4>);
+    auto kern = six ? a0_actor_step_enc2_kernel<2> : a0_actor_step_enc2_kernel<4>;
     static size_t configured[2] = {0, 0};
     if (lds > configured[six]) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1372,76 +1326,18 @@ __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_encode
 // ------------------------------------------------------------------------------------------------ fused data gradients
 // conv3 and conv2 data gradients of one observation back to back (84x84 geometry: d3 7x7x64 -> d2 9x9x64 -> d1 20x20x32), the
 // counterpart of autograd's conv backward-data for ConvEncoder (reference model.py:93-105, called from agent.py:136-141).  Both are
-// written as stride-1 "gather" convolutions over ZERO-PADDED LDS images, so a0_conv_stage runs them unchanged:
+// written as stride-1 "gather" convolutions over ZERO-PADDED LDS images, so the forward stages run them unchanged:
 //   d2[h][w][ci] = sum_{kh',kw',co} d3pad[h + kh'][w + kw'][co] * W3[co][ci][2 - kh'][2 - kw']                 (pad 2, 3x3 taps)
 //   d1[2h2+ph][2w2+pw][ci] = sum_{a',b',co} d2pad[h2 + a'][w2 + b'][co] * W2[co][ci][ph + 2(1-a')][pw + 2(1-b')]   (pad 1, 2x2 taps)
 // the second once per stride phase (ph, pw).  The ReLU masks (act2 > 0, act1 > 0) come from the forward activations in HBM; d2 and d1
-// go to HBM for the weight-gradient GEMMs, d2 also stays in LDS for the four phases.  66 KB of LDS: two workgroups per CU.
+// go to HBM for the weight-gradient GEMMs, d2 also stays in LDS for the four phases.
 struct a0_dgrad_args {
     const float *d3, *act1, *act2;
     float *d2, *d1;
-    const float *wd3, *wd2;          // fragment-major copies (a0_conv_wt_kernel): [576][64] and 4 x [256][32]
-    int B, rpa, rpb;                 // row pitches of the two padded 11 x 11 x 64 LDS images
+    const float *wd3, *wd2;          // the flipped / phase-split weights as three bf16 terms (a0_conv_wt_kernel, segments 8, 9): [576][64] and 4 x [256][32]
+    int B;
 };
-struct AFD3 {   // 3x3 taps over d3pad [11][rpa]; k = (kh'*3 + kw')*64 + co; output 9 wide
-    const float* img; int RP;
-    A0_D int row(int m) const { const int oh = m / 9, ow = m - oh * 9; return oh * RP + ow * A0_P2; }
-    A0_D int chunk_off(int c) const { const int cell = c >> 2; return (cell / 3) * RP + (cell % 3) * A0_P2 + 16 * (c & 3); }
-    A0_D int step_off(int j) const { return 4 * j; }
-    typedef float Raw;
-    A0_D Raw load(int addr) const { return img[addr]; }
-    static A0_D float value(Raw r) { return r; }
-};
-struct AFD2 {   // 2x2 taps over d2pad [11][rpb]; k = (a'*2 + b')*64 + co; output 10 wide
-    const float* img; int RP;
-    A0_D int row(int m) const { const int oh = m / 10, ow = m - oh * 10; return oh * RP + ow * A0_P2; }
-    A0_D int chunk_off(int c) const { const int cell = c >> 2; return (cell >> 1) * RP + (cell & 1) * A0_P2 + 16 * (c & 3); }
-    A0_D int step_off(int j) const { return 4 * j; }
-    typedef float Raw;
-    A0_D Raw load(int addr) const { return img[addr]; }
-    static A0_D float value(Raw r) { return r; }
-};
-constexpr int A0_RD3 = 6, A0_RD2 = 4;
-
-__global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_dgrad_fused_kernel(a0_dgrad_args P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* imgA = (float*)smem;                 // d3, padded by 2
-    float* imgB = imgA + 11 * P.rpa;            // d2, padded by 1 (last row / column unused)
-    for (int i = threadIdx.x; i < 11 * (P.rpa + P.rpb); i += A0_FUSED_THREADS) imgA[i] = 0.f;     // borders stay zero for the whole launch
-    a0_wring<64, 4, A0_RD3> ring3;
-    a0_wring<32, 2, A0_RD2> ringp[2];
-    ring3.init(P.wd3, 576);
-    ring3.prologue();
-    typedef EpiBwd<9, 1> E3;
-    typedef EpiBwd<10, 2> E2;
-    a0_pre<64, 4, 3, E3> pre3;
-    a0_pre<32, 2, 2, E2> prep[2];
-    auto epi3 = [&](int b) { return E3{P.act2 + (long long)b * 81 * 64, P.d2 + (long long)b * 81 * 64, imgB + P.rpb + A0_P2, A0_P2, P.rpb, 9, 0, 0, 64}; };
-    auto epi2 = [&](int b, int ph, int pw) { return E2{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, nullptr, 0, 0, 20, ph, pw, 32}; };
-    if ((int)blockIdx.x < P.B) pre3.load(epi3(blockIdx.x), 81);
-    __syncthreads();
-    for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
-        const a0_f4* src = (const a0_f4*)(P.d3 + (long long)b * 49 * 64);
-        for (int i = threadIdx.x; i < 49 * 16; i += A0_FUSED_THREADS) {
-            const a0_f4 v = src[i];
-            const int pos = i >> 4, c4 = (i & 15) * 4, h = pos / 7, w = pos - h * 7;
-            float* d = imgA + (h + 2) * P.rpa + (w + 2) * A0_P2 + c4;
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-        __syncthreads();
-        AFD3 f3{imgA, P.rpa};
-        AFD2 f2{imgB, P.rpb};
-        const int bn = b + gridDim.x < P.B ? b + gridDim.x : b;       // next observation of this workgroup (its masks are prefetched in the last slot)
-        // each `between` slot requests the NEXT layer's weights and ReLU masks before this layer's epilogue runs
-        a0_conv_stage<64, 4, 3, 3, A0_RD3>(f3, 81, 576, ring3, epi3(b), pre3, [&] { ringp[0].init(P.wd2, 256); ringp[0].prologue(); prep[0].load(epi2(b, 0, 0), 100); });
-        a0_conv_stage<32, 2, 2, 3, A0_RD2>(f2, 100, 256, ringp[0], epi2(b, 0, 0), prep[0], [&] { ringp[1].init(P.wd2 + 1 * 8192, 256); ringp[1].prologue(); prep[1].load(epi2(b, 0, 1), 100); });
-        a0_conv_stage<32, 2, 2, 3, A0_RD2>(f2, 100, 256, ringp[1], epi2(b, 0, 1), prep[1], [&] { ringp[0].init(P.wd2 + 2 * 8192, 256); ringp[0].prologue(); prep[0].load(epi2(b, 1, 0), 100); });
-        a0_conv_stage<32, 2, 2, 3, A0_RD2>(f2, 100, 256, ringp[0], epi2(b, 1, 0), prep[0], [&] { ringp[1].init(P.wd2 + 3 * 8192, 256); ringp[1].prologue(); prep[1].load(epi2(b, 1, 1), 100); });
-        a0_conv_stage<32, 2, 2, 3, A0_RD2>(f2, 100, 256, ringp[1], epi2(b, 1, 1), prep[1], [&] { ring3.prologue(); pre3.load(epi3(bn), 81); });
-    }
-}
-
-// ---- the same two data gradients on the bf16 pipe with both operands split exactly into three bf16 terms (see a0_conv_stage_x9):
+// Both run on the bf16 pipe with both operands split exactly into three bf16 terms (see a0_conv_stage_x9):
 // d3 is split when it is loaded, d2 by conv3's epilogue; both live in LDS as three zero-padded 11 x 11 term-plane images (116 KB:
 // one workgroup per CU, eight waves), the flipped / phase-split weights come pre-split from a0_conv_wt_kernel (segments 8, 9).
 // Nine v_mfma_f32_16x16x32_bf16 per 32 k replace eight v_mfma_f32_16x16x4_f32 of twice the pipe time each.
@@ -1603,7 +1499,8 @@ __global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_dgrad_fused_x9_ke
 
 // ---- weight copies for the fused kernels, from the packed [N][K] blocks (layouts: a0_wring1 / a0_wring):
 //   seg 1  conv1: fl(w/255) split exactly into three bf16 terms, 16-byte fragments ((t*32 + n)*4 + q)*3 + s   (12 C KB)
-//   seg 2,3 conv2, conv3 fragment-major fp32;  seg 4,5 the flipped / phase-split matrices of the data gradients (wd3 [576][64], wd2 4 x [256][32])
+//   seg 2,3 conv2, conv3 fragment-major fp32;  seg 4,5 the flipped / phase-split matrices of the data gradients (wd3 [576][64], wd2 4 x [256][32]; no kernel reads
+//           them any more, the layout keeps them: its size is a0_net_conv_wt_floats)
 //   seg 6,7 conv2, conv3 as three exact bf16 terms (a0_wring9 layout) for the split-operand forward path
 //   seg 8,9 the data-gradient matrices of seg 4,5 as three exact bf16 terms (a0_wring9 layout, N = 64 / 4 x N = 32)
 A0_HD uint32_t a0_bf16_trunc(float f) { return __float_as_uint(f) >> 16; }
@@ -1774,13 +1671,11 @@ extern "C" int a0_net_encoder_fwd_fused(int C, int H, int W, const float* wt, co
     const int mb1 = (P.H1 * P.W1 + 15) / 16, mb2 = (P.H2 * P.W2 + 15) / 16, mb3 = (P.H3 * P.W3 + 15) / 16;
     const bool standard = ((mb1 + 3) / 4 == 7) && ((mb2 + 1) / 2 == 3) && ((mb3 + 1) / 2 == 2) && W == 84;
     // instantiations: split-operand (all layers on the bf16 pipe; 84x84, C = 4; one observation per workgroup, or looping), fp32 conv2/conv3 for 84-wide inputs, generic
-    static const bool no_x9 = getenv("A0_NO_X9") != nullptr;
-    const bool x9 = standard && H == 84 && C == 4 && !no_x9;
+    const bool x9 = standard && H == 84 && C == 4;
     int which = x9 ? 2 : (standard ? 1 : 0);
     if (x9) lds = A0_X9_LDS_BYTES;            // image + act1 term planes (act2 planes reuse the image) + the biases
     static_assert(3 * 9 * A0_RP2X * 2 <= 2 * 4 * 84 * 84, "the act2 term planes fit into the dead image");
-    static const int grid_cap = getenv("A0_ENC_GRID") ? atoi(getenv("A0_ENC_GRID")) : 256;
-    const int gridx = (which == 2 && grid_cap > 0 && B > grid_cap) ? grid_cap : B;
+    const int gridx = (which == 2 && B > 256) ? 256 : B;
     if (which == 2 && gridx < B) which = 3;                  // the looping instantiation of the split-operand kernel
     static size_t configured[6] = {0, 0, 0, 0, 0, 0};
     const int six = a0_x9_products_now() == 6;
@@ -1795,7 +1690,7 @@ extern "C" int a0_net_encoder_fwd_fused(int C, int H, int W, const float* wt, co
     }
     // split-operand kernel: at most one workgroup per CU (152 KB of LDS each), looping over its observations (b += gridDim.x) when there are more
     // observations than that: ring set-up is paid once and the next observation's conv1 weights are requested behind conv3 (-4 % per 512
-    // observations, tools/ubench_encoder_fwd.py).  A0_ENC_GRID: tuning aid (0 = one workgroup per observation)
+    // observations, tools/ubench_encoder_fwd.py)
     // algorithmic FLOP of the three convolutions: 2 * (M1*32*K1 + M2*64*512 + M3*64*576) per observation
     const double per_obs = 2.0 * ((double)P.H1 * P.W1 * 32 * (P.C * 64) + (double)P.H2 * P.W2 * 64 * 512 + (double)P.H3 * P.W3 * 64 * 576);
     A0_LAUNCH_PROBED(A0_TAG_ENCODER_FUSED, per_obs * B, fn, dim3((which == 3 || which == 5) ? gridx : B), dim3(A0_FUSED_THREADS), lds, (hipStream_t)stream, P);
@@ -1808,8 +1703,7 @@ extern "C" int a0_net_encoder_fwd_fused(int C, int H, int W, const float* wt, co
 extern "C" int a0_net_encoder_fwd_fused_multi(int C, int H, int W, int n, const a0_encoder_pass* pass, void* stream) {
     A0_TRY
     if (n < 1 || n > 3 || !pass) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused_multi: 1 to 3 passes");
-    static const bool no_x9 = getenv("A0_NO_X9") != nullptr;
-    if (!(C == 4 && H == 84 && W == 84) || no_x9) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused_multi: 4 x 84 x 84 observations on the split-operand kernel only");
+    if (!(C == 4 && H == 84 && W == 84)) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused_multi: 4 x 84 x 84 observations on the split-operand kernel only");
     a0_fused_multi_args M;
     size_t lds = 0;
     long long total = 0;
@@ -1828,9 +1722,7 @@ extern "C" int a0_net_encoder_fwd_fused_multi(int C, int H, int W, int n, const 
     }
     for (int i = n; i < 3; ++i) M.p[i] = M.p[0];
     // at most one workgroup per CU; every pass at least one, shares proportional to the observations
-    static const int grid_cap = getenv("A0_ENC_GRID") ? atoi(getenv("A0_ENC_GRID")) : 256;
-    const int cap = grid_cap > 0 ? grid_cap : 256;
-    int grid = (int)(total < cap ? total : cap), used = 0;
+    int grid = (int)(total < 256 ? total : 256), used = 0;
     if (grid < n) grid = n;
     for (int i = 0; i < n; ++i) {
         M.first[i] = used;
@@ -1867,30 +1759,21 @@ extern "C" int a0_net_encoder_dgrad_fused(int C, int H, int W, const float* wt, 
     if (!a0_net_encoder_dgrad_fused_supported(C, H, W)) return a0_fail(A0_EINVAL, "a0_net_encoder_dgrad_fused: 84x84 observations only");
     a0_dgrad_args P;
     P.d3 = d3; P.act1 = act1; P.act2 = act2; P.d2 = d2; P.d1 = d1; P.B = B;
-    P.wd3 = wt + 48LL * C * 64 + 64LL * 512 + 64LL * 576;
-    P.wd2 = P.wd3 + 64LL * 576;
-    P.rpa = 11 * A0_P2; while ((P.rpa - 2 * 9) & 31) ++P.rpa;      // conflict-free A reads: RP = 2 * (output width) (mod 32)
-    P.rpb = 11 * A0_P2; while ((P.rpb - 2 * 10) & 31) ++P.rpb;
-    static const bool no_x9 = getenv("A0_NO_X9") != nullptr;       // fp32-chain variant (as for the forward kernel)
-    const bool x9 = !no_x9;
-    if (x9) {      // split weights behind the forward path's (segments 8, 9)
-        P.wd3 = P.wd2 + 4LL * 32 * 256 + 96LL * 512 + 96LL * 576;
-        P.wd2 = P.wd3 + 96LL * 576;
-    }
-    const size_t lds = x9 ? (size_t)3 * (A0_DTERMA + A0_DTERMB) * 2 + (A0_KSPLIT_D ? (4 * 4 + 4 * 3) * 1024 : 0) : (size_t)11 * (P.rpa + P.rpb) * 4;      // + the exchange regions of the N-stationary stages
-    static bool configured[3] = {false, false, false};
-    const int kv = x9 ? (a0_x9_products_now() == 6 ? 2 : 1) : 0;
-    typedef void (*a0_dg_kern)(a0_dgrad_args);
-    const a0_dg_kern fn = kv == 2 ? a0_encoder_dgrad_fused_x9_kernel<2> : kv == 1 ? a0_encoder_dgrad_fused_x9_kernel<4> : a0_encoder_dgrad_fused_kernel;
-    if (!configured[kv]) {
+    // the split weights of segments 8, 9, behind the fp32 copies (segments 2..5) and the forward path's split copies (segments 6, 7)
+    P.wd3 = wt + 48LL * C * 64 + 64LL * 512 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256 + 96LL * 512 + 96LL * 576;
+    P.wd2 = P.wd3 + 96LL * 576;
+    const size_t lds = (size_t)3 * (A0_DTERMA + A0_DTERMB) * 2 + (A0_KSPLIT_D ? (4 * 4 + 4 * 3) * 1024 : 0);      // + the exchange regions of the N-stationary stages
+    static bool configured[2] = {false, false};
+    const int six = a0_x9_products_now() == 6;
+    auto fn = six ? a0_encoder_dgrad_fused_x9_kernel<2> : a0_encoder_dgrad_fused_x9_kernel<4>;
+    if (!configured[six]) {
         A0_HIP_THROW(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured[kv] = true;
+        configured[six] = true;
     }
     // at most one workgroup per CU, each looping over its observations (b += gridDim.x): the next observation's masks and the first
     // stage's weights are prefetched in the last stage's `between` slot instead of at workgroup start (-5 us per 512 observations)
-    static const int grid_cap = getenv("A0_DGRAD_GRID") ? atoi(getenv("A0_DGRAD_GRID")) : 256;
-    const int gridx = (grid_cap > 0 && B > grid_cap) ? grid_cap : B;
-    A0_LAUNCH_PROBED(A0_TAG_ENCODER_DGRAD_FUSED, 2.0 * (81.0 * 64 * 576 + 400.0 * 32 * 256) * B, fn, dim3(x9 ? gridx : B), dim3(A0_FUSED_THREADS), lds, (hipStream_t)stream, P);
+    const int gridx = B > 256 ? 256 : B;
+    A0_LAUNCH_PROBED(A0_TAG_ENCODER_DGRAD_FUSED, 2.0 * (81.0 * 64 * 576 + 400.0 * 32 * 256) * B, fn, dim3(gridx), dim3(A0_FUSED_THREADS), lds, (hipStream_t)stream, P);
     A0_HIP_THROW(hipGetLastError());
     return A0_OK;
     A0_CATCH

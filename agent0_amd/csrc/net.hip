@@ -200,7 +200,7 @@ extern "C" int a0_probe_end(double* host_out3) {
 }
 
 static int g_gemm_x9 = (getenv("A0_GEMM") && std::string(getenv("A0_GEMM")) == "fp32") ? 0 : 1;
-static const long long g_x9_big_min = getenv("A0_X9_BIG_MIN") ? atoll(getenv("A0_X9_BIG_MIN")) : 256;     // tuning aid
+static constexpr long long A0_X9_BIG_TILES = 256;      // 128 x 128 tiles (times splits) from which the eight-wave tile takes a problem
 extern "C" int a0_gemm_mode(int mode) {
     const int prev = g_gemm_x9;
     if (mode >= 0) g_gemm_x9 = mode ? 1 : 0;
@@ -216,7 +216,7 @@ extern "C" int a0_x9_products(int n) {
     return prev;
 }
 
-static const long long g_x9_huge_min = getenv("A0_X9_HUGE_MIN") ? atoll(getenv("A0_X9_HUGE_MIN")) : 250;   // tuning aid (a huge value switches the 256 x 128 tile off)
+static constexpr long long A0_X9_HUGE_TILES = 250;     // 256 x 128 tiles (times splits) from which that tile takes a problem
 template <class OP> struct a0_is_mat { static constexpr bool value = false; };
 template <> struct a0_is_mat<OpMatKC> { static constexpr bool value = true; };
 template <> struct a0_is_mat<OpMatXC> { static constexpr bool value = true; };
@@ -248,7 +248,7 @@ struct a0_hip_backend {
             // them only when each split is at least 512 deep (the quantile networks' B*N-row reductions: fc1 1.12 vs 1.34 ms)
             constexpr bool wgrad_family = OA::MODE == A0_XC;
             const bool deep = K / sp >= 512;
-            const bool large = X >= 128 && Y >= 128 && big >= g_x9_big_min && (deep || !wgrad_family);
+            const bool large = X >= 128 && Y >= 128 && big >= A0_X9_BIG_TILES && (deep || !wgrad_family);
             // very large dense problems (the quantile networks' 32 768-row layers): 256 x 128 tiles of 16 k on eight waves, 64 x 64 per wave — a quarter less
             // staging and a third fewer LDS fragment reads per MFMA than the 128 x 128 x 32 tile, the same 36 MFMAs per wave between barriers; taken when
             // there is about a full round of such tiles (the actor's 8 192 rows would fill half the CUs and keep the smaller tile)
@@ -258,7 +258,7 @@ struct a0_hip_backend {
             // fqf's 16 384-row data gradient, 1600 tiles = 6.25 rounds, or its 15 872-row pass, 248 tiles, gained nothing: 384.7 vs 385.3 us, 347.9 vs 342.8 us)
             const double fill_huge = (double)huge / (256.0 * (double)((huge + 255) / 256)), fill_big = (double)big / (256.0 * (double)((big + 255) / 256));
             if constexpr (mats) {
-                if (x9 && X >= 256 && Y >= 128 && huge >= g_x9_huge_min && fill_huge >= 0.93 * fill_big && (deep || !wgrad_family)) {
+                if (x9 && X >= 256 && Y >= 128 && huge >= A0_X9_HUGE_TILES && fill_huge >= 0.93 * fill_big && (deep || !wgrad_family)) {
                     A0_HIP_THROW((a0_igemm_x9_launch<OA, OB, EP, 4, 2, 2, 2, 1>(st, pa, pb, pe, X, Y, K, splits, e0, e1)));
                     if (probe) a0_probe_commit(2.0 * (double)X * (double)Y * (double)K);
                     return;
@@ -288,8 +288,7 @@ struct a0_hip_backend {
         A0_HIP_THROW(a0_short_k_fwd_launch(st, X, ldx, W, b, M, group, Y, Y2, R, N, relu));
     }
     int conv1_wgrad_fused(const a0_net_core& n, const a0_frames_arg& f, int B, const float* d1, float* slabs) {
-        static const bool off = getenv("A0_NO_CONV1_WGRAD_FUSED") != nullptr;
-        if (off || !slabs) return 0;
+        if (!slabs) return 0;
         const bool probe = g_probe.tag != 0 && g_probe.tag == tag && g_probe.used + 2 <= g_probe.ev.size();
         if (probe) A0_HIP_THROW(hipEventRecord(g_probe.ev[g_probe.used], st));
         const int g = a0_conv1_wgrad_fused_launch(&f, n.C, n.H, n.W, B, d1, slabs, st);
@@ -441,7 +440,7 @@ extern "C" int a0_dense_fwd_wplanes(const float* X, int ldx, const unsigned int*
     // the tile choice of a0_hip_backend::igemm for unsplit matrix operands
     const long long huge = (long long)((R + 255) / 256) * ((N + 127) / 128), big = (long long)((R + 127) / 128) * ((N + 127) / 128);
     const double fill_huge = (double)huge / (256.0 * (double)((huge + 255) / 256)), fill_big = (double)big / (256.0 * (double)((big + 255) / 256));
-    if (R >= 256 && huge >= g_x9_huge_min && fill_huge >= 0.93 * fill_big) A0_HIP_THROW((a0_igemm_x9_launch<OpMatKC, OpPlanesKC, EpiBiasAct, 4, 2, 2, 2, 1>(st, a, bw, e, R, N, K, 1, e0, e1)));
+    if (R >= 256 && huge >= A0_X9_HUGE_TILES && fill_huge >= 0.93 * fill_big) A0_HIP_THROW((a0_igemm_x9_launch<OpMatKC, OpPlanesKC, EpiBiasAct, 4, 2, 2, 2, 1>(st, a, bw, e, R, N, K, 1, e0, e1)));
     else A0_HIP_THROW((a0_igemm_x9_launch<OpMatKC, OpPlanesKC, EpiBiasAct, 4, 2, 1, 2>(st, a, bw, e, R, N, K, 1, e0, e1)));
     if (probe) a0_probe_commit(2.0 * (double)R * (double)N * (double)K);
     return A0_OK;
@@ -486,22 +485,15 @@ extern "C" int a0_dense_fwd_mul_keep(const float* X, int ldx, const float* W, co
 
 // The split-K GEMM of a0_dense_fwd WITHOUT its reduction: slab z = X W^T over the z-th k range, [R][N] each at stride R*N; the caller's
 // next kernel sums the slabs (a0_dqn_head_loss_slabs, a0_actor_qhead).  Returns the slab count.
-// Tile of the split-K fc1 GEMM whose slabs a consumer kernel finishes (actor tail, DQN head + loss).  A0_FC1_VARIANT (tuning aid):
-// 0 = 128 x 64, waves 4 x 1, 1 = 128 x 64, waves 2 x 2, 2 = 64 x 64, 3 = 64 x 128, 4 = 128 x 32, 5 / 6 = 128 x 64 / 64 x 128 on EIGHT waves (two per
-// SIMD: one wave's staging work in the shadow of the other's MFMAs); unset: 64 x 64 up to 256 rows (the actor's
+// Tile of the split-K fc1 GEMM whose slabs a consumer kernel finishes (actor tail, DQN head + loss): 64 x 64 up to 256 rows (the actor's
 // batch: 8 slabs instead of 16 for the tail kernel to sum, GEMM + tail 19.9 vs 22.3 us at 256 rows; the eight-wave tiles need 16 slabs
-// there and lose), 128 x 64 on eight waves above (512 rows: GEMM + tail 26.5 vs 27.8 us on four waves, whole B = 512 update 380 vs 385 us) — tools/ubench_actor_tail.py, profiles/r02_encoder_experiments.md.
-static inline int a0_fc1_variant(int R) {
-    static const int v = getenv("A0_FC1_VARIANT") ? atoi(getenv("A0_FC1_VARIANT")) : -1;
-    return v >= 0 ? v : (R <= 256 ? 2 : 5);
-}
+// there and lose), 128 x 64 on EIGHT waves above (two per SIMD: one wave's staging work in the shadow of the other's MFMAs; 512 rows: GEMM + tail
+// 26.5 vs 27.8 us on four waves, whole B = 512 update 380 vs 385 us) — profiles/r02_encoder_experiments.md.
+static inline bool a0_fc1_small(int R) { return R <= 256; }
 static inline int a0_fc1_splits(int R, int N, int K) {
-    const int v = a0_fc1_variant(R);
-    const int bx = (v == 2 || v == 3 || v == 6) ? 64 : 128, by = (v == 3 || v == 6) ? 128 : (v == 4 ? 32 : 64);
-    static const int wg = getenv("A0_FC1_WGS") ? atoi(getenv("A0_FC1_WGS")) : 256;      // target workgroup count
+    const int bx = a0_fc1_small(R) ? 64 : 128, by = 64;
     const int blocks = ((R + bx - 1) / bx) * ((N + by - 1) / by);
-    if (v == 0 && wg == 256) return a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K);
-    int splits = blocks < wg ? wg / blocks : 1;
+    int splits = blocks < 256 ? 256 / blocks : 1;      // about 256 workgroups
     const int maxs = (K / 32) / 2;
     if (splits > maxs) splits = maxs;
     if (splits > 64) splits = 64;
@@ -509,15 +501,8 @@ static inline int a0_fc1_splits(int R, int N, int K) {
 }
 template <class BK>
 static void a0_fc1_partial_launch(BK& bk, const a0_mat_src& a, const a0_mat_src& bw, const EpiSlab::Params& ep, int R, int N, int K, int splits) {
-    switch (a0_fc1_variant(R)) {
-        case 1: bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 2, 2, 2, 1>(a, bw, ep, R, N, K, splits); break;
-        case 4: bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 4, 1, 1, 1>(a, bw, ep, R, N, K, splits); break;
-        case 2: bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 2, 2, 1, 1>(a, bw, ep, R, N, K, splits); break;
-        case 3: bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 2, 2, 1, 2>(a, bw, ep, R, N, K, splits); break;
-        case 5: bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 4, 2, 1, 1>(a, bw, ep, R, N, K, splits); break;      // 128 x 64, eight waves
-        case 6: bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 2, 4, 1, 1>(a, bw, ep, R, N, K, splits); break;      // 64 x 128, eight waves
-        default: bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 4, 1, 1, 2>(a, bw, ep, R, N, K, splits);
-    }
+    if (a0_fc1_small(R)) bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 2, 2, 1, 1>(a, bw, ep, R, N, K, splits);      // 64 x 64
+    else bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 4, 2, 1, 1>(a, bw, ep, R, N, K, splits);                       // 128 x 64, eight waves
 }
 
 extern "C" int a0_reduce_bias_act_multi(int n, const float* const* slabs, const long long* slab_stride, const int* nslab, const float* const* bias, float* const* out,
@@ -570,8 +555,7 @@ static int a0_fwd_multi_splits(int n, int R, int N, int K) {
     return splits < 1 ? 1 : splits;
 }
 extern "C" int a0_dense_fwd_partial_multi_ok(int n, int R, int N, int K) {
-    static const bool off = getenv("A0_NO_FWD_MULTI") != nullptr;       // tuning aid
-    return (!off && g_gemm_x9 != 0 && (n == 2 || n == 3) && R >= 257 && R <= 4096 && N > 32 && !(N & 3) && !(K & 3)) ? 1 : 0;
+    return (g_gemm_x9 != 0 && (n == 2 || n == 3) && R >= 257 && R <= 4096 && N > 32 && !(N & 3) && !(K & 3)) ? 1 : 0;
 }
 extern "C" int a0_dense_fwd_partial_multi_slabs(int n, int R, int N, int K) { return a0_fwd_multi_splits(n, R, N, K); }
 
@@ -691,7 +675,7 @@ extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const fl
     A0_CATCH
 }
 
-// a0_actor_qhead_env_step whose tail kernel goes on to encode the env's NEW observation (round 5, a0_actor_step_enc_kernel in encoder_fused.hip): fc1 GEMM over
+// a0_actor_qhead_env_step whose tail kernel goes on to encode the env's NEW observation (round 5, a0_actor_step_enc2_kernel in encoder_fused.hip): fc1 GEMM over
 // `feat` (this step's features), then one launch for tail + env step + the NEXT step's features into `act3_next` (which may be `feat` itself: the GEMM has read it).
 extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                                            float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
@@ -757,8 +741,7 @@ extern "C" int a0_dense_dgrad(const float* dY, const float* W, const float* act_
 // demb is bit-identical to the two calls' (the same accumulators times the same features); d3 sums the sample's rows in the tile's register order instead of row by row
 // (fp32 rounding: 1e-7 of the accumulated magnitude).
 extern "C" int a0_dense_dgrad_hadamard_ok(int R, int N, int K, int n) {
-    static const bool off = getenv("A0_NO_DGRAD_HADAMARD") != nullptr;      // tuning aid
-    return (!off && g_gemm_x9 != 0 && (n == 32 || n == 64) && R >= 4096 && !(R & 255) && !(R % n) && !(N & 15) && N >= 64 && !(K & 3) && K >= 128) ? 1 : 0;
+    return (g_gemm_x9 != 0 && (n == 32 || n == 64) && R >= 4096 && !(R & 255) && !(R % n) && !(N & 15) && N >= 64 && !(K & 3) && K >= 128) ? 1 : 0;
 }
 extern "C" int a0_dense_dgrad_hadamard(const float* dY, const float* W, const float* emb, const float* feat, float* demb, float* d3, int R, int N, int K, int n, void* stream) {
     A0_TRY
@@ -778,18 +761,16 @@ extern "C" int a0_dense_dgrad_hadamard(const float* dY, const float* W, const fl
 // weight gradient (N x K): N == R — as one launch (a0_igemm_x9_pair_kernel).  fc1 of a 512-row batch: dX = (dY W) * (X > 0) into dX, dW = dY^T X (+ bias row sums) into grad.
 // Bit-identical to the two calls.  Shapes: a0_dense_dgrad_wgrad_ok.
 extern "C" int a0_dense_dgrad_wgrad_ok(int R, int N, int K) {
-    static const bool off = getenv("A0_NO_DGRAD_WGRAD_PAIR") != nullptr || getenv("A0_DGRAD_VARIANT") != nullptr || getenv("A0_WGRAD_VARIANT") != nullptr;      // tuning aids
     const long long b128 = (long long)((R + 127) / 128) * ((K + 63) / 64), b64 = (long long)((N + 63) / 64) * ((K + 63) / 64);
-    return (!off && g_gemm_x9 != 0 && g_probe.tag == 0 && R == N && R >= 1 && R <= 1024 && !(N & 3) && !(K & 3) && b128 < 256 && b64 >= 256 && N >= 512 &&
-            (long long)((R + 127) / 128) * ((K + 127) / 128) < g_x9_big_min) ? 1 : 0;
+    return (g_gemm_x9 != 0 && g_probe.tag == 0 && R == N && R >= 1 && R <= 1024 && !(N & 3) && !(K & 3) && b128 < 256 && b64 >= 256 && N >= 512 &&
+            (long long)((R + 127) / 128) * ((K + 127) / 128) < A0_X9_BIG_TILES) ? 1 : 0;
 }
 // (round 5) a second class of shapes: SMALL layers whose two gradients together fit one round of 64 x 64 tiles — the head of a distributional learner at a 512-row batch
 // (c51: 64 + 32 tiles, qr: 64 + 104).  Alone, the data gradient occupies a quarter of the chip for its whole k loop and the weight gradient follows it; side by side
 // the launch lasts as long as the longer of the two.  The weight gradient is then an UNSPLIT sum on the bf16 pipe (a0_dense_wgrad: slabs on the fp32 pipe).
 static int a0_dense_dgrad_wgrad_small_ok(int R, int N, int K) {
-    static const bool off = getenv("A0_NO_HEAD_PAIR") != nullptr;      // tuning aid
     const long long t1 = (long long)((R + 63) / 64) * ((K + 63) / 64), t2 = (long long)((N + 63) / 64) * ((K + 63) / 64);
-    return (!off && g_gemm_x9 != 0 && g_probe.tag == 0 && R >= 64 && R <= 1024 && N >= 64 && !(N & 3) && !(K & 3) && t1 + t2 <= 256 && t2 >= 16) ? 1 : 0;
+    return (g_gemm_x9 != 0 && g_probe.tag == 0 && R >= 64 && R <= 1024 && N >= 64 && !(N & 3) && !(K & 3) && t1 + t2 <= 256 && t2 >= 16) ? 1 : 0;
 }
 extern "C" int a0_dense_dgrad_wgrad_ok2(int R, int N, int K) { return (a0_dense_dgrad_wgrad_ok(R, N, K) || a0_dense_dgrad_wgrad_small_ok(R, N, K)) ? 1 : 0; }
 extern "C" int a0_dense_dgrad_wgrad(const float* dY, const float* W, const float* X, int ldx, float* dX, float* grad, int R, int N, int K, void* stream) {
@@ -804,10 +785,8 @@ extern "C" int a0_dense_dgrad_wgrad(const float* dY, const float* W, const float
         return A0_OK;
     }
     // 128 x 64 tiles on eight waves (196 + 196 workgroups, one per CU at a time): the same sums as the 64 x 64 tiles of the separate calls (every output element's k loop is the
-    // same sequence of MFMAs), equal on the `main` schedule and ~2 % faster under `launch`, where the rollout's kernels share the chip (A0_PAIR_TILE=0: 64 x 64, tuning aid)
-    static const int pv = getenv("A0_PAIR_TILE") ? atoi(getenv("A0_PAIR_TILE")) : 1;
-    if (pv == 1) A0_HIP_THROW((a0_igemm_x9_pair_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 4, 2, 1, 1>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R)));
-    else A0_HIP_THROW((a0_igemm_x9_pair_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 2, 2, 1, 1>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R)));
+    // same sequence of MFMAs), equal on the `main` schedule and ~2 % faster under `launch`, where the rollout's kernels share the chip
+    A0_HIP_THROW((a0_igemm_x9_pair_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 4, 2, 1, 1>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R)));
     return A0_OK;
     A0_CATCH
 }
@@ -819,10 +798,8 @@ extern "C" int a0_dense_dgrad_wgrad(const float* dY, const float* W, const float
 // where it pays: heads of at most one row of 128 x 64 tiles (scalar heads: 8 workgroups).  Measured with wider heads in the launch (same box, alternating): c51's 16 tiles
 // 14.47 - 14.50 -> 14.57 ms, qr's 56 tiles 12.13 -> 12.16 ms — there the fp32-pipe split launch of its own stays; dqn 9.97 -> 9.85 ms, mdqn 11.69 -> 11.60.
 extern "C" int a0_dense_dgrad_wgrad2_ok(int R, int N, int K, int N2, int K2) {
-    static const bool off = getenv("A0_NO_TRIO") != nullptr;      // tuning aid (the head's weight gradient as a launch of its own: the same sum in another order)
-    static const int max_tiles = getenv("A0_TRIO_MAX_TILES") ? atoi(getenv("A0_TRIO_MAX_TILES")) : 8;
-    return (!off && a0_dense_dgrad_wgrad_ok(R, N, K) && N2 >= 4 && !(N2 & 3) && K2 >= 4 && !(K2 & 3) &&
-            (long long)((N2 + 127) / 128) * ((K2 + 63) / 64) <= max_tiles) ? 1 : 0;
+    return (a0_dense_dgrad_wgrad_ok(R, N, K) && N2 >= 4 && !(N2 & 3) && K2 >= 4 && !(K2 & 3) &&
+            (long long)((N2 + 127) / 128) * ((K2 + 63) / 64) <= 8) ? 1 : 0;
 }
 extern "C" int a0_dense_dgrad_wgrad2(const float* dY, const float* W, const float* X, int ldx, float* dX, float* grad, int R, int N, int K,
                                      const float* dY2, const float* X2, int ldx2, float* grad2, int N2, int K2, void* stream) {

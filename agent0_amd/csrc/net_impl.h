@@ -58,8 +58,6 @@ static inline a0_act_src a0_act(const float* x, int Hin, int Win, int C, int Hou
 
 // ---- split heuristics (pure functions of the shapes, shared by the *_scratch queries)
 static inline int a0_fwd_splits(int gx, int gy, int K) {
-    static const int forced = getenv("A0_FWD_SPLITS") ? atoi(getenv("A0_FWD_SPLITS")) : 0;     // tuning aid
-    if (forced > 0) return forced;
     int blocks = gx * gy, splits = 1;
     if (blocks < 256) {
         splits = 256 / blocks;          // one workgroup per CU: measured best for fc1 at 256 / 512 rows (tools/ubench_dense.py)
@@ -72,10 +70,9 @@ static inline int a0_fwd_splits(int gx, int gy, int K) {
 }
 
 static inline int a0_wgrad_splits(int gx, int gy, int R) {
-    static const int target = getenv("A0_WGRAD_TARGET") ? atoi(getenv("A0_WGRAD_TARGET")) : 512;     // tuning aid
     int blocks = gx * gy, splits = 1;
     if (blocks < 256) {
-        splits = (target + blocks - 1) / blocks;
+        splits = (512 + blocks - 1) / blocks;      // about 512 workgroups
         int maxs = (R + 63) / 64;
         if (splits > maxs) splits = maxs;
         if (splits > 256) splits = 256;
@@ -89,11 +86,10 @@ static inline int a0_wgrad_splits(int gx, int gy, int R) {
 // heuristic above gave 3 splits = 300 workgroups = TWO rounds of 10 923 rows (measured 1116 us at 32 768 rows, 94 TFLOP/s, while the forward
 // and data-gradient GEMMs of the same size run at 137-139).  Here the split count minimises rounds x rows-per-split plus the price of the
 // slabs (one slab = N*K*4 bytes written and read back: ~1 round-row unit per 4 MB at the measured rates): 5 splits = 500 workgroups = two
-// rounds of 6 554 rows.  A0_WGRAD_DEEP=0 restores the old choice (tuning aid).
+// rounds of 6 554 rows.
 static inline int a0_wgrad_splits_deep(int N, int K, int R) {
-    static const int on = getenv("A0_WGRAD_DEEP") ? atoi(getenv("A0_WGRAD_DEEP")) : 1;
     const long long tiles = (long long)((N + 127) / 128) * ((K + 127) / 128);
-    if (!on || R < 4096 || N < 128 || K < 128) return 0;                       // not the deep, large case: the caller keeps a0_wgrad_splits
+    if (R < 4096 || N < 128 || K < 128) return 0;                       // not the deep, large case: the caller keeps a0_wgrad_splits
     const double slab_rows = ((double)N * K * 4.0 / 4.0e6) * 20.0;             // one slab ~ 20 rows' worth of tile time per 4 MB (write + reduce read)
     int best = 1; double best_cost = 1e300;
     for (int sp = 1; sp <= 16; ++sp) {
@@ -108,15 +104,9 @@ static inline int a0_wgrad_splits_deep(int N, int K, int R) {
 
 // conv2 / conv3 weight gradients: 64 x 64 output tiles and a split count that gives two workgroups per CU, i.e. 400-650 reduction rows
 // and 25 MB of slabs instead of 200-330 rows and 40 MB with 64 x 128 tiles (106 vs 110 us for the three layers + reduction at B = 512,
-// tools/ubench_convwgrad.py).  A0_CONV_WGRAD_T64 = target workgroup count (tuning aid; 0 = the 64 x 128 tiles of a0_wgrad_splits).
-static inline int a0_conv_wgrad_t64() {
-    static const int target = getenv("A0_CONV_WGRAD_T64") ? atoi(getenv("A0_CONV_WGRAD_T64")) : 512;
-    return target;
-}
+// profiles/r02_encoder_experiments.md).
 static inline int a0_conv_wgrad_splits(int K, int M) {
-    const int t = a0_conv_wgrad_t64();
-    if (t <= 0) return a0_wgrad_splits(1, (K + 127) / 128, M);
-    int s = t / ((K + 63) / 64);
+    int s = 512 / ((K + 63) / 64);      // 512 workgroups
     const int maxs = (M + 255) / 256;
     if (s > maxs) s = maxs;
     return s < 1 ? 1 : s;
@@ -133,8 +123,7 @@ static inline long long a0_dense_fwd_scratch_impl(int R, int N, int K) {
 // (whose second half would be empty) on four waves — two workgroups per CU — and as many splits as fill those 512 slots once
 // (measured at 32 768 rows: 352 us with 64 x 128 tiles and 11 splits = 37 TFLOP/s).
 static inline bool a0_wgrad_narrow_deep(int R, int N, int K) {
-    static const int on = getenv("A0_WGRAD_DEEP") ? atoi(getenv("A0_WGRAD_DEEP")) : 1;
-    return on && K <= 64 && N >= 256 && R >= 4096;
+    return K <= 64 && N >= 256 && R >= 4096;
 }
 static inline int a0_dense_wgrad_splits(int R, int N, int K) {
     if (a0_wgrad_narrow_deep(R, N, K)) {
@@ -158,9 +147,8 @@ static inline long long a0_dense_wgrad_scratch_impl(int R, int N, int K) {
 // 4 parts, conv3 into 3, every (part, group) is one workgroup of equal cost per observation, and two workgroups share a CU: 7 G <= 2 x CUs;
 // a group's workgroups all run on XCD g % 8 (its L2 then serves the parts' common operands), so G is a multiple of 8 when it can be: 72.
 static inline bool a0_c23w_plan(const a0_net_core& n, int B, int* G2, int* G3) {
-    static const bool off = getenv("A0_NO_CONV23_WGRAD_FUSED") != nullptr;
-    static const int gmax = getenv("A0_C23W_GROUPS") ? atoi(getenv("A0_C23W_GROUPS")) : ((2 * 256) / 7) / 8 * 8;      // tuning aid
-    if (off || B < 1 || n.H1 != 20 || n.W1 != 20 || n.H2 != 9 || n.W2 != 9 || n.H3 != 7 || n.W3 != 7) return false;
+    const int gmax = ((2 * 256) / 7) / 8 * 8;
+    if (B < 1 || n.H1 != 20 || n.W1 != 20 || n.H2 != 9 || n.W2 != 9 || n.H3 != 7 || n.W3 != 7) return false;
     const int g = B < gmax ? B : gmax;
     *G2 = g; *G3 = g;
     return g >= 1;
@@ -228,8 +216,7 @@ static void a0_encoder_fwd_impl(BK& bk, const a0_net_core& n, const a0_encoder_w
 // Shapes of the short-reduction forward kernel (short_k_fwd.h): K = 64 exactly (the quantile networks' cosine embedding), rows of X
 // 16-byte aligned, enough rows and columns that the general kernel's tiles would be all prologue and epilogue.
 static inline bool a0_short_k_shape(int R, int N, int K, int ldx) {
-    static const bool off = getenv("A0_NO_SHORT_K") != nullptr;       // tuning aid
-    return !off && K == 64 && (ldx & 3) == 0 && ldx >= 64 && N >= 64 && R >= 256;
+    return K == 64 && (ldx & 3) == 0 && ldx >= 64 && N >= 64 && R >= 256;
 }
 
 template <class BK>
@@ -261,10 +248,8 @@ static void a0_dense_dgrad_impl(BK& bk, const float* dY, const float* W, const f
     bk.tag = A0_TAG_DENSE_DGRAD;
     if (act_mask) {
         EpiMaskMat::Params e{dX, act_mask, K};
-        static const int var = getenv("A0_DGRAD_VARIANT") ? atoi(getenv("A0_DGRAD_VARIANT")) : 0;      // tuning aid
         const long long blocks = (long long)((R + 127) / 128) * ((K + 63) / 64);
-        if (var == 1 || (var == 0 && blocks < 256)) bk.template igemm<OpMatKC, OpMatXC, EpiMaskMat, 2, 2, 1, 1>(a, bw, e, R, K, N, 1);   // 64x64 tiles: twice the workgroups
-        else if (var == 2) bk.template igemm<OpMatKC, OpMatXC, EpiMaskMat, 4, 1, 1, 1>(a, bw, e, R, K, N, 1);
+        if (blocks < 256) bk.template igemm<OpMatKC, OpMatXC, EpiMaskMat, 2, 2, 1, 1>(a, bw, e, R, K, N, 1);   // 64x64 tiles: twice the workgroups
         else bk.template igemm<OpMatKC, OpMatXC, EpiMaskMat, 4, 1, 1, 2>(a, bw, e, R, K, N, 1);
     } else {
         EpiSlab::Params e{dX, 0, K};
@@ -287,12 +272,11 @@ static void a0_dense_wgrad_impl(BK& bk, const float* dY, const float* X, int ldx
     a0_mat_src b{X, ldx};
     bk.tag = A0_TAG_DENSE_WGRAD;
     if (defer) *defer = a0_reduce_seg{nullptr, 0, 0, nullptr, 0};
-    static const int var = getenv("A0_WGRAD_VARIANT") ? atoi(getenv("A0_WGRAD_VARIANT")) : -1;      // tuning aid: 0 = always split, 1 = never for >= 256 tiles
     const long long blocks64 = (long long)((N + 63) / 64) * ((K + 63) / 64);
-    if (blocks64 >= 256 && (var == 1 || (var < 0 && R <= 1024))) {
+    if (blocks64 >= 256 && R <= 1024) {
         // 64x64 output tiles without a reduction split when the output alone has >= 256 tiles and the batch is short (fc1 of a 512-row batch:
         // 392 tiles).  As a lone kernel this is slower than 64x128 tiles + 3 slabs, but no slabs means 19 MB less to write and to reduce: the
-        // whole B = 512 update measures 419 vs 432 us (tools/ubench_update.py, profiles/r02_encoder_experiments.md).  The quantile networks'
+        // whole B = 512 update measures 419 vs 432 us (profiles/r02_encoder_experiments.md).  The quantile networks'
         // 32 768-row reductions keep the split kernel.
         EpiWgradSlab::Params e{grad, 0, K, wcount};
         bk.template igemm<OpMatXC, OpMatXC, EpiWgradSlab, 2, 2, 1, 1>(a, b, e, N, K, R, 1);
@@ -334,8 +318,7 @@ static void a0_encoder_bwd_impl(BK& bk, const a0_net_core& n, const a0_encoder_w
         a0_act_src b = a0_act(act2, n.H2, n.W2, 64, n.H3, n.W3, 1, 0, n.ktab3);
         EpiWgradSlab::Params e{splits > 1 ? sl : g3, splits > 1 ? wc + 64 : 0, n.K3, wc};
         bk.tag = A0_TAG_CONV3_WGRAD;
-        if (a0_conv_wgrad_t64() > 0) bk.template igemm<OpMatXC, OpActXC, EpiWgradSlab, 2, 2, 1, 1>(a, b, e, 64, n.K3, M3, splits);
-        else bk.template igemm<OpMatXC, OpActXC, EpiWgradSlab, 2, 2, 1, 2>(a, b, e, 64, n.K3, M3, splits);
+        bk.template igemm<OpMatXC, OpActXC, EpiWgradSlab, 2, 2, 1, 1>(a, b, e, 64, n.K3, M3, splits);      // 64 x 64 tiles (a0_conv_wgrad_splits)
         if (splits > 1) segs[nseg++] = a0_reduce_seg{sl, wc + 64, splits, g3, wc + 64};
     }
     if (with_dgrad) {   // conv3 data gradient -> d2 (masked by act2 > 0): gather form, 3x3 taps over d3 with pad 2
@@ -353,8 +336,7 @@ static void a0_encoder_bwd_impl(BK& bk, const a0_net_core& n, const a0_encoder_w
         a0_act_src b = a0_act(act1, n.H1, n.W1, 32, n.H2, n.W2, 2, 0, n.ktab2);
         EpiWgradSlab::Params e{splits > 1 ? sl : g2, splits > 1 ? wc + 64 : 0, n.K2, wc};
         bk.tag = A0_TAG_CONV2_WGRAD;
-        if (a0_conv_wgrad_t64() > 0) bk.template igemm<OpMatXC, OpActXC, EpiWgradSlab, 2, 2, 1, 1>(a, b, e, 64, n.K2, M2, splits);
-        else bk.template igemm<OpMatXC, OpActXC, EpiWgradSlab, 2, 2, 1, 2>(a, b, e, 64, n.K2, M2, splits);
+        bk.template igemm<OpMatXC, OpActXC, EpiWgradSlab, 2, 2, 1, 1>(a, b, e, 64, n.K2, M2, splits);      // 64 x 64 tiles (a0_conv_wgrad_splits)
         if (splits > 1) segs[nseg++] = a0_reduce_seg{sl, wc + 64, splits, g2, wc + 64};
     }
     // conv2 data gradient -> d1 (masked by act1 > 0): four stride phases, 2x2 taps over d2 with pad 1

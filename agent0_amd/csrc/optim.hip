@@ -399,8 +399,7 @@ extern "C" int a0_noisy_multi(int grad, int nmod, const float* const* mu, const 
         return a0_fail(A0_EINVAL, "a0_noisy_multi: bad argument");
     a0_noisy_multi_args A;
     int blocks = 0;
-    static const bool scalar_only = getenv("A0_NOISY_SCALAR") != nullptr;       // tuning aid: the element-wise kernel
-    bool v4 = !scalar_only;
+    bool v4 = true;      // the four-wide kernel, unless an operand is unaligned or K not a multiple of 4
     for (int m = 0; m < nmod && v4; ++m)
         v4 = mu[m] && eff[m] && noise_in[m] && K[m] % 4 == 0 && (long long)N[m] * K[m] < (1LL << 31) &&
              (((uintptr_t)mu[m] | (uintptr_t)eff[m] | (uintptr_t)noise_in[m] | (grad ? 0 : (uintptr_t)sigma[m])) & 15) == 0;

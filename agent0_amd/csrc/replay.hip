@@ -399,8 +399,7 @@ __global__ __launch_bounds__(1024) void a0_sumtree_top_kernel(float* __restrict_
 
 static bool a0_sumtree_sub_path(long long cap2) {
     const long long S = cap2 / A0_ST_TOP;        // leaves per subtree below the LDS-resident top
-    static const bool one_wg = getenv("A0_SUMTREE_ONE_WG") != nullptr;      // tuning aid: the single-workgroup kernel for every size
-    return !one_wg && (S == 64 || S == 128 || S == 256 || S == 512 || S == 1024);
+    return S == 64 || S == 128 || S == 256 || S == 512 || S == 1024;
 }
 static void a0_sumtree_sub_launch(float* tree, long long cap2, const long long* idx, const float* val, int n, const int* state, const float* loss, float eps, float alpha,
                                   float* pstate, hipStream_t st, bool defer_top = false) {
@@ -765,9 +764,8 @@ extern "C" int a0_replay_sample_gather(int mode, unsigned long long start, unsig
     if (mode != 0 && mode != 1) return a0_fail(A0_EINVAL, "a0_replay_sample_gather: mode");
     // three workgroups per row: 768 lanes x four 16-byte loads cover 3072 of a row's 3528 vectors in one unrolled trip (12.8 us per
     // 512-row batch = 2.25 TB/s sampled, 4.5 TB/s of HBM traffic; 14.4 us with four workgroups and one load in flight; non-temporal
-    // loads / stores measured slower: tools/ubench_gather.py).  A0_GATHER_GX: tuning aid.
-    static const int gx_cap = getenv("A0_GATHER_GX") ? atoi(getenv("A0_GATHER_GX")) : 3;
-    int gx = ((row_bytes >> 4) + 255) / 256; if (gx > gx_cap) gx = gx_cap;
+    // loads / stores measured slower: tools/ubench_gather.py)
+    int gx = ((row_bytes >> 4) + 255) / 256; if (gx > 3) gx = 3;
     hipLaunchKernelGGL(a0_sample_gather_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, mode, start, n_perm, seed, tree, cap2, xi, top, head, cap, frames,
                        row_bytes, r_act, r_rew, r_done, priority, B, out, idx_out, slot_out, act, rew, done, prio);
     return a0_fail_hip((int)hipGetLastError(), "a0_replay_sample_gather");

@@ -338,8 +338,7 @@ extern "C" int a0_actor_bind(a0_actor* a, const a0_learner* L, int own_network) 
             a->fwd_scratch = a->mem.alloc<float>(sc > 4 ? sc : 4);
             a->q_taus = a->mem.alloc<float>(ceil_to(R, 4)); a->q_cosx = a->mem.alloc<float>(R * 64); a->q_x = a->mem.alloc<float>(R * L->feat);
             if (fqf) { a->f_logits = a->mem.alloc<float>((long long)E * 32); a->f_tau_all = a->mem.alloc<float>((long long)E * (nt + 1)); }
-            static const bool no_planes = getenv("A0_NO_WPLANES") != nullptr;      // tuning aid (same bits)
-            if (!no_planes && a0_dense_fwd_wplanes_ok((int)R, 512, L->feat)) a->w_planes = a->mem.alloc<unsigned int>(a0_weight_planes_words(512, L->feat), false);
+            if (a0_dense_fwd_wplanes_ok((int)R, 512, L->feat)) a->w_planes = a->mem.alloc<unsigned int>(a0_weight_planes_words(512, L->feat), false);
         } else if (dist) {
             a->h = a->mem.alloc<float>((long long)E * 512);
             a->head_slabs = a->mem.alloc<float>((long long)a0_dense_fwd_partial_slabs(E, L->Npad, 512) * E * L->Npad);
@@ -448,10 +447,9 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
     if (planes && !(L->d.noisy && a->steps % freq == 0)) A0_CHECK(a0_split_planes(V.Wf(), a->w_planes, 512, L->feat, stream));
     // scalar heads (Actor._rollout): the tail + env-step launch of step t also encodes the env's new observation (a0_actor_qhead_env_step_enc), so that step t + 1
     // starts with its features in place; the convolution weights do not change inside a rollout, the last step has no next one
-    static const bool step_enc_on = getenv("A0_NO_X9") == nullptr && (getenv("A0_STEP_ENC") == nullptr || atoi(getenv("A0_STEP_ENC")) != 0);
     // (not for an actor with its own network — the launch schedule: its rollout runs beside the update block, the critical path there, and a workgroup that holds a CU's
     // LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives: 9.43 -> 9.75 ms)
-    const bool step_enc = step_enc_on && !a->own_flat;
+    const bool step_enc = !a->own_flat;
     bool feat_ready = false;
     for (int t = 0; t < a->T; ++t) {
         if (L->d.noisy && a->steps % freq == 0) {      // agent.py:52-53: self.model.reset_noise() every reset_noise_freq steps, from the ACTOR's stream

@@ -8,8 +8,8 @@
 // (96 VGPRs) and streams blocks of 32 rows through them; X goes from global memory straight into fragment registers (k contiguous: the
 // eight k of a lane are two 16-byte loads), is split exactly as in igemm_x9.h, and each block is 72 v_mfma_f32_32x32x16_bf16 + its
 // epilogue.  No LDS, no barriers: waves are independent, two per SIMD, one wave's loads, splits and stores beside the other's MFMAs.
-// Measured (tools/ubench_short_k.py): 38 / 144 us with the product, 49 / 187 us with both outputs.  The floor is the output stream:
-// with the loads and eight of nine MFMAs taken out the launch still takes 22 / 85 us = 4.8 TB/s of stores (tools/exp_sk).
+// Measured (profiles/r03_experiments.md): 38 / 144 us with the product, 49 / 187 us with both outputs.  The floor is the output stream:
+// with the loads and eight of nine MFMAs taken out the launch still takes 22 / 85 us = 4.8 TB/s of stores.
 //
 // Work is cut into units (strip, row block); XCD x (workgroup id mod 8) takes the x-th eighth of the rows, and within it the units go
 // strip-major to the waves as equal contiguous ranges, so a wave reloads its strip of W at most once or twice per launch.

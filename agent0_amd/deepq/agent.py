@@ -66,7 +66,7 @@ class Actor:
         self._head_slabs = ops.empty(ops.dense_fwd_partial_slabs(E, self.L.Npad, 512) * E * self.L.Npad) if self.dist_tail else None
         # quantile heads (iqn, fqf) on the device env: head GEMM slabs -> one kernel for the tail AND the env step (a0_actor_quantile_tail_env_step)
         self.quant_tail = (self.L.algo in ("iqn", "fqf") and hasattr(self.envs, "act_step_commit") and self.obs_bytes == 4 * 84 * 84
-                           and ops.dense_fwd_scratch(E * n_tau, self.L.feat, self.L.num_cosines) == 0 and os.environ.get("A0_QUANT_TAIL", "1") != "0")     # 0: tuning aid (same bytes)
+                           and ops.dense_fwd_scratch(E * n_tau, self.L.feat, self.L.num_cosines) == 0)
         if self.quant_tail:
             self._head_slabs = ops.empty(ops.dense_fwd_partial_slabs(E * n_tau, self.L.Npad, 512) * E * n_tau * self.L.Npad)
         self.qmax_all = ops.zeros(T * E) if (self.fused_tail or self.dist_tail or self.quant_tail) else None
@@ -130,7 +130,7 @@ class Actor:
     def _quant_tail_args(self, epsilon, ctrl, eps_ptr, t):
         """The quantile head up to the head GEMM's slabs (enqueued here), then the arguments of ``ops.actor_quantile_tail_env_step``."""
         L, ops, E, dev, rng = self.L, self.ops, self.E, self.model._dev, self.rng
-        fused_cos = hasattr(ops, "tau_cos_features") and os.environ.get("A0_TAU_COS", "1") != "0"      # round 6: the fractions and their cosine features in one launch (0: tuning aid, same bits)
+        fused_cos = hasattr(ops, "tau_cos_features")      # round 6: the fractions and their cosine features in one launch
         if L.algo == "fqf":
             dev.fqf_taus(self.ws, E, with_cos=fused_cos)
             taus, aux, mode = self.ws.tau_hat, self.ws.tau_all, 3
@@ -198,13 +198,12 @@ class Actor:
         dev = self.model._dev
         step_enc = ((self.tail_env and (self.fused_tail or self.dist_tail) or (self.quant_tail and self.fused_commit and hasattr(ops, "actor_quantile_tail_env_step_enc")))
                     and bound and not test and dev.fused and (self.L.C, self.L.H, self.L.W) == (4, 84, 84) and hasattr(ops, "actor_qhead_env_step_enc")
-                    and os.environ.get("A0_NO_X9") is None and os.environ.get("A0_STEP_ENC", "1") != "0"       # 0: tuning aid (same bytes, three launches per step)
                     # not on the launch schedule (the rollout into a stage ring): there the rollout runs BESIDE the update block, which is the critical path, and a
                     # workgroup that holds a CU's LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives (9.43 -> 9.75 ms)
                     and not isinstance(self.replay, StageRing))
         # quantile actors (round 6): fc1's weight operand as bf16 term planes for the rollout's T GEMMs of E * K rows, split once here and after every noise reset
-        # (a0_split_planes; the same exact terms the GEMM forms per tile, hence the same bits — A0_NO_WPLANES: tuning aid)
-        self._planes_on = bool(self.quant_tail and bound and not test and self.fused_commit and hasattr(ops, "dense_fwd_wplanes") and os.environ.get("A0_NO_WPLANES") is None
+        # (a0_split_planes; the same exact terms the GEMM forms per tile, hence the same bits)
+        self._planes_on = bool(self.quant_tail and bound and not test and self.fused_commit and hasattr(ops, "dense_fwd_wplanes")
                                and ops.dense_fwd_wplanes_ok(E * self.n_tau, 512, self.L.feat))
         if self._planes_on and not (cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0):
             dev.refresh_fc1_planes()

@@ -502,8 +502,7 @@ class DeviceLearner:
         """passes: [(net, ws, chan_off, keep)] — the encoder forward passes of one update over the same batch.  They are independent of one another (the reference
         runs them one after the other, agent.py:176-181 / 222-231): on the fused split-operand kernel they go out as ONE launch (a0_net_encoder_fwd_fused_multi)."""
         L, ops, B = self.L, self.ops, self.B
-        multi = (len(passes) > 1 and self.online.fused and (L.C, L.H, L.W) == (4, 84, 84) and hasattr(ops, "encoder_fwd_fused_multi")
-                 and os.environ.get("A0_ENC_MULTI", "1") != "0" and os.environ.get("A0_NO_X9") is None)
+        multi = len(passes) > 1 and self.online.fused and (L.C, L.H, L.W) == (4, 84, 84) and hasattr(ops, "encoder_fwd_fused_multi")
         if not multi:
             for net, ws, chan_off, keep in passes:
                 net.encode(ws, frames, slot, sample_stride, chan_off, B, keep=keep)
@@ -520,7 +519,7 @@ class DeviceLearner:
         L = self.L
         if L.noisy or not self.online.fused:
             return False
-        return (L.algo == "dqn" and L.A + (1 if L.dueling else 0) <= 24) or (L.algo == "c51" and hasattr(self.ops, "c51_head_loss_slabs") and os.environ.get("A0_C51_SEPARATE", "0") != "1")
+        return (L.algo == "dqn" and L.A + (1 if L.dueling else 0) <= 24) or (L.algo == "c51" and hasattr(self.ops, "c51_head_loss_slabs"))
 
     def _tstage_buf(self, p: int):
         if getattr(self, "_tst", None) is None:
@@ -541,7 +540,7 @@ class DeviceLearner:
     def _qr_fused_ok(self) -> bool:
         """QR's head path from the GEMM slabs to the loss in one launch (a0_qr_head_loss_slabs): the staged head outputs of a sample must fit in LDS."""
         L, ops = self.L, self.ops
-        if not hasattr(ops, "qr_head_loss_slabs") or os.environ.get("A0_QR_SEPARATE", "0") == "1":       # 1: tuning aid (same numbers, the eleven separate launches)
+        if not hasattr(ops, "qr_head_loss_slabs"):
             return False
         R_on = 2 * self.B if self.double_q else self.B
         return (L.A <= 32 and (3 * L.Npad + (L.T + 3) // 4 * 4) * 4 <= 150 * 1024 and L.Npad % 4 == 0
@@ -632,7 +631,7 @@ class DeviceLearner:
         wo, wt, wsel = self.ws_o, self.ws_t, self.ws_s
         frac = None
         have_draw = have_dh = False
-        if algo == "mdqn" and L.A + (1 if L.dueling else 0) <= 24 and hasattr(ops, "mdqn_head_loss_slabs") and os.environ.get("A0_MDQN_SEPARATE", "0") != "1":
+        if algo == "mdqn" and L.A + (1 if L.dueling else 0) <= 24 and hasattr(ops, "mdqn_head_loss_slabs"):
             # round 5: dqn's path with the Munchausen target (a0_mdqn_head_loss_slabs) — the three passes' encoders in one launch, their fc1 GEMMs in one grouped launch,
             # and one kernel from the fc1 slabs to loss, head gradient and dh.  The third pass is the TARGET network on the current observation (agent.py:202-204).
             wm = self.ws_m
@@ -688,7 +687,7 @@ class DeviceLearner:
                                     L.A, L.dueling, L.Npad, act, rew, done, wgt, self.gamma_n, B, self.loss, wo.q, wt.q, wo.draw, self.state, wo.dh)
             have_dh = True           # ... and the head's backward-data pass: dh is written by the same kernel
             have_draw = True
-        elif algo == "c51" and hasattr(ops, "c51_head_loss_slabs") and os.environ.get("A0_C51_SEPARATE", "0") != "1":      # 1: tuning aid (same numbers, the nine separate launches)
+        elif algo == "c51" and hasattr(ops, "c51_head_loss_slabs"):
             # three fc1 GEMMs (their split-K slabs finished by ONE reduction launch), the online head as ONE GEMM over [s ; s'] rows, the target head, and
             # one launch for everything behind them (a0_c51_head_loss_slabs: slab sums, dueling, greedy next action, projection + cross entropy, head gradient)
             buf, nh_on, nh_tg, R_on = self._dist_heads_to_slabs(frames, slot, sample_stride, tstage)

@@ -78,8 +78,8 @@ class Trainer:
             self.stage = StageRing(ops, 2 * cfg.actor.sample_steps * cfg.actor.num_envs, self.replay.obs_bytes)
             self.actors = [None, agents.Actor(cfg, None, replay=self.stage, ops=ops, rank=rank)]
             # high priority: a rollout kernel that becomes ready goes ahead of the update block's queued kernels.  No difference with the device env (9.43 - 9.49 ms
-            # either way); with a host env, whose workers wait for every step's actions, 23.5 -> 21.7 ms per iteration (profiles/r04_experiments.md).  A0_ACTOR_STREAM_PRIO=0: default priority
-            self.actor_stream = torch.cuda.Stream(priority=int(os.environ.get("A0_ACTOR_STREAM_PRIO", "-1")))
+            # either way); with a host env, whose workers wait for every step's actions, 23.5 -> 21.7 ms per iteration (profiles/r04_experiments.md)
+            self.actor_stream = torch.cuda.Stream(priority=-1)
             self.overlap = True
             self._pending = None
         self.epsilon_fn = epsilon_schedule(cfg)
@@ -282,8 +282,7 @@ class Trainer:
         if self._loss_means.numel() < L:
             self._loss_means = self.ops.zeros(L)
         if getattr(self, "_tstream", None) is None:
-            prio = os.environ.get("A0_TSTREAM_PRIO")
-            self._tstream = torch.cuda.Stream() if prio is None else torch.cuda.Stream(priority=int(prio))
+            self._tstream = torch.cuda.Stream()
             self._tev = [torch.cuda.Event(), torch.cuda.Event()]
             self._mev = torch.cuda.Event()
         self.pipelined_blocks = getattr(self, "pipelined_blocks", 0) + 1

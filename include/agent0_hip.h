@@ -201,7 +201,8 @@ int a0_gemm_mode(int mode);
  * weight gradient): with a = a0 + a1 + a2, b = b0 + b1 + b2 (exact bf16 terms, |a1| <= 2^-8 |a|, |a2| <= 2^-16 |a|)
  *   9 = all of them: every partial product of the fp32 fmaf chain, exactly (the strict mode);
  *   6 = those with i + j <= 2 (default): a1*b2, a2*b1, a2*b2 — each below 2^-24 of a*b, below the rounding the fp32 chain applies to every partial sum — are not
- *       formed; against fp64 the result is at least as close as the fp32 fmaf chain's at every reduction length of the path (profiles/r06_x6_accuracy.txt).
+ *       formed; against fp64 its rms error is within 0.6 % of the nine-product result's and 0.88 - 1.38 x the sequential fp32 fmaf chain's, with a small
+ *       negative bias that grows with the reduction length (profiles/r06_x6_accuracy.txt).
  * n = 6 or 9 sets it, anything else only queries; returns the previous value.  Environment: A0_X9_PRODUCTS=9.  Process-wide: change it between launches, never
  * during graph capture (captured graphs keep the kernels they were captured with).  conv1 (bytes x three weight terms) always forms all three. */
 int a0_x9_products(int n);
