@@ -135,17 +135,26 @@ def real_atari_available() -> bool:
     return True
 
 
-def make_atari(env_id: str, num_envs: int, episode_life: bool = True, seed: int = 42, rank: int = 0, ops=None, synthetic=None, num_workers=None, task: str = "stream"):
+def make_atari(env_id: str, num_envs: int, episode_life: bool = True, seed: int = 42, rank: int = 0, ops=None, synthetic=None, num_workers=None, task: str = "stream",
+               groups: int = 1):
     """``task``: reward task of the synthetic env (``cfg.env_task``: "stream" = the bench workload, "block" = learnable; ignored by the real Atari env).
     ``synthetic=None``: the real Atari env (through the host env pool) when gymnasium + ale-py are importable, else the device-resident
-    synthetic env.  ``num_workers``: env worker processes (default: one per 16 envs, at most 16; 0 = step in this process)."""
+    synthetic env.  ``num_workers``: env worker processes (default: one per 16 envs, at most 16; 0 = step in this process).
+    ``groups`` (``cfg.actor.env_groups``): host envs only — 2 or more splits the vector env into that many ``env_pool.HostEnvGroups`` groups, the workers divided
+    among them; 1 = one ``HostEnvPool``.  Ignored by the synthetic env."""
+    groups = int(groups)
+    if not 1 <= groups <= int(num_envs):
+        raise ValueError(f"make_atari: groups={groups} must lie in [1, num_envs={num_envs}] (actor.env_groups)")
     if synthetic is None:
         synthetic = not real_atari_available()
     if synthetic:
         return DeviceSynthVecEnv(env_id, num_envs, seed=seed, rank=rank, ops=ops, task=task)
-    from .env_pool import HostEnvPool
+    from .env_pool import HostEnvGroups, HostEnvPool
 
     if num_workers is None:
         num_workers = 0 if num_envs < 4 else min(16, max(1, num_envs // 16))
+    if groups >= 2:
+        return HostEnvGroups(AtariSlice(env_id, episode_life, seed + 1000003 * rank), num_envs, groups=groups, obs_shape=(4, 84, 84),
+                             action_dim=ACTION_DIMS.get(env_id, 18), num_workers=num_workers, ops=ops)
     return HostEnvPool(AtariSlice(env_id, episode_life, seed + 1000003 * rank), num_envs, obs_shape=(4, 84, 84), action_dim=ACTION_DIMS.get(env_id, 18),
                        num_workers=num_workers, ops=ops)

@@ -190,7 +190,9 @@ struct a0_dtenv_args {
 };
 // Wave 0's part of the body below: head slab sum, dueling, expectation / quantile mean, first maximum, epsilon-greedy draw, the env's scalar work with the action
 // (and, chase task, the block's new cell into *s_chase_cell_p).  No workgroup barrier inside.  g / slot / x: the step's counter, the replay slot and the env's Philox
-// draw as the body derives them.
+// draw as the body derives them.  ENV = false: the tail alone (a0_actor_quantile_tail_kernel, loss.hip) — the env's fields of P, g, slot, x and s_chase_cell_p are
+// not read, and the statements that remain are those of ENV = true.
+template <bool ENV = true>
 A0_D void a0_actor_dist_tail_wave0(const a0_dtenv_args& P, float* __restrict__ xs, int* __restrict__ s_chase_cell_p, uint32_t g, long long slot, const a0_u4& x) {
     const int lane = threadIdx.x & 63;
     const uint32_t e = blockIdx.x;
@@ -202,9 +204,11 @@ A0_D void a0_actor_dist_tail_wave0(const a0_dtenv_args& P, float* __restrict__ x
     if (P.ctrl) { steps += P.ctrl[A0_CTRL_ACTOR_STEPS]; off_a += (unsigned long long)P.ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)P.ctrl[A0_CTRL_RNG_UNIFORM]; }
     if (P.eps_ptr) eps = P.eps_ptr[0];
     a0_env_pre Z;
-    a0_env_commit_prefetch(Z, e, P.E, P.n, steps, P.ep_ret, P.ring_act, P.ring_rew, P.ring_done);
-    a0_env_pre_to_vgpr(Z);
-    const a0_env_out O = a0_env_out_vgpr(P.ep_ret, P.final_mask, P.final_ret, P.ring_act, P.ring_rew, P.ring_done, P.r_act, P.r_rew, P.r_done);
+    if constexpr (ENV) {
+        a0_env_commit_prefetch(Z, e, P.E, P.n, steps, P.ep_ret, P.ring_act, P.ring_rew, P.ring_done);
+        a0_env_pre_to_vgpr(Z);
+    }
+    const a0_env_out O = ENV ? a0_env_out_vgpr(P.ep_ret, P.final_mask, P.final_ret, P.ring_act, P.ring_rew, P.ring_done, P.r_act, P.r_rew, P.r_done) : a0_env_out{};
     A0_TO_VGPR(steps); A0_TO_VGPR(off_a); A0_TO_VGPR(off_u); A0_TO_VGPR(eps);
     int n_v = P.n, E_v = P.E, task_v = P.task; double gamma_v = P.gamma; unsigned long long seed_v = P.rng_seed; uint32_t sa_v = P.stream_a, su_v = P.stream_u;
     int* action_v = P.action; float* qmax_v = P.qmax;
@@ -308,10 +312,12 @@ A0_D void a0_actor_dist_tail_wave0(const a0_dtenv_args& P, float* __restrict__ x
             const float u = (float)(a0_philox_word(seed_v, su_v, off_u + (unsigned long long)e) >> 8) * 0x1.0p-24f;
             const int act = (u > eps) ? besta : ra;
             action_v[e] = act; qmax_v[e] = best;
-            float r_chase = 0.f;
-            if (chase) *s_chase_cell_p = a0_chase_step(a0_chase_cell(P.obs_in + ((size_t)e * 4 + 3) * A0_ENV_PIX, e), act, x.w, r_chase);
-            a0_env_commit_finish(Z, x, e, g, task_v, A, E_v, n_v, steps, gamma_v, act, O.ep_ret, O.final_mask, O.final_ret, O.ring_act, O.ring_rew, O.ring_done, O.r_act, O.r_rew,
-                                 O.r_done, slot, r_chase);
+            if constexpr (ENV) {
+                float r_chase = 0.f;
+                if (chase) *s_chase_cell_p = a0_chase_step(a0_chase_cell(P.obs_in + ((size_t)e * 4 + 3) * A0_ENV_PIX, e), act, x.w, r_chase);
+                a0_env_commit_finish(Z, x, e, g, task_v, A, E_v, n_v, steps, gamma_v, act, O.ep_ret, O.final_mask, O.final_ret, O.ring_act, O.ring_rew, O.ring_done, O.r_act, O.r_rew,
+                                     O.r_done, slot, r_chase);
+            }
         }
     }
 }

@@ -344,6 +344,34 @@ extern "C" int a0_actor_quantile_tail_env_step_enc(const float* slabs, long long
     return a0_actor_dist_step_enc_launch(P, lds, wt, w, act3_next, (hipStream_t)stream);
 }
 
+// The same quantile tail WITHOUT the env step, for every actor step that has no device env to merge it with: host environments (one group or several,
+// Actor._rollout_host / _rollout_groups) and test rollouts.  One wave per env runs wave 0 of a0_actor_dist_tail_env_kernel with the env's work compiled out
+// (a0_actor_dist_tail_wave0<false>): slab sum in slab order + bias, dueling combine per quantile, action values (modes 1 / 3), first maximum, epsilon-greedy
+// draw — the same bytes as the merged kernel and as the four launches it replaces (a0_reduce_bias_act, a0_dueling_fwd, a0_select_action, a0_actor_egreedy_rng).
+__global__ __launch_bounds__(64) void a0_actor_quantile_tail_kernel(a0_dtenv_args P) {
+    extern __shared__ float xs[];                        // [A*T + T] head outputs of this env
+    a0_actor_dist_tail_wave0<false>(P, xs, nullptr, 0u, 0, a0_u4{0u, 0u, 0u, 0u});
+}
+
+extern "C" int a0_actor_quantile_tail(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
+                                      const float* taus, int E, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                      unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
+    if (!slabs || !bias || !action || !qmax || E < 1 || A < 1 || T < 1 || nslab < 1 || ld < A + (dueling ? 1 : 0) || slab_stride < (long long)E * T * ld ||
+        (mode != 1 && mode != 3) || (mode == 3 && !taus))
+        return a0_fail(A0_EINVAL, "a0_actor_quantile_tail: bad argument");
+    const size_t lds = (size_t)(A * T + T) * sizeof(float);
+    if (lds > 64 * 1024) return a0_fail(A0_EINVAL, "a0_actor_quantile_tail: head too wide for LDS");
+    a0_dtenv_args P = {};
+    P.slabs = slabs; P.slab_stride = slab_stride; P.nslab = nslab; P.bias = bias; P.ld = ld; P.A = A; P.T = T; P.dueling = dueling; P.mode = mode; P.atoms = nullptr; P.E = E;
+    P.rng_seed = seed; P.stream_a = stream_a; P.stream_u = stream_u; P.off_a = off_a; P.off_u = off_u; P.eps = eps; P.ctrl = ctrl; P.eps_ptr = eps_ptr;
+    P.action = action; P.qmax = qmax;
+    P.task = A0_ENV_TASK_STREAM;
+    P.kt = 1; P.taus = taus;
+    P.vec4 = (!(ld & 3) && !(slab_stride & 3) && !((((uintptr_t)slabs) | ((uintptr_t)bias)) & 15)) ? 1 : 0;
+    hipLaunchKernelGGL(a0_actor_quantile_tail_kernel, dim3(E), dim3(64), lds, (hipStream_t)stream, P);
+    return a0_fail_hip((int)hipGetLastError(), "a0_actor_quantile_tail");
+}
+
 // mode 1: mean over the T quantiles (qr); mode 2: C51 expectation with `atoms` [T]
 extern "C" int a0_actor_dist_tail(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
                                   const float* atoms, int E, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,

@@ -404,6 +404,22 @@ extern "C" int a0_dense_fwd(const float* X, int ldx, const float* W, const float
     A0_CATCH
 }
 
+// a0_dense_fwd with the split count given by the caller (1 = unsplit): a grouped actor step runs each group's layers with the split count of the full batch's launch, so
+// every row's sum is formed in the same order as in a one-group step.  a0_dense_fwd_splits tells the count a0_dense_fwd itself would use.
+extern "C" int a0_dense_fwd_splits(int R, int N, int K) {
+    return R < 1 ? 1 : a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K);
+}
+extern "C" int a0_dense_fwd_n(const float* X, int ldx, const float* W, const float* b, float* Y, int R, int N, int K, int relu, int splits, float* scratch, void* stream) {
+    A0_TRY
+    if (!X || !W || !b || !Y || R < 1 || N < 4 || (N & 3) || (K & 3) || (ldx & 3)) return a0_fail(A0_EINVAL, "a0_dense_fwd_n: bad shape (N, K, ldx must be multiples of 4)");
+    if (splits < 1 || splits > 64 || splits > (K + 31) / 32) return a0_fail(A0_EINVAL, "a0_dense_fwd_n: splits must lie in [1, min(64, ceil(K / 32))]");
+    if (splits > 1 && !scratch) return a0_fail(A0_EINVAL, "a0_dense_fwd_n: split-K needs scratch (splits * R * N floats)");
+    a0_hip_backend bk{(hipStream_t)stream};
+    a0_dense_fwd_impl(bk, X, ldx, W, b, Y, R, N, K, relu, scratch, splits);
+    return A0_OK;
+    A0_CATCH
+}
+
 // ---- weights as term planes (round 6): W [N][K] fp32 -> the three bf16 term planes in OpPlanesKC's layout (igemm_x9.h), once per change of W; a0_dense_fwd_wplanes
 // is a0_dense_fwd for unsplit shapes (a0_dense_fwd_scratch == 0) with whole k tiles (K % 32 == 0) reading them: the same exact terms, so the same result bit for bit.
 __global__ void a0_split_planes_kernel(const a0_f4* __restrict__ W, uint32_t* __restrict__ planes, long long groups) {
@@ -543,6 +559,22 @@ extern "C" int a0_dense_fwd_partial(const float* X, int ldx, const float* W, int
     A0_CATCH
 }
 
+// a0_dense_fwd_partial with the split count given by the caller (the slab buffer holds splits * R * N floats): see a0_dense_fwd_n
+extern "C" int a0_dense_fwd_partial_n(const float* X, int ldx, const float* W, int R, int N, int K, int splits, float* slabs, void* stream) {
+    A0_TRY
+    if (!X || !W || !slabs || R < 1 || (N & 3) || (K & 3) || (ldx & 3)) return a0_fail(A0_EINVAL, "a0_dense_fwd_partial_n: bad shape (N, K, ldx must be multiples of 4)");
+    if (splits < 1 || splits > 64 || splits > (K + 31) / 32) return a0_fail(A0_EINVAL, "a0_dense_fwd_partial_n: splits must lie in [1, min(64, ceil(K / 32))]");
+    a0_hip_backend bk{(hipStream_t)stream};
+    a0_mat_src a{X, ldx};
+    a0_mat_src bw{W, K};
+    EpiSlab::Params ep{slabs, (long long)R * N, N};
+    bk.tag = A0_TAG_DENSE_FWD;
+    if (N <= 32) bk.template igemm<OpMatKC, OpMatKC, EpiSlab, 4, 1, 1, 1>(a, bw, ep, R, N, K, splits);
+    else a0_fc1_partial_launch(bk, a, bw, ep, R, N, K, splits);
+    return A0_OK;
+    A0_CATCH
+}
+
 // n = 2 or 3 passes of one dense layer shape — X[i] [R][ldx] x W[i]^T [N][K] -> slabs[i] [splits][R][N] — as ONE launch (a0_igemm_x9_group_kernel): the chip is
 // filled with a half / a third of the splits a single pass needs, so every workgroup's k loop is that much longer and the fixed cost of a launch is paid once.  The
 // slabs differ from a0_dense_fwd_partial's (fewer, deeper partial sums: another association of the same fp32 additions); a0_dense_fwd_partial_multi_slabs tells the
@@ -622,14 +654,14 @@ extern "C" long long a0_actor_qhead_scratch(int E, int K) {
     return (long long)splits * E * 512;
 }
 
-extern "C" int a0_actor_qhead(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
-                              float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
-                              unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
+extern "C" int a0_actor_qhead_n(const float* feat, int E, int K, int splits, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
     A0_TRY
     if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !action || !qmax || E < 1 || K < 4 || (K & 3) || A < 1 || A + (dueling ? 1 : 0) > 24)
         return a0_fail(A0_EINVAL, "a0_actor_qhead: bad argument (A + dueling <= 24: the head rows are staged in 48 KB of LDS)");
+    if (splits < 1 || splits > 64 || splits > (K + 31) / 32) return a0_fail(A0_EINVAL, "a0_actor_qhead_n: splits must lie in [1, min(64, ceil(K / 32))]");
     a0_hip_backend bk{(hipStream_t)stream};
-    const int splits = a0_fc1_splits(E, 512, K);
     a0_mat_src a{feat, K};
     a0_mat_src bw{W1, K};
     EpiSlab::Params ep{scratch, (long long)E * 512, 512};
@@ -640,6 +672,13 @@ extern "C" int a0_actor_qhead(const float* feat, int E, int K, const float* W1, 
     A0_HIP_THROW(hipGetLastError());
     return A0_OK;
     A0_CATCH
+}
+
+extern "C" int a0_actor_qhead(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                              float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                              unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
+    return a0_actor_qhead_n(feat, E, K, a0_fc1_splits(E, 512, K), W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action,
+                            qmax, stream);
 }
 
 extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,

@@ -219,14 +219,15 @@ static inline bool a0_short_k_shape(int R, int N, int K, int ldx) {
     return K == 64 && (ldx & 3) == 0 && ldx >= 64 && N >= 64 && R >= 256;
 }
 
+// `splits_in` > 0: the split count the caller asks for instead of the shape's own (a grouped actor step forms its rows' sums in the order of the full batch's launch)
 template <class BK>
 static void a0_dense_fwd_impl(BK& bk, const float* X, int ldx, const float* W, const float* b, float* Y, int R, int N, int K,
-                              int relu, float* scratch) {
+                              int relu, float* scratch, int splits_in = 0) {
     bk.tag = A0_TAG_DENSE_FWD;
-    if (a0_short_k_shape(R, N, K, ldx)) { bk.short_k_fwd(X, ldx, W, b, nullptr, 1, Y, nullptr, R, N, relu); return; }
+    if (splits_in <= 1 && a0_short_k_shape(R, N, K, ldx)) { bk.short_k_fwd(X, ldx, W, b, nullptr, 1, Y, nullptr, R, N, relu); return; }
     a0_mat_src a{X, ldx};
     a0_mat_src bw{W, K};
-    const int splits = a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K);
+    const int splits = splits_in > 0 ? splits_in : a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K);
     const bool narrow = (N <= 32);
     bk.tag = A0_TAG_DENSE_FWD;
     if (splits == 1) {

@@ -42,7 +42,8 @@ class Actor:
         self.cfg = cfg
         self.ops = ops = model.ops if model is not None else _ops_from(cfg, ops)
         self.rng = DeviceRng(ops, cfg.seed, rank)
-        self.envs = envs if envs is not None else make_atari(cfg.env_id, cfg.actor.num_envs, seed=cfg.seed, rank=rank, ops=ops, task=cfg.env_task)
+        self.envs = envs if envs is not None else make_atari(cfg.env_id, cfg.actor.num_envs, seed=cfg.seed, rank=rank, ops=ops, task=cfg.env_task,
+                                                             groups=int(cfg.actor.env_groups))
         self.obs, _ = self.envs.reset()             # a list of per-group observations for a grouped host env (env_pool.HostEnvGroups)
         self.model = model if model is not None else DeepQNet(cfg, ops=ops)
         self.replay = replay
@@ -67,9 +68,11 @@ class Actor:
         # quantile heads (iqn, fqf) on the device env: head GEMM slabs -> one kernel for the tail AND the env step (a0_actor_quantile_tail_env_step)
         self.quant_tail = (self.L.algo in ("iqn", "fqf") and hasattr(self.envs, "act_step_commit") and self.obs_bytes == 4 * 84 * 84
                            and ops.dense_fwd_scratch(E * n_tau, self.L.feat, self.L.num_cosines) == 0)
-        if self.quant_tail:
+        # quantile heads without the device env's merged step (host envs, test rollouts): head GEMM slabs -> the same tail without the env step (a0_actor_quantile_tail)
+        self.quant_slabs = self.L.algo in ("iqn", "fqf") and ops.dense_fwd_scratch(E * n_tau, self.L.feat, self.L.num_cosines) == 0
+        if self.quant_slabs:
             self._head_slabs = ops.empty(ops.dense_fwd_partial_slabs(E * n_tau, self.L.Npad, 512) * E * n_tau * self.L.Npad)
-        self.qmax_all = ops.zeros(T * E) if (self.fused_tail or self.dist_tail or self.quant_tail) else None
+        self.qmax_all = ops.zeros(T * E) if (self.fused_tail or self.dist_tail or self.quant_slabs) else None
         self._qh_scratch = ops.empty(ops.actor_qhead_scratch(E, self.L.feat)) if self.fused_tail else None
         self.stat_mask, self.stat_ret = ops.zeros(T * E), ops.zeros(T * E)
         self.ring_act, self.ring_rew, self.ring_done = ops.zeros(self.n * E, dtype=torch.int32), ops.zeros(self.n * E), ops.zeros(self.n * E)
@@ -97,19 +100,33 @@ class Actor:
         # a host env split into groups (env_pool.HostEnvGroups): per-group workspaces and n-step state; the CPU steps one group while the GPU infers the other
         self.groups = None
         if hasattr(self.envs, "pools"):
-            if not (self.fused_tail or self.dist_tail) or cfg.learner.noisy_net:
-                raise ValueError("a grouped host env needs a scalar or distributional head without NoisyNet (per-step noise resets and the quantile heads' tau draws are "
-                                 "ordered over the whole env batch); use one group")
+            if not (self.fused_tail or self.dist_tail or self.quant_slabs):
+                raise ValueError("a grouped host env needs a head with a one-kernel actor tail (scalar: A + dueling <= 24; c51 / qr: the head's outputs in LDS); use one group")
+            self._splits = self._split_plan()
+            rows = E * n_tau if self.quant_slabs else E
             self.groups = []
             for pool, off in zip(self.envs.pools, self.envs.offsets):
                 k = pool.E
-                g = dict(pool=pool, off=off, E=k, ws=Workspace(ops, self.L, k, 1), action=self.action[off:off + k],
+                g = dict(pool=pool, off=off, E=k, ws=Workspace(ops, self.L, k, n_tau), action=self.action[off:off + k],
                          ring_act=ops.zeros(self.n * k, dtype=torch.int32), ring_rew=ops.zeros(self.n * k), ring_done=ops.zeros(self.n * k),
                          out_act=ops.zeros(k, dtype=torch.int32), out_rew=ops.zeros(k), out_done=ops.zeros(k),
-                         scratch=ops.empty(ops.actor_qhead_scratch(k, self.L.feat)) if self.fused_tail else None,
-                         slabs=ops.empty(ops.dense_fwd_partial_slabs(k, self.L.Npad, 512) * k * self.L.Npad) if self.dist_tail else None,
+                         scratch=ops.empty(self._splits["qhead"] * k * 512) if self.fused_tail else None,
+                         slabs=ops.empty(self._splits["head"] * k * (rows // E) * self.L.Npad) if not self.fused_tail else None,
                          ring_obs=ops.zeros(self.ring_len * k * self.obs_bytes, dtype=torch.uint8) if self.n > 1 else None)
                 self.groups.append(g)
+
+    def _split_plan(self) -> dict:
+        """The split-K counts of the actor step's dense GEMMs at the FULL batch (E rows, E * n_tau for the quantile heads).  A group of k envs runs its GEMMs with
+        these counts instead of those of its own k (k * n_tau) rows, so that every row's sum is formed in the order of the one-group step: the split count of
+        a0_dense_fwd / a0_dense_fwd_partial / a0_actor_qhead depends on the row count, and a different count is a different association of the fp32 additions."""
+        L, ops, dev, E = self.L, self.ops, self.model._dev, self.E
+        if self.fused_tail:
+            return {"qhead": ops.dense_fwd_partial_slabs(E, 512, L.feat)}          # a0_actor_qhead: a0_fc1_splits(E, 512, K)
+        R = E * self.n_tau if self.quant_slabs else E
+        plan = {"fc1": dev.dense_splits("fc1", R), "head": ops.dense_fwd_partial_slabs(R, L.Npad, 512)}
+        if L.algo == "fqf":
+            plan["frac"] = dev.dense_splits("frac", E)
+        return plan
 
     # ------------------------------------------------------------------ agent.py:25-39
     def _qhead_args(self, epsilon, ctrl, eps_ptr, t):
@@ -127,8 +144,9 @@ class Actor:
         return (self._head_slabs, ns, bh, L.Npad, L.A, L.T, L.dueling, 2 if L.algo == "c51" else 1, self.atoms, E, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
                 rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), float(epsilon), self.action, self.qmax_all[t * E:(t + 1) * E], ctrl, eps_ptr)
 
-    def _quant_tail_args(self, epsilon, ctrl, eps_ptr, t):
-        """The quantile head up to the head GEMM's slabs (enqueued here), then the arguments of ``ops.actor_quantile_tail_env_step``."""
+    def _quant_tail_args(self, epsilon, ctrl, eps_ptr, t, w_planes=None):
+        """The quantile head up to the head GEMM's slabs (enqueued here), then the arguments of ``ops.actor_quantile_tail_env_step`` (and of ``ops.actor_quantile_tail``,
+        which takes them up to ``eps_ptr``).  ``w_planes=False``: fc1 from its weights, not from the term planes a training rollout keeps (``_rollout``)."""
         L, ops, E, dev, rng = self.L, self.ops, self.E, self.model._dev, self.rng
         fused_cos = hasattr(ops, "tau_cos_features")      # round 6: the fractions and their cosine features in one launch
         if L.algo == "fqf":
@@ -140,7 +158,8 @@ class Actor:
             else:
                 rng.uniform(rng.STREAM_TAUS, self.taus, E * self.n_tau)
             taus, aux, mode = self.taus, None, 1
-        ns = dev.head_slabs(self.ws, E, taus, self.n_tau, self._head_slabs, cos_ready=fused_cos, w_planes=getattr(self, "_planes_on", False))
+        ns = dev.head_slabs(self.ws, E, taus, self.n_tau, self._head_slabs, cos_ready=fused_cos,
+                            w_planes=getattr(self, "_planes_on", False) if w_planes is None else w_planes)
         _, bh = dev.wb("head")
         return (self._head_slabs, ns, bh, L.Npad, L.A, self.n_tau, L.dueling, mode, aux, E, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
                 rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), float(epsilon), self.action, self.qmax_all[t * E:(t + 1) * E], ctrl, eps_ptr)
@@ -156,6 +175,10 @@ class Actor:
             return
         if self.dist_tail:
             ops.actor_dist_tail(*self._dist_tail_args(epsilon, ctrl, eps_ptr, t))
+            return
+        if self.quant_slabs:
+            # host envs and test rollouts: the merged step's head and tail without its env step — one tail launch where the generic chain below takes four
+            ops.actor_quantile_tail(*self._quant_tail_args(epsilon, ctrl, eps_ptr, t, w_planes=False))
             return
         if L.algo == "fqf":
             dev.fqf_taus(self.ws, E)
@@ -175,7 +198,7 @@ class Actor:
     def act(self, epsilon):
         one = self.ops.zeros(1)
         self._act_device(epsilon, one)
-        if self.fused_tail or self.dist_tail:
+        if self.fused_tail or self.dist_tail or self.quant_slabs:
             self.ops.mean_rows(self.qmax_all, 1, self.E, one)
         return self.action.cpu().numpy().astype(np.int64), float(one[0])
 
@@ -263,7 +286,7 @@ class Actor:
                 stage["obs"][sl].copy_(obs0.view(E, -1)); stage["obs_next"][sl].copy_(obs_next.view(E, -1))
                 stage["act"][sl].copy_(self.out_act); stage["rew"][sl].copy_(self.out_rew); stage["done"][sl].copy_(self.out_done)
             self.obs = obs_next
-        if self.fused_tail or self.dist_tail or (self.quant_tail and bound and not test and self.fused_commit):
+        if self.fused_tail or self.dist_tail or self.quant_slabs:
             ops.mean_rows(self.qmax_all, T, E, self.qs)          # per-step mean max-Q (agent.py:38,88), all steps at once
 
     # ------------------------------------------------------------------ host envs (env_pool.HostEnvPool): nothing but inference between two env steps
@@ -310,60 +333,97 @@ class Actor:
             self.obs = obs_next
         bookkeeping(*pending)
         self.action = self._host_actions[0]
-        if self.fused_tail or self.dist_tail:
+        if self.fused_tail or self.dist_tail or self.quant_slabs:
             ops.mean_rows(self.qmax_all, T, E, self.qs)
 
     # ------------------------------------------------------------------ grouped host envs: CPU stepping of one group beside the GPU's inference of the other
     def _group_infer_send(self, g, obs, epsilon, t, offs):
-        """Actor.act for group ``g`` on its observations (agent.py:25-39), then the actions go to the group's workers without waiting for them."""
+        """Actor.act for group ``g`` on its observations (agent.py:25-39), then the actions go to the group's workers without waiting for them.  ``offs``: the step's
+        Philox offsets (epsilon-greedy action, uniform, and for iqn the fractions), reserved once for the whole batch; the group takes its envs' part of each.  Every
+        dense GEMM runs with the full batch's split count (``_split_plan``)."""
         L, ops, dev, rng, k, off = self.L, self.ops, self.model._dev, self.rng, g["E"], g["off"]
-        E = self.E
-        dev.encode(g["ws"], obs, None, self.obs_bytes, 0, k, keep=False)
+        E, ws, sp = self.E, g["ws"], self._splits
+        dev.encode(ws, obs, None, self.obs_bytes, 0, k, keep=False)
         qmax = self.qmax_all[t * E + off:t * E + off + k]
         if self.fused_tail:
             (W1, b1), (W2, b2) = dev.wb("fc1"), dev.wb("head")
-            ops.actor_qhead(g["ws"].act3, k, L.feat, W1, b1, W2, b2, L.A, L.dueling, g["scratch"], rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                            offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax)
-        else:
-            dev._dense(g["ws"].act3, L.feat, "fc1", g["ws"].h, k, True)
+            ops.actor_qhead_n(ws.act3, k, L.feat, sp["qhead"], W1, b1, W2, b2, L.A, L.dueling, g["scratch"], rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
+                              offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax)
+        elif self.dist_tail:
+            dev._dense(ws.act3, L.feat, "fc1", ws.h, k, True, splits=sp["fc1"])
             Wh, bh = dev.wb("head")
-            ns = ops.dense_fwd_partial(g["ws"].h, 512, Wh, k, L.Npad, 512, g["slabs"])
+            ns = ops.dense_fwd_partial_n(ws.h, 512, Wh, k, L.Npad, 512, sp["head"], g["slabs"])
             ops.actor_dist_tail(g["slabs"], ns, bh, L.Npad, L.A, L.T, L.dueling, 2 if L.algo == "c51" else 1, self.atoms, k, rng.seed, rng.STREAM_EGREEDY_A,
                                 rng.STREAM_EGREEDY_U, offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax)
+        else:
+            nt = self.n_tau
+            if L.algo == "fqf":
+                dev.fqf_taus(ws, k, with_cos=True, splits=sp["frac"])          # the fractions come from the group's own features: no draws
+                taus, aux, mode = ws.tau_hat, ws.tau_all, 3
+            else:
+                # the group's rows of the step's E * K fraction draws: env e's K fractions are draws [base + e K, base + (e + 1) K) whatever group it is in
+                ops.tau_cos_features(rng.seed, rng.STREAM_TAUS, offs[2] + off * nt, ws.taus, ws.cosx, k * nt, L.num_cosines)
+                taus, aux, mode = ws.taus, None, 1
+            ns = dev.head_slabs(ws, k, taus, nt, g["slabs"], cos_ready=True, splits=sp)
+            _, bh = dev.wb("head")
+            ops.actor_quantile_tail(g["slabs"], ns, bh, L.Npad, L.A, nt, L.dueling, mode, aux, k, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
+                                    offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax)
         g["pool"].step_send(g["action"])
 
-    def _rollout_groups(self, epsilon, T, start):
+    def _rollout_groups(self, epsilon, T, start, bound=True, test=False, stage=None, frames_out=None):
         """Actor.sample's loop (agent.py:48-88) over a grouped host env: while group A's worker processes step their envs, the GPU runs Actor.act for group B,
         and vice versa (the overlap the reference gets from ``num_actors`` actor processes, launch.py:30-61).  Every env sees exactly what it would see in
-        a one-group rollout — its own observations, the epsilon-greedy draws at its own offset of the step's Philox block, its own n-step window — and
-        group g's transitions of step t land in the ring slots [start + t E + off_g, ...): the same bytes in the same order (tests/test_gpu_trainer.py)."""
+        a one-group rollout — its own observations, the epsilon-greedy (and iqn fraction) draws at its own offset of the step's Philox block, its own n-step window,
+        the same NoisyNet noise — and group g's transitions of step t land in the ring slots [start + t E + off_g, ...): the same bytes in the same order
+        (tests/test_gpu_trainer.py, tests/test_gpu_host_env_groups.py).  ``test``: no n-step bookkeeping and no rows, the first four envs' newest frames per step
+        into ``frames_out``; ``bound=False`` (and not ``test``): the rows go to ``stage`` at the same positions."""
         cfg, ops, E, rng, rp = self.cfg, self.ops, self.E, self.rng, self.replay
-        R, gamma = self.ring_len, float(cfg.learner.discount)
-        reserve = lambda: (rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E))
+        R, gamma, ob = self.ring_len, float(cfg.learner.discount), self.obs_bytes
+        iqn = self.quant_slabs and self.L.algo == "iqn"
+        reserve = lambda: (rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), rng.reserve(rng.STREAM_TAUS, E * self.n_tau) if iqn else 0)
+        noisy, freq = bool(cfg.learner.noisy_net), int(cfg.learner.reset_noise_freq)
+        if noisy and self.steps % freq != 0:
+            self.model._dev.compose_noise()                     # as in _rollout
+        if noisy and self.steps % freq == 0:
+            self.model.reset_noise(rng=self.rng)                # step 0's noise, ahead of its first inference
         offs = reserve()
         for gi, g in enumerate(self.groups):                      # step 0's actions: nothing to overlap with yet
             self._group_infer_send(g, self.obs[gi], epsilon, 0, offs)
         for t in range(T):
             nxt_offs = reserve() if t + 1 < T else None
+            frames = []
             for gi, g in enumerate(self.groups):
                 k, off = g["E"], g["off"]
                 cur_obs = self.obs[gi]
-                if self.n > 1:
-                    slot = self.steps % R
-                    g["ring_obs"][slot * k * self.obs_bytes:(slot + 1) * k * self.obs_bytes].copy_(cur_obs)
-                    oldest = (self.steps - (min(self.steps + 1, self.n) - 1)) % R
-                    obs0 = g["ring_obs"][oldest * k * self.obs_bytes:(oldest + 1) * k * self.obs_bytes]
-                else:
-                    obs0 = cur_obs
                 sl = slice(t * E + off, t * E + off + k)
                 obs_next, reward, terminal, truncated, info = g["pool"].step_recv(self.stat_mask[sl], self.stat_ret[sl])      # waits for THIS group's workers only
-                ops.actor_nstep(k, self.n, self.steps, gamma, g["action"], reward, terminal, truncated, info.get("life_loss"), g["ring_act"], g["ring_rew"], g["ring_done"],
-                                g["out_act"], g["out_rew"], g["out_done"], None)
-                ops.replay_insert(rp.frames, rp.size, self.obs_bytes, (start + t * E + off) % rp.size, k, obs0, obs_next, g["out_act"], g["out_rew"], g["out_done"],
-                                  rp.act, rp.rew, rp.done, None)
+                if test:
+                    if off < 4:                                     # the newest frame of the first four envs (agent.py / trainer.py:131-132), gathered over the groups
+                        frames.append(obs_next.view(k, self.L.C, self.L.H, self.L.W)[:4 - off, -1:].cpu().numpy())
+                else:
+                    if self.n > 1:
+                        slot = self.steps % R
+                        g["ring_obs"][slot * k * ob:(slot + 1) * k * ob].copy_(cur_obs)
+                        oldest = (self.steps - (min(self.steps + 1, self.n) - 1)) % R
+                        obs0 = g["ring_obs"][oldest * k * ob:(oldest + 1) * k * ob]
+                    else:
+                        obs0 = cur_obs
+                    ops.actor_nstep(k, self.n, self.steps, gamma, g["action"], reward, terminal, truncated, info.get("life_loss"), g["ring_act"], g["ring_rew"],
+                                    g["ring_done"], g["out_act"], g["out_rew"], g["out_done"], None)
+                    if bound:
+                        ops.replay_insert(rp.frames, rp.size, ob, (start + t * E + off) % rp.size, k, obs0, obs_next, g["out_act"], g["out_rew"], g["out_done"],
+                                          rp.act, rp.rew, rp.done, None)
+                    else:
+                        stage["obs"][sl].copy_(obs0.view(k, -1)); stage["obs_next"][sl].copy_(obs_next.view(k, -1))
+                        stage["act"][sl].copy_(g["out_act"]); stage["rew"][sl].copy_(g["out_rew"]); stage["done"][sl].copy_(g["out_done"])
                 self.obs[gi] = obs_next
                 if nxt_offs is not None:                            # the next step's actions for this group, while the other group's workers are stepping
+                    if gi == 0 and noisy and (self.steps + 1) % freq == 0:
+                        # NoisyNet: the next step's noise, once, behind every group's inference of this step and ahead of any of the next
+                        self.model.reset_noise(rng=self.rng)
                     self._group_infer_send(g, obs_next, epsilon, t + 1, nxt_offs)
+            if test:
+                frames_out.append(np.concatenate(frames, axis=0))
             self.steps += 1
         ops.mean_rows(self.qmax_all, T, E, self.qs)
 
@@ -440,9 +500,7 @@ class Actor:
         start = self.replay.write_cursor() if bound else 0
         frames_out = []
         if self.groups is not None:
-            if not bound:
-                raise NotImplementedError("a grouped host env serves training rollouts into a replay ring (test / staged rollouts: use one group)")
-            self._rollout_groups(epsilon, T, start)
+            self._rollout_groups(epsilon, T, start, bound, test, st, frames_out)
         elif self._graph_eligible(T, bound, test, state_dict):
             self._rollout_graphed(epsilon, T, start)
         elif bound and hasattr(self.envs, "step_send") and os.environ.get("A0_HOST_ROLLOUT", "1") != "0":      # 0: the step-by-step order of _rollout (same bytes; a tuning aid)

@@ -14,6 +14,10 @@ Additions (all default to the reference's behaviour being available):
                    stream — the throughput workload) or ``block`` (learnable: +1 for naming the quadrant of the bright block in the newest frame,
                    -1 for the next class; chance 0, optimum +1 per step) or ``chase`` (temporal credit: the action moves the block on a 4 x 4 lattice, +1 only on
                    arrival at the target cell three to six moves away; optimum 0.25 per step) — what the learning tests train on.  Ignored by real Atari envs.
+  actor.env_groups int, default 1 — host environments only: the number of groups the vector env is split into (env_pool.HostEnvGroups), each with its
+                   own worker processes and page-locked ring, so that the CPU steps one group while the GPU infers the other (the counterpart of the
+                   reference's ``num_actors`` actor processes, launch.py:30-61).  1 = one HostEnvPool.  Every setting gives the same bytes; which one is
+                   fastest depends on the emulator's CPU cost per step, so it is the user's choice.  Ignored by the device-resident synthetic env.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -134,6 +138,7 @@ class ActorConfig:
     test_steps: int = 800
     min_eps: float = 0.01
     test_eps: float = 0.001
+    env_groups: int = 1
 
 
 @dataclass

@@ -189,10 +189,19 @@ class DeviceNet:
         else:
             self.ops.encoder_fwd(self.net, self.encoder_weights(), frames, slot, sample_stride, chan_off, B, ws.act1, ws.act2, ws.act3)
 
-    def _dense(self, X, ldx, name, Y, R, relu):
+    def dense_splits(self, name, R) -> int:
+        """The split-K count ``_dense`` uses for layer ``name`` over ``R`` rows."""
+        blk = self.L.eff[name] if (self.L.noisy and name in ("fc1", "head")) else self.L.blocks[name]
+        return self.ops.dense_fwd_splits(R, blk.N, blk.K)
+
+    def _dense(self, X, ldx, name, Y, R, relu, splits: Optional[int] = None):
+        """``splits``: the split-K count to use instead of the shape's own (a grouped actor step passes the full batch's, ``Actor._split_plan``)."""
         W, b = self.wb(name)
         blk = self.L.eff[name] if (self.L.noisy and name in ("fc1", "head")) else self.L.blocks[name]
         N, K = blk.N, blk.K
+        if splits is not None:
+            self.ops.dense_fwd_n(X, ldx, W, b, Y, R, N, K, relu, splits, self.scratch(splits * R * N if splits > 1 else 0))
+            return
         self.ops.dense_fwd(X, ldx, W, b, Y, R, N, K, relu, self.scratch(self.ops.dense_fwd_scratch(R, N, K)))
 
     def head(self, ws: Workspace, B, taus: Optional[torch.Tensor] = None, n_tau: int = 1, feat: Optional[torch.Tensor] = None):
@@ -231,10 +240,12 @@ class DeviceNet:
             self.fc1_planes = torch.empty(self.ops.weight_planes_words(512, self.L.feat), dtype=torch.int32, device=self.flat.device)
         self.ops.split_planes(W, self.fc1_planes, 512, self.L.feat)
 
-    def head_slabs(self, ws: Workspace, B, taus: torch.Tensor, n_tau: int, slabs: torch.Tensor, cos_ready: bool = False, w_planes: bool = False) -> int:
+    def head_slabs(self, ws: Workspace, B, taus: torch.Tensor, n_tau: int, slabs: torch.Tensor, cos_ready: bool = False, w_planes: bool = False,
+                   splits: Optional[dict] = None) -> int:
         """Quantile heads of a pass that is not differentiated, up to the head GEMM's split-K slabs [ns][B * n_tau][Npad] (the consumer kernel finishes
-        the layer: a0_actor_quantile_tail_env_step).  Returns the slab count.  ``cos_ready``: ``ws.cosx`` already holds the fractions' cosine features (the launch that
-        produced the fractions wrote them: a0_tau_cos_features / a0_fqf_taus_cos)."""
+        the layer: a0_actor_quantile_tail_env_step / a0_actor_quantile_tail).  Returns the slab count.  ``cos_ready``: ``ws.cosx`` already holds the fractions' cosine
+        features (the launch that produced the fractions wrote them: a0_tau_cos_features / a0_fqf_taus_cos).  ``splits``: {"fc1": n, "head": n} — the split counts of
+        another row count's launches (a grouped actor step: the full batch's)."""
         L, ops = self.L, self.ops
         R = B * n_tau
         if not cos_ready:
@@ -244,18 +255,21 @@ class DeviceNet:
         if w_planes:      # ``refresh_fc1_planes`` has run since fc1's effective weights last changed
             ops.dense_fwd_wplanes(ws.x, L.feat, self.fc1_planes, self.wb("fc1")[1], ws.h, R, 512, L.feat, True)
         else:
-            self._dense(ws.x, L.feat, "fc1", ws.h, R, True)
+            self._dense(ws.x, L.feat, "fc1", ws.h, R, True, splits=None if splits is None else splits["fc1"])
         Wh, _ = self.wb("head")
+        if splits is not None:
+            return ops.dense_fwd_partial_n(ws.h, 512, Wh, R, L.Npad, 512, splits["head"], slabs)
         return ops.dense_fwd_partial(ws.h, 512, Wh, R, L.Npad, 512, slabs)
 
     def fc1(self, ws: Workspace, B):
         """features -> relu(fc1) only (the fused DQN head kernel takes it from there)."""
         self._dense(ws.act3, self.L.feat, "fc1", ws.h, B, True)
 
-    def fqf_taus(self, ws: Workspace, B, with_cos: bool = False):
-        """FQFHead.prop_taus (model.py:268-278): fraction net on (detached) features -> taus, tau_hats (``with_cos``: and the tau_hats' cosine features into ``ws.cosx``)."""
+    def fqf_taus(self, ws: Workspace, B, with_cos: bool = False, splits: Optional[int] = None):
+        """FQFHead.prop_taus (model.py:268-278): fraction net on (detached) features -> taus, tau_hats (``with_cos``: and the tau_hats' cosine features into ``ws.cosx``).
+        ``splits``: the fraction GEMM's split count (see ``_dense``)."""
         L = self.L
-        self._dense(ws.act3, L.feat, "frac", ws.frac_logits, B, False)
+        self._dense(ws.act3, L.feat, "frac", ws.frac_logits, B, False, splits=splits)
         if with_cos:
             self.ops.fqf_taus_cos(ws.frac_logits, L.Fpad, ws.tau_all, ws.tau_hat, ws.cosx, L.num_cosines, B, L.F)
         else:

@@ -71,6 +71,9 @@ def eligible(tr) -> Optional[str]:
     lc = cfg.learner
     if os.environ.get("A0_NATIVE_LOOP", "1") == "0":
         return "A0_NATIVE_LOOP=0"
+    actor = tr.actors[1]
+    if not isinstance(actor.envs, DeviceSynthVecEnv) or actor.groups is not None:
+        return "host environments"
     algo = lc.algo.name
     if algo == "dqn":
         if cfg.action_dim + (1 if lc.dueling_head else 0) > 24:
@@ -88,9 +91,6 @@ def eligible(tr) -> Optional[str]:
         return f"no handle for {algo}"
     if tuple(cfg.obs_shape) != (4, 84, 84):
         return "observations other than 4 x 84 x 84"
-    actor = tr.actors[1]
-    if not isinstance(actor.envs, DeviceSynthVecEnv) or actor.groups is not None:
-        return "host environments"
     rp = tr.replay
     if rp.use_sumtree and lc.batch_size > 1024:
         return "prioritized batches above 1024"

@@ -276,6 +276,17 @@ class HipOps:
                                     _req(Y, torch.float32, R * N, "Y"), R, N, K, int(relu),
                                     _req(scratch, torch.float32, need, "scratch", optional=(need == 0)), _stream()), "a0_dense_fwd")
 
+    def dense_fwd_splits(self, R, N, K) -> int:
+        """The split-K count ``dense_fwd`` uses for this shape (1 = unsplit)."""
+        return int(self.lib.a0_dense_fwd_splits(R, N, K))
+
+    def dense_fwd_n(self, X, ldx, W, b, Y, R, N, K, relu, splits, scratch):
+        """``dense_fwd`` with the split count given by the caller (a0_dense_fwd_n); ``scratch``: splits * R * N floats when splits > 1."""
+        need = splits * R * N if splits > 1 else 0
+        check(self.lib.a0_dense_fwd_n(_req(X, torch.float32, (R - 1) * ldx + K, "X"), ldx, _req(W, torch.float32, N * K, "W"), _req(b, torch.float32, N, "b"),
+                                      _req(Y, torch.float32, R * N, "Y"), R, N, K, int(relu), int(splits),
+                                      _req(scratch, torch.float32, need, "scratch", optional=(need == 0)), _stream()), "a0_dense_fwd_n")
+
     def dense_dgrad_hadamard_ok(self, R, N, K, n) -> bool:
         return bool(self.lib.a0_dense_dgrad_hadamard_ok(R, N, K, n))
 
@@ -515,6 +526,12 @@ class HipOps:
                                             _req(slabs, torch.float32, ns * R * N, "slabs"), _stream()), "a0_dense_fwd_partial")
         return ns
 
+    def dense_fwd_partial_n(self, X, ldx, W, R, N, K, splits, slabs):
+        """``dense_fwd_partial`` with the slab count given by the caller (a0_dense_fwd_partial_n); returns it."""
+        check(self.lib.a0_dense_fwd_partial_n(_req(X, torch.float32, (R - 1) * ldx + K, "X"), ldx, _req(W, torch.float32, N * K, "W"), R, N, K, int(splits),
+                                              _req(slabs, torch.float32, splits * R * N, "slabs"), _stream()), "a0_dense_fwd_partial_n")
+        return int(splits)
+
     def dense_fwd_partial_multi_ok(self, n, R, N, K) -> bool:
         return bool(self.lib.a0_dense_fwd_partial_multi_ok(n, R, N, K))
 
@@ -601,6 +618,14 @@ class HipOps:
                                           _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
                                           _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_dist_tail")
 
+    def actor_quantile_tail(self, slabs, nslab, bias, ld, A, T, dueling, mode, taus, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl=None, eps_ptr=None):
+        """The quantile heads' actor tail without the env step (a0_actor_quantile_tail): ``actor_quantile_tail_env_step``'s arguments up to ``eps_ptr``."""
+        check(self.lib.a0_actor_quantile_tail(
+            _req(slabs, torch.float32, nslab * E * T * ld, "slabs"), E * T * ld, nslab, _req(bias, torch.float32, A + (1 if dueling else 0), "bias"), ld, A, T, int(dueling),
+            mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_quantile_tail")
+
     def actor_dist_tail_env_step(self, slabs, nslab, bias, ld, A, T, dueling, mode, atoms, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
                                  env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
                                  start_slot, r_act, r_rew, r_done, task=0):
@@ -677,6 +702,15 @@ class HipOps:
                                       _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
                                       _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
                                       _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_qhead")
+
+    def actor_qhead_n(self, feat, E, K, splits, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl=None, eps_ptr=None):
+        """``actor_qhead`` with the fc1 GEMM's split count given by the caller (a0_actor_qhead_n); ``scratch``: splits * E * 512 floats."""
+        nq = A + (1 if dueling else 0)
+        check(self.lib.a0_actor_qhead_n(_req(feat, torch.float32, E * K, "feat"), E, K, int(splits), _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
+                                        _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
+                                        _req(scratch, torch.float32, splits * E * 512, "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
+                                        _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+                                        _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_qhead_n")
 
     def actor_qhead_env_step(self, feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
                              env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,

@@ -116,6 +116,10 @@ int a0_net_encoder_wgrad(const a0_net* net, const a0_encoder_weights* w, const a
 long long a0_dense_fwd_scratch(int R, int N, int K);
 int a0_dense_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int R, int N, int K, int relu,
                  float* scratch, void* stream);
+/* a0_dense_fwd with the split-K count given by the caller (1 = unsplit; scratch: splits * R * N floats when splits > 1).  A grouped actor step runs every group's layers
+ * with the count of the full batch's launch (a0_dense_fwd_splits), so each row's sum is formed in the same order as in a one-group step. */
+int a0_dense_fwd_splits(int R, int N, int K);
+int a0_dense_fwd_n(const float* X, int ldx, const float* W, const float* b, float* Y, int R, int N, int K, int relu, int splits, float* scratch, void* stream);
 int a0_dense_dgrad(const float* dY, const float* W, const float* act_mask, float* dX, int R, int N, int K, void* stream);
 /* (round 4) a0_dense_dgrad with the ReLU mask X and the unsplit a0_dense_wgrad of ONE layer (loss.backward() through first_dense, agent.py:153-155) as one launch: the two
  * GEMMs have the same number of 64 x 64 tiles (R == N) and together keep the chip's workgroup slots filled; bit-identical to the two calls.  Shapes: _ok (fc1 of a 512-row batch) */
@@ -153,6 +157,8 @@ int a0_dense_fwd_mul_keep(const float* X, int ldx, const float* W, const float* 
  * a0_dense_fwd_partial_slabs(R, N, K) slabs in order, adds the bias and applies the activation (a0_dqn_head_loss_slabs) */
 int a0_dense_fwd_partial_slabs(int R, int N, int K);
 int a0_dense_fwd_partial(const float* X, int ldx, const float* W, int R, int N, int K, float* slabs, void* stream);
+/* the same with the slab count given by the caller (slabs: splits * R * N floats) — see a0_dense_fwd_n */
+int a0_dense_fwd_partial_n(const float* X, int ldx, const float* W, int R, int N, int K, int splits, float* slabs, void* stream);
 /* (round 4) n = 2 or 3 passes of ONE layer shape with their own inputs, weights and slab buffers — the target / online fc1 passes of an update (agent.py:176-181) — in one
  * launch: fewer, deeper splits per pass (a0_dense_fwd_partial_multi_slabs of them; the partial sums associate differently from a0_dense_fwd_partial's) because the passes
  * fill the chip together.  Host arrays of device pointers; shapes: a0_dense_fwd_partial_multi_ok */
@@ -223,6 +229,12 @@ int a0_select_action(const float* x, long long sb, long long sa, long long st, i
 int a0_actor_dist_tail(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
                        const float* atoms, int E, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                        unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream);
+/* the quantile networks' tail (iqn: mode 1; fqf: mode 3 with taus [E][T + 1]) without the env step: a0_actor_quantile_tail_env_step's arguments up to `qmax` — for actor
+ * steps on host environments and test rollouts.  Same arithmetic, hence the same action and qmax, as the merged kernel and as a0_reduce_bias_act + a0_dueling_fwd +
+ * a0_select_action + a0_actor_egreedy_rng. */
+int a0_actor_quantile_tail(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
+                           const float* taus, int E, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                           unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream);
 /* a0_actor_dist_tail + a0_env_synth_step_commit in ONE launch (a workgroup per env; the distributional counterpart of a0_actor_qhead_env_step):
  * arguments of a0_actor_dist_tail, then those of a0_env_synth_step_commit (the action is taken from, and written to, `action`). */
 int a0_actor_dist_tail_env_step(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
@@ -579,6 +591,11 @@ long long a0_actor_qhead_scratch(int E, int K);
 int a0_actor_qhead(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                    float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                    unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream);
+/* a0_actor_qhead with the fc1 GEMM's split count given by the caller (scratch: splits * E * 512 floats) — see a0_dense_fwd_n; a0_actor_qhead uses
+ * a0_dense_fwd_partial_slabs(E, 512, K) */
+int a0_actor_qhead_n(const float* feat, int E, int K, int splits, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                     float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                     unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream);
 /* a0_actor_qhead + a0_env_synth_step_commit in two launches instead of three (the fc1 GEMM, then ONE kernel with a workgroup per env: one
  * wave runs the tail and the env's scalar work with the chosen action while the others already write the new frame / stack / replay row).
  * Arguments: those of a0_actor_qhead, then those of a0_env_synth_step_commit (the action is taken from, and written to, `action`). */
