@@ -4,6 +4,7 @@
 // arrays and rounded to fp32 once, where the reference's Trainer casts them (trainer.py:88-90).
 #include "a0_internal.h"
 #include "philox.h"
+#include "nstep.h"
 
 #pragma clang fp contract(off)
 
@@ -61,10 +62,7 @@ extern "C" int a0_actor_egreedy_rng(const int* greedy, unsigned long long seed, 
     return a0_fail_hip((int)hipGetLastError(), "a0_actor_egreedy_rng");
 }
 
-// Ring of the last n (action, reward, done) per env; entry for step t lives at t % n.
-//   done_t = (terminal | life_loss) & ~truncated                      agent.py:57-62
-//   R = 0; D = 0; for k = newest .. oldest: D |= d_k; R = R*gamma*(1-d_k) + r_k      agent.py:64-69
-//   emitted action = action of the oldest entry                       agent.py:70-71
+// Ring of the last n (action, reward, done) per env; entry for step t lives at t % n (the per-env body: nstep.h, shared with host_step.hip).
 // steps = number of env steps taken BEFORE this one (so this step is written at steps % n).
 __global__ void a0_nstep_kernel(int E, int n, long long steps, double gamma, const int* __restrict__ action, const float* __restrict__ reward,
                                 const float* __restrict__ terminal, const float* __restrict__ truncated, const float* __restrict__ life_loss,
@@ -73,26 +71,8 @@ __global__ void a0_nstep_kernel(int E, int n, long long steps, double gamma, con
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
     if (ctrl) steps += ctrl[A0_CTRL_ACTOR_STEPS];
-    const bool done = ((terminal[e] != 0.f) || (life_loss && life_loss[e] != 0.f)) && !(truncated[e] != 0.f);
-    const int cur = (int)(steps % n);
-    ring_act[(long long)cur * E + e] = action[e];
-    ring_rew[(long long)cur * E + e] = reward[e];
-    ring_done[(long long)cur * E + e] = done ? 1.f : 0.f;
-    const long long have = steps + 1;
-    const int count = have < n ? (int)have : n;
-    double R = 0.0;
-    bool D = false;
-    for (int k = 0; k < count; ++k) {
-        const int idx = (int)(((steps - k) % n + n) % n);
-        const float dk = (k == 0) ? (done ? 1.f : 0.f) : ring_done[(long long)idx * E + e];
-        const float rk = (k == 0) ? reward[e] : ring_rew[(long long)idx * E + e];
-        D = D || (dk != 0.f);
-        R = R * gamma * (double)(1 - (dk != 0.f ? 1 : 0)) + (double)rk;
-    }
-    const int oldest = (int)(((steps - (count - 1)) % n + n) % n);
-    out_act[e] = (count == 1) ? action[e] : ring_act[(long long)oldest * E + e];
-    out_rew[e] = (float)R;
-    out_done[e] = D ? 1.f : 0.f;
+    a0_nstep_env(e, E, n, steps, gamma, action[e], reward[e], terminal[e], truncated[e], life_loss ? life_loss[e] : 0.f, ring_act, ring_rew, ring_done,
+                 out_act + e, out_rew + e, out_done + e);
 }
 
 extern "C" int a0_actor_nstep(int E, int n, long long steps, double gamma, const int* action, const float* reward, const float* terminal,
@@ -161,7 +141,7 @@ extern "C" int a0_env_pool_send(const int* action, int* act_host_dev, int E, lon
 extern "C" int a0_env_pool_upload(const uint8_t* new_host, uint8_t* new_dev, const float* scal_host, float* scal_dev, int n_scal, int advance_row,
                                   const uint8_t* obs_host, const uint8_t* prev, uint8_t* out, int E, int nstack, long long frame_bytes, int* n_whole,
                                   void* stream) {
-    if (!new_host || !new_dev || !scal_host || !scal_dev || !obs_host || !prev || !out || prev == out || E < 1 || nstack < 2 || n_scal < 1 || advance_row < 0 ||
+    if (!new_host || !new_dev || !scal_host || !scal_dev || !obs_host || !out || prev == out || E < 1 || nstack < 2 || n_scal < 1 || advance_row < 0 ||
         advance_row >= n_scal || frame_bytes < 16 || (frame_bytes % 16) || ((((uintptr_t)prev) | ((uintptr_t)new_dev) | ((uintptr_t)out)) % 16))
         return a0_fail(A0_EINVAL, "a0_env_pool_upload: bad argument (frames of a multiple of 16 bytes, 16-byte aligned, out != prev)");
     hipStream_t s = (hipStream_t)stream;
@@ -181,5 +161,6 @@ extern "C" int a0_env_pool_upload(const uint8_t* new_host, uint8_t* new_dev, con
     }
     if (n_whole) *n_whole = whole;
     if (err != hipSuccess) return a0_fail_hip((int)err, "a0_env_pool_upload: hipMemcpyAsync");
+    if (!prev) return A0_OK;      // DMA only: the host-step ingest kernel (host_step.hip) builds the advanced stacks
     return a0_env_frame_stack(prev, new_dev, scal_dev + (size_t)advance_row * E, out, E, nstack, frame_bytes, stream);
 }

@@ -12,6 +12,9 @@
 // (tests/test_gpu_trainer.py::test_native_handles_run_the_loop_like_the_python_trainer).
 #include "learner_state.h"
 
+#include <chrono>
+#include <thread>
+
 namespace {
 
 typedef a0_host_rng Rng;      // learner_state.h
@@ -300,6 +303,11 @@ struct a0_actor {
     // online network, NoisyNet buffers included: the reference's train actor SHARES the learner's module there (trainer.py:41-44).
     float *own_flat = nullptr, *own_wt = nullptr, *own_eff = nullptr, *own_noise = nullptr;
     unsigned int* w_planes = nullptr;     // quantile actors (round 6): fc1's weights as bf16 term planes (a0_split_planes), refreshed when a rollout starts and after every NoisyNet compose
+    // an attached host-env pool (a0_actor_attach_pool): the rollout steps it instead of the device env; ring_obs keeps the last n observations for n > 1
+    bool pool_on = false;
+    a0_env_pool_desc pool{};
+    uint8_t* ring_obs = nullptr;
+    long long pool_whole = 0;
 };
 
 // the network an actor acts with: the learner's online network, or the actor's own snapshot of it
@@ -406,6 +414,56 @@ extern "C" int a0_actor_create(const a0_actor_desc* d, a0_actor** out) {
 
 extern "C" int a0_actor_destroy(a0_actor* a) { delete a; return A0_OK; }
 
+extern "C" int a0_actor_attach_pool(a0_actor* a, const a0_env_pool_desc* d) {
+    A0_TRY
+    if (!a || !d) return a0_fail(A0_EINVAL, "a0_actor_attach_pool: null argument");
+    if (d->E != a->E || d->nstack < 2 || d->frame_bytes < 16 || d->frame_bytes % 16 || (long long)d->nstack * d->frame_bytes != a->obs_bytes || d->W < 1 || d->seq < 0 ||
+        !(d->timeout_s > 0.0) || !d->act_dev || !d->ctl_dev || !d->done_host || !d->new_dev || d->seq_mask <= 0)
+        return a0_fail(A0_EINVAL, "a0_actor_attach_pool: bad description (E and nstack * frame_bytes of the actor, at least one worker)");
+    for (int h = 0; h < 2; ++h)
+        if (!d->new_host[h] || !d->scal_host[h] || !d->obs_host[h] || !d->obs_dev[h] || !d->scal_dev[h]) return a0_fail(A0_EINVAL, "a0_actor_attach_pool: null buffer");
+    if (a->own_flat) return a0_fail(A0_ESTATE, "a0_actor_attach_pool: an actor with its own network (the launch schedule) does not drive a pool");
+    if (a->steps != 0) return a0_fail(A0_ESTATE, "a0_actor_attach_pool: attach before the first rollout");
+    if (a->n > 1 && !a->ring_obs) a->ring_obs = a->mem.alloc<uint8_t>((long long)a->n * a->E * a->obs_bytes);
+    a->pool = *d;
+    a->pool_on = true;
+    a->pool_whole = 0;
+    return A0_OK;
+    A0_CATCH
+}
+
+extern "C" int a0_actor_detach_pool(a0_actor* a) {
+    if (!a) return a0_fail(A0_EINVAL, "a0_actor_detach_pool: null handle");
+    a->pool_on = false;
+    return A0_OK;
+}
+
+extern "C" int a0_actor_pool_seq(a0_actor* a, long long* seq_out, long long* whole_out, long long set_seq) {
+    if (!a || !a->pool_on) return a0_fail(A0_ESTATE, "a0_actor_pool_seq: no pool attached");
+    if (seq_out) *seq_out = a->pool.seq;
+    if (whole_out) *whole_out = a->pool_whole;
+    if (set_seq >= 0) a->pool.seq = set_seq;
+    return A0_OK;
+}
+
+// HostEnvPool._wait_workers: every done word at `seq`; a negative word is a dead worker; give up after the timeout; sleep between polls after 2 ms
+static int a0_pool_wait(const a0_env_pool_desc& P, long long seq) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        bool all = true, dead = false;
+        for (int w = 0; w < P.W; ++w) {
+            const long long v = __atomic_load_n(P.done_host + w, __ATOMIC_ACQUIRE);
+            all = all && v == seq;
+            dead = dead || v < 0;
+        }
+        if (all) return A0_OK;
+        if (dead) return a0_fail(A0_ESTATE, "a0_actor_rollout: an env worker process died");
+        const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (waited > P.timeout_s) return a0_fail(A0_ESTATE, "a0_actor_rollout: the env workers did not finish a step within the pool's timeout");
+        if (waited > 2e-3) std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+}
+
 // Actor.sample (agent.py:44-90) with the learner's online network: T steps of [encoder, fc1 GEMM, tail + env step + n-step bookkeeping + replay row], the
 // rows written straight into the ring at its write cursor (call a0_rbuf_commit(replay, T * E) afterwards: ReplayDataset.extend), then the per-step mean max-Q.
 // Asynchronous like everything else; a0_actor_collect waits and returns the statistics.
@@ -422,6 +480,72 @@ static int a0_actor_compose(const a0_actor_net& V, void* stream) {
         nin[k] = V.noise + m.off_in; nw[k] = V.noise + m.off_w; nb[k] = V.noise + m.off_b;
     }
     return a0_noisy_multi(0, L->n_mods, mu, sg, eff, N, K, r0, r1, nin, nw, nb, stream);
+}
+
+// Actor._rollout_host over an attached pool (a0_env_pool_desc): the inference of Actor._act_device (the head's tail without an env step), the send, the wait for
+// the workers, the DMA-only upload and one ingest launch per step.  The step's bookkeeping runs ahead of the next step's inference (the Python classes enqueue it
+// after the next send); the kernels and their arguments are the same, so are the bytes.
+static int a0_actor_rollout_pool(a0_actor* a, a0_learner* L, a0_rbuf* R, float epsilon, const a0_actor_net& V, a0_encoder_weights& w, long long start, void* stream) {
+    a0_env_pool_desc& P = a->pool;
+    const int E = a->E, A = a->d.A;
+    const bool dist = L->d.algo == A0_ALGO_C51 || L->d.algo == A0_ALGO_QR, fqf = L->d.algo == A0_ALGO_FQF, quant = L->d.algo == A0_ALGO_IQN || fqf;
+    const int freq = a->d.reset_noise_freq > 0 ? a->d.reset_noise_freq : 4;
+    const int nt = fqf ? L->F : (quant ? L->d.iqn_K : 1);
+    if (!quant && !dist && A + (a->d.dueling ? 1 : 0) > 24) return a0_fail(A0_EINVAL, "a0_actor_rollout: scalar heads with A + dueling <= 24 actions");
+    for (int t = 0; t < a->T; ++t) {
+        if (L->d.noisy && a->steps % freq == 0) {
+            A0_CHECK(a0_rng_normal(a->rng.seed, 4 /* STREAM_NOISE */, a->rng.reserve(4, L->noise_len), 0.1f, V.noise, L->noise_len, stream));
+            A0_CHECK(a0_actor_compose(V, stream));
+        }
+        const long long seq = P.seq + 1;
+        const int half = (int)(seq & 1);
+        const uint8_t* cur = (const uint8_t*)P.obs_dev[half ^ 1];
+        uint8_t* nxt = (uint8_t*)P.obs_dev[half];
+        a0_frames_arg f{cur, nullptr, (long long)a->obs_bytes, 0};
+        A0_CHECK(a0_net_encoder_fwd_fused(L->C, L->H, L->W, V.wt, &w, &f, E, nullptr, nullptr, a->act3, stream));
+        float* qm = a->qmax_all + (long long)t * E;
+        if (quant) {
+            const int rows = E * nt;
+            const float* on = V.flat;
+            if (fqf) {
+                A0_CHECK(a0_dense_fwd(a->act3, L->feat, on + L->frac.w(), on + L->frac.b(), a->f_logits, E, 32, L->feat, 0, a->fwd_scratch, stream));
+                A0_CHECK(a0_fqf_taus_cos(a->f_logits, 32, a->f_tau_all, a->q_taus, a->q_cosx, 64, E, nt, stream));
+            } else {
+                A0_CHECK(a0_tau_cos_features(a->rng.seed, 3 /* STREAM_TAUS */, a->rng.reserve(3, rows), nullptr, 0, a->q_taus, a->q_cosx, rows, 64, stream));
+            }
+            A0_CHECK(a0_dense_fwd_mul(a->q_cosx, 64, on + L->cos.w(), on + L->cos.b(), a->act3, nt, a->q_x, rows, L->feat, 64, 1, stream));
+            A0_CHECK(a0_dense_fwd(a->q_x, L->feat, V.Wf(), V.bf(), a->h, rows, 512, L->feat, 1, a->fwd_scratch, stream));
+            const int ns = a0_dense_fwd_partial_slabs(rows, L->Npad, 512);
+            A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), rows, L->Npad, 512, a->head_slabs, stream));
+            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
+            A0_CHECK(a0_actor_quantile_tail(a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, fqf ? a->f_tau_all : nullptr,
+                                            E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr, a->action, qm, stream));
+        } else if (dist) {
+            A0_CHECK(a0_dense_fwd(a->act3, L->feat, V.Wf(), V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
+            const int ns = a0_dense_fwd_partial_slabs(E, L->Npad, 512);
+            A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), E, L->Npad, 512, a->head_slabs, stream));
+            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
+            A0_CHECK(a0_actor_dist_tail(a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, L->d.algo == A0_ALGO_C51 ? 2 : 1,
+                                        L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr,
+                                        a->action, qm, stream));
+        } else {
+            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
+            A0_CHECK(a0_actor_qhead(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0, a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U,
+                                    oa, ou, epsilon, nullptr, nullptr, a->action, qm, stream));
+        }
+        A0_CHECK(a0_env_pool_send(a->action, (int*)P.act_dev, E, (long long*)P.ctl_dev, P.step_word | (seq & P.seq_mask), stream));
+        A0_CHECK(a0_pool_wait(P, seq));
+        int whole = 0;
+        A0_CHECK(a0_env_pool_upload((const uint8_t*)P.new_host[half], (uint8_t*)P.new_dev, (const float*)P.scal_host[half], (float*)P.scal_dev[half], 7, 6,
+                                    (const uint8_t*)P.obs_host[half], nullptr, nxt, E, P.nstack, P.frame_bytes, &whole, stream));
+        a->pool_whole += whole;
+        A0_CHECK(a0_host_step_ingest(cur, (const uint8_t*)P.new_dev, (const float*)P.scal_dev[half], nxt, E, P.nstack, P.frame_bytes, P.use_life_loss, a->action, a->n, a->n,
+                                     a->steps, a->d.discount, a->ring_act, a->ring_rew, a->ring_done, a->ring_obs, R->frames, R->size, (start + (long long)t * E) % R->size,
+                                     R->act, R->rew, R->done, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, nullptr, stream));
+        P.seq = seq;
+        a->steps += 1;
+    }
+    return a0_mean_rows(a->qmax_all, a->T, E, a->qs, stream);
 }
 
 extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float epsilon, void* stream) {
@@ -449,6 +573,7 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
     // starts with its features in place; the convolution weights do not change inside a rollout, the last step has no next one
     // (not for an actor with its own network — the launch schedule: its rollout runs beside the update block, the critical path there, and a workgroup that holds a CU's
     // LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives: 9.43 -> 9.75 ms)
+    if (a->pool_on) return a0_actor_rollout_pool(a, L, R, epsilon, V, w, start, stream);
     const bool step_enc = !a->own_flat;
     bool feat_ready = false;
     for (int t = 0; t < a->T; ++t) {

@@ -12,7 +12,7 @@ Scope = what the handles cover (include/agent0_hip.h): all six learners (scalar 
 device-resident env's stream / block / chase tasks, uniform, sum-tree or (round 6) the reference-faithful flat-priority replay, one GPU or — round 6, the default — data
 parallelism over RCCL (the learner handle issues the two all-reduces itself: ``a0_learner_set_exchange``), the ``main`` AND the ``launch`` schedule — there the actor
 handle owns a copy of the network (a0_actor_bind(.., 1) / a0_actor_snapshot) and rolls out into the Trainer's stage ring on the actor stream while the update block runs
-(``run_iteration_lp``).  What stays on the Python classes: host environments (the worker pool is Python) and any Trainer whose hot-loop methods a test harness has wrapped.  Same launches, same order, same arguments: a run is BIT-identical either way (tests/test_gpu_trainer.py::test_native_loop_equals_the_python_classes).
+(``run_iteration_lp``).  A single HostEnvPool with worker processes is stepped by the actor handle itself (a0_actor_attach_pool: inference, send, the wait for the workers, the DMA and one ingest launch per step).  What stays on the Python classes: grouped host environments, in-process or whole-stack pools, and any Trainer whose hot-loop methods a test harness has wrapped (``pool_reason`` / ``eligible`` name the rest).  Same launches, same order, same arguments: a run is BIT-identical either way (tests/test_gpu_trainer.py::test_native_loop_equals_the_python_classes).
 """
 from __future__ import annotations
 
@@ -36,6 +36,41 @@ class _RbufDesc(C.Structure):
 class _ActorDesc(C.Structure):
     _fields_ = [("E", C.c_int), ("T", C.c_int), ("A", C.c_int), ("dueling", C.c_int), ("n_step", C.c_int), ("discount", C.c_double), ("seed", C.c_ulonglong), ("rank", C.c_uint),
                 ("env_task", C.c_int), ("reset_noise_freq", C.c_int)]
+
+
+class _PoolDesc(C.Structure):
+    """a0_env_pool_desc (include/agent0_hip.h): a HostEnvPool the actor handle steps itself."""
+    _fields_ = [("E", C.c_int), ("nstack", C.c_int), ("W", C.c_int), ("use_life_loss", C.c_int), ("frame_bytes", C.c_longlong),
+                ("new_host", C.c_void_p * 2), ("scal_host", C.c_void_p * 2), ("obs_host", C.c_void_p * 2), ("act_dev", C.c_void_p), ("ctl_dev", C.c_void_p),
+                ("done_host", C.c_void_p), ("obs_dev", C.c_void_p * 2), ("scal_dev", C.c_void_p * 2), ("new_dev", C.c_void_p), ("step_word", C.c_longlong),
+                ("seq_mask", C.c_longlong), ("seq", C.c_longlong), ("timeout_s", C.c_double)]
+
+
+def pool_desc(pool, timeout_s: float = 120.0) -> _PoolDesc:
+    """The descriptor of a HostEnvPool's shared block and device buffers (worker processes, library calls: env_pool.HostEnvPool)."""
+    from agent0_amd.common.host_envs import CMD_SHIFT, CMD_STEP, CTL_DONE0, SEQ_MASK
+    p = pool._p
+    two = lambda xs: (C.c_void_p * 2)(*xs)
+    return _PoolDesc(pool.E, pool.nstack, pool.W, int(bool(pool.has_life_loss)), pool.frame_bytes, two(p["new_h"]), two(p["scal_h"]), two(p["obs_h"]),
+                     p["act_dev"], p["ctl_dev"], pool._ctl_h[CTL_DONE0:].data_ptr(), two(p["obs_d"]), two(p["scal_d"]), p["new_d"], CMD_STEP << CMD_SHIFT, SEQ_MASK,
+                     pool.seq, float(timeout_s))
+
+
+def pool_reason(tr, envs) -> Optional[str]:
+    """None when the actor handle can step this HostEnvPool itself, else why not."""
+    if envs.W < 1:
+        return "host environments stepped in-process (0 workers)"
+    if not envs.newest_frame:
+        return "host environments in whole-stack mode"
+    if not envs.library_calls:
+        return "A0_ENV_POOL_CALLS=0"
+    if not envs.inline_upload:
+        return "host environments uploading on the pool's copy stream"
+    if tr.use_lp:
+        return "the launch schedule with host environments"
+    if tr.learner.engine.grad_hook is not None:
+        return "a gradient hook (data parallelism) with host environments"
+    return None
 
 
 class _LearnerBuffers(C.Structure):
@@ -67,19 +102,28 @@ def hook_ok(hook) -> bool:
 def eligible(tr) -> Optional[str]:
     """None when the Trainer's configuration is one the handles cover, else the reason it is not."""
     from agent0_amd.common.atari_wrappers import DeviceSynthVecEnv
+    from agent0_amd.common.env_pool import HostEnvGroups, HostEnvPool
     cfg = tr.cfg
     lc = cfg.learner
     if os.environ.get("A0_NATIVE_LOOP", "1") == "0":
         return "A0_NATIVE_LOOP=0"
     actor = tr.actors[1]
-    if not isinstance(actor.envs, DeviceSynthVecEnv) or actor.groups is not None:
+    if isinstance(actor.envs, HostEnvGroups) or actor.groups is not None:
+        return "host environment groups (actor.env_groups >= 2)"
+    if isinstance(actor.envs, HostEnvPool):
+        why = pool_reason(tr, actor.envs)
+        if why is not None:
+            return why
+    elif not isinstance(actor.envs, DeviceSynthVecEnv):
         return "host environments"
     algo = lc.algo.name
     if algo == "dqn":
         if cfg.action_dim + (1 if lc.dueling_head else 0) > 24:
             return "dqn handle: A + dueling <= 24"
     elif algo in ("iqn", "fqf"):
-        if cfg.action_dim + (1 if lc.dueling_head else 0) > 32 or not getattr(tr.actors[1], "quant_tail", False):
+        # the merged quantile tail (device env) or, on a host pool, the quantile tail without the env step (Actor.quant_slabs)
+        tail = getattr(actor, "quant_slabs", False) if isinstance(actor.envs, HostEnvPool) else getattr(actor, "quant_tail", False)
+        if cfg.action_dim + (1 if lc.dueling_head else 0) > 32 or not tail:
             return "quantile handles: A + dueling <= 32, the merged quantile tail"
     elif algo == "qr":
         if not getattr(tr.actors[1], "dist_tail", False):
@@ -160,6 +204,14 @@ class NativeLoop:
         # out into the Trainer's stage ring on the Trainer's actor stream
         self.lp = bool(tr.use_lp)
         ok(lib.a0_actor_bind(self.actor, self.learner, int(self.lp)), "a0_actor_bind")
+        # a HostEnvPool (one pool, worker processes): the handle steps it — the actions go out, the handle waits for the workers, the step comes in by DMA and one
+        # ingest launch; the pool's sequence number and current half are handed back after every rollout (_sync_pool)
+        from agent0_amd.common.env_pool import HostEnvPool
+        self.pool = actor.envs if isinstance(actor.envs, HostEnvPool) else None
+        if self.pool is not None:
+            self._pool_desc = pool_desc(self.pool)
+            ok(lib.a0_actor_attach_pool(self.actor, C.addressof(self._pool_desc)), "a0_actor_attach_pool")
+            self._pool_whole = 0
         self.stage = None
         if self.lp:
             sg = tr.stage
@@ -181,7 +233,23 @@ class NativeLoop:
     # ------------------------------------------------------------------ pieces of one iteration
     def _rollout(self, st):
         tr, lib = self.tr, self.lib
+        pool = self.pool
+        if pool is not None:                              # the pool may have been reset or stepped by the host since (HostEnvPool.reset / step)
+            self.ok(lib.a0_actor_pool_seq(self.actor, None, None, C.c_longlong(pool.seq)), "a0_actor_pool_seq")
         self.ok(lib.a0_actor_rollout(self.actor, self.learner, self.rbuf, C.c_float(tr.epsilon_fn(tr.frame_count)), st), "a0_actor_rollout")
+        if pool is not None:
+            self._sync_pool()
+
+    def _sync_pool(self):
+        """HostEnvPool and the Python Actor follow the handle: sequence number, step count, uploads, the current observation buffer."""
+        pool, actor = self.pool, self.tr.actors[1]
+        seq, whole = C.c_longlong(), C.c_longlong()
+        self.ok(self.lib.a0_actor_pool_seq(self.actor, C.byref(seq), C.byref(whole), C.c_longlong(-1)), "a0_actor_pool_seq")
+        pool.g += seq.value - pool.seq
+        pool.seq = seq.value
+        pool.full_uploads += whole.value - self._pool_whole
+        self._pool_whole = whole.value
+        actor.obs = pool._obs[pool.seq & 1]
 
     def _commit(self, st):
         tr, rp = self.tr, self.tr.replay

@@ -461,7 +461,7 @@ class Trainer:
                     self.logger.info("host loop: Python classes (%s)", self.native_loop_reason)
                 return None
             if self.primary:
-                self.logger.info("host loop: library handles over this Trainer's buffers (agent0_amd/deepq/native_loop.py); A0_NATIVE_LOOP=0 keeps the Python classes in charge")
+                self.logger.info("host loop: library handles over this Trainer's buffers, device env or one host-env pool (agent0_amd/deepq/native_loop.py); A0_NATIVE_LOOP=0 keeps the Python classes in charge")
         elif not ok_now:
             raise RuntimeError("Trainer: a gradient hook or a method wrapper was installed after the native loop had taken over the run")
         return nl

@@ -834,6 +834,20 @@ class HipOps:
                                           _req(advance, torch.float32, E, "advance"), _req(out, torch.uint8, E * nstack * frame_bytes, "out"), E, nstack,
                                           frame_bytes, _stream()), "a0_env_frame_stack")
 
+    def host_step_ingest(self, prev, newest, scal, out, E, nstack, frame_bytes, use_life_loss, action, n, ring_len, steps, gamma, ring_act, ring_rew, ring_done,
+                         ring_obs, frames, cap, start_slot, r_act, r_rew, r_done, stat_mask, stat_ret, ctrl=None):
+        """The ingest half of a host-env step in one launch (a0_host_step_ingest): frame stack, n-step window, replay row, observation ring, statistics."""
+        ob = nstack * frame_bytes
+        check(self.lib.a0_host_step_ingest(_req(prev, torch.uint8, E * ob, "prev"), _req(newest, torch.uint8, E * frame_bytes, "newest"),
+                                           _req(scal, torch.float32, 7 * E, "scal"), _req(out, torch.uint8, E * ob, "out"), E, nstack, frame_bytes, int(bool(use_life_loss)),
+                                           _req(action, torch.int32, E, "action"), n, ring_len, steps, gamma, _req(ring_act, torch.int32, n * E, "ring_act"),
+                                           _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
+                                           _req(ring_obs, torch.uint8, ring_len * E * ob, "ring_obs", optional=n == 1), _req(frames, torch.uint8, cap * 2 * ob, "frames"),
+                                           cap, start_slot, _req(r_act, torch.int32, cap, "r_act"), _req(r_rew, torch.float32, cap, "r_rew"),
+                                           _req(r_done, torch.float32, cap, "r_done"), _req(stat_mask, torch.float32, E, "stat_mask"),
+                                           _req(stat_ret, torch.float32, E, "stat_ret"), _req(ctrl, torch.int64, 8, "ctrl", optional=True), _stream()),
+              "a0_host_step_ingest")
+
     def rng_uniform(self, seed, stream_id, offset, out, n):
         check(self.lib.a0_rng_uniform(seed, stream_id, offset, _req(out, torch.float32, n, "out"), n, _stream()), "a0_rng_uniform")
 

@@ -502,6 +502,38 @@ int a0_actor_snapshot(a0_actor* actor, const a0_learner* learner, void* stream);
  * network's noise every reset_noise_freq steps from ITS Philox stream 4 and recomposes the effective weights, agent.py:52-53) */
 int a0_actor_rollout(a0_actor* actor, a0_learner* learner, a0_rbuf* replay, float epsilon, void* stream);
 int a0_actor_collect(a0_actor* actor, float* qs_host, float* returns_host, int max_returns, int* n_returns, void* stream);
+/* Host environments stepped by worker processes (agent0_amd/common/env_pool.py HostEnvPool): while a pool is attached, a0_actor_rollout steps IT instead of the
+ * device env.  Per step t: encoder, fc1 + head + the head's tail (a0_actor_qhead / a0_actor_dist_tail / a0_actor_quantile_tail, the full batch's split counts),
+ * a0_env_pool_send of the actions and the step word, a host-side wait for every worker's done word, the DMA-only a0_env_pool_upload, then a0_host_step_ingest
+ * (frame stack, n-step window, replay row, statistics).  The rows, parameters and statistics equal those of Actor._rollout_host.
+ *
+ * The shared page-locked block (host_envs.block_layout; one half per step parity h = seq & 1):
+ *   obs_host[h]   [E][nstack * frame_bytes] u8  whole stacks, read for the envs whose advance scalar is 0
+ *   scal_host[h]  [7][E] f32                    reward, terminated, truncated, life_loss, final mask, final return, advance (1: the stack moved on by one frame)
+ *   new_host[h]   [E][frame_bytes] u8           the newest frame of every env
+ *   actions       [E] i32                       written by the device through act_dev before the step word
+ *   control       i64 words: [0] the step word (step_word | (seq & seq_mask): host_envs.ctl_word(CMD_STEP, seq)), written through ctl_dev; [1] a reset's
+ *                 argument; [2 + w] the last sequence number worker w has completed (done_host points at [2]); a worker that dies stores -1 there.
+ * A worker polls word [0] for seq + 1, steps its envs with the actions, writes its envs' rows of half (seq + 1) & 1, then stores seq + 1 into its done word.
+ * obs_dev[2] is the device observation double buffer: the observation of sequence number s lives in obs_dev[s & 1].  `seq` is the pool's current sequence
+ * number at attach time; a0_actor_pool_seq reads it back after a rollout and sets it after the host has stepped or reset the pool itself.  The wait gives up
+ * with an error when a done word is negative or after timeout_s seconds; after 2 ms it sleeps between polls. */
+typedef struct a0_env_pool_desc {
+    int E, nstack, W, use_life_loss;                   /* envs, frames per stack, worker processes (>= 1), 0: ignore the life_loss row */
+    long long frame_bytes;                             /* bytes per frame (a multiple of 16) */
+    void* new_host[2]; void* scal_host[2]; void* obs_host[2];      /* page-locked host halves (host addresses) */
+    void* act_dev; void* ctl_dev;                      /* device addresses of the action slot and of control word 0 (a0_host_device_pointer) */
+    long long* done_host;                              /* host address of the W done words */
+    void* obs_dev[2]; void* scal_dev[2]; void* new_dev;   /* device buffers: observations, scalars per half, newest frames */
+    long long step_word, seq_mask;                     /* CMD_STEP << CMD_SHIFT, (1 << CMD_SHIFT) - 1 */
+    long long seq;                                     /* the pool's sequence number now */
+    double timeout_s;                                  /* give up waiting for the workers after this long */
+} a0_env_pool_desc;
+int a0_actor_attach_pool(a0_actor* actor, const a0_env_pool_desc* desc);
+int a0_actor_detach_pool(a0_actor* actor);
+/* *seq_out (optional) := the attached pool's sequence number, *whole_out (optional) := stacks uploaded whole since attach; then, set_seq >= 0: the sequence
+ * number := set_seq (the host stepped or reset the pool itself) */
+int a0_actor_pool_seq(a0_actor* actor, long long* seq_out, long long* whole_out, long long set_seq);
 /* a0_actor_collect (the rs / qs of Actor.sample, agent.py:85-90) in two halves, so that the next rollout can be enqueued before the host waits: _begin enqueues the copies of the statistics into page-locked
  * buffers of the handle and records an event (call it BEFORE the next a0_actor_rollout, which reuses the device buffers); _end waits for that event only */
 int a0_actor_collect_begin(a0_actor* actor, void* stream);
@@ -665,6 +697,22 @@ int a0_env_pool_upload(const uint8_t* new_host, uint8_t* new_dev, const float* s
                        const uint8_t* obs_host, const uint8_t* prev, uint8_t* out, int E, int nstack, long long frame_bytes, int* n_whole,
                        void* stream);
 int a0_env_pool_send(const int* action, int* act_host_dev, int E, long long* ctl_host_dev, long long word, void* stream);
+/* a0_env_pool_upload with prev = NULL is its DMA-only form: the newest frames, the scalars and the whole stacks (into `out`) are copied, and the frame stack
+ * is left to a0_host_step_ingest.  (prev, not out, marks it: out stays the destination of the whole stacks.)
+ * a0_host_step_ingest: the ingest half of a host-env step in ONE launch, after the DMA-only upload of the step — what a0_env_frame_stack + a0_actor_nstep +
+ *   a0_replay_insert + the two statistics copies leave, bit for bit:
+ *   - out[e] = prev[e][1:] || newest[e] where scal[6][e] != 0 (rows with advance 0 were uploaded whole into out and are only read);
+ *   - the n-step window of a0_actor_nstep (reward, terminal, truncated, life_loss = scal rows 0 - 3; life_loss ignored when use_life_loss == 0);
+ *   - n > 1: ring_obs[steps % ring_len][e] = prev[e] (ring_obs: [ring_len][E][nstack * frame_bytes] u8, ring_len >= n);
+ *   - the replay row at slot (start_slot + e) % cap: st = prev[e] (n = 1) or ring_obs[oldest][e], oldest = (steps - min(steps + 1, n) + 1) % ring_len
+ *     (n > 1), st_next = out[e]; r_act / r_rew / r_done[slot] = the emitted n-step transition;
+ *   - stat_mask[e] = scal[4][e], stat_ret[e] = scal[5][e] (pass the step's rows of the rollout's statistics).
+ *   scal: [7][E] f32 in env_pool's N_SCAL order (reward, terminated, truncated, life_loss, final mask, final return, advance); frames: [cap][2][obs] u8;
+ *   cap >= E.  ctrl adds its ACTOR_STEPS word to steps and its REPLAY_SLOT word to start_slot. */
+int a0_host_step_ingest(const uint8_t* prev, const uint8_t* newest, const float* scal, uint8_t* out, int E, int nstack, long long frame_bytes,
+                        int use_life_loss, const int* action, int n, int ring_len, long long steps, double gamma, int* ring_act, float* ring_rew,
+                        float* ring_done, uint8_t* ring_obs, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew,
+                        float* r_done, float* stat_mask, float* stat_ret, const long long* ctrl, void* stream);
 
 /* ---------------------------------------------------------------- device RNG + synthetic env (no reference counterpart) */
 int a0_rng_u32(unsigned long long seed, unsigned int stream_id, unsigned long long offset, unsigned int* out, long long n, void* stream);
