@@ -3,6 +3,12 @@
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
     python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed to DIR/*.npy: see dump_outputs)
+    python bench.py ... --full                           (after the timed steps, also the measurements that take runs of their own: see below)
+
+A plain run sets up, fills the replay, warms up, times the K steps, dumps if asked and prints the line.  ``--full`` adds, after the clock has
+stopped: the kernel probe behind ``roofline``, ``replay_sample_GBps``, ``at_reference_update_ratio`` (learner_steps = 320), ``other_entry`` (the other
+schedule on a second trainer) and ``cpu_baseline`` (the CPU oracle); in a plain run these fields are null.  ``--no-cpu-baseline``, ``--no-ratio320``,
+``--no-other-entry`` and ``A0_PROBE`` leave parts of a ``--full`` run out.
 
 One "step" is one Trainer iteration exactly as the reference times it (agent0/deepq/trainer.py:176-181):
 ``sample_steps`` (80) vectorized env steps on ``num_envs`` (256) envs — Q-network forward, epsilon-greedy, env step,
@@ -36,9 +42,12 @@ def parse():
     ap.add_argument("--learner-steps", type=int, default=20)
     ap.add_argument("--sample-steps", type=int, default=80)
     ap.add_argument("--env", default="Breakout")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ratio320", action="store_true", help="skip the extra learner_steps=320 measurement")
-    ap.add_argument("--no-other-entry", action="store_true", help="skip the extra measurement of the other entry point's schedule")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline probe, replay sample GB/s, the learner_steps=320 ratio, the other entry point's schedule "
+                         "and the CPU baseline (a plain run reports them as null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ratio320", action="store_true", help="with --full: skip the extra learner_steps=320 measurement")
+    ap.add_argument("--no-other-entry", action="store_true", help="with --full: skip the extra measurement of the other entry point's schedule")
     ap.add_argument("--entry", choices=("main", "launch"), default="main",
                     help="main: agent0.deepq.main schedule (rollout, then update block, strictly alternating); launch: agent0.deepq.launch schedule "
                          "(next rollout with a weight snapshot on a second stream while the update block runs)")
@@ -508,10 +517,11 @@ def main():
     # ---- roofline of the dominant kernel: the same iterations once more per candidate kernel family with the hipGraphs switched off, every launch of
     # the family carrying a HIP event pair on its stream (events cannot be read out of a replayed graph; single-kernel families take the dispatch's own begin / end
     # timestamps through hipExtLaunchKernelGGL — what rocprofv3's kernel trace reports).  The family with the largest share of the iteration is THE roofline kernel; the
-    # others are listed beside it.  Not part of `value`.
+    # others are listed beside it.  Not part of `value`.  This and the four measurements below (replay GB/s, learner_steps = 320, other entry point, CPU baseline)
+    # run only with --full.
     probes = []
     pick = os.environ.get("A0_PROBE", "auto")
-    families = [] if pick == "none" else list(PROBE_FAMILIES) if pick == "auto" else [pick]
+    families = [] if pick == "none" or not args.full else list(PROBE_FAMILIES) if pick == "auto" else [pick]
     if families:           # every rank repeats the iterations (they contain the gradient all-reduce); rank 0 records
         tr.learner.use_graph = False
         tr.actors[1].use_graph = False
@@ -532,7 +542,7 @@ def main():
     # ---- metric 2 of BASELINE.json: replay sample GB/s = B * 56 448 B / t(sample + gather); the update itself never gathers
     # (conv1 reads ring rows through the slot index), so the gather kernel is timed on its own here
     replay_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         rp = tr.replay
         out_rows = torch.empty(rp.B * rp.row_bytes, dtype=torch.uint8, device="cuda")
         for _ in range(3):
@@ -546,7 +556,7 @@ def main():
         replay_gbps = rp.B * rp.row_bytes * n_rep / (e0.elapsed_time(e1) * 1e-3) / 1e9
     # ---- the same metric at the reference's update:data ratio for 256 envs (learner_steps = 320 instead of 20)
     ratio320 = None
-    if not dp and not args.no_ratio320:
+    if args.full and not dp and not args.no_ratio320:
         tr.learner.use_graph = True
         tr.actors[1].use_graph = True
         if args.entry == "launch":
@@ -565,7 +575,7 @@ def main():
                     "updates_per_sec": round(320 / d1, 1)}
     # ---- the other entry point's schedule on the same workload (second trainer, own full replay), so that one bench line carries both
     other = None
-    if not dp and not args.no_other_entry:
+    if args.full and not dp and not args.no_other_entry:
         import copy
         cfg2 = copy.deepcopy(cfg)
         cfg2.trainer.training_start_steps = 1 << 62
@@ -587,7 +597,7 @@ def main():
     # the CPU baseline is a property of the box, not of the rank count: rank 0 times it at every N, while the other ranks wait in the barrier below (so that every rank
     # leaves the process group together)
     cpu_base = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(args, cfg)
         if world > 1:
             cpu_base["note"] = f"timed on rank 0's share of the host cores while the other {world - 1} ranks wait in a barrier; compare with the N = 1 line's"
@@ -629,11 +639,11 @@ def main():
                                  else "Python classes + hipGraphs"),
                    "gradient_exchange": exchange},
         "per_rank_ms_per_step": per_rank, "gradient_exchange": exchange, "rccl": rccl,
-        "device": arch, "replay_fill_s": round(t_fill, 2),
+        "device": arch, "replay_fill_s": round(t_fill, 2), "full": args.full,
         "at_reference_update_ratio": ratio320, "other_entry": other,
         "replay_sample_GBps": None if replay_gbps is None else round(replay_gbps, 1), "last_loss": None if last is None or last.get("loss") is None else float(last["loss"]),
     }
-    out["roofline"] = roofline_object(probes, cfg, args, tr.ops.x9_products(), dt / args.steps)
+    out["roofline"] = roofline_object(probes, cfg, args, tr.ops.x9_products(), dt / args.steps) if args.full else None
     out["cpu_baseline"] = cpu_base
     if dumped is not None:
         out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}

@@ -198,6 +198,22 @@ def test_bench_starts_its_own_launcher_as_a_child(monkeypatch, capsys):
     assert [m for m in ("agent0_amd.ops", "agent0_amd.deepq.trainer") if m in sys.modules] == gpu_stack, "the parent did not load the GPU stack"
 
 
+def test_bench_extra_measurements_need_full(monkeypatch):
+    """A plain bench run measures the headline figure only; the probe, replay GB/s, learner_steps=320, other entry point and CPU baseline
+    run behind ``--full``, and the ``--no-*`` switches still leave parts of a ``--full`` run out."""
+    import sys
+
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu_baseline is True and a.no_ratio320 is False and a.no_other_entry is False
+
+
 def test_no_kernel_of_the_library_uses_scratch_memory():
     """build.sh records the compiler's per-kernel resource remarks (agent0_amd/lib/kernel_resources.txt).  A kernel that spills registers
     to scratch still computes the right thing — only slower, with HBM traffic nobody asked for (round 2: ten spilled VGPRs of the fused

@@ -535,6 +535,7 @@ def test_data_parallel_path_with_one_rank_rccl_group_matches_plain_run(tmp_path)
     plain, dp = outs
     assert "rehearsal" in dp["config"]["workload"] and "inactive" in plain["config"]["workload"]
     assert dp["value"] > 0 and plain["value"] > 0
+    assert plain["full"] is False and plain["roofline"] is None and plain["cpu_baseline"] is None and plain["replay_sample_GBps"] is None      # no --full: headline only
     assert dp["last_loss"] == plain["last_loss"], (dp["last_loss"], plain["last_loss"])
     # the exchange goes through the C-ABI (a0_dp_allreduce over RCCL) and is part of the update's single hipGraph
     assert dp["config"]["gradient_exchange"].startswith("RcclGradAllReduce") and "captured" in dp["config"]["gradient_exchange"], dp["config"]["gradient_exchange"]

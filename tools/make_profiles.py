@@ -1,11 +1,12 @@
 """Builds the tracked evidence under profiles/ from the scratch output of tools/refresh_profiles.sh + tools/bench_configs.sh
-(gpurun_out/<round>/): bench lines, rocprofv3 kernel statistics, per-grid durations of the fused kernels, PMC traffic, the other
+(the round's output folder, or $OUT when set, as for tools/refresh_profiles.sh): bench lines, rocprofv3 kernel statistics, per-grid durations of the fused kernels, PMC traffic, the other
 BASELINE configurations, and the summary table.   usage: python tools/make_profiles.py [round_tag]"""
 import csv, json, os, shutil, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
 SRC = os.path.join(ROOT, "gpurun_out", tag)
+SRC = os.environ.get("OUT", SRC)
 DST = os.path.join(ROOT, "profiles")
 
 
@@ -50,7 +51,7 @@ for name, rd, wr, what in (("gather", 512 * 2 * OBS, 512 * 2 * OBS, "a0_sample_g
 traffic = {
     "kernels": "a0_encoder_fused_kernel<7,3,2,84,true[,true]> (enc: one observation per workgroup for the actor's 256, looping for the learner's 512), a0_encoder_dgrad_fused_x9_kernel (dgrad); "
                "a0_env_step_commit_kernel as the calibration kernel",
-    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, --kernel-trace only) -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline "
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes, --kernel-trace only) -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "
               "--no-ratio320 --no-other-entry --replay-size 100000 (tools/refresh_profiles.sh)",
     "corrections": "counter unit KB; FETCH_SIZE x2 on gfx950 (64 B counted per 128-B request on wide coalesced reads), WRITE_SIZE x1.  Calibrated IN THIS RUN on the kernels of "
                    "known traffic listed under `calibration` (" + "; ".join(f"{k}: read x{v['read_correction_implied']}, write x{v['write_correction_implied']}" for k, v in calib.items()) + ")"
@@ -97,7 +98,7 @@ json.dump(other, open(os.path.join(DST, f"{tag}_other_configs.json"), "w"), inde
 
 # ---- BASELINE configs[2..4] with their own kernel tables and roofline (tools/prof_configs.sh)
 cfg_lines = [f"# BASELINE configs[2..4] (+ qr, mdqn) at full size ({tag}, MI355X gfx950, 1 GPU): bench line with the roofline of that configuration's dominant kernel + rocprofv3 kernel statistics", "",
-             "`R=" + tag + " bash tools/prof_configs.sh`: per configuration `python3 bench.py --no-cpu-baseline --no-ratio320 --no-other-entry --steps 4 --warmup 2 --algo ...` once plain (the JSON line) "
+             "`R=" + tag + " bash tools/prof_configs.sh`: per configuration `python3 bench.py --full --no-cpu-baseline --no-ratio320 --no-other-entry --steps 4 --warmup 2 --algo ...` once on its own (the JSON line) "
              "and once under `rocprofv3 --kernel-trace --stats` (the table; it covers the untimed replay fill, warm-up, the timed and the probe iterations).", ""]
 for short, title in (("c51", "configs[2] Breakout c51 double-Q + dueling + NoisyNet, n_step = 3, prioritized sum-tree replay"), ("iqn", "configs[3] Asterix iqn (iqr)"),
                      ("fqf", "configs[4] Asterix fqf, one rank"), ("qr", "Breakout qr (quantile regression, 200 quantiles: named in north_star)"), ("mdqn", "Breakout mdqn (Munchausen dqn)")):
@@ -145,9 +146,9 @@ if os.path.exists(os.path.join(ROOT, "gpurun_out", f"{tag}_learning.json")):
 rows = list(csv.DictReader(open(os.path.join(SRC, "kernel_stats.csv"))))
 tot_ns = sum(float(r["TotalDurationNs"]) for r in rows)
 tot_calls = sum(int(r["Calls"]) for r in rows)
-lines = [f"# rocprofv3 --kernel-trace --stats  --  python3 bench.py --no-cpu-baseline --no-ratio320 --no-other-entry   ({tag}, MI355X gfx950, 1 GPU)", "",
+lines = [f"# rocprofv3 --kernel-trace --stats  --  python3 bench.py --full --no-cpu-baseline --no-ratio320 --no-other-entry   ({tag}, MI355X gfx950, 1 GPU)", "",
          "Commands (on the GPU box, `tools/refresh_profiles.sh`; this file is generated from their output by `tools/make_profiles.py`): `cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && "
-         "rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/<round>/prof -- python3 bench.py --no-cpu-baseline --no-ratio320 --no-other-entry`;",
+         "rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --full --no-cpu-baseline --no-ratio320 --no-other-entry`;",
          "HBM traffic from two further runs, `rocprofv3 --pmc FETCH_SIZE --kernel-trace ...` and `rocprofv3 --pmc WRITE_SIZE --kernel-trace ...` (counters never combined with other trace domains).",
          "The run covers the untimed replay fill (49 actor-only iterations), 2 warm-up, 8 timed iterations of BASELINE configs[1] and the 8 probe iterations (hipGraph replay off).",
          f"Files: `{tag}_bench_dqn_kernel_stats.csv` (full table), `{tag}_bench_dqn.json` (bench line of the un-profiled default run), `{tag}_bench_dqn_launch_entry.json` (`--entry launch`), "

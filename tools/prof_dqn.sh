@@ -1,7 +1,7 @@
 # headline configuration (BASELINE configs[1]): bench line + rocprofv3 kernel table of the same command -> gpurun_out/$R/dqn_{bench.json,kernel_stats.csv}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT; R=${R:-r04}
 mkdir -p gpurun_out/$R
-ARGS="--no-cpu-baseline --no-ratio320 --steps ${STEPS:-10} --warmup 3"
+ARGS="--full --no-cpu-baseline --no-ratio320 --steps ${STEPS:-10} --warmup 3"
 python3 bench.py $ARGS > gpurun_out/$R/dqn_bench.json 2> gpurun_out/$R/dqn_bench.err || exit 1
 python3 -c "
 import json; d=json.loads(open('gpurun_out/$R/dqn_bench.json').read().strip().splitlines()[-1]); r=d['roofline']
