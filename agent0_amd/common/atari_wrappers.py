@@ -120,6 +120,19 @@ class DeviceSynthVecEnv:
         self._cur = nxt
         return self._obs[nxt]
 
+    def state_dict(self) -> dict:
+        """Everything the next ``step`` reads that earlier steps wrote (resumable snapshots): the step counter, the observation buffers and which is current, the
+        running episode returns, and the seed / rank the env's Philox draws are keyed by."""
+        return {"g": int(self.g), "cur": int(self._cur), "seed": int(self.seed), "rank": int(self.rank), "obs": torch.stack(self._obs).cpu(), "ep_ret": self.ep_ret.cpu()}
+
+    def load_state_dict(self, sd: dict):
+        if len(sd["obs"]) != len(self._obs) or sd["obs"][0].numel() != self._obs[0].numel():
+            raise ValueError(f"env state: {len(sd['obs'])} observation buffers of {sd['obs'][0].numel()} bytes, this env keeps {len(self._obs)} of {self._obs[0].numel()}")
+        self.g, self._cur, self.seed, self.rank = int(sd["g"]), int(sd["cur"]), int(sd["seed"]), int(sd["rank"])
+        for dst, src in zip(self._obs, sd["obs"]):
+            dst.copy_(torch.as_tensor(src).reshape(-1))
+        self.ep_ret.copy_(torch.as_tensor(sd["ep_ret"]))
+
     def close(self):
         pass
 

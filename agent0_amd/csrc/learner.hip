@@ -20,6 +20,20 @@ extern "C" int a0_learner_set_rng(a0_learner* L, int stream_id, unsigned long lo
     return A0_OK;
 }
 
+// the learner's Philox state for resumable runs: words[0] = seed, words[1 .. 8] = the running offsets of streams 0 .. 7; set != 0 writes it into the handle
+extern "C" int a0_learner_rng_state(a0_learner* L, unsigned long long* words, int set) {
+    if (!L || !words) return a0_fail(A0_EINVAL, "a0_learner_rng_state: null argument");
+    if (set) {
+        for (int i = 0; i < 8; ++i) if (words[1 + i] & 3) return a0_fail(A0_EINVAL, "a0_learner_rng_state: offsets are multiples of four");
+        L->rng.seed = words[0];
+        for (int i = 0; i < 8; ++i) L->rng.off[i] = words[1 + i];
+    } else {
+        words[0] = L->rng.seed;
+        for (int i = 0; i < 8; ++i) words[1 + i] = L->rng.off[i];
+    }
+    return A0_OK;
+}
+
 extern "C" int a0_learner_create_on(const a0_learner_desc* d, const a0_learner_buffers* bufs, a0_learner** out) {
     A0_TRY
     if (!d || !out) return a0_fail(A0_EINVAL, "a0_learner_create: null argument");

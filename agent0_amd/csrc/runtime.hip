@@ -730,3 +730,110 @@ extern "C" int a0_actor_collect_end(a0_actor* a, float* qs_host, float* returns_
     return A0_OK;
     A0_CATCH
 }
+
+// ================================================================================================ handle state for resumable runs (Trainer.save_snapshot / load_snapshot)
+// What the handles own and no caller-visible buffer holds, as versioned flat blobs of 8-byte words (host memory) followed, for the actor, by copies of its device
+// arrays.  The layouts are part of the ABI (include/agent0_hip.h): agent0_amd/deepq/snapshot.py reads and writes them too, so that a snapshot written under the handles
+// loads under the Python classes and the other way round.  The seeds travel as state: a run resumed in a process configured with another seed continues the SAVED run.
+namespace {
+constexpr long long RBUF_MAGIC = 0x3153425230413041LL, ACTOR_MAGIC = 0x3154434130413041LL;      // "A0A0RBS1" / "A0A0ACT1" read as little-endian words
+constexpr int RBUF_WORDS = 32, ACTOR_WORDS = 32;
+inline long long dbits(double x) { long long w; __builtin_memcpy(&w, &x, 8); return w; }
+inline double bitsd(long long w) { double x; __builtin_memcpy(&x, &w, 8); return x; }
+long long actor_state_bytes(const a0_actor* a) {
+    const long long E = a->E, T = a->T, n = a->n;
+    return ACTOR_WORDS * 8 + (long long)a->K * E * a->obs_bytes + E * 4 + 3 * n * E * 4 + T * 4 + 2 * T * E * 4;
+}
+}  // namespace
+
+extern "C" long long a0_rbuf_state_size(const a0_rbuf* R) { return R ? RBUF_WORDS * 8 : 0; }
+
+extern "C" int a0_rbuf_state_save(a0_rbuf* R, void* blob, long long cap, void* stream) {
+    A0_TRY
+    if (!R || !blob || cap < RBUF_WORDS * 8) return a0_fail(A0_EINVAL, "a0_rbuf_state_save: a host buffer of a0_rbuf_state_size bytes");
+    hipStream_t st = (hipStream_t)stream;
+    if (R->tree && R->top_stale) { A0_CHECK(a0_sumtree_top_rebuild(R->tree, R->cap2, stream)); R->top_stale = false; }      // the caller saves the tree from its own buffer: every level up to date
+    float max_p = 0.f;
+    A0_HIP_THROW(hipMemcpyAsync(&max_p, R->pstate, 4, hipMemcpyDeviceToHost, st));
+    A0_HIP_THROW(hipStreamSynchronize(st));
+    long long* w = (long long*)blob;
+    for (int i = 0; i < RBUF_WORDS; ++i) w[i] = 0;
+    w[0] = RBUF_MAGIC; w[1] = 1; w[2] = R->size; w[3] = R->obs_bytes; w[4] = R->B; w[5] = R->d.prioritize; w[6] = R->top; w[7] = R->written;
+    w[8] = R->ep.open ? 1 : 0; w[9] = R->ep.top; w[10] = R->ep.nb; w[11] = R->ep.pos; w[12] = (long long)R->ep.seed;
+    for (int i = 0; i < 8; ++i) w[13 + i] = (long long)R->rng.off[i];
+    w[21] = dbits(R->beta_use); w[22] = dbits(R->sched_cur); w[23] = dbits((double)max_p); w[24] = (long long)R->rng.seed;
+    w[25] = dbits(R->d.alpha); w[26] = dbits(R->d.eps); w[27] = dbits(R->d.beta0); w[28] = R->d.total_steps;
+    return A0_OK;
+    A0_CATCH
+}
+
+extern "C" int a0_rbuf_state_load(a0_rbuf* R, const void* blob, long long bytes, void* stream) {
+    A0_TRY
+    if (!R || !blob || bytes < RBUF_WORDS * 8) return a0_fail(A0_EINVAL, "a0_rbuf_state_load: a blob of a0_rbuf_state_size bytes");
+    const long long* w = (const long long*)blob;
+    if (w[0] != RBUF_MAGIC || w[1] != 1) return a0_fail(A0_EINVAL, "a0_rbuf_state_load: not a replay state blob of version 1");
+    if (w[2] != R->size || w[3] != R->obs_bytes || w[4] != R->B || w[5] != R->d.prioritize)
+        return a0_fail(A0_EINVAL, "a0_rbuf_state_load: the blob was saved by a ring of another description (size, obs_bytes, B or prioritize differ)");
+    if (R->prio && (w[25] != dbits(R->d.alpha) || w[26] != dbits(R->d.eps) || w[27] != dbits(R->d.beta0) || w[28] != R->d.total_steps))
+        return a0_fail(A0_EINVAL, "a0_rbuf_state_load: the blob was saved by a ring of another description (alpha, eps, beta0 or total_steps differ)");
+    if (w[6] < 0 || w[6] > R->size || w[7] < w[6]) return a0_fail(A0_EINVAL, "a0_rbuf_state_load: counters out of range");
+    R->top = w[6]; R->written = w[7];
+    R->ep.open = w[8] != 0; R->ep.top = w[9]; R->ep.nb = w[10]; R->ep.pos = w[11]; R->ep.seed = (unsigned)w[12];
+    for (int i = 0; i < 8; ++i) R->rng.off[i] = (unsigned long long)w[13 + i];
+    R->beta_use = bitsd(w[21]); R->sched_cur = bitsd(w[22]); R->rng.seed = (unsigned long long)w[24];
+    R->top_stale = false;
+    const float max_p = (float)bitsd(w[23]);
+    A0_HIP_THROW(hipMemcpyAsync(R->pstate, &max_p, 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+    A0_HIP_THROW(hipStreamSynchronize((hipStream_t)stream));
+    return A0_OK;
+    A0_CATCH
+}
+
+extern "C" long long a0_actor_state_size(const a0_actor* a) { return a ? actor_state_bytes(a) : 0; }
+
+// words: 0 magic, 1 version, 2 E, 3 T, 4 A, 5 dueling, 6 n_step, 7 env_task, 8 reset_noise_freq, 9 discount (double bits), 10 K, 11 cur, 12 g, 13 steps, 14 Philox seed,
+// 15..22 Philox offsets, 23 env seed, 24 rank; then obs [K][E][obs_bytes] u8 | ep_ret [E] | ring_act [n][E] i32 | ring_rew | ring_done | qs [T] | stat_mask [T][E] | stat_ret
+static int actor_state_copy(a0_actor* a, uint8_t* p, bool save, hipStream_t st) {
+    const long long E = a->E, T = a->T, n = a->n;
+    auto cp = [&](void* dev, long long bytes) {
+        if (save) A0_HIP_THROW(hipMemcpyAsync(p, dev, (size_t)bytes, hipMemcpyDeviceToHost, st));
+        else A0_HIP_THROW(hipMemcpyAsync(dev, p, (size_t)bytes, hipMemcpyHostToDevice, st));
+        p += bytes;
+    };
+    for (int k = 0; k < a->K; ++k) cp(a->obs[k], E * a->obs_bytes);
+    cp(a->ep_ret, E * 4); cp(a->ring_act, n * E * 4); cp(a->ring_rew, n * E * 4); cp(a->ring_done, n * E * 4);
+    cp(a->qs, T * 4); cp(a->stat_mask, T * E * 4); cp(a->stat_ret, T * E * 4);
+    A0_HIP_THROW(hipStreamSynchronize(st));
+    return A0_OK;
+}
+
+extern "C" int a0_actor_state_save(a0_actor* a, void* blob, long long cap, void* stream) {
+    A0_TRY
+    if (!a || !blob || cap < actor_state_bytes(a)) return a0_fail(A0_EINVAL, "a0_actor_state_save: a host buffer of a0_actor_state_size bytes");
+    if (a->pool_on) return a0_fail(A0_ESTATE, "a0_actor_state_save: the environments of an attached host pool live in worker processes and cannot be saved");
+    long long* w = (long long*)blob;
+    for (int i = 0; i < ACTOR_WORDS; ++i) w[i] = 0;
+    w[0] = ACTOR_MAGIC; w[1] = 1; w[2] = a->E; w[3] = a->T; w[4] = a->d.A; w[5] = a->d.dueling ? 1 : 0; w[6] = a->n; w[7] = a->d.env_task; w[8] = a->d.reset_noise_freq;
+    w[9] = dbits(a->d.discount); w[10] = a->K; w[11] = a->cur; w[12] = (long long)a->g; w[13] = a->steps; w[14] = (long long)a->rng.seed;
+    for (int i = 0; i < 8; ++i) w[15 + i] = (long long)a->rng.off[i];
+    w[23] = (long long)a->d.seed; w[24] = (long long)a->d.rank;
+    return actor_state_copy(a, (uint8_t*)blob + ACTOR_WORDS * 8, true, (hipStream_t)stream);
+    A0_CATCH
+}
+
+extern "C" int a0_actor_state_load(a0_actor* a, const void* blob, long long bytes, void* stream) {
+    A0_TRY
+    if (!a || !blob || bytes < ACTOR_WORDS * 8) return a0_fail(A0_EINVAL, "a0_actor_state_load: null argument or a blob shorter than its header");
+    const long long* w = (const long long*)blob;
+    if (w[0] != ACTOR_MAGIC || w[1] != 1) return a0_fail(A0_EINVAL, "a0_actor_state_load: not an actor state blob of version 1");
+    if (w[2] != a->E || w[3] != a->T || w[4] != a->d.A || w[5] != (a->d.dueling ? 1 : 0) || w[6] != a->n || w[7] != a->d.env_task || w[8] != a->d.reset_noise_freq ||
+        w[9] != dbits(a->d.discount) || w[10] != a->K)
+        return a0_fail(A0_EINVAL, "a0_actor_state_load: the blob was saved by an actor of another description (E, T, A, dueling, n_step, env_task, reset_noise_freq or discount differ)");
+    if (bytes < actor_state_bytes(a) || w[11] < 0 || w[11] >= a->K || w[13] < 0) return a0_fail(A0_EINVAL, "a0_actor_state_load: truncated or damaged blob");
+    if (a->pool_on) return a0_fail(A0_ESTATE, "a0_actor_state_load: an actor with an attached host pool starts from reset environments");
+    a->cur = (int)w[11]; a->g = (unsigned)w[12]; a->steps = w[13]; a->rng.seed = (unsigned long long)w[14];
+    for (int i = 0; i < 8; ++i) a->rng.off[i] = (unsigned long long)w[15 + i];
+    a->d.seed = (unsigned long long)w[23]; a->d.rank = (unsigned)w[24];
+    return actor_state_copy(a, (uint8_t*)blob + ACTOR_WORDS * 8, false, (hipStream_t)stream);
+    A0_CATCH
+}

@@ -556,6 +556,51 @@ class Actor:
         ev.synchronize()
         return ret.numpy()[mask.numpy() != 0].tolist(), qs.tolist()
 
+    # ------------------------------------------------------------------ resumable snapshots (deepq/snapshot.py)
+    def _state_desc(self) -> dict:
+        cfg = self.cfg
+        return {"E": self.E, "T": int(cfg.actor.sample_steps), "A": int(self.L.A), "dueling": int(bool(self.L.dueling)), "n_step": self.n,
+                "env_task": int(getattr(self.envs, "task", 0)), "reset_noise_freq": int(cfg.learner.reset_noise_freq), "discount": float(cfg.learner.discount),
+                "K": len(getattr(self.envs, "_obs", ()))}
+
+    def state_dict(self) -> dict:
+        """What the next rollout reads that earlier rollouts wrote, in the fields of the actor handle's state blob (a0_actor_state_save): step counter, Philox seed and
+        offsets, the device env's state, the n-step windows and the last rollout's statistics.  Device-resident env only: the emulators of a host env live in worker
+        processes and cannot be saved — a resumed run resets them and starts with empty n-step windows."""
+        if not hasattr(self.envs, "state_dict"):
+            raise RuntimeError("Actor.state_dict: host environments cannot be saved")
+        env, T = self.envs.state_dict(), int(self.cfg.actor.sample_steps)
+        d = self._state_desc()
+        d.update(cur=env["cur"], g=env["g"], steps=int(self.steps), rng_seed=int(self.rng.seed), rng_off=[int(self.rng.offsets.get(i, 0)) for i in range(8)],
+                 env_seed=env["seed"], rank=env["rank"], obs=env["obs"].numpy(), ep_ret=env["ep_ret"].numpy(), ring_act=self.ring_act.cpu().numpy(),
+                 ring_rew=self.ring_rew.cpu().numpy(), ring_done=self.ring_done.cpu().numpy(), qs=self.qs[:T].cpu().numpy(),
+                 stat_mask=self.stat_mask[:T * self.E].cpu().numpy(), stat_ret=self.stat_ret[:T * self.E].cpu().numpy())
+        return d
+
+    def load_state_dict(self, d: dict):
+        from .snapshot import check_actor_desc
+        check_actor_desc(d, self._state_desc())
+        E, T, K = self.E, int(self.cfg.actor.sample_steps), d["K"]
+        self.envs.load_state_dict({"g": d["g"], "cur": d["cur"], "seed": d["env_seed"], "rank": d["rank"], "obs": torch.from_numpy(np.asarray(d["obs"])).reshape(K, -1),
+                                   "ep_ret": torch.from_numpy(np.asarray(d["ep_ret"]))})
+        self.obs = self.envs.obs
+        self.steps = int(d["steps"])
+        self.rng.seed = int(d["rng_seed"])
+        self.rng.offsets = {i: int(o) for i, o in enumerate(d["rng_off"]) if o}
+        dev = self.ops.device
+        for name in ("ring_act", "ring_rew", "ring_done"):
+            getattr(self, name).copy_(torch.from_numpy(np.asarray(d[name])).to(dev))
+        self.qs[:T].copy_(torch.from_numpy(np.asarray(d["qs"])).to(dev))
+        self.stat_mask[:T * E].copy_(torch.from_numpy(np.asarray(d["stat_mask"])).to(dev))
+        self.stat_ret[:T * E].copy_(torch.from_numpy(np.asarray(d["stat_ret"])).to(dev))
+        self._graph, self._graph_warm = None, 0          # a captured rollout holds the counters it was captured at
+
+    def pending_from(self, start: int):
+        """The handle of a rollout that had been issued ahead when the snapshot was taken and whose rows and statistics the loaded state holds."""
+        ev = torch.cuda.Event()
+        ev.record()
+        return (int(self.cfg.actor.sample_steps), True, False, None, int(start), [], ev)
+
     def close(self):
         self.envs.close()
 

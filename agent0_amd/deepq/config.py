@@ -128,6 +128,7 @@ class TrainerConfig:
     log_freq: int = 10
     test_freq: int = 500
     test_episodes: int = 20
+    snapshot_freq: int = 0                 # iterations between resumable snapshots into <logdir>/snapshot (Trainer.save_snapshot); 0 = off
 
 
 @dataclass

@@ -397,6 +397,60 @@ class NativeLoop:
             self.ok(self.lib.a0_actor_collect(self.actor, self._qs, self._rs, self.T * self.E, C.addressof(self._nret), self.tr.actor_stream.cuda_stream), "a0_actor_collect")
             self._lp_pending = None
 
+    # ------------------------------------------------------------------ resumable snapshots (Trainer.save_snapshot / load_snapshot; deepq/snapshot.py)
+    def wait_pending(self):
+        """A rollout issued ahead (``run_iteration(prefetch=True)``, or the launch schedule's rollout in flight) is waited for and STAYS pending: its rows and
+        statistics travel with the snapshot and the resumed run consumes it as this one would have.  -> the ``pending`` record of the snapshot."""
+        if self.lp:
+            if self._lp_pending is not None:
+                self.tr.actor_stream.synchronize()
+                return {"kind": "launch", "start": int(self._lp_pending)}
+            return None
+        torch.cuda.synchronize()
+        return {"kind": "main", "start": int(self.lib.a0_rbuf_write_cursor(self.rbuf))} if self._pending_rollout else None
+
+    def state(self) -> dict:
+        """What the handles own (module docstring): the actor's and the sampler's state blobs and the learner's Philox state, as uint8 / int64 CPU tensors."""
+        lib, ok = self.lib, self.ok
+        st = torch.cuda.current_stream().cuda_stream
+        out = {}
+        if self.pool is None:
+            n = int(lib.a0_actor_state_size(self.actor))
+            blob = np.empty(n, dtype=np.uint8)
+            ok(lib.a0_actor_state_save(self.actor, blob.ctypes.data, n, st), "a0_actor_state_save")
+            out["actor"] = torch.from_numpy(blob)
+        n = int(lib.a0_rbuf_state_size(self.rbuf))
+        blob = np.empty(n, dtype=np.uint8)
+        ok(lib.a0_rbuf_state_save(self.rbuf, blob.ctypes.data, n, st), "a0_rbuf_state_save")
+        out["replay"] = torch.from_numpy(blob)
+        if self.prio and not self.flat:
+            self.tr.replay._top_stale = False              # a0_rbuf_state_save brought the tree's top levels up to date
+        words = (C.c_ulonglong * 9)()
+        ok(lib.a0_learner_rng_state(self.learner, words, 0), "a0_learner_rng_state")
+        out["learner_rng"] = [int(x) for x in words]
+        return out
+
+    def load_state(self, state: dict, pending):
+        """The inverse, into handles just created over the restored buffers."""
+        from . import snapshot as snap
+        lib, ok, tr = self.lib, self.ok, self.tr
+        st = torch.cuda.current_stream().cuda_stream
+        if self.pool is None and state.get("actor") is not None:
+            blob = np.ascontiguousarray(state["actor"].numpy())
+            ok(lib.a0_actor_state_load(self.actor, blob.ctypes.data, blob.size, st), "a0_actor_state_load")
+        blob = np.ascontiguousarray(state["replay"].numpy())
+        ok(lib.a0_rbuf_state_load(self.rbuf, blob.ctypes.data, blob.size, st), "a0_rbuf_state_load")
+        words = (C.c_ulonglong * 9)(*[int(x) for x in state["learner_rng"]])
+        ok(lib.a0_learner_rng_state(self.learner, words, 1), "a0_learner_rng_state")
+        if self.lp:
+            sg, rc, cfg = tr.stage, tr.cfg.replay, tr.cfg
+            sb = snap.replay_blob(int(sg.size), int(sg.obs_bytes), min(self.B, int(sg.size)), 0, min(int(sg.written), int(sg.size)), int(sg.written), None,
+                                  (int(cfg.seed) + 7) & 0xFFFFFFFF, [0] * 8, 0.0, 0.0, 0.0, float(rc.alpha), float(rc.eps), float(rc.beta0), int(cfg.trainer.total_steps))
+            ok(lib.a0_rbuf_state_load(self.stage, sb.ctypes.data, sb.size, st), "a0_rbuf_state_load (stage)")
+            self._lp_pending = int(pending["start"]) if pending else None
+        else:
+            self._pending_rollout = bool(pending)
+
     def detach_exchange(self):
         """The handle stops exchanging gradients (before the communicator's owner destroys it)."""
         if self.learner:

@@ -212,6 +212,36 @@ class ReplayDataset:
                 self.ops.priority_tail(self.priority, self.size, min(n, self.size), self._pstate, float(self.cfg.replay.alpha))
             self.beta = self.beta_schedule(n)
 
+    # ------------------------------------------------------------------ resumable snapshots (deepq/snapshot.py)
+    def _state_desc(self) -> dict:
+        return {"size": self.size, "obs_bytes": self.obs_bytes, "B": self.B, "prioritize": (1 if self.use_sumtree else 2) if self.prioritize else 0}
+
+    def state_dict(self) -> dict:
+        """The sampler's state in the fields of the replay handle's state blob (a0_rbuf_state_save): counters, the open epoch, Philox seed and offsets, the importance
+        exponent in use and the schedule's position, max_p.  The ring's buffers (frames, act / rew / done, priorities or sum-tree) are saved by the caller."""
+        rc = self.cfg.replay
+        _ = self.tree if self.use_sumtree else None          # every level of the tree up to date before the caller copies it
+        d = self._state_desc()
+        d.update(top=int(self.top), written=int(self.written), epoch=None if self._epoch is None else dict(self._epoch), rng_seed=int(self.rng.seed),
+                 rng_off=[int(self.rng.offsets.get(i, 0)) for i in range(8)], beta_use=float(self.beta) if self.prioritize else 0.0,
+                 sched_cur=float(self.beta_schedule.current) if self.prioritize else 0.0, max_p=self.max_p, alpha=float(rc.alpha), eps=float(rc.eps), beta0=float(rc.beta0),
+                 total_steps=int(self.cfg.trainer.total_steps))
+        return d
+
+    def load_state_dict(self, d: dict):
+        mine = self._state_desc()
+        diff = [k for k in mine if d[k] != mine[k]]
+        if diff:
+            raise ValueError("replay state was saved by a ring of another description; differing keys: " + ", ".join(f"{k} (saved {d[k]!r}, here {mine[k]!r})" for k in diff))
+        self.top, self.written = int(d["top"]), int(d["written"])
+        self._epoch = None if d["epoch"] is None else dict(d["epoch"])
+        self.rng.seed = int(d["rng_seed"])
+        self.rng.offsets = {i: int(o) for i, o in enumerate(d["rng_off"]) if o}
+        if self.prioritize:
+            self.beta, self.beta_schedule.current = float(d["beta_use"]), float(d["sched_cur"])
+        self._pstate.fill_(float(d["max_p"]))
+        self._top_stale = False
+
     # ------------------------------------------------------------------ host-side item access (API parity, slow path)
     def __getitem__(self, idx: int):
         idx = idx % self.top

@@ -152,6 +152,161 @@ class Trainer:
             self._updates_done = None
             self.learner.updates_issued = int(eng.state[6])      # the device's count of loss-ring entries travels with the state block
 
+    # ------------------------------------------------------------------ resumable snapshots: the run CONTINUES (deepq/snapshot.py, csrc/snapshot.hip)
+    def _snapshot_geometry(self):
+        from . import snapshot as snap
+        env = "device" if hasattr(self.actors[1].envs, "state_dict") else "host"
+        return snap.geometry(to_dict(self.cfg), "launch" if self.use_lp else "main", env)
+
+    def _snapshot_dir(self, path: str) -> str:
+        return os.path.join(path, f"rank{self.rank}") if int(os.environ.get("WORLD_SIZE", "1")) > 1 else path
+
+    def save_snapshot(self, path: str) -> str:
+        """Everything a fresh process needs to continue THIS run: ``path/checkpoint.pth`` (``save_checkpoint``), ``path/state.pth`` (sampler, actor and learner
+        state, the ring's metadata and priorities, the statistics windows) and ``path/frames.bin`` (the ring's frames, deduplicated by a0_snapshot_pack on their way
+        out: each chunk of at most 4 096 rows goes through one device buffer and one page-locked host buffer, so host memory does not grow with ``replay.size``).
+        A rollout issued ahead is waited for and saved as pending — the resumed run consumes it as this one would have.  Written to ``path.tmp`` and renamed, so a job
+        killed mid-write leaves the previous snapshot intact.
+
+        The continuation is bit-identical for the device-resident env.  HOST environments (emulator processes) cannot be saved: the snapshot restores learner,
+        replay and sampler; the envs are reset, the actor's n-step windows start empty and a rollout in flight is booked first.  Data parallel: every rank writes
+        ``path/rank<k>/``, no collective is added (untested beyond one rank, like everything multi-GPU here)."""
+        from . import snapshot as snap
+        path = self._snapshot_dir(path)
+        nl = getattr(self, "_nl", None) or None
+        actor, rp, eng = self.actors[1], self.replay, self.learner.engine
+        device_env = hasattr(actor.envs, "state_dict")
+        # ---- what is in flight
+        if not device_env:
+            self._book_in_flight()
+            pending = None
+        elif nl is not None:
+            pending = nl.wait_pending()
+        elif self.use_lp:
+            pending = None
+            if self._pending is not None:
+                self._pending[6].synchronize()
+                pending = {"kind": "launch", "start": int(self._pending[4])}
+        else:
+            pf = getattr(self, "_prefetched", None)
+            pending = None if pf is None else {"kind": "main", "start": int(pf[4])}
+        torch.cuda.synchronize()
+        # ---- handle / class state
+        if nl is not None:
+            st = nl.state()
+        else:
+            st = {"replay": torch.from_numpy(snap.replay_blob(**rp.state_dict())), "learner_rng": [int(self.learner.rng.seed)] + [int(self.learner.rng.offsets.get(i, 0)) for i in range(8)]}
+            if device_env:
+                st["actor"] = torch.from_numpy(snap.actor_blob(actor.state_dict()))
+        cpu = lambda t: None if t is None else t.detach().cpu().clone()
+        st.update(pending=pending, frame_count=int(self.frame_count), updates_issued=int(self.learner.updates_issued),
+                  windows={"Ls": list(self.Ls), "Rs": list(self.Rs), "RTs": list(self.RTs), "Qs": list(self.Qs), "FLs": list(self.FLs)},
+                  act=cpu(rp.act), rew=cpu(rp.rew), done=cpu(rp.done), max_p=cpu(rp._pstate), priority=cpu(rp.priority) if rp.prioritize and not rp.use_sumtree else None,
+                  tree=cpu(rp.tree) if rp.use_sumtree else None,
+                  net={"online": cpu(eng.online.flat), "target": cpu(eng.target.flat), "eff_online": cpu(eng.online.eff), "eff_target": cpu(eng.target.eff),
+                       "noise": cpu(eng.noise_joint) if eng.noise_joint is not None else ([cpu(eng.online.noise_buf), cpu(eng.target.noise_buf)] if eng.L.noisy else None),
+                       "scalars": cpu(eng.scalars), "loss_ring": cpu(eng.loss_ring)})
+        if self.use_lp:
+            sg = self.stage
+            st["stage"] = {"written": int(sg.written), "act": cpu(sg.act), "rew": cpu(sg.rew), "done": cpu(sg.done)}
+        # ---- files
+        tmp = snap.begin_write(path)
+        self.save_checkpoint(os.path.join(tmp, "checkpoint.pth"))
+        n_pending = self.num_transitions if (pending and pending["kind"] == "main") else 0       # rows of a rollout issued ahead lie at the write cursor, not yet committed
+        plan = snap.chunk_plan(rp.size, min(rp.top + n_pending, rp.size), rp.written + n_pending)
+        ff = snap.FrameFile(self.ops, rp.obs_bytes // 4, max((c["rows"] for c in plan), default=1))
+        with open(os.path.join(tmp, "frames.bin"), "wb") as f:
+            chunks = ff.write(f, rp.frames, plan, int(self.cfg.actor.num_envs), "replay")
+            if self.use_lp:
+                sg = self.stage
+                chunks += ff.write(f, sg.frames, snap.chunk_plan(sg.size, min(sg.written, sg.size), sg.written, ff.max_rows), int(self.cfg.actor.num_envs), "stage")
+            f.flush()
+            os.fsync(f.fileno())
+        st["meta"] = snap.make_meta(to_dict(self.cfg), self._snapshot_geometry(), chunks, rp.obs_bytes // 4,
+                                    {"seed": int(self.cfg.seed), "packed_bytes": int(sum(c["bytes"] for c in chunks)), "ring_bytes": int(sum(c["rows"] for c in chunks)) * rp.row_bytes})
+        torch.save(st, os.path.join(tmp, "state.pth"))
+        snap.commit_write(path)
+        return path
+
+    def _book_in_flight(self):
+        """A rollout issued ahead and never consumed is booked into the replay, a launch-schedule rollout in flight is waited for and dropped (what ``final`` does)."""
+        if self.use_lp and self._pending is not None:
+            self.actors[1].sample_finish(self._pending)
+            self._pending = None
+        if getattr(self, "_nl", None):
+            self._nl.drain_lp() if self.use_lp else self._nl.drain()
+        if getattr(self, "_prefetched", None) is not None:
+            pending, self._prefetched = self._prefetched, None
+            transitions, returns, qmax = self.actors[1].sample_finish(pending)
+            self.replay.extend(transitions)
+            self.frame_count += self.num_transitions
+            self.Qs.extend(qmax)
+            self.Rs.extend(returns)
+
+    def load_snapshot(self, path: str):
+        """The inverse of ``save_snapshot``, into a freshly constructed Trainer of the same configuration (refused, with the differing keys named, when ring
+        geometry, algo, ``num_envs``, ``n_step_q``, replay policy, schedule or env kind differ).  The seed is part of the state: a Trainer built with another seed
+        continues the SAVED run.  The first iteration after it hands the loop to the library's handles as a new run would — over the restored buffers, with the
+        restored state — or keeps it on the Python classes; a snapshot written under one loads under the other."""
+        from . import snapshot as snap
+        if self.frame_count != 0 or self.replay.written != 0 or getattr(self, "_nl", None):
+            raise RuntimeError("load_snapshot needs a freshly constructed Trainer")
+        path = snap.resolve_dir(self._snapshot_dir(path))
+        st = torch.load(os.path.join(path, "state.pth"), map_location="cpu", weights_only=True)
+        meta = st["meta"]
+        snap.check_meta(meta)
+        snap.check_geometry(meta["geometry"], self._snapshot_geometry(), f"snapshot {path}")
+        actor, rp, eng, ln = self.actors[1], self.replay, self.learner.engine, self.learner
+        dev = self.ops.device
+        self.cfg.seed = int(meta["seed"])
+        self.load_checkpoint(os.path.join(path, "checkpoint.pth"))
+        net = st["net"]
+        eng.online.flat.copy_(net["online"]); eng.target.flat.copy_(net["target"])
+        eng.online.refresh_wt(); eng.target.refresh_wt()
+        if net["eff_online"] is not None:
+            eng.online.eff.copy_(net["eff_online"]); eng.target.eff.copy_(net["eff_target"])
+        if net["noise"] is not None:
+            if eng.noise_joint is not None:
+                eng.noise_joint.copy_(net["noise"])
+            else:
+                eng.online.noise_buf.copy_(net["noise"][0]); eng.target.noise_buf.copy_(net["noise"][1])
+        eng.scalars.copy_(net["scalars"]); eng.loss_ring.copy_(net["loss_ring"])
+        ln.rng.seed = int(st["learner_rng"][0])
+        ln.rng.offsets = {i: int(o) for i, o in enumerate(st["learner_rng"][1:]) if o}
+        ln.updates_issued = int(st["updates_issued"])
+        # ---- replay: metadata, priorities, sampler state, frames
+        rp.act.copy_(st["act"]); rp.rew.copy_(st["rew"]); rp.done.copy_(st["done"])
+        if st["priority"] is not None:
+            rp.priority.copy_(st["priority"])
+        if st["tree"] is not None:
+            rp._tree.copy_(st["tree"])
+        rp.load_state_dict(snap.parse_replay_blob(st["replay"].numpy()))
+        rp._pstate.copy_(st["max_p"])
+        if self.use_lp:
+            sg = self.stage
+            sg.written = int(st["stage"]["written"])
+            sg.act.copy_(st["stage"]["act"]); sg.rew.copy_(st["stage"]["rew"]); sg.done.copy_(st["stage"]["done"])
+        ff = snap.FrameFile(self.ops, int(meta["frame_bytes"]), max((c["rows"] for c in meta["chunks"]), default=1))
+        with open(os.path.join(path, "frames.bin"), "rb") as f:
+            ff.read(f, rp.frames, [c for c in meta["chunks"] if c["buf"] == "replay"])
+            if self.use_lp:
+                ff.read(f, self.stage.frames, [c for c in meta["chunks"] if c["buf"] == "stage"])
+        # ---- actor (device env), statistics, what was in flight
+        pending = st.get("pending")
+        if st.get("actor") is not None and hasattr(actor.envs, "state_dict"):
+            actor.load_state_dict(snap.parse_actor_blob(st["actor"].numpy(), rp.obs_bytes))
+            if pending and pending["kind"] == "main":
+                self._prefetched = actor.pending_from(pending["start"])
+            elif pending and self.use_lp:
+                self._pending = actor.pending_from(pending["start"])
+        w = st["windows"]
+        self.Ls, self.Rs, self.RTs, self.Qs, self.FLs = list(w["Ls"]), list(w["Rs"]), list(w["RTs"]), list(w["Qs"]), list(w["FLs"])
+        self.frame_count = int(st["frame_count"])
+        self._updates_done = None
+        self._resume = {"actor": st.get("actor"), "replay": st["replay"], "learner_rng": st["learner_rng"], "pending": pending}
+        torch.cuda.synchronize()
+        return path
+
     # ------------------------------------------------------------------ trainer.py:74-119
     def step(self, transitions, returns, qmax):
         self.Qs.extend(qmax)
@@ -448,12 +603,20 @@ class Trainer:
         ok_now = native_loop.hook_ok(self.learner.engine.grad_hook) and not any(native_loop._wrapped(o) for o in (self, self.replay, self.learner, self.actors[1]))
         if nl is None:
             why = native_loop.eligible(self)
-            if why is not None or not ok_now or getattr(self, "_prefetched", None) is not None or self.replay.written != 0 or self.actors[1].steps != 0 or getattr(self, "_pending", None) is not None:
+            resume = getattr(self, "_resume", None)        # a loaded snapshot is the second legitimate starting point: the handles take over its state
+            under_way = resume is None and (getattr(self, "_prefetched", None) is not None or self.replay.written != 0 or self.actors[1].steps != 0 or getattr(self, "_pending", None) is not None)
+            self._resume = None
+            if why is not None or not ok_now or under_way:
                 self._nl = False
                 self.native_loop_reason = why or "hot-loop methods wrapped, a gradient hook, or a run already under way"
                 return None
             try:
                 nl = self._nl = native_loop.NativeLoop(self)
+                if resume is not None:
+                    nl.load_state(resume, resume["pending"])
+                    self._prefetched = None                # the handles hold what was in flight
+                    if self.use_lp:
+                        self._pending = None
             except RuntimeError as e:            # a create call refused the configuration: NativeLoop has destroyed what it had created; the Python classes run the loop
                 self._nl = False
                 self.native_loop_reason = f"handle creation failed: {e}"
@@ -515,14 +678,20 @@ class Trainer:
         if cfg.mode.name in ("finetune", "play"):
             if not cfg.checkpoint:
                 raise ValueError(f"mode={cfg.mode.name} needs checkpoint=<path>")
-            self.load_checkpoint(cfg.checkpoint, weights_only=(cfg.mode.name == "play"))
+            if cfg.mode.name == "finetune" and os.path.isdir(cfg.checkpoint):
+                self.load_snapshot(cfg.checkpoint)           # a snapshot directory: the run continues (replay, sampler, actor and all)
+            else:
+                self.load_checkpoint(cfg.checkpoint, weights_only=(cfg.mode.name == "play"))
         if cfg.mode.name == "play":
             return self.final(save=False)
         remaining = max(cfg.trainer.total_steps - self.frame_count, 0)
         trainer_steps = remaining // self.num_transitions + 1
         ahead = os.environ.get("A0_PREFETCH_ROLLOUT", "1") != "0"
+        snap_freq = int(cfg.trainer.snapshot_freq)
         for i in range(trainer_steps):
             self.logging(self.run_iteration(prefetch=ahead and i + 1 < trainer_steps))
+            if snap_freq > 0 and (i + 1) % snap_freq == 0 and i + 1 < trainer_steps:
+                self.save_snapshot(os.path.join(cfg.logdir, "snapshot"))
         self.final()
 
     def final(self, save: bool = True):
@@ -538,6 +707,11 @@ class Trainer:
             self.frame_count += self.num_transitions
             self.Qs.extend(qmax)
             self.Rs.extend(returns)
+        if save and int(self.cfg.trainer.snapshot_freq) > 0:
+            try:
+                self.save_snapshot(os.path.join(self.cfg.logdir, "snapshot"))
+            except OSError:
+                pass
         try:
             if self.primary:
                 self.test()

@@ -799,6 +799,27 @@ class HipOps:
     def sumtree_top_rebuild(self, tree, cap2):
         check(self.lib.a0_sumtree_top_rebuild(_req(tree, torch.float32, 2 * cap2, "tree"), cap2, _stream()), "a0_sumtree_top_rebuild")
 
+    # ------------------------------------------------------------------ replay snapshots (csrc/snapshot.hip)
+    def snapshot_pack_bound(self, rows, frames_per_row, frame_bytes) -> int:
+        n = int(self.lib.a0_snapshot_pack_bound(rows, frames_per_row, frame_bytes))
+        if n < 0:
+            check(-1, "a0_snapshot_pack_bound")
+        return n
+
+    def snapshot_literal_offset(self, rows, frames_per_row) -> int:
+        return int(self.lib.a0_snapshot_literal_offset(rows, frames_per_row))
+
+    def snapshot_pack(self, rows_u8, n_rows, frames_per_row, frame_bytes, stride, packed, work):
+        """``rows_u8``: n_rows consecutive ring rows; ``packed``: uint8 [snapshot_pack_bound]; ``work``: int32 [n_rows * frames_per_row] (used as u32)."""
+        check(self.lib.a0_snapshot_pack(_req(rows_u8, torch.uint8, n_rows * frames_per_row * frame_bytes, "rows"), n_rows, frames_per_row, frame_bytes, stride,
+                                        _req(packed, torch.uint8, self.snapshot_pack_bound(n_rows, frames_per_row, frame_bytes), "packed"),
+                                        _req(work, torch.int32, n_rows * frames_per_row, "work"), _stream()), "a0_snapshot_pack")
+
+    def snapshot_unpack(self, packed, n_rows, frames_per_row, frame_bytes, rows_out, bad_flag=None):
+        check(self.lib.a0_snapshot_unpack(_req(packed, torch.uint8, self.snapshot_literal_offset(n_rows, frames_per_row), "packed"), n_rows, frames_per_row, frame_bytes,
+                                          _req(rows_out, torch.uint8, n_rows * frames_per_row * frame_bytes, "rows_out"), _req(bad_flag, torch.int32, 1, "bad_flag", optional=True),
+                                          _stream()), "a0_snapshot_unpack")
+
     def sumtree_set_from_loss(self, tree, cap2, idx, loss, n, eps, alpha, pstate, state=None, defer_top=False):
         check(self.lib.a0_sumtree_set_from_loss(_req(tree, torch.float32, 2 * cap2, "tree"), cap2, _req(idx, torch.int64, n, "idx"), _req(loss, torch.float32, n, "loss"), n,
                                                 float(eps), float(alpha), _req(pstate, torch.float32, 1, "pstate"), _req(state, torch.int32, 8, "state", optional=True),

@@ -409,6 +409,8 @@ typedef struct a0_learner_buffers {
 int a0_learner_create_on(const a0_learner_desc* desc, const a0_learner_buffers* buffers, a0_learner** out);
 /* the next draw offset of one of the learner's Philox streams (3 = the quantile fractions of agent.py:300-310, 4 = NoisyNet's reset_noise of agent.py:125-127) */
 int a0_learner_set_rng(a0_learner* learner, int stream_id, unsigned long long offset);
+/* the handle's Philox state, for resumable runs: words[0] = seed, words[1 .. 8] = the running offsets of streams 0 .. 7; set != 0 writes them into the handle, 0 reads them */
+int a0_learner_rng_state(a0_learner* learner, unsigned long long* words, int set);
 int a0_learner_destroy(a0_learner* learner);
 long long a0_learner_param_floats(const a0_learner* learner);
 /* Data parallelism through the handle (one process per GPU, the reference itself has no multi-GPU learner — launch.py:30-61's actor processes
@@ -538,6 +540,36 @@ int a0_actor_pool_seq(a0_actor* actor, long long* seq_out, long long* whole_out,
  * buffers of the handle and records an event (call it BEFORE the next a0_actor_rollout, which reuses the device buffers); _end waits for that event only */
 int a0_actor_collect_begin(a0_actor* actor, void* stream);
 int a0_actor_collect_end(a0_actor* actor, float* qs_host, float* returns_host, int max_returns, int* n_returns);
+
+/* ---------------------------------------------------------------- resumable runs (Trainer.save_snapshot / load_snapshot; csrc/runtime.hip, csrc/snapshot.hip)
+ * What the handles own and no caller-visible buffer holds, as versioned flat blobs in HOST memory: 32 little-endian 8-byte words (doubles as their bit patterns),
+ * for the actor followed by copies of its device arrays.  _save waits for `stream`; _load refuses a blob whose description differs from the handle's, with a message.
+ * The seeds are state: a blob loaded into a handle created with another seed continues the saved run.
+ *   replay  0 magic, 1 version (1), 2 size, 3 obs_bytes, 4 B, 5 prioritize, 6 top, 7 written, 8 epoch open, 9 epoch top, 10 epoch batches, 11 epoch position,
+ *           12 epoch seed, 13..20 Philox offsets, 21 beta in use, 22 beta schedule, 23 max_p, 24 Philox seed, 25 alpha, 26 eps, 27 beta0, 28 total_steps.
+ *           _save brings the sum-tree's top levels up to date first (like a0_rbuf_read), so that the caller can save the tree from its own buffer.
+ *   actor   0 magic, 1 version (1), 2 E, 3 T, 4 A, 5 dueling, 6 n_step, 7 env_task, 8 reset_noise_freq, 9 discount, 10 observation buffers K, 11 current buffer,
+ *           12 env step counter, 13 actor step counter, 14 Philox seed, 15..22 Philox offsets, 23 env seed, 24 rank; then obs [K][E][obs_bytes] u8, ep_ret [E] f32,
+ *           ring_act [n][E] i32, ring_rew, ring_done [n][E] f32, qs [T], stat_mask [T][E], stat_ret [T][E] f32 (the last rollout's statistics: a rollout issued ahead
+ *           and not yet collected is collected after the load).  An actor with an attached host pool has no saveable env state: A0_ESTATE. */
+long long a0_rbuf_state_size(const a0_rbuf* replay);
+int a0_rbuf_state_save(a0_rbuf* replay, void* blob_host, long long capacity, void* stream);
+int a0_rbuf_state_load(a0_rbuf* replay, const void* blob_host, long long bytes, void* stream);
+long long a0_actor_state_size(const a0_actor* actor);
+int a0_actor_state_save(a0_actor* actor, void* blob_host, long long capacity, void* stream);
+int a0_actor_state_load(a0_actor* actor, const void* blob_host, long long bytes, void* stream);
+/* Frame deduplication of ring rows on the way to a snapshot file and back (csrc/snapshot.hip).  A chunk is `rows` consecutive ring rows of frames_per_row frames of
+ * frame_bytes bytes (a multiple of 16), at most 32 768 frames.  a0_snapshot_pack looks, for every frame in row order, for the first byte-identical frame among the
+ * earlier frames of its row and then the frames of the row `stride` earlier in the chunk (stride = num_envs: the same env's previous step; 0: same row only), by
+ * comparing bytes, and writes
+ *     u32 lit_id[rows * frames_per_row] | u32 n_lit | pad to 16 B | u8 literals[n_lit][frame_bytes]        (literals at a0_snapshot_literal_offset)
+ * to `packed` (a0_snapshot_pack_bound bytes: every frame a literal); lit_id names each frame's literal with reference chains resolved, literals are in row order, and
+ * the bytes are a function of the chunk's bytes alone.  `work`: rows * frames_per_row u32 of device scratch.  a0_snapshot_unpack writes frame (r, j) =
+ * literals[lit_id[r][j]] into `rows_out`; an id >= n_lit (a damaged file) writes nothing and sets *bad_flag (device int, may be NULL) to 1.  Device pointers, 16-byte aligned. */
+long long a0_snapshot_pack_bound(long long rows, int frames_per_row, int frame_bytes);
+long long a0_snapshot_literal_offset(long long rows, int frames_per_row);
+int a0_snapshot_pack(const uint8_t* rows, long long n_rows, int frames_per_row, int frame_bytes, long long stride, uint8_t* packed, unsigned int* work, void* stream);
+int a0_snapshot_unpack(const uint8_t* packed, long long n_rows, int frames_per_row, int frame_bytes, uint8_t* rows_out, int* bad_flag, void* stream);
 
 /* data parallelism: this rank's NaN flag as a float (1.0 / 0.0) that rides at the tail of a SUM-reduced gradient bucket; the reduced value
  * comes back through extra_nan_flag (nonzero = some rank saw a NaN: every rank skips the step), NULL on one GPU */
