@@ -26,15 +26,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-// Cross products a_i * b_j of the three-term splits that are formed: those with i + j <= A0_X9_MAXORD.  4 = all nine (every partial product
-// of the fp32 fmaf chain, exactly) — the default.  2 = six: a1*b2, a2*b1 and a2*b2 are left out — each is below 2^-24 of a*b (|a1| <= 2^-8 |a|, |b2| <= 2^-16 |b|),
-// i.e. below the rounding the fp32 chain itself applies to every partial SUM, which for a K-term dot product is ~sqrt(K) times larger.
-// Measured (tools/build_variant.sh x6 -DA0_X9_MAXORD=2; profiles/r02_encoder_experiments.md): a third fewer conv2 / conv3 MFMAs shorten the
-// forward kernel by 7-9 % and the data-gradient kernel by 9 % with every parity test unchanged — the stages are not matrix-pipe-bound —
-// and the build keeps all nine: exact products are worth more here than 3.6 % of an iteration.
-#ifndef A0_X9_MAXORD
-#define A0_X9_MAXORD 4
-#endif
 typedef float a0_acc4 __attribute__((ext_vector_type(4)));
 
 struct a0_fused_args {
@@ -49,11 +40,33 @@ struct a0_fused_args {
     int rp1, rp2;                        // LDS row pitches (floats) of act1 / act2, padded so that A-fragment reads are bank-conflict free
 };
 
+// The weight-copy buffer `wt` that a0_conv_wt_kernel fills from the packed [N][K] weights and every fused kernel reads: the length of each
+// segment and its offset, in floats, for C input channels.  This is the only description of the layout in the library.
+struct a0_wt_layout {
+    int C;
+    constexpr int n_conv1x() const { return 48 * 64 * C; }      // conv1: fl(w/255) as three exact bf16 terms, a0_wring1 layout (32 x 64 C x 3 x 2 bytes)
+    static constexpr int n_conv2 = 64 * 512;                    // conv2 fp32, fragment-major (a0_wring layout)
+    static constexpr int n_conv3 = 64 * 576;                    // conv3 fp32, fragment-major
+    static constexpr int n_conv2x = 96 * 512;                   // conv2 as three exact bf16 terms (a0_wring9 layout, N = 64): 64 x K x 3 x 2 bytes
+    static constexpr int n_conv3x = 96 * 576;                   // conv3 likewise
+    static constexpr int n_dgrad3x = 96 * 576;                  // conv3's data-gradient matrix (flipped taps) [576][64] as three bf16 terms, a0_wring9 layout, N = 64
+    static constexpr int n_dgrad2x_phase = 48 * 256;            // conv2's data-gradient matrix of one stride phase [256][32], a0_wring9 layout, N = 32; four of them
+    constexpr int conv1x() const { return 0; }
+    constexpr int conv2() const { return n_conv1x(); }
+    constexpr int conv3() const { return conv2() + n_conv2; }
+    constexpr int conv2x() const { return conv3() + n_conv3; }
+    constexpr int conv3x() const { return conv2x() + n_conv2x; }
+    constexpr int dgrad3x() const { return conv3x() + n_conv3x; }
+    constexpr int dgrad2x() const { return dgrad3x() + n_dgrad3x; }
+    constexpr int total() const { return dgrad2x() + 4 * n_dgrad2x_phase; }
+};
+A0_HD void a0_fused_set_wt(a0_fused_args& P, const float* wt, int C) {
+    const a0_wt_layout T{C};
+    P.wt1 = wt + T.conv1x(); P.wt2 = wt + T.conv2(); P.wt3 = wt + T.conv3(); P.wx2 = wt + T.conv2x(); P.wx3 = wt + T.conv3x();
+}
+
 // Eight waves per workgroup = two per SIMD: while one wave waits for its LDS operands the other keeps the matrix pipe busy.
-#ifndef A0_FUSED_WAVES_D
-#define A0_FUSED_WAVES_D 8
-#endif
-constexpr int A0_FUSED_WAVES = A0_FUSED_WAVES_D;
+constexpr int A0_FUSED_WAVES = 8;
 constexpr int A0_WMG1 = A0_FUSED_WAVES / 2;       // conv1: two waves along N, the rest along M
 constexpr int A0_FUSED_THREADS = 64 * A0_FUSED_WAVES;
 // LDS layout of the activations: [row][pixel][channel] with pixel pitch P and row pitch RP.  An A-fragment read (ds_read_b32) is served
@@ -156,40 +169,28 @@ struct EpiFwd {                 // y = relu(acc + bias[n]) -> LDS image [oh][ow]
 // Epilogues with TR = true receive TRANSPOSED accumulators (the split-operand stages issue their MFMAs with the operands swapped, weights
 // as A and activations as B): a lane then holds four consecutive output CHANNELS n0 .. n0+3 (n0 = 4 * (lane >> 4) within the 16-column
 // block) of ONE output position m = lane & 15, instead of four positions of one channel — so one bf16 term of its four values is a
-// single 8-byte LDS write (was four 2-byte writes), its fp32 values one 16-byte global store, and a ReLU mask one 16-byte load.
+// single 8-byte LDS write, its fp32 values one 16-byte global store, and a ReLU mask one 16-byte load.  They read their biases from LDS and
+// their masks inside the stage (a0_conv_stage_x9k): for them this object is empty and load() is never called.
 template <int N, int WN, int MBW, class EPI>
 struct a0_pre {
     static constexpr int NBW = N / 16 / WN, WMG = A0_FUSED_WAVES / WN;
     float pc[NBW][EPI::TR ? 4 : 1], pe[EPI::PER_ELEM ? MBW : 1][NBW][4];
     A0_D void load(const EPI& epi, int M) {
+        static_assert(!EPI::TR, "transposed epilogues prefetch nothing");
         const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         const int wn = wave % WN, wmg = wave / WN, q = lane >> 4, r16 = lane & 15;
 #pragma unroll
         for (int j = 0; j < NBW; ++j) {
-            if constexpr (EPI::TR) {
-                const int n0 = (wn * NBW + j) * 16 + 4 * q;
+            const int n = (wn * NBW + j) * 16 + r16;
+            pc[j][0] = epi.pre_col(n);
+            if constexpr (EPI::PER_ELEM) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) pc[j][r] = epi.pre_col(n0 + r);
-                if constexpr (EPI::PER_ELEM) {
+                for (int i = 0; i < MBW; ++i)
 #pragma unroll
-                    for (int i = 0; i < MBW; ++i) {
-                        const int m = (wmg + i * WMG) * 16 + r16;
-                        const a0_f4 v = epi.pre_elem4(m < M ? m : M - 1, n0);
-                        pe[i][j][0] = v.x; pe[i][j][1] = v.y; pe[i][j][2] = v.z; pe[i][j][3] = v.w;
+                    for (int r = 0; r < 4; ++r) {
+                        const int m = (wmg + i * WMG) * 16 + 4 * q + r;
+                        pe[i][j][r] = epi.pre_elem(m < M ? m : M - 1, n);
                     }
-                }
-            } else {
-                const int n = (wn * NBW + j) * 16 + r16;
-                pc[j][0] = epi.pre_col(n);
-                if constexpr (EPI::PER_ELEM) {
-#pragma unroll
-                    for (int i = 0; i < MBW; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int m = (wmg + i * WMG) * 16 + 4 * q + r;
-                            pe[i][j][r] = epi.pre_elem(m < M ? m : M - 1, n);
-                        }
-                }
             }
         }
     }
@@ -409,7 +410,8 @@ struct a0_wring9 {          // uint4 index ((t*N + n)*4 + q)*3 + s: the eight k 
     const uint4* base;
     const uint4* p;
     int nst, left, stride;
-    // WK > 1 (a0_conv_stage_x9k): the waves wave / WN = 0 .. WK-1 share the k steps round-robin; this ring walks steps wk, wk + WK, ...
+    // The waves wave / WN = 0 .. WK-1 share the k steps round-robin; this ring walks steps wk, wk + WK, ...  Every stage that uses the ring
+    // (a0_conv_stage_x9k) has WK = 2.
     A0_D void init(const float* wp, int K) {
         const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         base = (const uint4*)wp + (((wave % WN) * (NBW * 16) + (lane & 15)) * 4 + (lane >> 4)) * 3 + (WK > 1 ? (wave / WN) * (N * 12) : 0);
@@ -468,7 +470,6 @@ struct EpiFwdX {            // y = relu(acc + bias[n]) -> three bf16 planes in L
     static constexpr bool TR = true;
     static_assert(OWC > 0 && (P % 4) == 0 && (RP % 4) == 0 && (term % 4) == 0, "output width known at compile time; 8-byte aligned plane writes");
     const float* bias; uint16_t* planes; float* glb; int N;          // bias: the workgroup's LDS copy (one 16-byte read per block; kept in registers across the launch the biases cost 12 VGPRs the kernel does not have)
-    A0_D float pre_col(int) const { return 0.f; }
     A0_D void emit_n4(int m, int n0, const a0_acc4& acc, const float*) const {       // channels n0 .. n0+3 of output position m
         const a0_f4 bv = *(const a0_f4*)(bias + n0);
         float v[4] = {acc[0] + bv.x, acc[1] + bv.y, acc[2] + bv.z, acc[3] + bv.w};
@@ -487,7 +488,6 @@ struct EpiFwdT {            // y = relu(acc + bias[n]) -> fp32 global [m][N] (co
     static constexpr bool ROW4 = false;
     static constexpr bool TR = true;
     const float* bias; float* glb; int N;          // bias: LDS copy, as in EpiFwdX
-    A0_D float pre_col(int) const { return 0.f; }
     A0_D void emit_n4(int m, int n0, const a0_acc4& acc, const float*) const {
         const a0_f4 bv = *(const a0_f4*)(bias + n0);
         float v[4] = {acc[0] + bv.x, acc[1] + bv.y, acc[2] + bv.z, acc[3] + bv.w};
@@ -497,95 +497,19 @@ struct EpiFwdT {            // y = relu(acc + bias[n]) -> fp32 global [m][N] (co
     }
 };
 
-template <int ORD, int N, int WN, int MBW, int R, int MBWP, class AFX, class EPI, class Between>
-A0_D void a0_conv_stage_x9(const AFX& af, int M, a0_wring9<N, WN, R>& ring, const EPI& epi, const a0_pre<N, WN, MBWP, EPI>& pre, Between&& between) {
-    constexpr int NB = N / 16, NBW = NB / WN, WMG = A0_FUSED_WAVES / WN;
-    static_assert(NBW >= 1 && (R % 2) == 0 && MBWP >= MBW, "tile shape");
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave % WN, wmg = wave / WN;
-    const int q = lane >> 4, r16 = lane & 15;
-    const int MB = (M + 15) >> 4, NST = ring.nst;       // NST is a multiple of R for every supported shape
-    int rows[MBW];
-#pragma unroll
-    for (int i = 0; i < MBW; ++i) {
-        const int m = (wmg + i * WMG) * 16 + r16;
-        rows[i] = af.row(m < M ? m : 0) + 8 * q;
-    }
-    a0_acc4 acc[MBW][NBW];
-#pragma unroll
-    for (int i = 0; i < MBW; ++i)
-#pragma unroll
-        for (int j = 0; j < NBW; ++j) acc[i][j] = a0_acc4{0.f, 0.f, 0.f, 0.f};
-    uint4 a[2][MBW][3];
-    auto fetch = [&](int slot, int off) {
-#pragma unroll
-        for (int i = 0; i < MBW; ++i)
-#pragma unroll
-            for (int t = 0; t < 3; ++t) a[slot][i][t] = *(const uint4*)(af.planes + rows[i] + off + t * AFX::term);
-    };
-    fetch(0, af.step_off(0));
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): see a0_conv_stage
-#pragma unroll 1
-    for (int tb = 0; tb < NST; tb += R) {
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int nxt = tb + u + 1;
-            fetch((u + 1) & 1, af.step_off(nxt < NST ? nxt : NST - 1));          // past the end: re-read the last step (never consumed)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ta = 0; ta < 3; ++ta)
-#pragma unroll
-                for (int tw = 0; tw < 3; ++tw)
-#pragma unroll
-                    for (int i = 0; i < MBW; ++i)
-#pragma unroll
-                        for (int jn = 0; jn < NBW; ++jn) {
-                            if (ta + tw > ORD) continue;      // see A0_X9_MAXORD
-                            const a0_u32x4 av = {a[u & 1][i][ta].x, a[u & 1][i][ta].y, a[u & 1][i][ta].z, a[u & 1][i][ta].w};
-                            const a0_u32x4 bv = {ring.v[u][jn][tw].x, ring.v[u][jn][tw].y, ring.v[u][jn][tw].z, ring.v[u][jn][tw].w};
-                            if constexpr (EPI::TR) acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(a0_bf16x8, bv), __builtin_bit_cast(a0_bf16x8, av), acc[i][jn], 0, 0, 0);
-                            else acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(a0_bf16x8, av), __builtin_bit_cast(a0_bf16x8, bv), acc[i][jn], 0, 0, 0);
-                        }
-            __builtin_amdgcn_sched_barrier(0);
-            ring.fill(u);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    between();
-#pragma unroll
-    for (int i = 0; i < MBW; ++i) {
-        const int mb = wmg + i * WMG;
-        if (mb < MB) {
-            if constexpr (EPI::TR) {
-                const int m = mb * 16 + r16;
-                if (m < M) {
-#pragma unroll
-                    for (int j = 0; j < NBW; ++j) epi.emit_n4(m, (wn * NBW + j) * 16 + 4 * q, acc[i][j], EPI::PER_ELEM ? pre.pe[EPI::PER_ELEM ? i : 0][j] : pre.pc[j]);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < NBW; ++j) {
-                    const int n = (wn * NBW + j) * 16 + r16;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int m = mb * 16 + 4 * q + r;
-                        if (m < M) epi.emit(m, n, acc[i][j][r], EPI::PER_ELEM ? pre.pe[EPI::PER_ELEM ? i : 0][j][r] : pre.pc[j][0]);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-}
-// N-stationary form of a0_conv_stage_x9 for the forward stages (N = 64: four waves along N, the two groups of four along K).  In the form
-// above the two groups of waves along M both stream the complete weight set (1 MB per observation and CU through the vector L1), and the
-// kernel is more sensitive to that stream than to anything else (profiles/r02_encoder_experiments.md: half the weight loads = -8 %, half the
-// LDS fragment reads = -2 %).  Here wave (wn, wk) owns column block wn, ALL 16-row blocks and the k steps wk, wk + 2, ...: every weight
-// fragment is loaded by exactly one wave.  A k step is processed in two halves of MBT / 2 row blocks (the A fragments of the next half are in
-// flight while this one's MFMAs issue: same register ring as above).  At the end the two waves of a column block exchange partial sums
-// through LDS — wave wk finishes row-block half wk, so each sends the other's half — which costs one barrier and 2 x 4 KB x MBT of LDS traffic.
-// `xch`: 8 * MBT / 2 KB of LDS nobody reads any more when the first wave leaves its k loop.  Association of the k sum: (even steps) + (odd steps).
+// One split-operand convolution stage, N-stationary (N = 64: four waves along N, the two groups of four along K).  Wave (wn, wk) owns column
+// block wn, ALL 16-row blocks and the k steps wk, wk + 2, ...: every weight fragment is loaded by exactly one wave — the kernel is more
+// sensitive to the weight stream through the vector L1 than to anything else (profiles/r02_encoder_experiments.md: half the weight loads =
+// -8 %, half the LDS fragment reads = -2 %).  A k step is processed in two halves of MBT / 2 row blocks (the A fragments of the next half are
+// in flight while this one's MFMAs issue; register ring and pipeline discipline as in a0_conv_stage).  At the end the two waves of a column
+// block exchange partial sums through LDS — wave wk finishes row-block half wk, so each sends the other's half — which costs one barrier and
+// 2 x 4 KB x MBT of LDS traffic.  `xch`: 8 * MBT / 2 KB of LDS nobody reads any more when the first wave leaves its k loop.  Association of
+// the k sum: (even steps) + (odd steps).
+// ORD: the cross products a_i * b_j of the three-term splits that are formed are those with i + j <= ORD.  4 = all nine (every partial
+// product of the fp32 fmaf chain, exactly), the default of the run-time switch A0_X9_PRODUCTS.  2 = six: a1*b2, a2*b1 and a2*b2 are left out —
+// each is below 2^-24 of a*b (|a1| <= 2^-8 |a|, |b2| <= 2^-16 |b|), i.e. below the rounding the fp32 chain itself applies to every partial
+// SUM, which for a K-term dot product is ~sqrt(K) times larger.  A third fewer conv2 / conv3 MFMAs shorten the forward kernel by 7-9 % and
+// the data-gradient kernel by 9 % (profiles/r02_encoder_experiments.md).  Both forms are instantiated; the launchers pick one.
 template <int ORD, int N, int WN, int MBT, int R, int LR, class AFX, class EPI, class Between>
 A0_D void a0_conv_stage_x9k(const AFX& af, int M, a0_wring9<N, WN, R, A0_FUSED_WAVES / WN>& ring, const EPI& epi, float* xch0, float* xch1, Between&& between) {
     constexpr int WK = A0_FUSED_WAVES / WN, HB0 = (MBT + 1) / 2, HB1 = MBT / 2;       // row blocks of the two halves of a k step: [0, HB0) and [HB0, MBT)
@@ -632,7 +556,7 @@ A0_D void a0_conv_stage_x9k(const AFX& af, int M, a0_wring9<N, WN, R, A0_FUSED_W
                     for (int tw = 0; tw < 3; ++tw)
 #pragma unroll
                         for (int i = 0; i < HB0; ++i) {
-                            if (ta + tw > ORD || h * HB0 + i >= MBT) continue;      // see A0_X9_MAXORD
+                            if (ta + tw > ORD || h * HB0 + i >= MBT) continue;      // ORD: see above
                             const a0_u32x4 av = {a[h][i][ta].x, a[h][i][ta].y, a[h][i][ta].z, a[h][i][ta].w};
                             const a0_u32x4 bv = {ring.v[u][0][tw].x, ring.v[u][0][tw].y, ring.v[u][0][tw].z, ring.v[u][0][tw].w};
                             acc[h * HB0 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(a0_bf16x8, bv), __builtin_bit_cast(a0_bf16x8, av), acc[h * HB0 + i], 0, 0, 0);
@@ -704,62 +628,30 @@ constexpr int A0_P1X = 40, A0_P2X = 80;       // pixel pitches (bf16 elements) o
 // 256-byte bank row, but a 16-row block spans two or three image rows, and with rows packed back to back the reads behind a row wrap
 // fell onto slots already taken: 8.0 (conv2) and 7.0 (conv3) LDS cycles per wave-read instead of 4.  The pads below are the smallest that
 // bring the average over all blocks and taps down to 4.7 / 5.0 cycles (tools/lds_bank_model.py enumerates the layouts).
-#ifndef A0_PADS
-#define A0_PADS 1                             // tuning aid: 0 = image rows packed back to back (the round-1 layout)
-#endif
-constexpr int A0_RP1X = 20 * A0_P1X + (A0_PADS ? 8 : 0);      // act1 planes: 20 pixels per row + 16 bytes
-constexpr int A0_RP2X = 9 * A0_P2X + (A0_PADS ? 96 : 0);      // act2 planes: 9 pixels per row + 192 bytes
-#ifndef A0_RX2_D
-#define A0_RX2_D 4
-#endif
-#ifndef A0_RX3_D
-#define A0_RX3_D 6
-#endif
-[[maybe_unused]] constexpr int A0_RX2 = A0_RX2_D, A0_RX3 = A0_RX3_D;         // 32-k steps of split weights in flight (tuning aids: -DA0_RX2_D / -DA0_RX3_D)
-#ifndef A0_KSPLIT_D
-#define A0_KSPLIT_D 1                         // 1: N-stationary stages in the data-gradient kernel too (two stride phases per stage)
-#endif
-#ifndef A0_KSPLIT
-#define A0_KSPLIT 1                           // 1: N-stationary conv2 / conv3 stages of the forward kernel (a0_conv_stage_x9k); 0: M x N wave tiling (a0_conv_stage_x9)
-#endif
-#ifndef A0_WNX
-#define A0_WNX 4                              // waves along N in the split-operand conv2 / conv3 stages
-#endif
+constexpr int A0_RP1X = 20 * A0_P1X + 8;       // act1 planes: 20 pixels per row + 16 bytes
+constexpr int A0_RP2X = 9 * A0_P2X + 96;       // act2 planes: 9 pixels per row + 192 bytes
 
 // Register-ring depths (16-k chunks in flight per wave): >= 2 us of MFMA work ahead of every weight load.
 constexpr int A0_R1 = 4, A0_R2 = 4, A0_R3 = 6;     // conv1: 32-k steps (three 16-byte terms each); conv2 / conv3: 16-k chunks
 
-#ifndef A0_FUSED_MINWAVES
-#define A0_FUSED_MINWAVES 1
-#endif
 template <int MBW1, int MBW2, int MBW3, int WC, bool X9, bool LOOP = false, int ORD = 4>
-__global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_encoder_fused_kernel(a0_fused_args P);
+__global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_fused_kernel(a0_fused_args P);
 
 // Split-operand variant (84 x 84 geometry): all three layers on the bf16 pipe.  LDS: bf16 image [0, 56 448), act1 term planes behind it;
 // the act2 term planes reuse the image's bytes (the image is dead once conv1 has finished).
 constexpr int A0_X9_BIAS_OFF = 2 * 4 * 84 * 84 + 3 * 20 * A0_RP1X * 2;      // bf16 image + act1 term planes
-#ifndef A0_RK2_D
-#define A0_RK2_D 2
-#endif
-#ifndef A0_RK3_D
-#define A0_RK3_D 3
-#endif
-constexpr int A0_RK2 = A0_RK2_D, A0_RK3 = A0_RK3_D;      // weight-ring depths of the N-stationary stages, in own k steps (8 resp. 9 per wave)
+constexpr int A0_RK2 = 2, A0_RK3 = 3;      // weight-ring depths of the N-stationary stages, in own k steps (8 resp. 9 per wave)
 constexpr int A0_X9_XCH0 = 3 * 9 * A0_RP2X * 2;             // conv2 exchange region 0: behind the act2 planes, inside the (dead) image
 constexpr int A0_X9_XCH1 = A0_X9_BIAS_OFF + 160 * 4;        // region 1: behind the biases (4 waves x (2 KB + 64 B))
 static_assert(A0_X9_XCH0 + 4 * 3 * 1024 <= 2 * 4 * 84 * 84, "conv2 exchange region 0 fits into the image");
-constexpr int A0_X9_LDS_BYTES = A0_X9_XCH1 + (A0_KSPLIT ? 4 * (2 * 64 + 4) * 16 : 0);
+constexpr int A0_X9_LDS_BYTES = A0_X9_XCH1 + 4 * (2 * 64 + 4) * 16;
 static_assert(A0_X9_LDS_BYTES <= 160 * 1024, "LDS");
-// conv2 + conv3 of the split-operand encoder for observation b, behind conv1's epilogue (act1 term planes in LDS): shared by a0_encoder_fused_x9_body and the actor-step
-// kernel that overlaps conv1 with the step's tail (a0_actor_step_enc2_kernel).
-#if A0_KSPLIT
+static_assert(A0_FUSED_WAVES == 8, "N-stationary stages: four waves along N, two along K");
 typedef a0_wring9<64, 4, A0_RK2, 2> a0_ring2_t;      // 8 own steps of conv2's 16
 typedef a0_wring9<64, 4, A0_RK3, 2> a0_ring3_t;      // 9 own steps of conv3's 18
-#else
-typedef a0_wring9<64, A0_WNX, A0_RX2> a0_ring2_t;
-typedef a0_wring9<64, A0_WNX, A0_RX3> a0_ring3_t;
-#endif
-template <int ORD, int MBW2, int MBW3, bool LOOP>
+// conv2 + conv3 of the split-operand encoder for observation b, behind conv1's epilogue (act1 term planes in LDS): shared by a0_encoder_fused_x9_body and the actor-step
+// kernel that overlaps conv1 with the step's tail (a0_actor_step_enc2_kernel).
+template <int ORD, bool LOOP>
 A0_D void a0_x9_conv23(const a0_fused_args& P, int b, unsigned char* smem, float* bias_lds, a0_wring1<A0_R1>& ring1, a0_ring2_t& ring2, a0_ring3_t& ring3) {
     const int obs_bytes = P.C * P.H * P.W;
     const int M2 = P.H2 * P.W2, M3 = P.H3 * P.W3;
@@ -767,46 +659,36 @@ A0_D void a0_x9_conv23(const a0_fused_args& P, int b, unsigned char* smem, float
     constexpr int term1 = 20 * A0_RP1X, term2 = 9 * A0_RP2X;
     uint16_t* a2p = (uint16_t*)smem;
     typedef EpiFwdX<9, A0_P2X, A0_RP2X, term2> E2X;
-    constexpr int WNX = A0_WNX, WMGX = A0_FUSED_WAVES / WNX;
-    constexpr int MBW2X = (6 + WMGX - 1) / WMGX, MBW3X = (4 + WMGX - 1) / WMGX;
-    static_assert(MBW2X <= MBW2 * 2 && MBW3X <= MBW3 * 2, "84x84 geometry");
-#if !A0_KSPLIT
-    a0_pre<64, WNX, MBW2X, E2X> pre2;
-    a0_pre<64, WNX, MBW3X, EpiFwdT> pre3;
-#endif
-    (void)a1p; (void)term1;
-    {
-        const AF2X<term1> f2{a1p, A0_RP1X, P.W2, A0_P1X};
-        const E2X e2{bias_lds + 32, a2p, P.act2 ? P.act2 + (long long)b * M2 * 64 : nullptr, 64};
-#if A0_KSPLIT
-        // exchange buffers, all dead while their stage's k loops run: conv2's partial sums go behind the act2 planes-to-be (the top 12 KB of the
-        // image region) and into the tail of the LDS allocation, conv3's where act1 was
-        const AF3X<term2> f3k{a2p, A0_RP2X, P.W3, A0_P2X};
-        const EpiFwdT e3k{bias_lds + 96, P.act3 + (long long)b * M3 * 64, 64};
-        a0_conv_stage_x9k<ORD, 64, 4, 6, A0_RK2, 1>(f2, M2, ring2, e2, (float*)(smem + A0_X9_XCH0), (float*)(smem + A0_X9_XCH1), [&] { ring3.prologue(); });
-        a0_conv_stage_x9k<ORD, 64, 4, 4, A0_RK3, 16>(f3k, M3, ring3, e3k, (float*)a1p, (float*)a1p + 4 * 2 * 256, [&] { if (LOOP) ring1.prologue(); });
-#else
-        const int wmgx = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) / WNX;
-        constexpr bool uneven2 = MBW2X > 1 && MBW2X * WMGX > 6, uneven3 = MBW3X > 1 && MBW3X * WMGX > 4;      // some M groups own one block less
-        if (uneven2 && wmgx + (MBW2X - 1) * WMGX >= 6)
-            a0_conv_stage_x9<ORD, 64, WNX, (MBW2X > 1 ? MBW2X - 1 : 1), A0_RX2>(f2, M2, ring2, e2, pre2, [&] { ring3.prologue(); });
-        else
-            a0_conv_stage_x9<ORD, 64, WNX, MBW2X, A0_RX2>(f2, M2, ring2, e2, pre2, [&] { ring3.prologue(); });
-        const AF3X<term2> f3{a2p, A0_RP2X, P.W3, A0_P2X};
-        const EpiFwdT e3{bias_lds + 96, P.act3 + (long long)b * M3 * 64, 64};
-        if (uneven3 && wmgx + (MBW3X - 1) * WMGX >= 4)
-            a0_conv_stage_x9<ORD, 64, WNX, (MBW3X > 1 ? MBW3X - 1 : 1), A0_RX3>(f3, M3, ring3, e3, pre3, [&] { if (LOOP) ring1.prologue(); });
-        else
-            a0_conv_stage_x9<ORD, 64, WNX, MBW3X, A0_RX3>(f3, M3, ring3, e3, pre3, [&] { if (LOOP) ring1.prologue(); });
-#endif
+    const AF2X<term1> f2{a1p, A0_RP1X, P.W2, A0_P1X};
+    const E2X e2{bias_lds + 32, a2p, P.act2 ? P.act2 + (long long)b * M2 * 64 : nullptr, 64};
+    const AF3X<term2> f3{a2p, A0_RP2X, P.W3, A0_P2X};
+    const EpiFwdT e3{bias_lds + 96, P.act3 + (long long)b * M3 * 64, 64};
+    // exchange buffers, all dead while their stage's k loops run: conv2's partial sums go behind the act2 planes-to-be (the top 12 KB of the
+    // image region) and into the tail of the LDS allocation, conv3's where act1 was
+    a0_conv_stage_x9k<ORD, 64, 4, 6, A0_RK2, 1>(f2, M2, ring2, e2, (float*)(smem + A0_X9_XCH0), (float*)(smem + A0_X9_XCH1), [&] { ring3.prologue(); });
+    a0_conv_stage_x9k<ORD, 64, 4, 4, A0_RK3, 16>(f3, M3, ring3, e3, (float*)a1p, (float*)a1p + 4 * 2 * 256, [&] { if (LOOP) ring1.prologue(); });
+}
+
+// 16 observation bytes -> 16 bf16 at element 16 * idx16 of the LDS image [C][H][W]; (float)byte is exact and its low 16 bits are zero
+A0_D void a0_bytes16_to_img(uint16_t* img, int idx16, const uint4& v) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t f0 = __float_as_uint((float)(w[k] & 0xffu)), f1 = __float_as_uint((float)((w[k] >> 8) & 0xffu));
+        const uint32_t f2 = __float_as_uint((float)((w[k] >> 16) & 0xffu)), f3 = __float_as_uint((float)(w[k] >> 24));
+        o[2 * k] = __builtin_amdgcn_perm(f1, f0, 0x07060302u);          // high halves of f0 (low) and f1 (high)
+        o[2 * k + 1] = __builtin_amdgcn_perm(f3, f2, 0x07060302u);
     }
+    ((uint4*)img)[2 * idx16] = uint4{o[0], o[1], o[2], o[3]};
+    ((uint4*)img)[2 * idx16 + 1] = uint4{o[4], o[5], o[6], o[7]};
 }
 
 // LOOP: the workgroup walks over several observations (b += gridDim.x; launches of more observations than CUs) and requests the next
 // observation's conv1 weights behind conv3; without it (the actor's launches: one observation per workgroup) that request is not made.
 // bid / nblk: this workgroup's index among the workgroups that serve P and their number (blockIdx.x / gridDim.x for a launch of one pass;
 // a0_encoder_fused_multi_kernel hands every pass a share of the grid).
-template <int ORD, int MBW1, int MBW2, int MBW3, bool LOOP>
+template <int ORD, bool LOOP>
 A0_D void a0_encoder_fused_x9_body(const a0_fused_args& P, int bid, int nblk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* img = (uint16_t*)smem;
@@ -815,26 +697,14 @@ A0_D void a0_encoder_fused_x9_body(const a0_fused_args& P, int bid, int nblk) {
     uint16_t* a1p = (uint16_t*)(smem + 2 * obs_bytes);
     constexpr int term1 = 20 * A0_RP1X;
     typedef EpiFwdX<20, A0_P1X, A0_RP1X, term1> E1X;
-    // conv2 / conv3 wave tiling: WNX waves along N (each owns 64 / 16 / WNX column blocks), 8 / WNX groups along M.  An A fragment read
-    // from LDS feeds 9 * NBW MFMAs, and the waves along N re-read the same fragments: with four waves along N (NBW = 1) the two stages
-    // moved 72 / 48 KB of LDS per 32-k step against 864 / 576 matrix-pipe cycles — LDS-bound at 128 B/clk.  Two waves along N halve that.
-    // Four M groups over conv2's six 16-row blocks: groups 0, 1 own two blocks, groups 2, 3 one (the MBW - 1 instantiation); a SIMD hosts
-    // one wave of each kind (wave w and w + 4), so the matrix pipes stay evenly loaded.  conv3: four blocks, one per group.
-    constexpr int WNX = A0_WNX, WMGX = A0_FUSED_WAVES / WNX;
-    constexpr int MBW2X = (6 + WMGX - 1) / WMGX, MBW3X = (4 + WMGX - 1) / WMGX;
-    static_assert(MBW2X <= MBW2 * 2 && MBW3X <= MBW3 * 2, "84x84 geometry");
     a0_wring1<A0_R1> ring1;
-#if A0_KSPLIT
-    static_assert(WNX == 4 && A0_FUSED_WAVES == 8, "N-stationary stages: four waves along N, two along K");
-#endif
     a0_ring2_t ring2;
     a0_ring3_t ring3;
     ring1.init(P.wt1, P.C);
     ring2.init(P.wx2, 512);
     ring3.init(P.wx3, 576);
     ring1.prologue();
-    constexpr int MBW1X = (25 + A0_WMG1 - 1) / A0_WMG1;
-    static_assert(A0_FUSED_WAVES != 8 || MBW1X == MBW1, "84x84 geometry");
+    constexpr int MBW1X = (25 + A0_WMG1 - 1) / A0_WMG1;      // conv1's 25 row blocks over the four M groups: 7 + 6 + 6 + 6
     a0_pre<32, 2, MBW1X, E1X> pre1;           // (empty: these epilogues take nothing from global memory)
     float* bias_lds = (float*)(smem + A0_X9_BIAS_OFF);      // b1 | b2 | b3 behind the activation planes; visible after the first barrier below
     if (threadIdx.x < 160) bias_lds[threadIdx.x] = threadIdx.x < 32 ? P.b1[threadIdx.x] : threadIdx.x < 96 ? P.b2[threadIdx.x - 32] : P.b3[threadIdx.x - 96];
@@ -853,19 +723,8 @@ A0_D void a0_encoder_fused_x9_body(const a0_fused_args& P, int bid, int nblk) {
             }
 #pragma unroll
             for (int j = 0; j < TRIPS; ++j) {
-                int i = i0 + j * A0_FUSED_THREADS;
-                i = i < n16 ? i : n16 - 1;
-                const uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-                uint32_t o[8];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t f0 = __float_as_uint((float)(w[k] & 0xffu)), f1 = __float_as_uint((float)((w[k] >> 8) & 0xffu));
-                    const uint32_t f2 = __float_as_uint((float)((w[k] >> 16) & 0xffu)), f3 = __float_as_uint((float)(w[k] >> 24));
-                    o[2 * k] = __builtin_amdgcn_perm(f1, f0, 0x07060302u);
-                    o[2 * k + 1] = __builtin_amdgcn_perm(f3, f2, 0x07060302u);
-                }
-                ((uint4*)img)[2 * i] = uint4{o[0], o[1], o[2], o[3]};
-                ((uint4*)img)[2 * i + 1] = uint4{o[4], o[5], o[6], o[7]};
+                const int i = i0 + j * A0_FUSED_THREADS;
+                a0_bytes16_to_img(img, i < n16 ? i : n16 - 1, v[j]);
             }
         }
         __syncthreads();
@@ -875,7 +734,7 @@ A0_D void a0_encoder_fused_x9_body(const a0_fused_args& P, int bid, int nblk) {
             a0_conv1_stage<(MBW1X > 1 ? MBW1X - 1 : 1), A0_R1, 84>(img, P.H * P.W, P.W, P.W1, M1, ring1, e1, pre1, [&] { ring2.prologue(); });
         else
             a0_conv1_stage<MBW1X, A0_R1, 84>(img, P.H * P.W, P.W, P.W1, M1, ring1, e1, pre1, [&] { ring2.prologue(); });
-        a0_x9_conv23<ORD, MBW2, MBW3, LOOP>(P, b, smem, bias_lds, ring1, ring2, ring3);
+        a0_x9_conv23<ORD, LOOP>(P, b, smem, bias_lds, ring1, ring2, ring3);
         if constexpr (!LOOP) break;
     }
 }
@@ -894,7 +753,7 @@ struct a0_step_enc_args { const float *wt, *b1, *b2, *b3; float* act3; };
 // The distributional heads' step (c51 / qr): a0_actor_dist_tail_env_kernel's body (head slab sum, dueling, expectation or quantile mean, first maximum, epsilon-greedy,
 // env step, replay row), a barrier, then the whole encoder.
 template <int ORD>
-__global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_actor_dist_step_enc_kernel(a0_dtenv_args Q, a0_step_enc_args N) {
+__global__ __launch_bounds__(A0_FUSED_THREADS) void a0_actor_dist_step_enc_kernel(a0_dtenv_args Q, a0_step_enc_args N) {
     __shared__ int s_chase_cell;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long v_wt = (unsigned long long)N.wt, v_b1 = (unsigned long long)N.b1, v_b2 = (unsigned long long)N.b2, v_b3 = (unsigned long long)N.b3,
@@ -910,13 +769,12 @@ __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_actor_
     const float* wt = (const float*)uni(v_wt);
     a0_fused_args P;
     P.frames = (const uint8_t*)uni(v_obs); P.slot = nullptr; P.sample_stride = 4 * 84 * 84; P.chan_off = 0;
-    P.wt1 = wt; P.wt2 = wt + 48LL * 4 * 64; P.wt3 = P.wt2 + 64LL * 512;
-    P.wx2 = P.wt3 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256; P.wx3 = P.wx2 + 96LL * 512;
+    a0_fused_set_wt(P, wt, 4);
     P.b1 = (const float*)uni(v_b1); P.b2 = (const float*)uni(v_b2); P.b3 = (const float*)uni(v_b3);
     P.act1 = nullptr; P.act2 = nullptr; P.act3 = (float*)uni(v_a3); P.B = __builtin_amdgcn_readfirstlane(v_E);
     P.C = 4; P.H = 84; P.W = 84; P.H1 = 20; P.W1 = 20; P.H2 = 9; P.W2 = 9; P.H3 = 7; P.W3 = 7;
     P.off_act1 = 0; P.off_act2 = 0; P.off_end = 0; P.rp1 = 0; P.rp2 = 0;
-    a0_encoder_fused_x9_body<ORD, 7, 3, 2, false>(P, (int)blockIdx.x, (int)gridDim.x);
+    a0_encoder_fused_x9_body<ORD, false>(P, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---- Round 5, second form: the step's tail BESIDE conv1 (scalar heads).  In the first form (tail, barrier, whole encoder, as a0_actor_dist_step_enc_kernel) seven
@@ -932,20 +790,6 @@ __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_actor_
 // order, so behind a pending store every wait for a weight fragment is a wait for the stores' acknowledgements.
 // Measured (profiles/r05_experiments.md): 32.3 -> 31.1 us per launch by the kernel trace.  Timing-only builds of this kernel: without the 21.7 MB of stores 29.9 us,
 // without the head's evaluation 30.7, without both and without wave 0's catch-up 28.7 — the floor of the structure; the stand-alone encoder is 25.7.
-A0_D void a0_bytes16_to_img(uint16_t* img, int idx16, const uint4 v) {      // 16 pixels -> 16 bf16 (exact) at element 16 * idx16 of the [4][84 * 84] image
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t o[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t f0 = __float_as_uint((float)(w[k] & 0xffu)), f1 = __float_as_uint((float)((w[k] >> 8) & 0xffu));
-        const uint32_t f2 = __float_as_uint((float)((w[k] >> 16) & 0xffu)), f3 = __float_as_uint((float)(w[k] >> 24));
-        o[2 * k] = __builtin_amdgcn_perm(f1, f0, 0x07060302u);
-        o[2 * k + 1] = __builtin_amdgcn_perm(f3, f2, 0x07060302u);
-    }
-    ((uint4*)img)[2 * idx16] = uint4{o[0], o[1], o[2], o[3]};
-    ((uint4*)img)[2 * idx16 + 1] = uint4{o[4], o[5], o[6], o[7]};
-}
-
 // a0_conv1_stage for the 4 x 84 x 84 image with the k loop cut behind step 5: steps 0..5 (channels 0..2) run before `mid()` on waves with first_before_mid, behind it on
 // the others; steps 6, 7 behind it on all.  Same fetch / MFMA / ring-fill sequence per step as a0_conv1_stage.
 template <int MBW, class EPI, class Mid, class Between>
@@ -1060,8 +904,7 @@ A0_D void a0_actor_step_enc2_body(const typename TAIL::Args& Q, const a0_step_en
     // ---- the encoder's set-up: weight rings, biases (a0_encoder_fused_x9_body)
     a0_fused_args P;
     P.frames = nullptr; P.slot = nullptr; P.sample_stride = 4 * HW; P.chan_off = 0;
-    P.wt1 = N.wt; P.wt2 = N.wt + 48LL * 4 * 64; P.wt3 = P.wt2 + 64LL * 512;
-    P.wx2 = P.wt3 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256; P.wx3 = P.wx2 + 96LL * 512;
+    a0_fused_set_wt(P, N.wt, 4);
     P.b1 = N.b1; P.b2 = N.b2; P.b3 = N.b3;
     P.act1 = nullptr; P.act2 = nullptr; P.act3 = N.act3; P.B = Q.E;
     P.C = 4; P.H = 84; P.W = 84; P.H1 = 20; P.W1 = 20; P.H2 = 9; P.W2 = 9; P.H3 = 7; P.W3 = 7;
@@ -1187,11 +1030,11 @@ A0_D void a0_actor_step_enc2_body(const typename TAIL::Args& Q, const a0_step_en
     else
         a0_conv1_stage_split<MBW1X>(img, ring1, e1, before, mid, [&] { ring2.prologue(); });
     P.act3 = (float*)uni((unsigned long long)act3_v);
-    a0_x9_conv23<ORD, 3, 2, false>(P, (int)e, smem, bias_lds, ring1, ring2, ring3);
+    a0_x9_conv23<ORD, false>(P, (int)e, smem, bias_lds, ring1, ring2, ring3);
 }
 
 template <int ORD>
-__global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_actor_step_enc2_kernel(a0_qenv_args Q, a0_step_enc_args N) { a0_actor_step_enc2_body<ORD, TailScalar>(Q, N); }
+__global__ __launch_bounds__(A0_FUSED_THREADS) void a0_actor_step_enc2_kernel(a0_qenv_args Q, a0_step_enc_args N) { a0_actor_step_enc2_body<ORD, TailScalar>(Q, N); }
 
 static bool a0_fused_layout(int C, int H, int W, a0_fused_args& P, size_t& lds_bytes);
 int a0_actor_dist_step_enc_launch(const a0_dtenv_args& Q, size_t tail_lds, const float* wt, const a0_encoder_weights* w, float* act3, hipStream_t st) {
@@ -1241,16 +1084,17 @@ int a0_actor_step_enc_launch(const a0_qenv_args& Q, const float* wt, const a0_en
 // of the grid proportional to its observations; its workgroups run the unchanged per-pass body with their own weights, frames and outputs.
 struct a0_fused_multi_args { a0_fused_args p[3]; int first[4]; };
 template <int ORD>
-__global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_encoder_fused_multi_kernel(a0_fused_multi_args M) {
+__global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_fused_multi_kernel(a0_fused_multi_args M) {
     const int bid = (int)blockIdx.x;
     const int k = bid >= M.first[2] ? 2 : (bid >= M.first[1] ? 1 : 0);
-    a0_encoder_fused_x9_body<ORD, 7, 3, 2, true>(M.p[k], bid - M.first[k], M.first[k + 1] - M.first[k]);
+    a0_encoder_fused_x9_body<ORD, true>(M.p[k], bid - M.first[k], M.first[k + 1] - M.first[k]);
 }
 
 template <int MBW1, int MBW2, int MBW3, int WC, bool X9, bool LOOP, int ORD>
-__global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_encoder_fused_kernel(a0_fused_args P) {
+__global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_fused_kernel(a0_fused_args P) {
     if constexpr (X9) {
-        a0_encoder_fused_x9_body<ORD, MBW1, MBW2, MBW3, LOOP>(P, (int)blockIdx.x, (int)gridDim.x);
+        static_assert(MBW1 == 7 && MBW2 == 3 && MBW3 == 2 && WC == 84, "the split-operand body is written for the 4 x 84 x 84 geometry");
+        a0_encoder_fused_x9_body<ORD, LOOP>(P, (int)blockIdx.x, (int)gridDim.x);
         return;
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1275,7 +1119,7 @@ __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_encode
     pre2.load(EpiFwd<OW2>{P.b2, nullptr, 0, 0, 1, nullptr, 64}, M2);
     pre3.load(EpiFwd<0>{P.b3, nullptr, 0, 0, 1, nullptr, 64}, M3);
     for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
-        // ---- observation -> LDS as bf16: 16 bytes in, 32 bytes out per lane and trip; (float)byte is exact and its low 16 bits are zero
+        // ---- observation -> LDS as bf16: 16 bytes in, 32 bytes out per lane and trip
         const long long s = P.slot ? (long long)P.slot[b] : (long long)b;
         const uint4* src = (const uint4*)(P.frames + s * P.sample_stride + P.chan_off);
         // (all of a lane's loads are requested before the first is converted: one HBM latency per observation, not one per trip)
@@ -1290,19 +1134,8 @@ __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_encode
             }
 #pragma unroll
             for (int j = 0; j < TRIPS; ++j) {
-                int i = i0 + j * A0_FUSED_THREADS;
-                i = i < n16 ? i : n16 - 1;                 // lanes past the end redo the last group (same bytes, same address): no branch
-                const uint32_t w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-                uint32_t o[8];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t f0 = __float_as_uint((float)(w[k] & 0xffu)), f1 = __float_as_uint((float)((w[k] >> 8) & 0xffu));
-                    const uint32_t f2 = __float_as_uint((float)((w[k] >> 16) & 0xffu)), f3 = __float_as_uint((float)(w[k] >> 24));
-                    o[2 * k] = __builtin_amdgcn_perm(f1, f0, 0x07060302u);          // high halves of f0 (low) and f1 (high)
-                    o[2 * k + 1] = __builtin_amdgcn_perm(f3, f2, 0x07060302u);
-                }
-                ((uint4*)img)[2 * i] = uint4{o[0], o[1], o[2], o[3]};
-                ((uint4*)img)[2 * i + 1] = uint4{o[4], o[5], o[6], o[7]};
+                const int i = i0 + j * A0_FUSED_THREADS;
+                a0_bytes16_to_img(img, i < n16 ? i : n16 - 1, v[j]);      // lanes past the end redo the last group (same bytes, same address): no branch
             }
         }
         __syncthreads();
@@ -1334,16 +1167,16 @@ __global__ __launch_bounds__(A0_FUSED_THREADS, A0_FUSED_MINWAVES) void a0_encode
 struct a0_dgrad_args {
     const float *d3, *act1, *act2;
     float *d2, *d1;
-    const float *wd3, *wd2;          // the flipped / phase-split weights as three bf16 terms (a0_conv_wt_kernel, segments 8, 9): [576][64] and 4 x [256][32]
+    const float *wd3, *wd2;          // the flipped / phase-split weights as three bf16 terms (a0_wt_layout dgrad3x, dgrad2x): [576][64] and 4 x [256][32]
     int B;
 };
-// Both run on the bf16 pipe with both operands split exactly into three bf16 terms (see a0_conv_stage_x9):
+// Both run on the bf16 pipe with both operands split exactly into three bf16 terms (see a0_conv_stage_x9k):
 // d3 is split when it is loaded, d2 by conv3's epilogue; both live in LDS as three zero-padded 11 x 11 term-plane images (116 KB:
-// one workgroup per CU, eight waves), the flipped / phase-split weights come pre-split from a0_conv_wt_kernel (segments 8, 9).
+// one workgroup per CU, eight waves), the flipped / phase-split weights come pre-split from a0_conv_wt_kernel.
 // Nine v_mfma_f32_16x16x32_bf16 per 32 k replace eight v_mfma_f32_16x16x4_f32 of twice the pipe time each.
 // padded images: 11 x 11 pixels, A0_P2X bf16 per pixel (64 channels + 16); image rows padded like the forward planes, per image (3x3 taps,
 // 9-wide output: +192 bytes -> 4.7 LDS cycles per fragment read instead of 8.0; 2x2 taps, 10-wide output: +96 bytes -> 4.6 instead of 7.4)
-constexpr int A0_RPDA = 11 * A0_P2X + (A0_PADS ? 96 : 0), A0_RPDB = 11 * A0_P2X + (A0_PADS ? 48 : 0);
+constexpr int A0_RPDA = 11 * A0_P2X + 96, A0_RPDB = 11 * A0_P2X + 48;
 constexpr int A0_DTERMA = 11 * A0_RPDA, A0_DTERMB = 11 * A0_RPDB;      // elements per term plane
 struct AFD3X {   // 3x3 taps over the d3pad planes; MFMA step = half (32 channels) of tap st >> 1; output 9 wide
     static constexpr int term = A0_DTERMA;
@@ -1362,7 +1195,6 @@ struct EpiBwd3X {               // d2 = act2 > 0 ? acc : 0 -> global [81][64] an
     static constexpr bool ROW4 = false;
     static constexpr bool TR = true;
     const float* mask; float* dst; uint16_t* planes;
-    A0_D float pre_col(int) const { return 0.f; }
     A0_D a0_f4 pre_elem4(int m, int n0) const { return *(const a0_f4*)(mask + (unsigned)(m * 64 + n0)); }
     A0_D void emit_n4(int m, int n0, const a0_acc4& acc, const float* pre) const {
         float v[4];
@@ -1377,19 +1209,6 @@ struct EpiBwd3X {               // d2 = act2 > 0 ? acc : 0 -> global [81][64] an
     }
 };
 static_assert((A0_RPDB % 4) == 0 && (A0_DTERMB % 4) == 0 && (A0_P2X % 4) == 0, "8-byte aligned plane writes");
-template <int OW, int S>
-struct EpiBwdT {                // dx = mask > 0 ? acc : 0 at pixel (oh*S + ph, ow*S + pw) of a Wfull-wide NHWC image in global memory; transposed accumulators
-    static constexpr bool PER_ELEM = true;
-    static constexpr bool ROW4 = false;
-    static constexpr bool TR = true;
-    const float* mask; float* dst; int Wfull, ph, pw, N;
-    A0_D unsigned gi(int m, int n) const { const int oh = m / OW, ow = m - oh * OW; return (unsigned)(((oh * S + ph) * Wfull + ow * S + pw) * N + n); }
-    A0_D float pre_col(int) const { return 0.f; }
-    A0_D a0_f4 pre_elem4(int m, int n0) const { return *(const a0_f4*)(mask + gi(m, n0)); }
-    A0_D void emit_n4(int m, int n0, const a0_acc4& acc, const float* pre) const {
-        *(a0_f4*)(dst + gi(m, n0)) = a0_f4{pre[0] > 0.f ? acc[0] : 0.f, pre[1] > 0.f ? acc[1] : 0.f, pre[2] > 0.f ? acc[2] : 0.f, pre[3] > 0.f ? acc[3] : 0.f};
-    }
-};
 struct EpiBwdPair {             // two stride phases of conv2's data gradient side by side: virtual column n0 -> phase p0 + (n0 >> 5), channel n0 & 31; transposed accumulators
     static constexpr bool PER_ELEM = true;
     static constexpr bool ROW4 = false;
@@ -1399,71 +1218,30 @@ struct EpiBwdPair {             // two stride phases of conv2's data gradient si
         const int p = p0 + (n0 >> 5), oh = m / 10, ow = m - oh * 10;
         return (unsigned)(((oh * 2 + (p >> 1)) * 20 + ow * 2 + (p & 1)) * 32 + (n0 & 31));
     }
-    A0_D float pre_col(int) const { return 0.f; }
     A0_D a0_f4 pre_elem4(int m, int n0) const { return *(const a0_f4*)(mask + gi(m, n0)); }
     A0_D void emit_n4(int m, int n0, const a0_acc4& acc, const float* pre) const {
         *(a0_f4*)(dst + gi(m, n0)) = a0_f4{pre[0] > 0.f ? acc[0] : 0.f, pre[1] > 0.f ? acc[1] : 0.f, pre[2] > 0.f ? acc[2] : 0.f, pre[3] > 0.f ? acc[3] : 0.f};
     }
 };
-constexpr int A0_RXD3 = 6, A0_RXD2 = 4;               // 32-k steps of split weights in flight (18 and 8 steps per stage)
-
 template <int ORD>
 __global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_dgrad_fused_x9_kernel(a0_dgrad_args P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* plA = (uint16_t*)smem;                  // d3, padded by 2: three term planes
     uint16_t* plB = plA + 3 * A0_DTERMA;              // d2, padded by 1 (last row / column unused)
     for (int i = threadIdx.x; i < 3 * (A0_DTERMA + A0_DTERMB) / 2; i += A0_FUSED_THREADS) ((uint32_t*)smem)[i] = 0u;     // both images; borders stay zero for the whole launch
-#if A0_KSPLIT_D
     // N-stationary stages (a0_conv_stage_x9k): conv3's data gradient as in the forward kernel; conv2's four stride phases share their A operand
     // (the d2pad taps), so two phases at a time form ONE stage of 64 virtual columns — column block wn = phase (wn >> 1) of the pair, channel
-    // block wn & 1 — and every weight fragment of the kernel is loaded once per workgroup (was twice / four times), every d2pad fragment
+    // block wn & 1 — and every weight fragment of the kernel is loaded once per workgroup, every d2pad fragment
     // read for two phases at once.  Partial sums are exchanged through the 38 KB the two padded images leave free.
     float* const xch0 = (float*)(smem + 3 * (A0_DTERMA + A0_DTERMB) * 2);
     float* const xch1 = xch0 + 4 * 4 * 256;                // region 0: 4 column blocks x up to 4 row blocks x 1 KB
-    {
-        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wn = wave & 3, wk = wave >> 2;
-        a0_wring9<64, 4, 3, 2> ring3;
-        a0_wring9<64, 4, 2, 2> ringq[2];
-        ring3.init(P.wd3, 576);
-        ring3.prologue();
-        // phase matrices: 4 x [256 k][32 n] in the N = 32 ring layout (3072 uint4 each, 384 per k step)
-        const uint4* const wq = (const uint4*)P.wd2 + (((wn & 1) * 16 + (lane & 15)) * 4 + (lane >> 4)) * 3 + (wn >> 1) * 3072 + wk * 384;
-        __syncthreads();
-        for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
-            const a0_f4* src = (const a0_f4*)(P.d3 + (long long)b * 49 * 64);
-            for (int i = threadIdx.x; i < 49 * 16; i += A0_FUSED_THREADS) {
-                const a0_f4 v = src[i];
-                const int pos = i >> 4, c4 = (i & 15) * 4, h = pos / 7, w = pos - h * 7;
-                const float x[4] = {v.x, v.y, v.z, v.w};
-                uint2 hi, mid, lo;
-                a0_split4(x, hi, mid, lo);
-                uint16_t* d = plA + (h + 2) * A0_RPDA + (w + 2) * A0_P2X + c4;
-                *(uint2*)(d) = hi; *(uint2*)(d + A0_DTERMA) = mid; *(uint2*)(d + 2 * A0_DTERMA) = lo;
-            }
-            __syncthreads();
-            const AFD3X f3{plA};
-            const AFD2X f2{plB};
-            const EpiBwd3X e3{P.act2 + (long long)b * 81 * 64, P.d2 + (long long)b * 81 * 64, plB};
-            const EpiBwdPair e2a{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, 0};
-            const EpiBwdPair e2b{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, 2};
-            a0_conv_stage_x9k<ORD, 64, 4, 6, 3, 1>(f3, 81, ring3, e3, xch0, xch1, [&] { ringq[0].init_at(wq, 4, 768); ringq[0].prologue(); });
-            a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4>(f2, 100, ringq[0], e2a, xch0, xch1, [&] { ringq[1].init_at(wq + 2 * 3072, 4, 768); ringq[1].prologue(); });
-            a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4>(f2, 100, ringq[1], e2b, xch0, xch1, [&] { ring3.prologue(); });
-        }
-        return;
-    }
-#endif
-    a0_wring9<64, 4, A0_RXD3> ring3;
-    a0_wring9<32, 2, A0_RXD2> ringp[2];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wn = wave & 3, wk = wave >> 2;
+    a0_wring9<64, 4, 3, 2> ring3;
+    a0_wring9<64, 4, 2, 2> ringq[2];
     ring3.init(P.wd3, 576);
     ring3.prologue();
-    typedef EpiBwd3X E3;
-    typedef EpiBwdT<10, 2> E2;
-    a0_pre<64, 4, 3, E3> pre3;
-    a0_pre<32, 2, 2, E2> prep[2];
-    auto epi3 = [&](int b) { return E3{P.act2 + (long long)b * 81 * 64, P.d2 + (long long)b * 81 * 64, plB}; };
-    auto epi2 = [&](int b, int ph, int pw) { return E2{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, 20, ph, pw, 32}; };
-    if ((int)blockIdx.x < P.B) pre3.load(epi3(blockIdx.x), 81);
+    // phase matrices: 4 x [256 k][32 n] in the N = 32 ring layout (3072 uint4 each, 384 per k step)
+    const uint4* const wq = (const uint4*)P.wd2 + (((wn & 1) * 16 + (lane & 15)) * 4 + (lane >> 4)) * 3 + (wn >> 1) * 3072 + wk * 384;
     __syncthreads();
     for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
         const a0_f4* src = (const a0_f4*)(P.d3 + (long long)b * 49 * 64);
@@ -1471,40 +1249,35 @@ __global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_dgrad_fused_x9_ke
             const a0_f4 v = src[i];
             const int pos = i >> 4, c4 = (i & 15) * 4, h = pos / 7, w = pos - h * 7;
             const float x[4] = {v.x, v.y, v.z, v.w};
-            uint32_t hh[4], mm[4], ll[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                hh[e] = __float_as_uint(x[e]);
-                const float r1 = x[e] - __uint_as_float(hh[e] & 0xffff0000u);
-                mm[e] = __float_as_uint(r1);
-                ll[e] = __float_as_uint(r1 - __uint_as_float(mm[e] & 0xffff0000u));
-            }
+            uint2 hi, mid, lo;
+            a0_split4(x, hi, mid, lo);
             uint16_t* d = plA + (h + 2) * A0_RPDA + (w + 2) * A0_P2X + c4;
-            *(uint2*)(d) = uint2{__builtin_amdgcn_perm(hh[1], hh[0], 0x07060302u), __builtin_amdgcn_perm(hh[3], hh[2], 0x07060302u)};
-            *(uint2*)(d + A0_DTERMA) = uint2{__builtin_amdgcn_perm(mm[1], mm[0], 0x07060302u), __builtin_amdgcn_perm(mm[3], mm[2], 0x07060302u)};
-            *(uint2*)(d + 2 * A0_DTERMA) = uint2{__builtin_amdgcn_perm(ll[1], ll[0], 0x07060302u), __builtin_amdgcn_perm(ll[3], ll[2], 0x07060302u)};
+            *(uint2*)(d) = hi; *(uint2*)(d + A0_DTERMA) = mid; *(uint2*)(d + 2 * A0_DTERMA) = lo;
         }
         __syncthreads();
         const AFD3X f3{plA};
         const AFD2X f2{plB};
-        const int bn = b + gridDim.x < P.B ? b + gridDim.x : b;       // next observation of this workgroup (its masks are prefetched in the last slot)
-        // each `between` slot requests the NEXT stage's weights and ReLU masks before this stage's epilogue runs
-        a0_conv_stage_x9<ORD, 64, 4, 3, A0_RXD3>(f3, 81, ring3, epi3(b), pre3, [&] { ringp[0].init(P.wd2, 256); ringp[0].prologue(); prep[0].load(epi2(b, 0, 0), 100); });
-        a0_conv_stage_x9<ORD, 32, 2, 2, A0_RXD2>(f2, 100, ringp[0], epi2(b, 0, 0), prep[0], [&] { ringp[1].init(P.wd2 + 1 * 12288, 256); ringp[1].prologue(); prep[1].load(epi2(b, 0, 1), 100); });
-        a0_conv_stage_x9<ORD, 32, 2, 2, A0_RXD2>(f2, 100, ringp[1], epi2(b, 0, 1), prep[1], [&] { ringp[0].init(P.wd2 + 2 * 12288, 256); ringp[0].prologue(); prep[0].load(epi2(b, 1, 0), 100); });
-        a0_conv_stage_x9<ORD, 32, 2, 2, A0_RXD2>(f2, 100, ringp[0], epi2(b, 1, 0), prep[0], [&] { ringp[1].init(P.wd2 + 3 * 12288, 256); ringp[1].prologue(); prep[1].load(epi2(b, 1, 1), 100); });
-        a0_conv_stage_x9<ORD, 32, 2, 2, A0_RXD2>(f2, 100, ringp[1], epi2(b, 1, 1), prep[1], [&] { ring3.prologue(); pre3.load(epi3(bn), 81); });
+        const EpiBwd3X e3{P.act2 + (long long)b * 81 * 64, P.d2 + (long long)b * 81 * 64, plB};
+        const EpiBwdPair e2a{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, 0};
+        const EpiBwdPair e2b{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, 2};
+        a0_conv_stage_x9k<ORD, 64, 4, 6, 3, 1>(f3, 81, ring3, e3, xch0, xch1, [&] { ringq[0].init_at(wq, 4, 768); ringq[0].prologue(); });
+        a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4>(f2, 100, ringq[0], e2a, xch0, xch1, [&] { ringq[1].init_at(wq + 2 * 3072, 4, 768); ringq[1].prologue(); });
+        a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4>(f2, 100, ringq[1], e2b, xch0, xch1, [&] { ring3.prologue(); });
     }
 }
 
-// ---- weight copies for the fused kernels, from the packed [N][K] blocks (layouts: a0_wring1 / a0_wring):
-//   seg 1  conv1: fl(w/255) split exactly into three bf16 terms, 16-byte fragments ((t*32 + n)*4 + q)*3 + s   (12 C KB)
-//   seg 2,3 conv2, conv3 fragment-major fp32;  seg 4,5 the flipped / phase-split matrices of the data gradients (wd3 [576][64], wd2 4 x [256][32]; no kernel reads
-//           them any more, the layout keeps them: its size is a0_net_conv_wt_floats)
-//   seg 6,7 conv2, conv3 as three exact bf16 terms (a0_wring9 layout) for the split-operand forward path
-//   seg 8,9 the data-gradient matrices of seg 4,5 as three exact bf16 terms (a0_wring9 layout, N = 64 / 4 x N = 32)
+// ---- weight copies for the fused kernels, from the packed [N][K] blocks: the segments of a0_wt_layout
 A0_HD uint32_t a0_bf16_trunc(float f) { return __float_as_uint(f) >> 16; }
 A0_HD float a0_bf16_up(uint32_t h) { return __uint_as_float(h << 16); }
+// w = hi + mid + lo EXACTLY, three bf16 terms of 8 significant bits each: term s (0 = hi, 1 = mid, 2 = lo) as bf16 bits
+A0_HD uint32_t a0_bf16_term(float w, int s) {
+    const uint32_t hi = a0_bf16_trunc(w);
+    const float r1 = w - a0_bf16_up(hi);              // exact: at most 16 significant bits left
+    const uint32_t mid = a0_bf16_trunc(r1);
+    const float r2 = r1 - a0_bf16_up(mid);            // exact: at most 8 significant bits left
+    return s == 0 ? hi : s == 1 ? mid : a0_bf16_trunc(r2);
+}
+// One dword per thread.
 // wt2 / state: optional second destination (the target network's copies), written only when state[4] ("sync now", optim.hip) is set.
 // commit (a0_adam_step_sync_wt): the folded Adam kernel left the new step count in state[5]; this kernel, the next on the stream, moves it
 // to state[1] and clears the NaN flag state[0] — words the Adam kernel's workgroups were still reading.
@@ -1512,96 +1285,45 @@ __global__ void a0_conv_wt_kernel(const float* __restrict__ w1, const float* __r
                                   float* __restrict__ wt2, const int* __restrict__ state, int* __restrict__ commit) {
     const bool mirror = wt2 != nullptr && state[4] != 0;
     if (commit != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { commit[1] = commit[5]; commit[0] = 0; }
-    const int n1 = 48 * K1, n2 = 64 * 512, n3 = 64 * 576, n4 = 64 * 576, n5 = 4 * 32 * 256;      // n1: 32 channels x K1 x 3 terms x 2 bytes, in floats
-    const int n6 = 96 * 512, n7 = 96 * 576;                                                       // conv2 / conv3 as three bf16 terms: 64 x K x 3 x 2 bytes
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    float* dst = wt + i;
-    if (i < n1) {      // one dword = two consecutive k of one (t, s, n, q) fragment
-        const int pair = i & 3, f = i >> 2, s = f % 3, q = (f / 3) & 3, n = (f / 12) & 31, t = f / 384;
-        uint32_t out = 0;
+    const a0_wt_layout T{K1 / 64};
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.total()) return;
+    uint32_t out = 0;
+    if (i >= T.conv2() && i < T.conv2x()) {      // fp32, a0_wring layout: float ((c*64 + n)*4 + q)*4 + j holds W[n][k = 16c + 4j + q]
+        const bool c3 = i >= T.conv3();
+        const int e = i - (c3 ? T.conv3() : T.conv2());
+        const int j = e & 3, q = (e >> 2) & 3, n = (e >> 4) & 63, k = 16 * (e >> 10) + 4 * j + q;
+        out = __float_as_uint(c3 ? w3[n * 576 + k] : w2[n * 512 + k]);
+    } else {      // bf16 terms, a0_wring1 / a0_wring9 layout: uint4 ((t*N + n)*4 + q)*3 + s holds k = 32t + 8q .. +7 of column n, term s; a dword is two consecutive k
+        enum { CONV1, CONV2, CONV3, DGRAD3, DGRAD2 } seg;
+        int e, N = 64, phase = 0;
+        if (i < T.conv2()) { seg = CONV1; e = i; N = 32; }
+        else if (i < T.conv3x()) { seg = CONV2; e = i - T.conv2x(); }
+        else if (i < T.dgrad3x()) { seg = CONV3; e = i - T.conv3x(); }
+        else if (i < T.dgrad2x()) { seg = DGRAD3; e = i - T.dgrad3x(); }
+        else { seg = DGRAD2; e = i - T.dgrad2x(); phase = e / T.n_dgrad2x_phase; e -= phase * T.n_dgrad2x_phase; N = 32; }
+        const int pair = e & 3, f = e >> 2, s = f % 3, q = (f / 3) & 3, n = (f / 12) % N, t = f / (12 * N);
         for (int h = 0; h < 2; ++h) {
-            const int k = 32 * t + 8 * q + 2 * pair + h;
-            const float w = w1[n * K1 + k] / 255.0f;          // conv1 multiplies raw bytes: the reference's /255 is folded in here
-            const uint32_t hi = a0_bf16_trunc(w);
-            const float r1 = w - a0_bf16_up(hi);              // exact
-            const uint32_t mid = a0_bf16_trunc(r1);
-            const float r2 = r1 - a0_bf16_up(mid);            // exact, at most 8 significant bits left
-            const uint32_t lo = a0_bf16_trunc(r2);
-            out |= (s == 0 ? hi : s == 1 ? mid : lo) << (16 * h);
-        }
-        { *(uint32_t*)dst = out; if (mirror) *(uint32_t*)(wt2 + (dst - wt)) = out; }
-        return;
-    }
-    i -= n1;
-    {   // seg 6 / 7: exact three-term bf16 split of conv2 / conv3, same fragment layout as seg 1 with 64 output channels
-        const int j6 = i - (n2 + n3 + n4 + n5);
-        if (j6 >= 0) {
-            if (j6 >= n6 + n7) {       // seg 8 / 9: the data-gradient matrices (seg 4 / 5) as three exact bf16 terms, a0_wring9 layout
-                const int j8 = j6 - (n6 + n7), n8 = 96 * 576, n9p = 48 * 256;
-                if (j8 >= n8 + 4 * n9p) return;
-                const bool d2 = j8 >= n8;
-                const int phase = d2 ? (j8 - n8) / n9p : 0;
-                const int jj = d2 ? (j8 - n8) - phase * n9p : j8, N = d2 ? 32 : 64;
-                const int pair = jj & 3, f = jj >> 2, s = f % 3, q = (f / 3) & 3, n = (f / 12) % N, t = f / (12 * N);
-                uint32_t out = 0;
-                for (int h = 0; h < 2; ++h) {
-                    const int k = 32 * t + 8 * q + 2 * pair + h, cell = k >> 6, co = k & 63;
-                    float w;
-                    if (!d2) { const int kh = 2 - cell / 3, kw = 2 - cell % 3; w = w3[co * 576 + (kh * 3 + kw) * 64 + n]; }
-                    else { const int kh = (phase >> 1) + 2 * (1 - (cell >> 1)), kw = (phase & 1) + 2 * (1 - (cell & 1)); w = w2[co * 512 + (kh * 4 + kw) * 32 + n]; }
-                    const uint32_t hi = a0_bf16_trunc(w);
-                    const float r1 = w - a0_bf16_up(hi);
-                    const uint32_t mid = a0_bf16_trunc(r1);
-                    const uint32_t lo = a0_bf16_trunc(r1 - a0_bf16_up(mid));
-                    out |= (s == 0 ? hi : s == 1 ? mid : lo) << (16 * h);
-                }
-                { *(uint32_t*)dst = out; if (mirror) *(uint32_t*)(wt2 + (dst - wt)) = out; }
-                return;
+            const int k = 32 * t + 8 * q + 2 * pair + h, cell = k >> 6, co = k & 63;      // cell, co: tap and output channel of a data-gradient k
+            float w;
+            if (seg == CONV1) w = w1[n * K1 + k] / 255.0f;          // conv1 multiplies raw bytes: the reference's /255 is folded in here
+            else if (seg == CONV2) w = w2[n * 512 + k];
+            else if (seg == CONV3) w = w3[n * 576 + k];
+            else if (seg == DGRAD3) {                            // k = (kh'*3 + kw')*64 + co, n = ci: W3[co][2-kh'][2-kw'][ci]
+                const int kh = 2 - cell / 3, kw = 2 - cell % 3;
+                w = w3[co * 576 + (kh * 3 + kw) * 64 + n];
+            } else {                                             // k = (a'*2 + b')*64 + co, n = ci: W2[co][ph + 2(1-a')][pw + 2(1-b')][ci]
+                const int kh = (phase >> 1) + 2 * (1 - (cell >> 1)), kw = (phase & 1) + 2 * (1 - (cell & 1));
+                w = w2[co * 512 + (kh * 4 + kw) * 32 + n];
             }
-            const bool c3 = j6 >= n6;
-            const int jj = c3 ? j6 - n6 : j6, K = c3 ? 576 : 512;
-            const float* wsrc = c3 ? w3 : w2;
-            const int pair = jj & 3, f = jj >> 2, s = f % 3, q = (f / 3) & 3, n = (f / 12) & 63, t = f / 768;
-            uint32_t out = 0;
-            for (int h = 0; h < 2; ++h) {
-                const float w = wsrc[n * K + 32 * t + 8 * q + 2 * pair + h];
-                const uint32_t hi = a0_bf16_trunc(w);
-                const float r1 = w - a0_bf16_up(hi);
-                const uint32_t mid = a0_bf16_trunc(r1);
-                const uint32_t lo = a0_bf16_trunc(r1 - a0_bf16_up(mid));
-                out |= (s == 0 ? hi : s == 1 ? mid : lo) << (16 * h);
-            }
-            { *(uint32_t*)dst = out; if (mirror) *(uint32_t*)(wt2 + (dst - wt)) = out; }
-            return;
+            out |= a0_bf16_term(w, s) << (16 * h);
         }
     }
-    int N, seg;
-    if (i < n2) { seg = 2; N = 64; }
-    else if ((i -= n2) < n3) { seg = 3; N = 64; }
-    else if ((i -= n3) < n4) { seg = 4; N = 64; }
-    else if ((i -= n4) < n5) { seg = 5; N = 32; }
-    else return;
-    const int phase = seg == 5 ? i / 8192 : 0;
-    if (seg == 5) i -= phase * 8192;
-    const int j = i & 3, q = (i >> 2) & 3, n = (i >> 4) % N, c = (i >> 4) / N;
-    const int k = 16 * c + 4 * j + q;
-    float v;
-    if (seg == 2) v = w2[n * 512 + k];
-    else if (seg == 3) v = w3[n * 576 + k];
-    else if (seg == 4) {                               // k = (kh'*3 + kw')*64 + co, n = ci: W3[co][2-kh'][2-kw'][ci]
-        const int cell = k >> 6, co = k & 63, kh = 2 - cell / 3, kw = 2 - cell % 3;
-        v = w3[co * 576 + (kh * 3 + kw) * 64 + n];
-    } else {                                           // k = (a'*2 + b')*64 + co, n = ci: W2[co][ph + 2(1-a')][pw + 2(1-b')][ci]
-        const int cell = k >> 6, co = k & 63, kh = (phase >> 1) + 2 * (1 - (cell >> 1)), kw = (phase & 1) + 2 * (1 - (cell & 1));
-        v = w2[co * 512 + (kh * 4 + kw) * 32 + n];
-    }
-    *dst = v;
-    if (mirror) wt2[dst - wt] = v;
+    *(uint32_t*)(wt + i) = out;
+    if (mirror) *(uint32_t*)(wt2 + i) = out;
 }
 
-extern "C" long long a0_net_conv_wt_floats(int C) {
-    return 48LL * C * 64 + 64LL * 512 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256 + 96LL * 512 + 96LL * 576 + 96LL * 576 + 4LL * 48 * 256;
-}
+extern "C" long long a0_net_conv_wt_floats(int C) { return a0_wt_layout{C}.total(); }
 
 extern "C" int a0_net_conv_wt_refresh(const a0_encoder_weights* w, int C, float* wt, void* stream) {
     if (!w || !w->w1 || !w->w2 || !w->w3 || !wt || C < 1) return a0_fail(A0_EINVAL, "a0_net_conv_wt_refresh: bad argument");
@@ -1648,6 +1370,17 @@ static bool a0_fused_layout(int C, int H, int W, a0_fused_args& P, size_t& lds_b
     return lds_bytes <= 160 * 1024;
 }
 
+// Everything a launch of the fused forward passes to the kernel; false when the fused kernels do not support the shape.
+static bool a0_fused_fill(int C, int H, int W, const float* wt, const a0_encoder_weights* w, const a0_frames_arg* f, float* act1, float* act2, float* act3, int B,
+                          a0_fused_args& P, size_t& lds_bytes) {
+    if (!a0_fused_layout(C, H, W, P, lds_bytes)) return false;
+    P.frames = f->frames; P.slot = f->slot; P.sample_stride = f->sample_stride; P.chan_off = f->chan_off;
+    a0_fused_set_wt(P, wt, C);
+    P.b1 = w->b1; P.b2 = w->b2; P.b3 = w->b3;
+    P.act1 = act1; P.act2 = act2; P.act3 = act3; P.B = B;
+    return true;
+}
+
 extern "C" int a0_net_encoder_fused_supported(int C, int H, int W) {
     a0_fused_args P; size_t lds;
     return a0_fused_layout(C, H, W, P, lds) ? 1 : 0;
@@ -1660,13 +1393,8 @@ extern "C" int a0_net_encoder_fwd_fused(int C, int H, int W, const float* wt, co
     if (!wt || !w || !w->b1 || !w->b2 || !w->b3 || !f || !f->frames || !act3 || B < 1) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused: bad argument");
     a0_fused_args P;
     size_t lds = 0;
-    if (!a0_fused_layout(C, H, W, P, lds)) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused: observation shape not supported by the fused kernel");
+    if (!a0_fused_fill(C, H, W, wt, w, f, act1, act2, act3, B, P, lds)) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused: observation shape not supported by the fused kernel");
     if ((f->sample_stride % 16) || (f->chan_off % 16) || (((uintptr_t)f->frames) % 16)) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused: frames must be 16-byte aligned");
-    P.frames = f->frames; P.slot = f->slot; P.sample_stride = f->sample_stride; P.chan_off = f->chan_off;
-    P.wt1 = wt; P.wt2 = wt + 48LL * C * 64; P.wt3 = P.wt2 + 64LL * 512;
-    P.wx2 = P.wt3 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256; P.wx3 = P.wx2 + 96LL * 512;      // behind the data-gradient copies
-    P.b1 = w->b1; P.b2 = w->b2; P.b3 = w->b3;
-    P.act1 = act1; P.act2 = act2; P.act3 = act3; P.B = B;
     // 16-row blocks per wave: conv1 ceil(MB1/4), conv2 ceil(MB2/2), conv3 ceil(MB3/2); exact for 84x84, generous otherwise
     const int mb1 = (P.H1 * P.W1 + 15) / 16, mb2 = (P.H2 * P.W2 + 15) / 16, mb3 = (P.H3 * P.W3 + 15) / 16;
     const bool standard = ((mb1 + 3) / 4 == 7) && ((mb2 + 1) / 2 == 3) && ((mb3 + 1) / 2 == 2) && W == 84;
@@ -1711,13 +1439,8 @@ extern "C" int a0_net_encoder_fwd_fused_multi(int C, int H, int W, int n, const 
         const a0_encoder_pass& q = pass[i];
         if (!q.wt || !q.w || !q.w->b1 || !q.w->b2 || !q.w->b3 || !q.f || !q.f->frames || !q.act3 || q.B < 1) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused_multi: bad pass");
         if ((q.f->sample_stride % 16) || (q.f->chan_off % 16) || (((uintptr_t)q.f->frames) % 16)) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused_multi: frames must be 16-byte aligned");
-        a0_fused_args& P = M.p[i];
-        if (!a0_fused_layout(C, H, W, P, lds)) return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused_multi: observation shape");
-        P.frames = q.f->frames; P.slot = q.f->slot; P.sample_stride = q.f->sample_stride; P.chan_off = q.f->chan_off;
-        P.wt1 = q.wt; P.wt2 = q.wt + 48LL * C * 64; P.wt3 = P.wt2 + 64LL * 512;
-        P.wx2 = P.wt3 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256; P.wx3 = P.wx2 + 96LL * 512;
-        P.b1 = q.w->b1; P.b2 = q.w->b2; P.b3 = q.w->b3;
-        P.act1 = q.act1; P.act2 = q.act2; P.act3 = q.act3; P.B = q.B;
+        if (!a0_fused_fill(C, H, W, q.wt, q.w, q.f, q.act1, q.act2, q.act3, q.B, M.p[i], lds))
+            return a0_fail(A0_EINVAL, "a0_net_encoder_fwd_fused_multi: observation shape");
         total += q.B;
     }
     for (int i = n; i < 3; ++i) M.p[i] = M.p[0];
@@ -1759,10 +1482,8 @@ extern "C" int a0_net_encoder_dgrad_fused(int C, int H, int W, const float* wt, 
     if (!a0_net_encoder_dgrad_fused_supported(C, H, W)) return a0_fail(A0_EINVAL, "a0_net_encoder_dgrad_fused: 84x84 observations only");
     a0_dgrad_args P;
     P.d3 = d3; P.act1 = act1; P.act2 = act2; P.d2 = d2; P.d1 = d1; P.B = B;
-    // the split weights of segments 8, 9, behind the fp32 copies (segments 2..5) and the forward path's split copies (segments 6, 7)
-    P.wd3 = wt + 48LL * C * 64 + 64LL * 512 + 64LL * 576 + 64LL * 576 + 4LL * 32 * 256 + 96LL * 512 + 96LL * 576;
-    P.wd2 = P.wd3 + 96LL * 576;
-    const size_t lds = (size_t)3 * (A0_DTERMA + A0_DTERMB) * 2 + (A0_KSPLIT_D ? (4 * 4 + 4 * 3) * 1024 : 0);      // + the exchange regions of the N-stationary stages
+    P.wd3 = wt + a0_wt_layout{C}.dgrad3x(); P.wd2 = wt + a0_wt_layout{C}.dgrad2x();
+    const size_t lds = (size_t)3 * (A0_DTERMA + A0_DTERMB) * 2 + (4 * 4 + 4 * 3) * 1024;      // + the exchange regions of the N-stationary stages
     static bool configured[2] = {false, false};
     const int six = a0_x9_products_now() == 6;
     auto fn = six ? a0_encoder_dgrad_fused_x9_kernel<2> : a0_encoder_dgrad_fused_x9_kernel<4>;

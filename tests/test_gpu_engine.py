@@ -474,15 +474,23 @@ def test_conv1_bf16_split_is_exact_and_fp32_accurate():
     w1 = net.encoder_weights()["w1"].cpu().numpy().reshape(32, K1)
     want = (w1 / np.float32(255.0)).astype(np.float32)
     assert np.array_equal(got.astype(np.float32), want) and np.array_equal(got, want.astype(np.float64))
-    # conv2 / conv3 (split-operand path): same exactness for the weight terms, fragment layout [t][n][q][s][8] with 64 channels
-    off = 48 * K1 + 64 * 512 + 64 * 576 + 64 * 576 + 4 * 32 * 256
-    for name, K, length in (("w2", 512, 96 * 512), ("w3", 576, 96 * 576)):
-        raw = net.wt[off:off + length].view(torch.int32).cpu().numpy().view(np.uint16).reshape(K // 32, 64, 4, 3, 8)
+    # conv2 / conv3 (split-operand path) and the data gradients' matrices: same exactness for the weight terms, fragment layout [t][n][q][s][8]
+    off = 48 * K1 + 64 * 512 + 64 * 576           # behind conv1's terms and the fp32 copies of conv2 / conv3
+    w2 = net.encoder_weights()["w2"].cpu().numpy().reshape(64, 4, 4, 32)      # [co][kh][kw][ci]
+    w3 = net.encoder_weights()["w3"].cpu().numpy().reshape(64, 3, 3, 64)
+    # the data gradients' matrices [ci][k = tap * 64 + co]: conv3 with flipped taps; conv2 per stride phase (ph, pw), taps (ph + 2(1-a'), pw + 2(1-b'))
+    wd3 = np.transpose(w3[:, ::-1, ::-1, :], (3, 1, 2, 0)).reshape(64, 576)
+    wd2 = [np.transpose(w2[:, [ph + 2, ph]][:, :, [pw + 2, pw]], (3, 1, 2, 0)).reshape(32, 256) for ph in (0, 1) for pw in (0, 1)]
+    segments = [("w2", 64, 512, w2.reshape(64, 512)), ("w3", 64, 576, w3.reshape(64, 576)), ("wd3", 64, 576, wd3)]
+    segments += [(f"wd2[{p}]", 32, 256, wd2[p]) for p in range(4)]
+    for name, N, K, want in segments:
+        length = 3 * N * K // 2
+        raw = net.wt[off:off + length].view(torch.int32).cpu().numpy().view(np.uint16).reshape(K // 32, N, 4, 3, 8)
         terms = (raw.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-        got = np.transpose(terms[:, :, :, 0] + terms[:, :, :, 1] + terms[:, :, :, 2], (1, 0, 2, 3)).reshape(64, K)
-        want = net.encoder_weights()[name].cpu().numpy().reshape(64, K)
+        got = np.transpose(terms[:, :, :, 0] + terms[:, :, :, 1] + terms[:, :, :, 2], (1, 0, 2, 3)).reshape(N, K)
         assert np.array_equal(got, want.astype(np.float64)), name
         off += length
+    assert off == net.wt.numel()
     # ---- (2) accuracy against fp64
     B = 2
     g = recipe.gen(77)
