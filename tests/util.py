@@ -157,3 +157,95 @@ def scale_err(got, want, scale):
     got, want, scale = _np(got), _np(want), _np(scale)
     assert got.shape == want.shape == scale.shape, (got.shape, want.shape, scale.shape)
     return (got - want) / np.maximum(scale, 1e-30)
+
+
+# ------------------------------------------------------------------------------------------------ float64 action-selection references (numpy)
+# What the actor's tail kernels compute between a head GEMM's split-K slabs and the action (slab sum + bias, dueling combine, action values, first maximum),
+# in float64, every result with its accumulated magnitude: the same computation on absolute values, the scale an fp32 evaluation's rounding error is
+# measured on.  No import of the library (tests/test_actor_tail_reference_helpers.py checks them against oracle/nets.py).
+def _dueling64(x, A):
+    """q(a) = v + (x(a) - mean_a x) over axis 1 of x [E][A + 1][T] (row A: the value stream)."""
+    return x[:, A:A + 1] + (x[:, :A] - x[:, :A].mean(1, keepdims=True))
+
+
+def head_from_slabs64(slabs, bias, A, T, dueling, kt):
+    """(q, scale) [E][A][T] of a head GEMM's split-K slabs [nslab][rows][ld]: slab sum + bias, then the dueling combine per atom.  ``kt`` = 0: one row per
+    env, columns (a, t) followed by the value stream's T columns, a bias per column; ``kt`` = 1: rows (env, quantile), columns a followed by the value
+    column, a bias per column.  Pad columns beyond those are ignored."""
+    s, b = np.asarray(slabs, np.float64), np.asarray(bias, np.float64)
+    NQ = A + (1 if dueling else 0)
+
+    def arrange(x, bb):
+        raw = x.sum(0)
+        if kt:
+            return (raw.reshape(-1, T, raw.shape[-1])[:, :, :NQ] + bb[:NQ]).transpose(0, 2, 1)
+        return (raw[:, :NQ * T] + bb[:NQ * T]).reshape(-1, NQ, T)
+
+    q, m = arrange(s, b), arrange(np.abs(s), np.abs(b))
+    if dueling:
+        q, m = _dueling64(q, A), m[:, A:A + 1] + (m[:, :A] + m[:, :A].mean(1, keepdims=True))
+    return np.ascontiguousarray(q), np.ascontiguousarray(m)
+
+
+def action_values64(q, mode, aux=None, qscale=None):
+    """(values, scale) [E][A] of q [E][A][T] (``qscale``: q's own accumulated magnitude, |q| if not given).  mode 0: q[..., 0]; 1: mean over t;
+    2: sum_t softmax_t(q) atoms[t] (``aux`` = atoms [T]; scale sum_t p_t |atoms[t]|, the magnitude the expectation's errors are relative to);
+    3: sum_t (tau[t + 1] - tau[t]) q (``aux`` = tau [E][T + 1])."""
+    q = np.asarray(q, np.float64)
+    m = np.abs(q) if qscale is None else np.asarray(qscale, np.float64)
+    if mode == 0:
+        return q[:, :, 0].copy(), m[:, :, 0].copy()
+    if mode == 1:
+        return q.mean(2), m.mean(2)
+    if mode == 2:
+        z = np.asarray(aux, np.float64)
+        p = np.exp(q - q.max(2, keepdims=True))
+        p /= p.sum(2, keepdims=True)
+        return (p * z).sum(2), (p * np.abs(z)).sum(2)
+    if mode == 3:
+        tau = np.asarray(aux, np.float64)
+        d = (tau[:, 1:] - tau[:, :-1])[:, None, :]
+        return (d * q).sum(2), (np.abs(d) * m).sum(2)
+    raise ValueError(mode)
+
+
+def qhead64(feat, W1, b1, W2, b2, A, dueling):
+    """(q, scale) [E][A] of the scalar head: h = relu(feat W1^T + b1), raw = h W2^T + b2, dueling combine.  The scale carries fc1's accumulated
+    magnitude (|feat| |W1|^T + |b1|, which bounds |h|: ReLU is 1-Lipschitz) through |W2| and |b2| and the combine, as encoder_chain64 carries a layer's."""
+    f, w1, bb1, w2, bb2 = (np.asarray(x, np.float64) for x in (feat, W1, b1, W2, b2))
+    h = np.maximum(f @ w1.T + bb1, 0.0)
+    s1 = np.abs(f) @ np.abs(w1).T + np.abs(bb1)
+    # row by row, every row summed in the same order: bit-identical head rows give bit-identical values (a BLAS product does not promise that)
+    q, m = (h[:, None, :] * w2[None]).sum(2) + bb2, (s1[:, None, :] * np.abs(w2)[None]).sum(2) + np.abs(bb2)
+    if dueling:
+        q, m = _dueling64(q[:, :, None], A)[:, :, 0], m[:, A:A + 1] + (m[:, :A] + m[:, :A].mean(1, keepdims=True))
+    return np.ascontiguousarray(q[:, :A]), np.ascontiguousarray(m[:, :A])
+
+
+def greedy_check(values64, tol, got_action, got_qmax, what="", exclude=None, tie=None, allow_empty=False):
+    """Judges a device's greedy actions and their values against float64 action values [E][A] with a per-element error bound ``tol`` [E][A].  Env e is
+    DECIDED when exactly one action lies within tol[e, a] + tol[e, a*] of the maximum: there the device's action must be the float64 argmax; on an
+    undecided env it must be one of those candidates.  ``got_qmax`` must lie within tol of the float64 value of the action the device chose.  ``tie`` =
+    (i, j), i < j: two actions whose inputs are bit-identical — wherever their float64 values are equal the device may never answer j (the first maximum
+    wins).  Returns the share of undecided envs among those not flagged in ``exclude`` (bool [E]); if that leaves no env to judge the check fails, unless
+    ``allow_empty`` (a single env, or two actions that are the tied pair: nothing but the tie can be asked for)."""
+    v, tol = np.asarray(values64, np.float64), np.asarray(tol, np.float64)
+    act, qm = np.asarray(got_action).astype(np.int64).reshape(-1), np.asarray(got_qmax, np.float64).reshape(-1)
+    E, A = v.shape
+    assert tol.shape == v.shape and act.shape == (E,) and qm.shape == (E,), (v.shape, tol.shape, act.shape, qm.shape)
+    assert ((act >= 0) & (act < A)).all(), f"{what}: actions outside [0, {A}): {act}"
+    best = v.argmax(1)
+    rows = np.arange(E)
+    cand = (v[rows, best][:, None] - v) <= (tol + tol[rows, best][:, None])
+    undecided = cand.sum(1) > 1
+    assert cand[rows, act].all(), f"{what}: envs {np.nonzero(~cand[rows, act])[0]}: action {act[~cand[rows, act]]}, float64 argmax {best[~cand[rows, act]]}"
+    err = np.abs(qm - v[rows, act])
+    bad = ~(err <= tol[rows, act])
+    assert not bad.any(), f"{what}: max-Q of envs {np.nonzero(bad)[0]} off by {err[bad]} (bound {tol[rows, act][bad]})"
+    if tie is not None:
+        i, j = tie
+        wrong = (act == j) & (v[:, i] == v[:, j])
+        assert not wrong.any(), f"{what}: envs {np.nonzero(wrong)[0]}: of two equal actions {i} and {j} the later one was chosen"
+    keep = np.ones(E, bool) if exclude is None else ~np.asarray(exclude, bool)
+    assert keep.any() or allow_empty, f"{what}: every env is excluded, no free maximum is judged"
+    return float(undecided[keep].mean()) if keep.any() else 0.0
