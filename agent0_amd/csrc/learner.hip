@@ -293,6 +293,19 @@ extern "C" int a0_learner_set_exchange(a0_learner* L, long long comm) {
     A0_CATCH
 }
 
+extern "C" int a0_learner_set_grad_clip(a0_learner* L, double max_norm, float* norm_ring_dev, int ring_cap) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_grad_clip: null handle");
+    if (!(max_norm > 0.0)) { L->clip_max_norm = 0.f; return A0_OK; }
+    if (norm_ring_dev && ring_cap < 1) return a0_fail(A0_EINVAL, "a0_learner_set_grad_clip: a caller's ring needs ring_cap >= 1");
+    if (!L->gnorm_partials) L->gnorm_partials = L->alloc<double>(A0_GRAD_NORM_PARTIALS, true);
+    if (norm_ring_dev) { L->gnorm_ring = norm_ring_dev; L->gnorm_ring_cap = ring_cap; }
+    else { L->gnorm_ring_cap = ring_cap > 0 ? ring_cap : 1024; L->gnorm_ring = L->alloc<float>(L->gnorm_ring_cap, true); }
+    L->clip_max_norm = (float)max_norm;
+    return A0_OK;
+    A0_CATCH
+}
+
 extern "C" int a0_learner_set_params(a0_learner* L, const float* online_packed, const float* target_packed, void* stream) {
     A0_TRY
     if (!L || !online_packed) return a0_fail(A0_EINVAL, "a0_learner_set_params: null argument");
@@ -324,6 +337,7 @@ extern "C" int a0_learner_peek(const a0_learner* L, int what, float** dev_ptr, l
         case A0_PEEK_ACT3: *dev_ptr = L->act3_o; *count = B * L->feat; break;
         case A0_PEEK_FC1: *dev_ptr = (L->d.algo == A0_ALGO_IQN || L->d.algo == A0_ALGO_FQF) ? L->qo.h : L->h; *count = ((L->d.algo == A0_ALGO_IQN || L->d.algo == A0_ALGO_FQF) ? L->qo.R : B) * 512; break;
         case A0_PEEK_LOSS: *dev_ptr = L->loss; *count = B; break;
+        case A0_PEEK_GRAD_NORM_RING: *dev_ptr = L->gnorm_ring; *count = L->gnorm_ring_cap; break;
         default: return a0_fail(A0_EINVAL, "a0_learner_peek: unknown buffer");
     }
     if (!*dev_ptr) return a0_fail(A0_ESTATE, "a0_learner_peek: this learner does not keep that buffer");
@@ -686,6 +700,14 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
         A0_CHECK(a0_rmsprop_step(on + L->frac.off, L->grads + L->frac.off, L->rms_sq, L->frac.size(), L->d.lr / 2e4, 0.95, 1e-5, L->d.max_grad_norm > 0.0 ? L->d.max_grad_norm : -1.0, L->clip, stream));
     // ---- Adam (eps = 1e-2 / B unless given), NaN guard, update counter, target copy every target_update_freq updates, weight-copy refresh (agent.py:102-106,152-161)
     const double eps = L->d.adam_eps > 0.0 ? L->d.adam_eps : 1e-2 / (double)B;
+    if (L->clip_max_norm > 0.f) {
+        // learner.clip_grad_norm (DeviceLearner.apply): every gradient Adam owns is final here — summed over the ranks behind the join above — so one launch takes
+        // its sum of squares and the Adam launch turns it into the norm, the coefficient and the ring entry
+        A0_CHECK(a0_grad_norm_partials(L->grads, L->n_adam, L->gnorm_partials, stream));
+        A0_CHECK(a0_adam_step_sync_wt_clip(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, L->d.target_update_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
+                                           L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, L->gnorm_partials, L->clip_max_norm, L->gnorm_ring, L->gnorm_ring_cap, stream));
+        return A0_OK;
+    }
     A0_CHECK(a0_adam_step_sync_wt(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, L->d.target_update_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
                                   L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, stream));
     return A0_OK;

@@ -65,6 +65,11 @@ struct a0_learner {
     int ns_fc1 = 1;
     long long slab_off[2] = {0, 0}, enc_slab_off = 0;
     int loss_ring_cap = 1024;
+    // ---- global gradient-norm clipping in front of Adam (a0_learner_set_grad_clip): off while clip_max_norm <= 0
+    float clip_max_norm = 0.f;
+    double* gnorm_partials = nullptr;
+    float* gnorm_ring = nullptr;
+    int gnorm_ring_cap = 0;
     // library-owned HBM
     float *online = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *scalars = nullptr, *loss_ring = nullptr;
     float *wt_on = nullptr, *wt_tg = nullptr;

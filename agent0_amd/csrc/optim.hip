@@ -68,12 +68,77 @@ extern "C" int a0_adam_step(float* params, const float* grads, float* exp_avg, f
 // state[2..4] as the prep kernel does, the scalars, and the NEW step count in state[5].  state[1] <- state[5] and state[0] <- 0 are
 // committed by the next kernel on the stream (a0_conv_wt_kernel with `commit`), because other workgroups of this one may still have to read them.
 struct a0_adam_fold { double lr, b1, b2; int target_freq; const float* extra_flag; int* state_w; float* scal_w; const float* loss; int loss_n; float* loss_ring; int ring_cap; };
-template <bool FOLD>
+
+// Global gradient-norm clipping (learner.clip_grad_norm; torch.nn.utils.clip_grad_norm_ with its defaults), stage 1: the sum of squares of g[0, n) as
+// A0_GRAD_NORM_PARTIALS partial sums.  Workgroup b owns the elements [b * chunk, (b + 1) * chunk) — chunk a multiple of four, a function of n alone — and writes
+// partials[b] with a plain store (0 when its range is empty): no atomics, no "last workgroup" counter, and the same bits on every run.  Squares and sums are doubles:
+// the square of a float is exact in double, so the only rounding of the norm that matters is stage 2's final cast.  vec4: g is 16-byte aligned (16-byte loads, a
+// scalar tail); otherwise element by element.
+__global__ __launch_bounds__(256) void a0_grad_sumsq_kernel(const float* __restrict__ g, long long n, long long chunk, int vec4, double* __restrict__ partials) {
+    __shared__ double red[256];
+    const long long lo = (long long)blockIdx.x * chunk;
+    const long long hi = lo + chunk < n ? lo + chunk : n;
+    double s = 0.0;
+    if (lo < hi) {
+        long long done = 0;
+        if (vec4) {
+            const long long n4 = (hi - lo) >> 2;
+            const a0_f4* g4 = (const a0_f4*)(g + lo);
+            for (long long j = threadIdx.x; j < n4; j += 256) {
+                const a0_f4 x = g4[j];
+                s += (double)x.x * (double)x.x; s += (double)x.y * (double)x.y; s += (double)x.z * (double)x.z; s += (double)x.w * (double)x.w;
+            }
+            done = n4 << 2;
+        }
+        for (long long i = lo + done + threadIdx.x; i < hi; i += 256) s += (double)g[i] * (double)g[i];
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+extern "C" int a0_grad_norm_partials(const float* grads, long long n, double* partials, void* stream) {
+    if (!grads || !partials || n < 1 || (((uintptr_t)grads) & 3) || (((uintptr_t)partials) & 7)) return a0_fail(A0_EINVAL, "a0_grad_norm_partials: bad argument");
+    const long long chunk = ((n + A0_GRAD_NORM_PARTIALS - 1) / A0_GRAD_NORM_PARTIALS + 3) / 4 * 4;
+    hipLaunchKernelGGL(a0_grad_sumsq_kernel, dim3(A0_GRAD_NORM_PARTIALS), dim3(256), 0, (hipStream_t)stream, grads, n, chunk, (((uintptr_t)grads) & 15) == 0 ? 1 : 0, partials);
+    return a0_fail_hip((int)hipGetLastError(), "a0_grad_norm_partials");
+}
+
+// the product alone, rounded to fp32: never contracted into the subtraction or the multiply-add that consumes it, so that stepping on g * coef gives the bits of
+// a0_adam_step_sync on a gradient buffer multiplied by coef beforehand
+A0_D float a0_mul_rounded(float a, float b) {
+    float r;
+    {
+#pragma clang fp contract(off)
+        r = a * b;
+    }
+    asm volatile("" : "+v"(r));      // the Adam arithmetic behind it sees a plain register value, as it sees a loaded gradient
+    return r;
+}
+
+// stage 2 (CLIP): every workgroup sums the partials in the same order, so all of them step on the same coefficient; workgroup 0 files the norm
+struct a0_adam_clip { const double* partials; float max_norm; float* norm_ring; int ring_cap; };
+template <bool FOLD, bool CLIP>
 __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                     long long n, const int* __restrict__ state, const float* __restrict__ scal,
-                                    float w1, float b2, float w2, float eps, float* __restrict__ target, long long n_total, int vec4, a0_adam_fold F) {
+                                    float w1, float b2, float w2, float eps, float* __restrict__ target, long long n_total, int vec4, a0_adam_fold F, a0_adam_clip K) {
     bool skip, sync;
     float step_size, bc2_sqrt;
+    float coef = 1.f;
+    if constexpr (CLIP) {
+        // ||g|| = sqrt(sum of the partials), rounded to fp32 once; coef = min(1, max_norm / (||g|| + 1e-6)) in fp32.  The pre-clip norm goes to ring slot
+        // state[6] % cap — the slot of this update's loss mean, read before workgroup 0 advances the counter below — on skipped (NaN) steps too.
+        static_assert(A0_GRAD_NORM_PARTIALS == 256, "one partial per lane of the 256-lane workgroup");
+        __shared__ double cred[256];
+        cred[threadIdx.x] = K.partials[threadIdx.x];
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) cred[threadIdx.x] += cred[threadIdx.x + o]; __syncthreads(); }
+        const float norm = (float)sqrt(cred[0]);
+        if (blockIdx.x == 0 && threadIdx.x == 0) K.norm_ring[(FOLD ? F.state_w[6] : state[6]) % K.ring_cap] = norm;
+        const float c = K.max_norm / (norm + 1e-6f);
+        coef = c < 1.f ? c : 1.f;
+    }
     if constexpr (FOLD) {
         __shared__ float sh_f[2];
         __shared__ int sh_i[2];
@@ -121,7 +186,7 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
                 float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float gi = gp[e];
+                    const float gi = CLIP ? a0_mul_rounded(gp[e], coef) : gp[e];
                     float mi = mp[e], vi = vp[e];
                     mi = mi + (gi - mi) * w1;
                     vi = vi * b2 + (w2 * gi) * gi;
@@ -138,7 +203,7 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
     for (; i < end; i += stride) {
         float pi = p[i];
         if (i < n && !skip) {
-            const float gi = g[i];
+            const float gi = CLIP ? a0_mul_rounded(g[i], coef) : g[i];
             float mi = m[i], vi = v[i];
             mi = mi + (gi - mi) * w1;
             vi = vi * b2 + (w2 * gi) * gi;
@@ -152,44 +217,92 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
     }
 }
 
-extern "C" int a0_adam_step_sync(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
-                                 double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
-                                 const float* extra_nan_flag, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n)
-        return a0_fail(A0_EINVAL, "a0_adam_step_sync: bad argument");
+static int a0_adam_sync_plain(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                              double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                              const float* extra_nan_flag, const a0_adam_clip* clip, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n) return a0_fail(A0_EINVAL, who);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(a0_adam_prep_kernel, dim3(1), dim3(1), 0, st, state, scalars, lr, beta1, beta2, target_update_freq, extra_nan_flag);
     const int vec4 = ((n | n_total) % 4 == 0) &&
                      ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
     long long blocks = ((vec4 ? n_total / 4 : n_total) + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(a0_adam_sync_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, state, scalars,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, a0_adam_fold{0.0, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1});
-    return a0_fail_hip((int)hipGetLastError(), "a0_adam_step_sync");
+    const a0_adam_fold F{0.0, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1};
+    if (clip)
+        hipLaunchKernelGGL((a0_adam_sync_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, *clip);
+    else
+        hipLaunchKernelGGL((a0_adam_sync_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, a0_adam_clip{nullptr, 0.f, nullptr, 1});
+    return a0_fail_hip((int)hipGetLastError(), who);
+}
+
+extern "C" int a0_adam_step_sync(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                                 double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                                 const float* extra_nan_flag, void* stream) {
+    return a0_adam_sync_plain("a0_adam_step_sync: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                              extra_nan_flag, nullptr, stream);
+}
+
+static bool a0_clip_args_ok(const double* partials, float max_norm, const float* norm_ring, int norm_ring_cap) {
+    return partials && (((uintptr_t)partials) & 7) == 0 && max_norm > 0.f && norm_ring && norm_ring_cap >= 1;
+}
+
+// a0_adam_step_sync on g * min(1, max_norm / (||g|| + 1e-6)), ||g|| from the partials a0_grad_norm_partials left for this gradient buffer
+extern "C" int a0_adam_step_sync_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                                      double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                                      const float* extra_nan_flag, const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream) {
+    if (!a0_clip_args_ok(partials, max_norm, norm_ring, norm_ring_cap)) return a0_fail(A0_EINVAL, "a0_adam_step_sync_clip: partials, max_norm > 0 and a norm ring of at least one slot");
+    const a0_adam_clip clip{partials, max_norm, norm_ring, norm_ring_cap};
+    return a0_adam_sync_plain("a0_adam_step_sync_clip: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                              extra_nan_flag, &clip, stream);
 }
 
 // The optimizer tail of a network with fused-kernel weight copies, in TWO launches: Adam with the step's bookkeeping folded in (no one-thread
 // prep kernel in front), then the refresh of the online net's weight copies (mirrored into the target's on a sync step), which also commits
 // the step counter.  Same results as a0_adam_step_sync + a0_net_conv_wt_refresh_sync.
 int a0_conv_wt_refresh_commit(const a0_encoder_weights* w, int C, float* wt, float* wt_target, int* state, hipStream_t st);      // encoder_fused.hip
-extern "C" int a0_adam_step_sync_wt(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
-                                    double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
-                                    const float* extra_nan_flag, const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n,
-                                    float* loss_ring, int ring_cap, void* stream) {
+static int a0_adam_sync_fold(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                             double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                             const float* extra_nan_flag, const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n,
+                             float* loss_ring, int ring_cap, const a0_adam_clip* clip, void* stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n || !w || !wt || !wt_target || C < 1)
-        return a0_fail(A0_EINVAL, "a0_adam_step_sync_wt: bad argument");
+        return a0_fail(A0_EINVAL, who);
     if (loss && (!loss_ring || loss_n < 1 || ring_cap < 1)) return a0_fail(A0_EINVAL, "a0_adam_step_sync_wt: loss statistics need a ring of at least one slot");
     hipStream_t st = (hipStream_t)stream;
     const int vec4 = ((n | n_total) % 4 == 0) &&
                      ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
     long long blocks = ((vec4 ? n_total / 4 : n_total) + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(a0_adam_sync_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4,
-                       a0_adam_fold{lr, beta1, beta2, target_update_freq, extra_nan_flag, state, scalars, loss, loss_n, loss_ring, ring_cap > 0 ? ring_cap : 1});
-    int e = a0_fail_hip((int)hipGetLastError(), "a0_adam_step_sync_wt");
+    const a0_adam_fold F{lr, beta1, beta2, target_update_freq, extra_nan_flag, state, scalars, loss, loss_n, loss_ring, ring_cap > 0 ? ring_cap : 1};
+    if (clip)
+        hipLaunchKernelGGL((a0_adam_sync_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, *clip);
+    else
+        hipLaunchKernelGGL((a0_adam_sync_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, a0_adam_clip{nullptr, 0.f, nullptr, 1});
+    int e = a0_fail_hip((int)hipGetLastError(), who);
     if (e != A0_OK) return e;
     return a0_conv_wt_refresh_commit(w, C, wt, wt_target, state, st);
+}
+
+extern "C" int a0_adam_step_sync_wt(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                                    double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                                    const float* extra_nan_flag, const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n,
+                                    float* loss_ring, int ring_cap, void* stream) {
+    return a0_adam_sync_fold("a0_adam_step_sync_wt: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                             extra_nan_flag, w, C, wt, wt_target, loss, loss_n, loss_ring, ring_cap, nullptr, stream);
+}
+
+// a0_adam_step_sync_wt on the clipped gradient (see a0_adam_step_sync_clip); the norm goes to norm_ring[state[6] % norm_ring_cap], beside the loss mean's slot
+extern "C" int a0_adam_step_sync_wt_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                                         double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                                         const float* extra_nan_flag, const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n,
+                                         float* loss_ring, int ring_cap, const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream) {
+    if (!a0_clip_args_ok(partials, max_norm, norm_ring, norm_ring_cap)) return a0_fail(A0_EINVAL, "a0_adam_step_sync_wt_clip: partials, max_norm > 0 and a norm ring of at least one slot");
+    const a0_adam_clip clip{partials, max_norm, norm_ring, norm_ring_cap};
+    return a0_adam_sync_fold("a0_adam_step_sync_wt_clip: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                             extra_nan_flag, w, C, wt, wt_target, loss, loss_n, loss_ring, ring_cap, &clip, stream);
 }
 
 // out[0] = 1.0f if this rank's NaN flag (state[0], set by the loss kernels) is up, else 0.0f — a float so that it can ride along in

@@ -18,6 +18,11 @@ Additions (all default to the reference's behaviour being available):
                    own worker processes and page-locked ring, so that the CPU steps one group while the GPU infers the other (the counterpart of the
                    reference's ``num_actors`` actor processes, launch.py:30-61).  1 = one HostEnvPool.  Every setting gives the same bytes; which one is
                    fastest depends on the emulator's CPU cost per step, so it is the user's choice.  Ignored by the device-resident synthetic env.
+  learner.clip_grad_norm  float, default -1.0 (off; any value <= 0 is off).  > 0: every update scales the gradient Adam steps on — the whole Q-network: conv blocks, fc1,
+                   the head, NoisyNet sigmas, the cosine embedding; not the fqf fraction net, which keeps ``max_grad_norm`` and its RMSprop step — by
+                   min(1, clip_grad_norm / (norm + 1e-6)), i.e. ``torch.nn.utils.clip_grad_norm_`` with its defaults, and the pre-clip norm is reported as
+                   ``grad_norm``.  The norm is that of the batch-SUM gradient (the loss is summed over the batch, quirk Q5), after the data-parallel exchange has
+                   summed the ranks: a recipe's "10" for a batch-mean loss corresponds to 10 * batch_size here, times the world size under data parallelism.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -107,6 +112,7 @@ class LearnerConfig:
     learning_rate: float = 5e-4
     fraction_lr: float = 2.5e-8
     max_grad_norm: float = -1.0
+    clip_grad_norm: float = -1.0
     target_update_freq: int = 500
     learner_steps: int = 20
     double_q: bool = False

@@ -22,6 +22,11 @@ from .layout import Block, NetLayout
 MODE_IDENT, MODE_MEAN, MODE_C51, MODE_FQF = 0, 1, 2, 3
 
 
+def clip_limit(value) -> float:
+    """``learner.clip_grad_norm`` as the learner uses it: the limit when it is positive, -1.0 (off) for anything else — zero, a negative number, None."""
+    return float(value) if value is not None and value > 0 else -1.0
+
+
 class Workspace:
     """Activations of one forward pass over ``B`` observations (``n_tau`` quantile samples each for IQN/FQF)."""
 
@@ -295,7 +300,7 @@ class DeviceLearner:
 
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
-                 mdqn_tau=0.03, mdqn_lo=-1.0):
+                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -314,6 +319,11 @@ class DeviceLearner:
         self.scalars = ops.zeros(4)
         # batch means of the last 1024 updates' per-sample losses, written by the Adam launch itself (a0_adam_step_sync_wt: ring slot = state[6] % 1024)
         self.loss_ring = ops.zeros(1024)
+        # learner.clip_grad_norm > 0: the gradient Adam steps on is scaled to this global L2 norm (torch.nn.utils.clip_grad_norm_); the pre-clip norm of every
+        # update goes to gnorm_ring, slot for slot beside loss_ring.  Off (<= 0): neither buffer exists and apply() issues what it always did.
+        self.clip_grad_norm = clip_limit(clip_grad_norm)
+        self.gnorm_partials = ops.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64) if self.clip_grad_norm > 0 else None
+        self.gnorm_ring = ops.zeros(1024) if self.clip_grad_norm > 0 else None
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -504,6 +514,18 @@ class DeviceLearner:
             blk = L.blocks["frac"]
             ops.rmsprop_step(on.flat[blk.all], self.grads[blk.all], self.rms_sq, blk.size, self.lr / 2e4, 0.95, 1e-5, self.max_grad_norm, self.clip)
         tail = self.grads[L.n_params_padded: L.n_params_padded + 1] if self._bucketed_hook() else None
+        if self.clip_grad_norm > 0:
+            # one launch more: the sum of squares over everything Adam owns (the fqf fraction net lies behind n_adam), taken here — behind the data-parallel
+            # exchange — so that every rank derives the same coefficient; the Adam launch finishes the norm, clips and files it (a0_adam_step_sync_clip)
+            ops.grad_norm_partials(self.grads, L.n_adam, self.gnorm_partials)
+            if on.fused:
+                ops.adam_step_sync_wt_clip(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
+                                           self.target_update_freq, tg.flat, L.n_params_padded, tail, on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring,
+                                           self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
+            else:
+                ops.adam_step_sync_clip(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
+                                        self.target_update_freq, tg.flat, L.n_params_padded, tail, self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
+            return
         if on.fused:
             # two launches: Adam with its bookkeeping and the target copy folded in; the online conv copies, mirrored to the target's on a sync
             ops.adam_step_sync_wt(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,

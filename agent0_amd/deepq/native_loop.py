@@ -183,6 +183,8 @@ class NativeLoop:
         if lc.algo.name == "c51":
             atoms = (C.c_float * L.T)(*[float(x) for x in eng.atoms.cpu().tolist()])
             ok(lib.a0_learner_set_support(self.learner, atoms), "a0_learner_set_support")
+        if eng.clip_grad_norm > 0:      # learner.clip_grad_norm: the handle clips as DeviceLearner.apply does, and files the norms in the engine's ring
+            ok(lib.a0_learner_set_grad_clip(self.learner, C.c_double(eng.clip_grad_norm), p(eng.gnorm_ring), int(eng.gnorm_ring.numel())), "a0_learner_set_grad_clip")
         hook = eng.grad_hook
         if hook is not None:      # hook_ok: dist.RcclGradAllReduce — its communicator moves into the handle (an inactive hook, A0_DP_DRYRUN=1, exchanges nothing there either)
             ok(lib.a0_learner_set_exchange(self.learner, C.c_longlong(int(hook.comm) if hook.active else 0)), "a0_learner_set_exchange")
@@ -285,6 +287,7 @@ class NativeLoop:
     def _block(self, st) -> int:
         tr, lib, ok = self.tr, self.lib, self.ok
         cfg = tr.cfg
+        tr._gn0, tr.GNs = None, []
         if int(lib.a0_rbuf_len(self.rbuf)) <= cfg.trainer.training_start_steps:
             return 0
         ln = tr.learner
@@ -300,6 +303,7 @@ class NativeLoop:
                 if self.fqf:                              # the `fraction_loss` statistic (trainer.py:99-101): batch mean of the update's fraction losses
                     ok(lib.a0_learner_get_frac_loss(self.learner, self._floss.data_ptr(), st), "a0_learner_get_frac_loss")
                     tr.ops.mean_rows(self._floss, 1, self.B, tr._floss_means[i:i + 1])
+        tr._gn0 = tr._gnorm_ring_start()                  # ... and, with learner.clip_grad_norm on, the pre-clip gradient norms beside them
         tr._ring0 = ln.updates_issued                     # the Adam launch wrote the block's batch-mean losses to ring slots ring0 .. ring0 + n - 1
         ln.updates_issued += n
         if self.prio and not self.flat:

@@ -115,6 +115,7 @@ class Trainer:
                 pass
         self.num_transitions = cfg.actor.sample_steps * cfg.actor.num_envs
         self.Ls, self.Rs, self.RTs, self.Qs, self.FLs = [], [], [], [], []
+        self.GNs = []                                     # learner.clip_grad_norm: the pre-clip gradient norms of the last update block
         self.frame_count = 0
         L = int(cfg.learner.learner_steps)
         self._loss_means = ops.zeros(max(L, 1))
@@ -206,6 +207,8 @@ class Trainer:
                   net={"online": cpu(eng.online.flat), "target": cpu(eng.target.flat), "eff_online": cpu(eng.online.eff), "eff_target": cpu(eng.target.eff),
                        "noise": cpu(eng.noise_joint) if eng.noise_joint is not None else ([cpu(eng.online.noise_buf), cpu(eng.target.noise_buf)] if eng.L.noisy else None),
                        "scalars": cpu(eng.scalars), "loss_ring": cpu(eng.loss_ring)})
+        if eng.gnorm_ring is not None:
+            st["net"]["gnorm_ring"] = cpu(eng.gnorm_ring)
         if self.use_lp:
             sg = self.stage
             st["stage"] = {"written": int(sg.written), "act": cpu(sg.act), "rew": cpu(sg.rew), "done": cpu(sg.done)}
@@ -271,6 +274,8 @@ class Trainer:
             else:
                 eng.online.noise_buf.copy_(net["noise"][0]); eng.target.noise_buf.copy_(net["noise"][1])
         eng.scalars.copy_(net["scalars"]); eng.loss_ring.copy_(net["loss_ring"])
+        if net.get("gnorm_ring") is not None and eng.gnorm_ring is not None:      # absent from snapshots written without learner.clip_grad_norm
+            eng.gnorm_ring.copy_(net["gnorm_ring"])
         ln.rng.seed = int(st["learner_rng"][0])
         ln.rng.offsets = {i: int(o) for i, o in enumerate(st["learner_rng"][1:]) if o}
         ln.updates_issued = int(st["updates_issued"])
@@ -323,6 +328,8 @@ class Trainer:
         n_upd = 0
         has_frac = False
         self._ring0 = None
+        self._gn0 = self._gnorm_ring_start()
+        self.GNs = []
         if len(self.replay) > cfg.trainer.training_start_steps and self._pipeline_ok():
             with self.ops.range("update_block"):
                 n_upd = self._update_block_pipelined()
@@ -348,6 +355,8 @@ class Trainer:
             return self._block_stats_async(n_upd, has_frac)
         if n_upd:
             self.Ls.extend(self._block_loss_means(n_upd))                   # the one device->host read of the update block
+            if self._gn0 is not None:
+                self.GNs = self._block_grad_norms(self.learner.engine.gnorm_ring.cpu(), n_upd)
             # the device's update count (NaN-skipped steps do not count) for the next block's pipelining decision: read here, where the host has just waited
             # for the block anyway, so that the next block can be enqueued behind the rollout without a stop
             self._updates_done = int(self.learner.engine.state[1]) if self._pipeline_candidate() else None
@@ -376,12 +385,22 @@ class Trainer:
             host[fk].copy_(self._floss_means, non_blocking=True)
             fl = host[fk]
         self._updates_done = None
-        return (n_upd, ring0, host[key], fl)
+        gn = None
+        if getattr(self, "_gn0", None) is not None:      # the ring of gradient norms travels with the loss means: one more small copy per block, none per update
+            ring = self.learner.engine.gnorm_ring
+            gk = ("gnorm", ring.numel())
+            if gk not in host:
+                host[gk] = torch.empty(ring.numel(), dtype=ring.dtype).pin_memory()
+            host[gk].copy_(ring, non_blocking=True)
+            gn = host[gk]
+        return (n_upd, ring0, host[key], fl, gn)
 
     def _block_stats_finish(self, handle):
-        n_upd, ring0, buf, fl = handle
+        n_upd, ring0, buf, fl = handle[:4]
         if not n_upd:
             return
+        if len(handle) > 4 and handle[4] is not None:
+            self.GNs = self._block_grad_norms(handle[4], n_upd)
         if ring0 is None:
             self.Ls.extend(buf[:n_upd].tolist())
         else:
@@ -400,6 +419,20 @@ class Trainer:
               and "train_batch" not in vars(ln) and os.environ.get("A0_LOSS_RING", "1") != "0")
         self._ring0 = ln.updates_issued if ok else None
         return self._ring0
+
+    def _gnorm_ring_start(self):
+        """learner.clip_grad_norm: the Adam launch files every update's pre-clip gradient norm in DeviceLearner.gnorm_ring, in the slot of the update's loss mean
+        (update count % ring length).  Returns the first slot of the block about to be issued, or None when the setting is off."""
+        ln = self.learner
+        return int(getattr(ln, "updates_issued", 0)) if getattr(ln.engine, "gnorm_ring", None) is not None else None
+
+    def _block_grad_norms(self, ring, n_upd: int):
+        """The block's norms out of a host copy of the ring (its newest ring-length entries when the block is longer than the ring)."""
+        cap = ring.numel()
+        if not self.learner.engine.online.fused:      # the unfused optimizer tail does not advance the slot counter: the slot holds the block's last update
+            return [float(ring[int(self.learner.engine.state[6]) % cap])]
+        n = min(n_upd, cap)
+        return [float(ring[(self._gn0 + n_upd - n + i) % cap]) for i in range(n)]
 
     def _block_loss_means(self, n_upd: int):
         if getattr(self, "_ring0", None) is None:
@@ -465,7 +498,12 @@ class Trainer:
         return L
 
     def _result(self):
-        """The result dict of trainer.py:111-118."""
+        """The result dict of trainer.py:111-118; with learner.clip_grad_norm on also ``grad_norm``, the mean pre-clip gradient norm over the last block's updates."""
+        if getattr(self.learner.engine, "gnorm_ring", None) is not None:
+            return dict(self._result_base(), grad_norm=np.mean(self.GNs) if len(self.GNs) > 0 else None)
+        return self._result_base()
+
+    def _result_base(self):
         return dict(
             frames=self.frame_count,
             fraction_loss=np.mean(self.FLs[-20:]) if len(self.FLs) > 0 else None,
@@ -522,7 +560,7 @@ class Trainer:
                 self.writer.add_scalar(k, v, self.frame_count)
             if self._wandb is not None:
                 self._wandb.log({k: v, "frame": self.frame_count})
-            if k in ["frames", "loss", "qmax", "fps"] or "return" in k:
+            if k in ["frames", "loss", "qmax", "fps", "grad_norm"] or "return" in k:
                 msg += f"{k}: {v:.2f} | "
         self.logger.info(msg)
 
@@ -536,9 +574,10 @@ class Trainer:
             new = not os.path.exists(path)
             with open(path, "a", newline="") as f:
                 w = csv.writer(f)
+                cols = PROGRESS_COLUMNS + (("grad_norm",) if "grad_norm" in result else ())      # only with learner.clip_grad_norm on
                 if new:
-                    w.writerow(PROGRESS_COLUMNS)
-                w.writerow(["" if result.get(k) is None else result[k] for k in PROGRESS_COLUMNS])
+                    w.writerow(cols)
+                w.writerow(["" if result.get(k) is None else result[k] for k in cols])
         except OSError:
             pass
 

@@ -98,6 +98,18 @@ class NativeLearner:
         check(self.lib.a0_learner_get(self.h, on.data_ptr(), tg.data_ptr(), m.data_ptr(), v.data_ptr(), st.data_ptr(), _stream()), "a0_learner_get")
         return on, tg, m, v, st
 
+    def set_grad_clip(self, max_norm, norm_ring=None):
+        """learner.clip_grad_norm through the handle (a0_learner_set_grad_clip); ``norm_ring`` None: the handle's own 1024 slots.  <= 0 switches it off."""
+        check(self.lib.a0_learner_set_grad_clip(self.h, float(max_norm), _req(norm_ring, torch.float32, 1, "norm_ring", optional=True),
+                                                0 if norm_ring is None else int(norm_ring.numel())), "a0_learner_set_grad_clip")
+
+    def grad_norm_ring(self):
+        """A copy of the ring of pre-clip gradient norms (A0_PEEK_GRAD_NORM_RING)."""
+        ptr, cnt = C.c_void_p(), C.c_longlong()
+        check(self.lib.a0_learner_peek(self.h, 6, C.addressof(ptr), C.addressof(cnt)), "a0_learner_peek")
+        view = type("_Ring", (), {"__cuda_array_interface__": {"shape": (int(cnt.value),), "typestr": "<f4", "data": (int(ptr.value), False), "version": 3}})()
+        return torch.as_tensor(view, device="cuda").clone()
+
     def update(self, frames, slot, row_bytes, act, rew, done, wgt, loss_out=None):
         B = self.B
         check(self.lib.a0_learner_update(self.h, _req(frames, torch.uint8, row_bytes, "frames"), _req(slot, torch.int32, B, "slot", optional=True), int(row_bytes),
@@ -434,6 +446,37 @@ class HipOps:
                                             _req(wt, torch.float32, nw, "wt"), _req(wt_target, torch.float32, nw, "wt_target"),
                                             _req(loss, torch.float32, max(loss_n, 1), "loss", optional=True), int(loss_n), _req(loss_ring, torch.float32, 1, "loss_ring", optional=True),
                                             0 if loss_ring is None else int(loss_ring.numel()), _stream()), "a0_adam_step_sync_wt")
+
+    GRAD_NORM_PARTIALS = 256      # A0_GRAD_NORM_PARTIALS (include/agent0_hip.h)
+
+    def grad_norm_partials(self, grads, n, partials):
+        """Stage 1 of learner.clip_grad_norm: the sum of squares of ``grads[:n]`` as GRAD_NORM_PARTIALS float64 partial sums (a0_grad_norm_partials)."""
+        check(self.lib.a0_grad_norm_partials(_req(grads, torch.float32, n, "grads"), n, _req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), _stream()),
+              "a0_grad_norm_partials")
+
+    def adam_step_sync_clip(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag, partials, max_norm, norm_ring):
+        """``adam_step_sync`` on ``grads * min(1, max_norm / (norm + 1e-6))``, the norm from ``partials``; it is written to norm_ring[state[6] % len(norm_ring)]."""
+        check(self.lib.a0_adam_step_sync_clip(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
+                                              _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
+                                              lr, b1, b2, eps, target_freq, _req(target, torch.float32, n_total, "target"), n_total,
+                                              _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True),
+                                              _req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), float(max_norm), _req(norm_ring, torch.float32, 1, "norm_ring"),
+                                              int(norm_ring.numel()), _stream()), "a0_adam_step_sync_clip")
+
+    def adam_step_sync_wt_clip(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag, w, C_, wt, wt_target, loss, loss_n,
+                               loss_ring, partials, max_norm, norm_ring):
+        """``adam_step_sync_wt`` on the clipped gradient (see ``adam_step_sync_clip``); the norm lands in the ring slot of the update's loss mean."""
+        ew = self._enc_w(w)
+        nw = self.conv_wt_floats(C_)
+        check(self.lib.a0_adam_step_sync_wt_clip(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
+                                                 _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
+                                                 lr, b1, b2, eps, target_freq, _req(target, torch.float32, n_total, "target"), n_total,
+                                                 _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True), C.addressof(ew), C_,
+                                                 _req(wt, torch.float32, nw, "wt"), _req(wt_target, torch.float32, nw, "wt_target"),
+                                                 _req(loss, torch.float32, max(loss_n, 1), "loss", optional=True), int(loss_n), _req(loss_ring, torch.float32, 1, "loss_ring", optional=True),
+                                                 0 if loss_ring is None else int(loss_ring.numel()),
+                                                 _req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), float(max_norm), _req(norm_ring, torch.float32, 1, "norm_ring"),
+                                                 int(norm_ring.numel()), _stream()), "a0_adam_step_sync_wt_clip")
 
     def nan_flag_export(self, state, out):
         check(self.lib.a0_nan_flag_export(_req(state, torch.int32, 8, "state"), _req(out, torch.float32, 1, "out"), _stream()), "a0_nan_flag_export")

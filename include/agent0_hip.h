@@ -355,6 +355,22 @@ int a0_adam_step_sync(float* params, const float* grads, float* exp_avg, float* 
 int a0_adam_step_sync_wt(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars2, double lr,
                          double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total, const float* extra_nan_flag,
                          const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n, float* loss_ring, int ring_cap, void* stream);
+/* Global gradient-norm clipping in front of Adam (learner.clip_grad_norm; torch.nn.utils.clip_grad_norm_ with its defaults), two stages and ONE extra launch per update.
+ * Stage 1, a0_grad_norm_partials: the sum of squares of grads[0, n) as A0_GRAD_NORM_PARTIALS doubles (squares and sums in double; a fixed split of the range that
+ * depends on n alone, plain stores, unused partials zero: the same bits on every run).  grads 16-byte aligned: 16-byte loads; otherwise element by element.
+ * Stage 2 rides in the Adam launch of the _clip entry points — the two above plus (partials, max_norm > 0, norm_ring, norm_ring_cap): every workgroup sums the partials
+ * in the same order, rounds ||g|| = sqrt(sum) to fp32, forms c = max_norm / (||g|| + 1e-6f), coef = c < 1 ? c : 1 in fp32 and steps on g[i] * coef — bit for bit the
+ * unclipped entry point on a buffer holding g * coef.  The pre-clip norm is written to norm_ring[state[6] % norm_ring_cap] (the slot of the same update's loss mean;
+ * a0_adam_step_sync_clip does not advance state[6]), on NaN-skipped steps too. */
+#define A0_GRAD_NORM_PARTIALS 256
+int a0_grad_norm_partials(const float* grads, long long n, double* partials, void* stream);
+int a0_adam_step_sync_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars2, double lr,
+                           double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total, const float* extra_nan_flag,
+                           const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream);
+int a0_adam_step_sync_wt_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars2, double lr,
+                              double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total, const float* extra_nan_flag,
+                              const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n, float* loss_ring, int ring_cap,
+                              const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream);
 /* ---------------------------------------------------------------- a whole learner behind one handle (opaque handles, library-owned HBM)
  * BaseLearner (agent.py:97-169) with DQNLearner.train_step (173-190) for scalar heads on 4 x 84 x 84 observations — BASELINE configs[1]: online + target parameters
  * in the packed layout (agent0_amd/deepq/layout.py: conv1 | conv2 | conv3 | fc1 | head, each [W (N x K) | b (N)], head rows padded to a multiple of 32), gradients,
@@ -419,6 +435,12 @@ long long a0_learner_param_floats(const a0_learner* learner);
  * if any rank saw a NaN.  Same buckets and order as agent0_amd/deepq/dist.py::RcclGradAllReduce, issued eagerly.  Collective: every rank sets it before its first
  * update and calls a0_learner_update the same number of times.  comm = 0 switches the exchange off; the caller keeps ownership of the communicator. */
 int a0_learner_set_exchange(a0_learner* learner, long long comm);
+/* learner.clip_grad_norm through the handle: with max_norm > 0 every a0_learner_update scales the gradient Adam steps on — [0, n_adam) of the flat buffer, i.e.
+ * everything but the fqf fraction net, whose own max_grad_norm clip and RMSprop step stay as they are — by min(1, max_norm / (||g|| + 1e-6)), ||g|| taken after the
+ * data-parallel exchange has summed both buckets (a0_grad_norm_partials behind the join, then a0_adam_step_sync_wt_clip), and files the pre-clip norm in
+ * norm_ring_dev[state[6] % ring_cap] (ring_cap floats the caller owns; NULL: the handle allocates ring_cap slots, 1024 when ring_cap < 1; A0_PEEK_GRAD_NORM_RING
+ * returns the ring either way).  max_norm <= 0 switches clipping off again.  Call it between updates, not while one is being captured. */
+int a0_learner_set_grad_clip(a0_learner* learner, double max_norm, float* norm_ring_dev, int ring_cap);
 /* parameters in the packed layout (device pointers, a0_learner_param_floats floats each); target_packed = NULL: target = copy of online (agent.py:100) */
 int a0_learner_set_params(a0_learner* learner, const float* online_packed, const float* target_packed, void* stream);
 /* copies of what the handle holds (any pointer may be NULL): parameters, target parameters, Adam moments (param_floats each), the eight status words */
@@ -429,7 +451,7 @@ int a0_learner_loss_buffer(const a0_learner* learner, float** loss_dev);
 /* (round 5) borrowed views of the handle's HBM for inspection — the flat gradient buffer (layout of the parameters) and the differentiated pass's activations
  * (NHWC; their signs are the ReLU decisions of the last update), which a0_learner_get does not copy out: *dev_ptr / *count (floats).  Valid until the next call on
  * the handle.  tests/test_gpu_trace.py walks the handle path against the CPU oracle with them. */
-enum { A0_PEEK_GRADS = 0, A0_PEEK_ACT1 = 1, A0_PEEK_ACT2 = 2, A0_PEEK_ACT3 = 3, A0_PEEK_FC1 = 4, A0_PEEK_LOSS = 5 };
+enum { A0_PEEK_GRADS = 0, A0_PEEK_ACT1 = 1, A0_PEEK_ACT2 = 2, A0_PEEK_ACT3 = 3, A0_PEEK_FC1 = 4, A0_PEEK_LOSS = 5, A0_PEEK_GRAD_NORM_RING = 6 /* a0_learner_set_grad_clip */ };
 int a0_learner_peek(const a0_learner* learner, int what, float** dev_ptr, long long* count);
 /* fqf: a copy of the per-sample fraction losses [B] of the last update (the `fraction_loss` statistic, trainer.py:99-101) into out_dev */
 int a0_learner_get_frac_loss(const a0_learner* learner, float* out_dev, void* stream);
