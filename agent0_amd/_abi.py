@@ -57,6 +57,10 @@ class PendingReduce(C.Structure):
     _fields_ = [("seg", ReduceSeg * 4), ("n", C.c_int)]
 
 
+class UpdateTailPlan(C.Structure):
+    _fields_ = [("seg", ReduceSeg * 8), ("n", C.c_int)]
+
+
 class EncoderPass(C.Structure):
     _fields_ = [("wt", C.c_void_p), ("w", C.c_void_p), ("f", C.c_void_p), ("B", C.c_int), ("act1", C.c_void_p), ("act2", C.c_void_p), ("act3", C.c_void_p)]
 

@@ -47,7 +47,9 @@ struct a0_trace_scope {
 #if defined(__HIPCC__)
 bool a0_probe_start(int tag, hipStream_t st);
 // conv1_wgrad.hip: per-observation conv1 weight gradient on the bf16 pipe; returns the slab count (0 = unsupported shape)
-int a0_conv1_wgrad_fused_launch(const a0_frames_arg* f, int C, int H, int W, int B, const float* d1, float* slabs, hipStream_t st);
+// prep (optional, update_tail.h): the optimizer step's one-thread bookkeeping, done by the launch's first workgroup when its slab is written
+struct a0_tail_prep;
+int a0_conv1_wgrad_fused_launch(const a0_frames_arg* f, int C, int H, int W, int B, const float* d1, float* slabs, const a0_tail_prep* prep, hipStream_t st);
 void a0_probe_stop(hipStream_t st, double flops);
 // Kernel-exact form for launches of ONE kernel: the probe hands out its next event pair and the launch carries it (hipExtLaunchKernelGGL: the events take the
 // dispatch's own begin / end timestamps, what rocprofv3's kernel trace reports) — an event recorded in front of a launch also counts the ~2.5 us between the

@@ -17,6 +17,7 @@
 // Every wave owns all 32 output channels x 32 taps (four 16x16 accumulators) for the whole launch; a workgroup adds up its
 // observations in registers and writes one slab [32][256] + bias[32]; the slabs meet in a0_reduce_slabs_kernel (deterministic).
 #include "a0_internal.h"
+#include "update_tail.h"
 
 #include <cstdint>
 
@@ -36,6 +37,7 @@ struct a0_c1w_args {
     const float* d1;        // [B][400][32], ReLU-masked
     float* slabs;           // [gridDim.x][32*256 + 32]
     int B;
+    a0_tail_prep prep;      // state != nullptr: the optimizer step's bookkeeping rides along (update_tail.h)
 };
 
 A0_D uint32_t a0w_trunc(float f) { return __float_as_uint(f) >> 16; }
@@ -188,14 +190,16 @@ __global__ __launch_bounds__(A0W_THREADS) void a0_conv1_wgrad_fused_kernel(a0_c1
         for (int j = 0; j < A0W_THREADS / 32; ++j) s += red[j * 32 + tid];
         out[32 * 256 + tid] = s;
     }
+    if (P.prep.state != nullptr && blockIdx.x == 0 && tid == 0) a0_tail_prep_run(P.prep);
 }
 
 // slabs: gridDim.x x (32*256 + 32) floats; returns the number of slabs written (0 = shape not supported, nothing launched)
-int a0_conv1_wgrad_fused_launch(const a0_frames_arg* f, int C, int H, int W, int B, const float* d1, float* slabs, hipStream_t st) {
+int a0_conv1_wgrad_fused_launch(const a0_frames_arg* f, int C, int H, int W, int B, const float* d1, float* slabs, const a0_tail_prep* prep, hipStream_t st) {
     if (C != 4 || H != 84 || W != 84 || B < 1 || (f->sample_stride & 3) || (f->chan_off & 3) || (((uintptr_t)f->frames) & 3)) return 0;
     a0_c1w_args P;
     P.frames = f->frames; P.slot = f->slot; P.sample_stride = f->sample_stride; P.chan_off = f->chan_off;
     P.d1 = d1; P.slabs = slabs; P.B = B;
+    P.prep = prep ? *prep : a0_tail_prep{nullptr, nullptr, 0.0, 0.0, 0.0, 0};
     const int grid = B < 256 ? B : 256;
     const size_t lds = (size_t)(A0W_XP_ELEMS + 3 * A0W_T_TERM) * 2;
     static bool configured = false;

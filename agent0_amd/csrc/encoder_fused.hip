@@ -22,6 +22,7 @@
 #include "a0_internal.h"
 #include "net_tables.h"
 #include "operands.h"
+#include "update_tail.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -40,26 +41,7 @@ struct a0_fused_args {
     int rp1, rp2;                        // LDS row pitches (floats) of act1 / act2, padded so that A-fragment reads are bank-conflict free
 };
 
-// The weight-copy buffer `wt` that a0_conv_wt_kernel fills from the packed [N][K] weights and every fused kernel reads: the length of each
-// segment and its offset, in floats, for C input channels.  This is the only description of the layout in the library.
-struct a0_wt_layout {
-    int C;
-    constexpr int n_conv1x() const { return 48 * 64 * C; }      // conv1: fl(w/255) as three exact bf16 terms, a0_wring1 layout (32 x 64 C x 3 x 2 bytes)
-    static constexpr int n_conv2 = 64 * 512;                    // conv2 fp32, fragment-major (a0_wring layout)
-    static constexpr int n_conv3 = 64 * 576;                    // conv3 fp32, fragment-major
-    static constexpr int n_conv2x = 96 * 512;                   // conv2 as three exact bf16 terms (a0_wring9 layout, N = 64): 64 x K x 3 x 2 bytes
-    static constexpr int n_conv3x = 96 * 576;                   // conv3 likewise
-    static constexpr int n_dgrad3x = 96 * 576;                  // conv3's data-gradient matrix (flipped taps) [576][64] as three bf16 terms, a0_wring9 layout, N = 64
-    static constexpr int n_dgrad2x_phase = 48 * 256;            // conv2's data-gradient matrix of one stride phase [256][32], a0_wring9 layout, N = 32; four of them
-    constexpr int conv1x() const { return 0; }
-    constexpr int conv2() const { return n_conv1x(); }
-    constexpr int conv3() const { return conv2() + n_conv2; }
-    constexpr int conv2x() const { return conv3() + n_conv3; }
-    constexpr int conv3x() const { return conv2x() + n_conv2x; }
-    constexpr int dgrad3x() const { return conv3x() + n_conv3x; }
-    constexpr int dgrad2x() const { return dgrad3x() + n_dgrad3x; }
-    constexpr int total() const { return dgrad2x() + 4 * n_dgrad2x_phase; }
-};
+// The weight-copy buffer `wt` that a0_conv_wt_kernel fills and every fused kernel reads: a0_wt_layout (update_tail.h)
 A0_HD void a0_fused_set_wt(a0_fused_args& P, const float* wt, int C) {
     const a0_wt_layout T{C};
     P.wt1 = wt + T.conv1x(); P.wt2 = wt + T.conv2(); P.wt3 = wt + T.conv3(); P.wx2 = wt + T.conv2x(); P.wx3 = wt + T.conv3x();
@@ -1267,16 +1249,7 @@ __global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_dgrad_fused_x9_ke
 }
 
 // ---- weight copies for the fused kernels, from the packed [N][K] blocks: the segments of a0_wt_layout
-A0_HD uint32_t a0_bf16_trunc(float f) { return __float_as_uint(f) >> 16; }
-A0_HD float a0_bf16_up(uint32_t h) { return __uint_as_float(h << 16); }
-// w = hi + mid + lo EXACTLY, three bf16 terms of 8 significant bits each: term s (0 = hi, 1 = mid, 2 = lo) as bf16 bits
-A0_HD uint32_t a0_bf16_term(float w, int s) {
-    const uint32_t hi = a0_bf16_trunc(w);
-    const float r1 = w - a0_bf16_up(hi);              // exact: at most 16 significant bits left
-    const uint32_t mid = a0_bf16_trunc(r1);
-    const float r2 = r1 - a0_bf16_up(mid);            // exact: at most 8 significant bits left
-    return s == 0 ? hi : s == 1 ? mid : a0_bf16_trunc(r2);
-}
+// (the bf16 terms a0_bf16_term: update_tail.h)
 // One dword per thread.
 // wt2 / state: optional second destination (the target network's copies), written only when state[4] ("sync now", optim.hip) is set.
 // commit (a0_adam_step_sync_wt): the folded Adam kernel left the new step count in state[5]; this kernel, the next on the stream, moves it

@@ -679,6 +679,15 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
         }
     }
     A0_CHECK(a0_net_encoder_dgrad_fused(L->C, L->H, L->W, L->wt_on, L->d3, L->act1, L->act2, B, L->d2, L->d1, stream));
+    // the update's tail as one launch (DeviceLearner.backward_encoder(fuse_tail=True)): the slab sums wait for the Adam launch — not under data parallelism or clipping,
+    // which need the summed gradient first, nor when NoisyNet's sigma gradients wait for deferred dense sums
+    a0_update_tail_plan tail;
+    const bool fuse_tail = !dp && L->clip_max_norm <= 0.f && !(L->d.noisy && pend.n > 0);
+    if (fuse_tail)
+        A0_CHECK(a0_net_encoder_wgrad_tail(L->net, &w_on, &f_obs, B, L->act1, L->act2, L->d3, L->d2, L->d1, L->grads + L->conv1.off, L->grads + L->conv2.off,
+                                           L->grads + L->conv3.off, L->slabs + L->enc_slab_off, &pend, &tail, L->state, L->scalars, L->d.lr, 0.9, 0.999,
+                                           L->d.target_update_freq, stream));
+    else
     A0_CHECK(a0_net_encoder_wgrad(L->net, &w_on, &f_obs, B, L->act1, L->act2, L->d3, L->d2, L->d1, L->grads + L->conv1.off, L->grads + L->conv2.off, L->grads + L->conv3.off,
                                   L->slabs + L->enc_slab_off, &pend, stream));
     if (dp) {
@@ -700,6 +709,11 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
         A0_CHECK(a0_rmsprop_step(on + L->frac.off, L->grads + L->frac.off, L->rms_sq, L->frac.size(), L->d.lr / 2e4, 0.95, 1e-5, L->d.max_grad_norm > 0.0 ? L->d.max_grad_norm : -1.0, L->clip, stream));
     // ---- Adam (eps = 1e-2 / B unless given), NaN guard, update counter, target copy every target_update_freq updates, weight-copy refresh (agent.py:102-106,152-161)
     const double eps = L->d.adam_eps > 0.0 ? L->d.adam_eps : 1e-2 / (double)B;
+    if (fuse_tail) {
+        A0_CHECK(a0_update_tail(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, 0.9, 0.999, eps, tg, L->n_pad, &tail, &w_on, L->C, L->wt_on, L->wt_tg, L->loss, B,
+                                L->loss_ring, L->loss_ring_cap, stream));
+        return A0_OK;
+    }
     if (L->clip_max_norm > 0.f) {
         // learner.clip_grad_norm (DeviceLearner.apply): every gradient Adam owns is final here — summed over the ranks behind the join above — so one launch takes
         // its sum of squares and the Adam launch turns it into the norm, the coefficient and the ring entry

@@ -5,6 +5,7 @@
 #include "short_k_fwd.h"
 #include "a0_internal.h"
 #include "net_impl.h"
+#include "update_tail.h"
 
 #include <vector>
 
@@ -95,20 +96,7 @@ __global__ __launch_bounds__(256) void a0_reduce_segments_kernel(a0_reduce_multi
     if (A.vec[si]) {
         const long long i4 = blk * 32 + c;                    // float4 index
         const long long n4 = S.count >> 2, st4 = S.slab_stride >> 2;
-        a0_f4 s = a0_zero4();
-        if (i4 < n4) {
-            const a0_f4* p = (const a0_f4*)S.slabs + i4;
-            // four of this row group's slabs requested before any is added (same order of additions): the loads of a 72-slab segment overlap instead of queueing
-            for (int z = g; z < S.nslab; z += 32) {
-                a0_f4 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = (z + 8 * u < S.nslab) ? p[(long long)(z + 8 * u) * st4] : a0_zero4();
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (z + 8 * u < S.nslab) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
-            }
-        }
-        red4[g][c] = s;
+        red4[g][c] = i4 < n4 ? a0_rowgroup_sum4((const a0_f4*)S.slabs + i4, st4, g, S.nslab) : a0_zero4();      // update_tail.h
         __syncthreads();
         if (g == 0 && i4 < n4) {
             a0_f4 t = a0_zero4();
@@ -120,10 +108,7 @@ __global__ __launch_bounds__(256) void a0_reduce_segments_kernel(a0_reduce_multi
     }
     float* red = (float*)red4;                                 // [8][33] floats
     const long long i = blk * 32 + c;
-    float s = 0.f;
-    if (i < S.count)
-        for (int z = g; z < S.nslab; z += 8) s += S.slabs[(long long)z * S.slab_stride + i];
-    red[g * 33 + c] = s;
+    red[g * 33 + c] = i < S.count ? a0_rowgroup_sum1(S.slabs + i, S.slab_stride, g, S.nslab) : 0.f;
     __syncthreads();
     if (g == 0 && i < S.count) {
         float t = 0.f;
@@ -227,6 +212,8 @@ template <> struct a0_is_gather<OpActXC> { static constexpr bool value = true; }
 struct a0_hip_backend {
     hipStream_t st;
     int tag = 0;
+    const a0_tail_prep* prep = nullptr;      // a0_net_encoder_wgrad_tail: bookkeeping to ride in the per-observation conv1 launch; prep_done: it did
+    bool prep_done = false;
     template <class OA, class OB, class EP, int WM, int WN, int MT, int NT>
     void igemm(const typename OA::Params& pa, const typename OB::Params& pb, const typename EP::Params& pe, int X, int Y, int K, int splits) {
         // the probe's event pair travels IN the split-operand launches (the dispatch's own timestamps, as for the fused kernels); the fp32-chain kernel is bracketed
@@ -291,7 +278,8 @@ struct a0_hip_backend {
         if (!slabs) return 0;
         const bool probe = g_probe.tag != 0 && g_probe.tag == tag && g_probe.used + 2 <= g_probe.ev.size();
         if (probe) A0_HIP_THROW(hipEventRecord(g_probe.ev[g_probe.used], st));
-        const int g = a0_conv1_wgrad_fused_launch(&f, n.C, n.H, n.W, B, d1, slabs, st);
+        const int g = a0_conv1_wgrad_fused_launch(&f, n.C, n.H, n.W, B, d1, slabs, prep, st);
+        if (g > 0 && prep) prep_done = true;
         if (probe && g > 0) {
             A0_HIP_THROW(hipEventRecord(g_probe.ev[g_probe.used + 1], st));
             g_probe.used += 2;
@@ -904,6 +892,30 @@ extern "C" int a0_net_encoder_wgrad(const a0_net* n, const a0_encoder_weights* w
     if (pend && (pend->n < 0 || pend->n > 4)) return a0_fail(A0_EINVAL, "a0_net_encoder_wgrad: bad pending reductions");
     a0_hip_backend bk{(hipStream_t)stream};
     a0_encoder_bwd_impl(bk, n->core, *w, *f, B, act1, act2, d3, const_cast<float*>(d2), const_cast<float*>(d1), g1, g2, g3, slabs, false, pend);
+    return A0_OK;
+    A0_CATCH
+}
+
+__global__ void a0_tail_prep_kernel(a0_tail_prep P) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) a0_tail_prep_run(P);
+}
+
+extern "C" int a0_net_encoder_wgrad_tail(const a0_net* n, const a0_encoder_weights* w, const a0_frames_arg* f, int B, const float* act1, const float* act2,
+                                         const float* d3, const float* d2, const float* d1, float* g1, float* g2, float* g3, float* slabs, const a0_pending_reduce* pend,
+                                         a0_update_tail_plan* plan, int* state, float* scalars, double lr, double beta1, double beta2, int target_update_freq, void* stream) {
+    A0_TRY
+    if (!n || !w || !f || !f->frames || !act1 || !act2 || !d3 || !d2 || !d1 || !g1 || !g2 || !g3 || B < 1 || !plan || !state || !scalars)
+        return a0_fail(A0_EINVAL, "a0_net_encoder_wgrad_tail: null argument");
+    if (a0_encoder_bwd_scratch_impl(n->core, B) > 0 && !slabs) return a0_fail(A0_EINVAL, "a0_net_encoder_wgrad_tail: needs slab scratch");
+    if (pend && (pend->n < 0 || pend->n > 4)) return a0_fail(A0_EINVAL, "a0_net_encoder_wgrad_tail: bad pending reductions");
+    const a0_tail_prep prep{state, scalars, lr, beta1, beta2, target_update_freq};
+    a0_hip_backend bk{(hipStream_t)stream};
+    bk.prep = &prep;
+    a0_encoder_bwd_impl(bk, n->core, *w, *f, B, act1, act2, d3, const_cast<float*>(d2), const_cast<float*>(d1), g1, g2, g3, slabs, false, pend, plan);
+    if (!bk.prep_done) {       // conv1's weight gradient was a GEMM launch: the bookkeeping goes out on its own
+        hipLaunchKernelGGL(a0_tail_prep_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, prep);
+        A0_HIP_THROW(hipGetLastError());
+    }
     return A0_OK;
     A0_CATCH
 }

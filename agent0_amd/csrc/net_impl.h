@@ -296,7 +296,8 @@ static void a0_dense_wgrad_impl(BK& bk, const float* dY, const float* X, int ldx
 template <class BK>
 static void a0_encoder_bwd_impl(BK& bk, const a0_net_core& n, const a0_encoder_weights& w, const a0_frames_arg& f, int B,
                                 const float* act1, const float* act2, const float* d3, float* d2, float* d1,
-                                float* g1, float* g2, float* g3, float* slabs, bool with_dgrad = true, const a0_pending_reduce* pend = nullptr) {
+                                float* g1, float* g2, float* g3, float* slabs, bool with_dgrad = true, const a0_pending_reduce* pend = nullptr,
+                                a0_update_tail_plan* tail = nullptr) {
     // with_dgrad == false: d2 / d1 already hold the data gradients (a0_net_encoder_dgrad_fused); only the weight gradients run
     const int M3 = B * n.H3 * n.W3, M2 = B * n.H2 * n.W2, M1 = B * n.H1 * n.W1;
     const a0_enc_slab_plan plan = a0_encoder_slab_plan(n, B);
@@ -368,5 +369,11 @@ static void a0_encoder_bwd_impl(BK& bk, const a0_net_core& n, const a0_encoder_w
         }
     }
     // the three layers' slab reductions (weights and the bias row sums behind them) in one launch
+    // ... or none: the update tail (a0_update_tail) forms these sums where it steps the parameters
+    if (tail) {
+        tail->n = nseg;
+        for (int k = 0; k < nseg; ++k) tail->seg[k] = segs[k];
+        return;
+    }
     if (nseg > 0) bk.reduce_segments(segs, nseg);
 }

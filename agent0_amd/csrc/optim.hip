@@ -4,6 +4,9 @@
 // target_update_freq successful updates) without the two host syncs per update the reference pays (quirk Q14):
 // the NaN flag, the step counter and the "sync now" decision all live in a small device-side state block.
 #include "a0_internal.h"
+#include "update_tail.h"
+
+#include <algorithm>
 
 // state block (ints): see a0_learner_state in include/agent0_hip.h
 //   [0] nan_flag      set by the loss kernels (atomicOr) when a per-sample loss is NaN
@@ -303,6 +306,283 @@ extern "C" int a0_adam_step_sync_wt_clip(float* params, const float* grads, floa
     const a0_adam_clip clip{partials, max_norm, norm_ring, norm_ring_cap};
     return a0_adam_sync_fold("a0_adam_step_sync_wt_clip: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
                              extra_nan_flag, w, C, wt, wt_target, loss, loss_n, loss_ring, ring_cap, &clip, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the update tail in one launch
+// a0_reduce_segments_kernel + a0_adam_sync_kernel<true, false> + a0_conv_wt_kernel as ONE kernel without a second pass over anything: [0, n_total) is cut into
+// regions — the planned slab segments, and the ranges between them — and every workgroup serves one piece of one region:
+//   * segment, 16-byte path: 128 parameters — eight row groups x 32 lanes form the sums as a0_reduce_segments_kernel does, row group 0 adds the eight partial sums
+//     0..7 from zero, writes the gradient and steps its four parameters on it; scalar path: 32 parameters likewise;
+//   * between segments: a0_adam_sync_kernel's body, 1024 parameters per workgroup on the 16-byte path, 256 on the scalar path.
+// The step's decisions were derived one launch earlier (a0_tail_prep_run): state[3], state[4] and the scalars are only read here, so there is nothing to commit and
+// no workgroup waits for another.  The lane that holds a new convolution weight also files it in the fused kernels' copies (the inverse of a0_conv_wt_kernel's gather).
+struct a0_tail_region { long long lo, hi; int first_block, seg, vec, pad_; };      // [lo, hi) of the flat buffer; seg < 0: not a slab segment
+struct a0_tail_args {
+    float *p, *g, *m, *v, *target;
+    long long n, n_total;
+    const int* state; const float* scal;
+    float w1, b2, w2, eps;
+    int vec4;                                   // a0_adam_sync_kernel's: n, n_total multiples of four and every buffer 16-byte aligned
+    a0_reduce_seg seg[8];
+    a0_tail_region reg[17];
+    int nreg;
+    const float* loss; int loss_n; float* loss_ring; int ring_cap; int* state_w;
+    long long o1, o2, o3;                       // first weight of conv1 / conv2 / conv3 in the flat buffer
+    int K1, wt4;                                // wt4: o1, o2, o3 multiples of four (four consecutive k of one row per 16-byte lane)
+    float *wt, *wt_t;
+};
+
+struct a0_tail_step { bool skip, sync; float step_size, bc2_sqrt; };
+
+A0_D void a0_tail_put16(const a0_tail_args& A, const a0_tail_step& S, long long u16, uint32_t bits) {
+    if (!S.skip) ((uint16_t*)A.wt)[u16] = (uint16_t)bits;
+    if (S.sync) ((uint16_t*)A.wt_t)[u16] = (uint16_t)bits;
+}
+A0_D void a0_tail_put32(const a0_tail_args& A, const a0_tail_step& S, int dw, uint32_t bits) {
+    if (!S.skip) ((uint32_t*)A.wt)[dw] = bits;
+    if (S.sync) ((uint32_t*)A.wt_t)[dw] = bits;
+}
+// dword of term s of weight (n, k) in an a0_wring1 / a0_wring9 segment of N columns: uint4 ((t*N + n)*4 + q)*3 + s holds k = 32t + 8q .. +7; a dword is two consecutive k
+A0_D int a0_tail_term_dword(int N, int n, int k, int s) { return ((((k >> 5) * N + n) * 4 + ((k >> 3) & 3)) * 3 + s) * 4 + ((k >> 1) & 3); }
+// the data-gradient copies of one weight: conv3's flipped taps, conv2's stride phases (see a0_conv_wt_kernel)
+A0_D void a0_tail_wt_dgrad(const a0_tail_args& A, const a0_tail_step& S, const a0_wt_layout& T, bool c3, int co, int k, float w) {
+    int base, N, n, kk;
+    if (c3) {              // k = (kh*3 + kw)*64 + ci  ->  n = ci, k' = ((2-kh)*3 + (2-kw))*64 + co
+        const int cell = k >> 6;
+        n = k & 63; kk = (8 - cell) * 64 + co; base = T.dgrad3x(); N = 64;
+    } else {               // k = (kh*4 + kw)*32 + ci  ->  phase (kh & 1, kw & 1), n = ci, k' = ((1 - kh/2)*2 + (1 - kw/2))*64 + co
+        const int tap = k >> 5, kh = tap >> 2, kw = tap & 3;
+        n = k & 31; kk = ((1 - (kh >> 1)) * 2 + (1 - (kw >> 1))) * 64 + co; base = T.dgrad2x() + ((kh & 1) * 2 + (kw & 1)) * T.n_dgrad2x_phase; N = 32;
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) a0_tail_put16(A, S, 2LL * (base + a0_tail_term_dword(N, n, kk, s)) + (kk & 1), a0_bf16_term(w, s));
+}
+// every copy of the weight at flat index idx (new value w): nothing to do outside the three convolution weight blocks
+A0_D void a0_tail_wt1(const a0_tail_args& A, const a0_tail_step& S, long long idx, float w) {
+    const a0_wt_layout T{A.K1 / 64};
+    if (idx >= A.o1 && idx < A.o1 + 32LL * A.K1) {
+        const int e = (int)(idx - A.o1), n = e / A.K1, k = e - n * A.K1;
+        const float x = w / 255.0f;             // conv1 multiplies raw bytes: the reference's /255 is folded in here
+#pragma unroll
+        for (int s = 0; s < 3; ++s) a0_tail_put16(A, S, 2LL * (T.conv1x() + a0_tail_term_dword(32, n, k, s)) + (k & 1), a0_bf16_term(x, s));
+    } else if ((idx >= A.o2 && idx < A.o2 + 64 * 512) || (idx >= A.o3 && idx < A.o3 + 64 * 576)) {
+        const bool c3 = idx >= A.o3 && idx < A.o3 + 64 * 576;
+        const int K = c3 ? 576 : 512, e = (int)(idx - (c3 ? A.o3 : A.o2)), n = e / K, k = e - n * K;
+        // fp32, a0_wring layout: float ((c*64 + n)*4 + q)*4 + j holds W[n][k = 16c + 4j + q]
+        a0_tail_put32(A, S, (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4 + (k & 3)) * 4 + ((k >> 2) & 3), __float_as_uint(w));
+#pragma unroll
+        for (int s = 0; s < 3; ++s) a0_tail_put16(A, S, 2LL * ((c3 ? T.conv3x() : T.conv2x()) + a0_tail_term_dword(64, n, k, s)) + (k & 1), a0_bf16_term(w, s));
+        a0_tail_wt_dgrad(A, S, T, c3, n, k, w);
+    }
+}
+// four consecutive weights idx .. idx + 3 of one row (idx a multiple of four floats behind its block's start): the terms of four k are 8 adjacent bytes
+A0_D void a0_tail_wt4(const a0_tail_args& A, const a0_tail_step& S, long long idx, const a0_f4& pv) {
+    const a0_wt_layout T{A.K1 / 64};
+    const float w[4] = {pv.x, pv.y, pv.z, pv.w};
+    int base, N, n, k;
+    bool c1 = false, c3 = false;
+    if (idx >= A.o1 && idx < A.o1 + 32LL * A.K1) { const int e = (int)(idx - A.o1); n = e / A.K1; k = e - n * A.K1; base = T.conv1x(); N = 32; c1 = true; }
+    else if (idx >= A.o2 && idx < A.o2 + 64 * 512) { const int e = (int)(idx - A.o2); n = e >> 9; k = e & 511; base = T.conv2x(); N = 64; }
+    else if (idx >= A.o3 && idx < A.o3 + 64 * 576) { const int e = (int)(idx - A.o3); n = e / 576; k = e - n * 576; base = T.conv3x(); N = 64; c3 = true; }
+    else return;
+    float x[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = c1 ? w[e] / 255.0f : w[e];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const uint2 t{a0_bf16_term(x[0], s) | (a0_bf16_term(x[1], s) << 16), a0_bf16_term(x[2], s) | (a0_bf16_term(x[3], s) << 16)};
+        const int dw = base + a0_tail_term_dword(N, n, k, s);          // k a multiple of four: an even dword
+        if (!S.skip) *(uint2*)((uint32_t*)A.wt + dw) = t;
+        if (S.sync) *(uint2*)((uint32_t*)A.wt_t + dw) = t;
+    }
+    if (c1) return;
+    const int ring = (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4) * 4 + ((k >> 2) & 3);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        a0_tail_put32(A, S, ring + 4 * e, __float_as_uint(w[e]));
+        a0_tail_wt_dgrad(A, S, T, c3, n, k + e, w[e]);
+    }
+}
+
+// a0_adam_sync_kernel's element, 16-byte form: float4 i of the flat buffer; HAVE_G: the gradient is the sum this lane has just formed
+template <bool HAVE_G>
+A0_D void a0_tail_adam4(const a0_tail_args& A, const a0_tail_step& S, long long i, a0_f4 gsum) {
+    const long long n4 = A.n >> 2, end4 = (S.sync ? A.n_total : A.n) >> 2;
+    if ((S.skip && !S.sync) || i >= end4) return;
+    const float w1 = A.w1, b2 = A.b2, w2 = A.w2, eps = A.eps, step_size = S.step_size, bc2_sqrt = S.bc2_sqrt;
+    a0_f4 pv = ((a0_f4*)A.p)[i];
+    if (i < n4 && !S.skip) {
+        a0_f4 gv;
+        if constexpr (HAVE_G) gv = gsum; else gv = ((const a0_f4*)A.g)[i];
+        a0_f4 mv = ((a0_f4*)A.m)[i], vv = ((a0_f4*)A.v)[i];
+        float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            // a0_adam_sync_kernel's 16-byte path as it is compiled (v_pk_fma): written out, so that no choice of the compiler's contraction can part the two kernels
+#pragma clang fp contract(off)
+            const float gi = gp[e];
+            float mi = mp[e], vi = vp[e];
+            mi = __builtin_fmaf(gi - mi, w1, mi);
+            vi = __builtin_fmaf(w2 * gi, gi, vi * b2);
+            const float denom = sqrtf(vi) / bc2_sqrt + eps;
+            pp[e] = __builtin_fmaf(-step_size, mi / denom, pp[e]);
+            mp[e] = mi; vp[e] = vi;
+        }
+        ((a0_f4*)A.p)[i] = pv; ((a0_f4*)A.m)[i] = mv; ((a0_f4*)A.v)[i] = vv;
+    }
+    if (S.sync) ((a0_f4*)A.target)[i] = pv;
+    if (A.wt4) a0_tail_wt4(A, S, 4 * i, pv);
+    else { a0_tail_wt1(A, S, 4 * i, pv.x); a0_tail_wt1(A, S, 4 * i + 1, pv.y); a0_tail_wt1(A, S, 4 * i + 2, pv.z); a0_tail_wt1(A, S, 4 * i + 3, pv.w); }
+}
+// ... and its scalar form
+template <bool HAVE_G>
+A0_D void a0_tail_adam1(const a0_tail_args& A, const a0_tail_step& S, long long i, float gsum) {
+    const long long end = S.sync ? A.n_total : A.n;
+    if ((S.skip && !S.sync) || i >= end) return;
+    const float w1 = A.w1, b2 = A.b2, w2 = A.w2, eps = A.eps, step_size = S.step_size, bc2_sqrt = S.bc2_sqrt;
+    float pi = A.p[i];
+    if (i < A.n && !S.skip) {
+        // a0_adam_sync_kernel's scalar path as it is compiled: both moments from rounded products (v_mul / v_pk_mul, then v_add), the step as one v_fma
+#pragma clang fp contract(off)
+        const float gi = HAVE_G ? gsum : A.g[i];
+        float mi = A.m[i], vi = A.v[i];
+        mi = mi + (gi - mi) * w1;
+        vi = vi * b2 + (w2 * gi) * gi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        pi = __builtin_fmaf(-step_size, mi / denom, pi);
+        A.p[i] = pi;
+        A.m[i] = mi;
+        A.v[i] = vi;
+    }
+    if (S.sync) A.target[i] = pi;
+    a0_tail_wt1(A, S, i, pi);
+}
+// a sum leaves as a plain register value, as a loaded gradient would arrive
+A0_D float a0_tail_settle(float r) { asm volatile("" : "+v"(r)); return r; }
+
+__global__ __launch_bounds__(256) void a0_update_tail_kernel(a0_tail_args A) {
+    __shared__ a0_f4 red4[8][33];
+    // workgroup 0: the batch mean of this update's per-sample losses into its ring slot, statement for statement as in a0_adam_sync_kernel<true, ...>
+    if (blockIdx.x == 0 && A.loss) {
+        __shared__ float red[256];
+        float s = 0.f;
+        for (int e = threadIdx.x; e < A.loss_n; e += 256) s += A.loss[e];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+        if (threadIdx.x == 0) { const int c = A.state_w[6]; A.loss_ring[c % A.ring_cap] = red[0] / (float)A.loss_n; A.state_w[6] = c + 1; }
+    }
+    const a0_tail_step S{A.state[3] != 0, A.state[4] != 0, A.scal[0], A.scal[1]};
+    int ri = 0;
+    for (int k = 1; k < A.nreg; ++k) ri += ((int)blockIdx.x >= A.reg[k].first_block) ? 1 : 0;
+    const a0_tail_region R = A.reg[ri];
+    const long long blk = (long long)((int)blockIdx.x - R.first_block);
+    if (R.seg < 0) {           // between the segments
+        if (R.vec) {
+            const long long i4 = (R.lo >> 2) + blk * 256 + threadIdx.x;
+            if (i4 < (R.hi >> 2)) a0_tail_adam4<false>(A, S, i4, a0_zero4());
+        } else {
+            const long long i = R.lo + blk * 256 + threadIdx.x;
+            if (i < R.hi) a0_tail_adam1<false>(A, S, i, 0.f);
+        }
+        return;
+    }
+    const a0_reduce_seg G = A.seg[R.seg];
+    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
+    if (R.vec) {
+        const long long i4 = blk * 32 + c;                    // float4 index in the segment
+        const long long n4 = G.count >> 2, st4 = G.slab_stride >> 2;
+        red4[g][c] = i4 < n4 ? a0_rowgroup_sum4((const a0_f4*)G.slabs + i4, st4, g, G.nslab) : a0_zero4();
+        __syncthreads();
+        if (g == 0 && i4 < n4) {
+            a0_f4 t = a0_zero4();
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const a0_f4 v = red4[j][c]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
+            ((a0_f4*)G.out)[i4] = t;
+            t.x = a0_tail_settle(t.x); t.y = a0_tail_settle(t.y); t.z = a0_tail_settle(t.z); t.w = a0_tail_settle(t.w);
+            if (A.vec4) a0_tail_adam4<true>(A, S, (R.lo >> 2) + i4, t);
+            else {
+                const long long i = R.lo + 4 * i4;
+                a0_tail_adam1<true>(A, S, i, t.x); a0_tail_adam1<true>(A, S, i + 1, t.y); a0_tail_adam1<true>(A, S, i + 2, t.z); a0_tail_adam1<true>(A, S, i + 3, t.w);
+            }
+        }
+        return;
+    }
+    // scalar path: 32 flat indices per workgroup from R.lo on — the segment's first float, rounded down to a multiple of four where Adam takes its 16-byte form, so
+    // that every aligned group of four parameters is stepped by ONE lane with that form's arithmetic, as a0_adam_sync_kernel would step it (the forms differ in how the
+    // compiler pairs and contracts them); which lane forms an output's sum does not change the sum
+    float* red = (float*)red4;                                 // [8][33] floats
+    const long long F = R.lo + blk * 32 + c, i = F - (G.out - A.g);
+    const bool in = i >= 0 && i < G.count;
+    red[g * 33 + c] = in ? a0_rowgroup_sum1(G.slabs + i, G.slab_stride, g, G.nslab) : 0.f;
+    __syncthreads();
+    float t = 0.f;
+    if (g == 0 && in) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t += red[j * 33 + c];
+        G.out[i] = t;
+        t = a0_tail_settle(t);
+        if (!A.vec4) a0_tail_adam1<true>(A, S, F, t);
+    }
+    if (!A.vec4) return;
+    __syncthreads();
+    if (g == 0 && F < R.hi) red[c] = in ? t : A.g[F];          // a neighbour outside the segment: its gradient is final in memory
+    __syncthreads();
+    if (g == 0 && (c & 3) == 0 && F < R.hi) a0_tail_adam4<true>(A, S, F >> 2, a0_f4{red[c], red[c + 1], red[c + 2], red[c + 3]});
+}
+
+extern "C" int a0_update_tail(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, const float* scalars, double beta1, double beta2,
+                              double eps, float* target, long long n_total, const a0_update_tail_plan* plan, const a0_encoder_weights* w, int C, float* wt, float* wt_target,
+                              const float* loss, int loss_n, float* loss_ring, int ring_cap, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n || !plan || plan->n < 0 || plan->n > 8 || !w || !w->w1 ||
+        !w->w2 || !w->w3 || !wt || !wt_target || C < 1)
+        return a0_fail(A0_EINVAL, "a0_update_tail: bad argument");
+    if (loss && (!loss_ring || loss_n < 1 || ring_cap < 1)) return a0_fail(A0_EINVAL, "a0_update_tail: loss statistics need a ring of at least one slot");
+    a0_tail_args A;
+    A.p = params; A.g = grads; A.m = exp_avg; A.v = exp_avg_sq; A.target = target; A.n = n; A.n_total = n_total;
+    A.state = state; A.scal = scalars; A.w1 = (float)(1.0 - beta1); A.b2 = (float)beta2; A.w2 = (float)(1.0 - beta2); A.eps = (float)eps;
+    A.vec4 = ((n | n_total) % 4 == 0) && ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
+    A.loss = loss; A.loss_n = loss_n; A.loss_ring = loss_ring; A.ring_cap = ring_cap > 0 ? ring_cap : 1; A.state_w = state;
+    A.K1 = C * 64; A.wt = wt; A.wt_t = wt_target;
+    A.o1 = w->w1 - params; A.o2 = w->w2 - params; A.o3 = w->w3 - params;
+    if (A.o1 < 0 || A.o1 + 32LL * A.K1 > n_total || A.o2 < 0 || A.o2 + 64 * 512 > n_total || A.o3 < 0 || A.o3 + 64 * 576 > n_total)
+        return a0_fail(A0_EINVAL, "a0_update_tail: the convolution weights must lie inside params");
+    A.wt4 = ((A.o1 | A.o2 | A.o3) % 4 == 0) ? 1 : 0;
+    // the segments in the order of their place in the flat buffer, the ranges between them, and each region's share of the grid
+    int order[8];
+    for (int k = 0; k < plan->n; ++k) {
+        const a0_reduce_seg& s = plan->seg[k];
+        if (!s.slabs || !s.out || s.nslab < 1 || s.count < 1 || s.out < grads || (s.out - grads) + s.count > n_total) return a0_fail(A0_EINVAL, "a0_update_tail: a segment outside grads[0, n_total)");
+        A.seg[k] = s; order[k] = k;
+    }
+    for (int k = plan->n; k < 8; ++k) A.seg[k] = a0_reduce_seg{nullptr, 0, 0, nullptr, 0};
+    std::sort(order, order + plan->n, [&](int a, int b) { return plan->seg[a].out < plan->seg[b].out; });
+    long long at = 0, blocks = 0;
+    int nreg = 0;
+    auto gap = [&](long long lo, long long hi) {
+        if (lo >= hi) return;
+        const int vec = A.vec4 && lo % 4 == 0 && hi % 4 == 0;
+        A.reg[nreg++] = a0_tail_region{lo, hi, (int)blocks, -1, vec, 0};
+        blocks += vec ? ((hi - lo) / 4 + 255) / 256 : (hi - lo + 255) / 256;
+    };
+    for (int j = 0; j < plan->n; ++j) {
+        const a0_reduce_seg& s = plan->seg[order[j]];
+        long long lo = s.out - grads, hi = lo + s.count;
+        // a0_reduce_segments_kernel's choice of path
+        const int vec = ((s.count | s.slab_stride) % 4 == 0) && ((((uintptr_t)s.slabs) | ((uintptr_t)s.out)) % 16 == 0);
+        if (!vec && A.vec4) { lo = lo / 4 * 4; hi = (hi + 3) / 4 * 4; }       // 16-byte Adam: a scalar segment's region grows to whole groups of four (see the kernel)
+        if (lo < at) return a0_fail(A0_EINVAL, "a0_update_tail: segments overlap or share a 16-byte group of parameters");
+        gap(at, lo);
+        A.reg[nreg++] = a0_tail_region{lo, hi, (int)blocks, order[j], vec, 0};
+        blocks += vec ? (s.count / 4 + 31) / 32 : (hi - lo + 31) / 32;
+        at = hi;
+    }
+    gap(at, n_total);
+    A.nreg = nreg;
+    for (int k = nreg; k < 17; ++k) A.reg[k] = a0_tail_region{0, 0, 0x7fffffff, -1, 0, 0};
+    if (blocks < 1 || blocks > 0x7fffffffLL) return a0_fail(A0_EINVAL, "a0_update_tail: grid");
+    hipLaunchKernelGGL(a0_update_tail_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
+    return a0_fail_hip((int)hipGetLastError(), "a0_update_tail");
 }
 
 // out[0] = 1.0f if this rank's NaN flag (state[0], set by the loss kernels) is up, else 0.0f — a float so that it can ride along in

@@ -1,0 +1,78 @@
+// What the one-launch update tail (optim.hip: a0_update_tail_kernel) shares with the kernels it replaces per update: the row-group sums of
+// a0_reduce_segments_kernel (net.hip), the weight-copy layout and the bf16 terms of a0_conv_wt_kernel (encoder_fused.hip), and the one-thread
+// bookkeeping of an optimizer step, which rides in the launch in front of the tail (conv1_wgrad.hip, or a launch of its own).
+#pragma once
+#include "a0_defs.h"
+
+#include <cstdint>
+
+// ---- slab sums: row group g of a workgroup adds the slabs z = g, g + 8, ... in increasing z; the eight partial sums meet in LDS and are added 0..7 from zero
+// four of this row group's slabs requested before any is added (same order of additions): the loads of a 72-slab segment overlap instead of queueing
+A0_D a0_f4 a0_rowgroup_sum4(const a0_f4* p, long long st4, int g, int nslab) {
+    a0_f4 s = a0_zero4();
+    for (int z = g; z < nslab; z += 32) {
+        a0_f4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = (z + 8 * u < nslab) ? p[(long long)(z + 8 * u) * st4] : a0_zero4();
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (z + 8 * u < nslab) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
+    }
+    return s;
+}
+A0_D float a0_rowgroup_sum1(const float* p, long long slab_stride, int g, int nslab) {
+    float s = 0.f;
+    for (int z = g; z < nslab; z += 8) s += p[(long long)z * slab_stride];
+    return s;
+}
+
+// ---- The weight-copy buffer `wt` that a0_conv_wt_kernel fills from the packed [N][K] weights and every fused kernel reads: the length of each
+// segment and its offset, in floats, for C input channels.  This is the only description of the layout in the library.
+struct a0_wt_layout {
+    int C;
+    constexpr int n_conv1x() const { return 48 * 64 * C; }      // conv1: fl(w/255) as three exact bf16 terms, a0_wring1 layout (32 x 64 C x 3 x 2 bytes)
+    static constexpr int n_conv2 = 64 * 512;                    // conv2 fp32, fragment-major (a0_wring layout)
+    static constexpr int n_conv3 = 64 * 576;                    // conv3 fp32, fragment-major
+    static constexpr int n_conv2x = 96 * 512;                   // conv2 as three exact bf16 terms (a0_wring9 layout, N = 64): 64 x K x 3 x 2 bytes
+    static constexpr int n_conv3x = 96 * 576;                   // conv3 likewise
+    static constexpr int n_dgrad3x = 96 * 576;                  // conv3's data-gradient matrix (flipped taps) [576][64] as three bf16 terms, a0_wring9 layout, N = 64
+    static constexpr int n_dgrad2x_phase = 48 * 256;            // conv2's data-gradient matrix of one stride phase [256][32], a0_wring9 layout, N = 32; four of them
+    constexpr int conv1x() const { return 0; }
+    constexpr int conv2() const { return n_conv1x(); }
+    constexpr int conv3() const { return conv2() + n_conv2; }
+    constexpr int conv2x() const { return conv3() + n_conv3; }
+    constexpr int conv3x() const { return conv2x() + n_conv2x; }
+    constexpr int dgrad3x() const { return conv3x() + n_conv3x; }
+    constexpr int dgrad2x() const { return dgrad3x() + n_dgrad3x; }
+    constexpr int total() const { return dgrad2x() + 4 * n_dgrad2x_phase; }
+};
+
+#if defined(__HIPCC__)
+A0_HD uint32_t a0_bf16_trunc(float f) { return __float_as_uint(f) >> 16; }
+A0_HD float a0_bf16_up(uint32_t h) { return __uint_as_float(h << 16); }
+// w = hi + mid + lo EXACTLY, three bf16 terms of 8 significant bits each: term s (0 = hi, 1 = mid, 2 = lo) as bf16 bits
+A0_HD uint32_t a0_bf16_term(float w, int s) {
+    const uint32_t hi = a0_bf16_trunc(w);
+    const float r1 = w - a0_bf16_up(hi);              // exact: at most 16 significant bits left
+    const uint32_t mid = a0_bf16_trunc(r1);
+    const float r2 = r1 - a0_bf16_up(mid);            // exact: at most 8 significant bits left
+    return s == 0 ? hi : s == 1 ? mid : a0_bf16_trunc(r2);
+}
+
+// ---- an optimizer step's bookkeeping, one thread (the arithmetic of a0_adam_prep_kernel and of the folded Adam kernel, optim.hip, and the commit the weight-copy
+// refresh carried): NaN skip, step count, bias corrections, "sync now".  It needs the NaN flag to be final — the loss kernel ran — and nothing else, so it rides
+// in the last launch in front of the tail, whose workgroups then only read state[3], state[4] and the scalars: words nobody writes while they run.
+struct a0_tail_prep { int* state; float* scal; double lr, b1, b2; int target_freq; };
+A0_D void a0_tail_prep_run(const a0_tail_prep& P) {
+    int* const state = P.state;
+    const int sk = state[0] != 0;
+    const int steps = state[1] + (sk ? 0 : 1);
+    const int t = steps > 0 ? steps : 1;
+    const float ss = (float)(P.lr / (1.0 - pow(P.b1, (double)t))), bc = (float)sqrt(1.0 - pow(P.b2, (double)t));
+    const int sy = (P.target_freq > 0 && (steps % P.target_freq) == 0) ? 1 : 0;
+    if (sk) state[2] += 1;
+    state[3] = sk; state[4] = sy; state[5] = steps;
+    P.scal[0] = ss; P.scal[1] = bc;
+    state[1] = steps; state[0] = 0;
+}
+#endif

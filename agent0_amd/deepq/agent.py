@@ -698,7 +698,7 @@ class BaseLearner:
                     out = eng.forward_dense(frames, slot, row_bytes, act, rew, done, weights, rand, tstage=tstage)
                     if not hooked:                                # the whole update is one graph, in-graph exchange included
                         eng.exchange_begin()
-                        eng.backward_encoder()
+                        eng.backward_encoder(fuse_tail=True)
                         eng.exchange_end()
                         eng.apply()
             except Exception as e:      # noqa: BLE001

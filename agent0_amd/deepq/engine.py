@@ -375,6 +375,10 @@ class DeviceLearner:
             self._enc_slab_off, self._defer_dense = ops.dense_wgrad_multi_scratch(shapes), True
             n_slab = max(n_slab, self._enc_slab_off + ops.encoder_bwd_scratch(self.net, B))
         self._pend = None
+        # the update's tail as one launch (ops.update_tail: slab sums, Adam, target copy, weight copies); a backend without it composes the three launches
+        self.fused_tail = self._defer_dense and hasattr(ops, "update_tail")
+        self.fused_tail_reason = "one-launch update tail" if self.fused_tail else "three-launch update tail: the backend has no update_tail or the encoder is not fused"
+        self._tail_plan = None
         self.slabs = ops.empty(n_slab)
         self.obs_bytes = L.C * L.H * L.W
         self.grad_hook = None       # data parallelism: callable(grads, state) run between backward and the optimizer (dist.GradAllReduce)
@@ -447,17 +451,24 @@ class DeviceLearner:
             mods.append((self.grads[mu.all], None, self.grads[sg.all], mu.N, mu.K, r0, r1, nz["noise_in"], nz["noise_out_weight"], nz["noise_out_bias"]))
         self.ops.noisy_multi(True, mods)
 
-    def backward_encoder(self):
+    def backward_encoder(self, fuse_tail: bool = False):
         """d3 -> the three convolution blocks' gradients (flat range [0, L.conv_end)); the second half of the backward pass, on the
-        batch of the last forward_dense call."""
+        batch of the last forward_dense call.  ``fuse_tail``: apply() follows at once, so the slab sums may be left to its launch (ops.update_tail) — not under a
+        gradient hook or clipping, which need the summed gradient first, nor when NoisyNet's sigma gradients wait for deferred dense sums."""
         L, ops, on = self.L, self.ops, self.online
         ws, frames, slot, stride, B = self._bw
         g1, g2, g3 = self.grads[L.blocks["conv1"].all], self.grads[L.blocks["conv2"].all], self.grads[L.blocks["conv3"].all]
+        self._tail_plan = None
         if on.fused and on.fused_dgrad:
             # both data gradients per observation in one kernel (LDS-resident d2), then the three weight-gradient GEMMs
             ops.encoder_dgrad_fused(self.net, on.wt, ws.d3, ws.act1, ws.act2, B, ws.d2, ws.d1)
             pend, self._pend = self._pend, None
-            if pend is not None:
+            if (fuse_tail and self.fused_tail and pend is not None and self.grad_hook is None and self.clip_grad_norm <= 0 and not (L.noisy and pend.n > 0)):
+                self._tail_plan = ops.encoder_wgrad_tail(self.net, on.encoder_weights(), frames, slot, stride, 0, B, ws.act1, ws.act2, ws.d3, ws.d2, ws.d1, g1, g2, g3,
+                                                         self.slabs[self._enc_slab_off:], pend, self.state, self.scalars, self.lr, 0.9, 0.999, self.target_update_freq)
+                if L.noisy:
+                    self._noisy_sigma_grads()
+            elif pend is not None:
                 ops.encoder_wgrad(self.net, on.encoder_weights(), frames, slot, stride, 0, B, ws.act1, ws.act2, ws.d3, ws.d2, ws.d1, g1, g2, g3, self.slabs[self._enc_slab_off:],
                                   pend=pend)
                 if L.noisy:
@@ -474,7 +485,7 @@ class DeviceLearner:
         run into the buffers of that parity (``target_stage``)."""
         out = self.forward_dense(frames, slot, sample_stride, act, rew, done, wgt, rand, tstage=tstage)
         self.exchange_begin()
-        self.backward_encoder()
+        self.backward_encoder(fuse_tail=True)
         self.exchange_end()
         self.apply()
         return out
@@ -513,6 +524,12 @@ class DeviceLearner:
         if L.algo == "fqf":           # unconditional, like the reference's fqf_optimizer.step() in front of the NaN guard (agent.py:139-148)
             blk = L.blocks["frac"]
             ops.rmsprop_step(on.flat[blk.all], self.grads[blk.all], self.rms_sq, blk.size, self.lr / 2e4, 0.95, 1e-5, self.max_grad_norm, self.clip)
+        plan, self._tail_plan = self._tail_plan, None
+        if plan is not None:
+            # backward_encoder(fuse_tail=True) left the slab sums and the step's bookkeeping to this launch
+            ops.update_tail(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, 0.9, 0.999, self.adam_eps, tg.flat, L.n_params_padded, plan,
+                            on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring)
+            return
         tail = self.grads[L.n_params_padded: L.n_params_padded + 1] if self._bucketed_hook() else None
         if self.clip_grad_norm > 0:
             # one launch more: the sum of squares over everything Adam owns (the fqf fraction net lies behind n_adam), taken here — behind the data-parallel

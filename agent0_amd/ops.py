@@ -275,6 +275,37 @@ class HipOps:
             _req(g1, torch.float32, 32 * net.K1 + 32, "g1"), _req(g2, torch.float32, 64 * net.K2 + 64, "g2"), _req(g3, torch.float32, 64 * net.K3 + 64, "g3"),
             _req(slabs, torch.float32, need, "slabs", optional=(need == 0)), None if pend is None else C.addressof(pend), _stream()), "a0_net_encoder_wgrad")
 
+    def encoder_wgrad_tail(self, net, w, frames, slot, sample_stride, chan_off, B, act1, act2, d3, d2, d1, g1, g2, g3, slabs, pend, state, scalars, lr, b1, b2, target_freq):
+        """``encoder_wgrad`` without its slab-reduction launch: -> the a0_update_tail_plan that ``update_tail`` finishes.  The optimizer step's bookkeeping
+        (state[0..5], scalars) rides in the last weight-gradient launch."""
+        from ._abi import UpdateTailPlan
+        fa = self._frames(net, frames, slot, sample_stride, chan_off, B)
+        ew = self._enc_w(w)
+        need = self.encoder_bwd_scratch(net, B)
+        plan = UpdateTailPlan()
+        plan.n = 0
+        check(self.lib.a0_net_encoder_wgrad_tail(
+            net.h, C.addressof(ew), C.addressof(fa), B,
+            _req(act1, torch.float32, B * net.H1 * net.W1 * 32, "act1"), _req(act2, torch.float32, B * net.H2 * net.W2 * 64, "act2"),
+            _req(d3, torch.float32, B * net.feat, "d3"), _req(d2, torch.float32, B * net.H2 * net.W2 * 64, "d2"),
+            _req(d1, torch.float32, B * net.H1 * net.W1 * 32, "d1"),
+            _req(g1, torch.float32, 32 * net.K1 + 32, "g1"), _req(g2, torch.float32, 64 * net.K2 + 64, "g2"), _req(g3, torch.float32, 64 * net.K3 + 64, "g3"),
+            _req(slabs, torch.float32, need, "slabs", optional=(need == 0)), None if pend is None else C.addressof(pend), C.addressof(plan),
+            _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"), lr, b1, b2, target_freq, _stream()), "a0_net_encoder_wgrad_tail")
+        return plan
+
+    def update_tail(self, params, grads, m, v, n, state, scalars, b1, b2, eps, target, n_total, plan, w, C_, wt, wt_target, loss=None, loss_n=0, loss_ring=None):
+        """The planned slab sums, Adam, the target copy, the loss mean's ring slot and the fused kernels' weight copies in ONE launch (a0_update_tail): the results of
+        ``encoder_wgrad``'s reduction launch followed by ``adam_step_sync_wt``, bit for bit."""
+        ew = self._enc_w(w)
+        nw = self.conv_wt_floats(C_)
+        check(self.lib.a0_update_tail(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n_total, "grads"), _req(m, torch.float32, n, "m"),
+                                      _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
+                                      b1, b2, eps, _req(target, torch.float32, n_total, "target"), n_total, C.addressof(plan), C.addressof(ew), C_,
+                                      _req(wt, torch.float32, nw, "wt"), _req(wt_target, torch.float32, nw, "wt_target"),
+                                      _req(loss, torch.float32, max(loss_n, 1), "loss", optional=True), int(loss_n), _req(loss_ring, torch.float32, 1, "loss_ring", optional=True),
+                                      0 if loss_ring is None else int(loss_ring.numel()), _stream()), "a0_update_tail")
+
     # ------------------------------------------------------------------ dense
     def dense_fwd_scratch(self, R, N, K) -> int:
         return int(self.lib.a0_dense_fwd_scratch(R, N, K))

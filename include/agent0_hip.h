@@ -111,6 +111,15 @@ int a0_net_encoder_wgrad(const a0_net* net, const a0_encoder_weights* w, const a
                          const float* d3, const float* d2, const float* d1, float* g1, float* g2, float* g3, float* slabs, const a0_pending_reduce* pend,
                          void* stream);
 
+/* The update tail in one launch (loss.backward()'s last sums + optimizer.step() + the target copy, agent.py:153-161).  a0_net_encoder_wgrad_tail is a0_net_encoder_wgrad
+ * WITHOUT its slab-reduction launch: the reductions (pend's first, then the encoder's) are filed in *plan, and the step's one-thread bookkeeping — NaN skip, step count, bias
+ * corrections, "sync now": state[0..5] and scalars2 exactly as a0_adam_step_sync_wt leaves them — rides in the last weight-gradient launch (a launch of its own where that
+ * is not the per-observation conv1 kernel).  Until a0_update_tail has run the gradients of the planned segments are not final and their slabs must stay untouched. */
+typedef struct a0_update_tail_plan { a0_reduce_seg seg[8]; int n; } a0_update_tail_plan;
+int a0_net_encoder_wgrad_tail(const a0_net* net, const a0_encoder_weights* w, const a0_frames_arg* frames, int B, const float* act1, const float* act2,
+                              const float* d3, const float* d2, const float* d1, float* g1, float* g2, float* g3, float* slabs, const a0_pending_reduce* pend,
+                              a0_update_tail_plan* plan, int* state, float* scalars2, double lr, double beta1, double beta2, int target_update_freq, void* stream);
+
 /* nn.Linear / NoisyLinear forward+backward (model.py:54-62,112-114): Y = act(X W^T + b), W [N][K] row-major.
  * N, K, ldx multiples of 4.  scratch sizes from the *_scratch functions (0 => may pass NULL). */
 long long a0_dense_fwd_scratch(int R, int N, int K);
@@ -371,6 +380,16 @@ int a0_adam_step_sync_wt_clip(float* params, const float* grads, float* exp_avg,
                               double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total, const float* extra_nan_flag,
                               const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n, float* loss_ring, int ring_cap,
                               const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream);
+/* ONE launch for what a0_net_encoder_wgrad's reduction launch and the two launches of a0_adam_step_sync_wt do, bit for bit: every planned slab sum is formed in
+ * a0_net_encoder_wgrad's order by the workgroup that owns those parameters, written to grads and stepped on at once; every other parameter takes the Adam path of
+ * a0_adam_step_sync; target copy on a sync step and loss-mean ring slot as in a0_adam_step_sync_wt; and the lane that holds a new convolution weight writes it to every
+ * place of `wt` (and, on a sync step, of `wt_target`) that a0_net_conv_wt_refresh would copy it to.  Call it behind a0_net_encoder_wgrad_tail, which has already derived
+ * the step's decisions into state / scalars2; here state[3], state[4] and the scalars are only read (state[6], the ring counter, advances as before).
+ * plan->seg[k].out must lie inside grads[0, n_total), the segments must not overlap; w->w1 / w2 / w3 must lie inside params; `wt` must hold the copies of the weights
+ * as they are before the call (a NaN-skipped step leaves it alone).  No data-parallel flag and no clipping: those paths keep the three-launch chain. */
+int a0_update_tail(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, const float* scalars2, double beta1, double beta2, double eps,
+                   float* target, long long n_total, const a0_update_tail_plan* plan, const a0_encoder_weights* w, int C, float* wt, float* wt_target,
+                   const float* loss, int loss_n, float* loss_ring, int ring_cap, void* stream);
 /* ---------------------------------------------------------------- a whole learner behind one handle (opaque handles, library-owned HBM)
  * BaseLearner (agent.py:97-169) with DQNLearner.train_step (173-190) for scalar heads on 4 x 84 x 84 observations — BASELINE configs[1]: online + target parameters
  * in the packed layout (agent0_amd/deepq/layout.py: conv1 | conv2 | conv3 | fc1 | head, each [W (N x K) | b (N)], head rows padded to a multiple of 32), gradients,

@@ -88,6 +88,8 @@ def model(cfg):
         "a0_qr_head_loss_slabs_kernel": ("QR from head slabs to quantile Huber loss + head gradient", "valu", max(LAUNCH, 512 * 200 * 200 * 8 / 64 * 2 / SIMDS / GHZ * 1e6 * 256 / 200) + 2.0,
                                          "20.5 M pairs x 8 vector instructions; lanes 200 of 256 busy; + staging of 3 x 4 KB per sample"),
         "a0_adam_sync_kernel": ("Adam + target copy + loss statistic", "hbm", hbm_us(n_par * 4 * 7), "28 B per parameter (p, g, m, v read; p, m, v written)"),
+        "a0_update_tail_kernel": ("update tail in one launch: slab sums + Adam + target copy + loss statistic + weight copies", "hbm", hbm_us(n_par * 4 * 7 + 8.4e6 + 3e6),
+                                  "28 B per parameter + conv1's 256 slabs x 32 KB + conv2 / conv3 / pending dense slabs; the gradient and the new conv weights are not read back"),
         "a0_reduce_segments_kernel": ("slab reductions of the weight gradients", "hbm / L2", max(LAUNCH, hbm_us(8.4e6 + 3e6)), "conv1's 256 slabs x 32 KB + conv2 / conv3 / head slabs"),
         "a0_reduce_bias_act_multi_kernel": ("fc1 slab sums of the update's passes", "launch", LAUNCH, ""),
         "a0_conv_wt_kernel": ("refresh of the fused kernels' weight copies", "launch", LAUNCH, "0.5 MB"),
