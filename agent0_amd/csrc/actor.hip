@@ -39,12 +39,13 @@ __global__ __launch_bounds__(256) void a0_egreedy_rng_kernel(const int* __restri
                                                               const long long* __restrict__ ctrl, const float* __restrict__ eps_ptr) {
     __shared__ float red[256];
     if (ctrl) { off_a += (unsigned long long)ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)ctrl[A0_CTRL_RNG_UNIFORM]; }
+    const bool per_env = eps_ptr && eps == A0_EPS_PER_ENV;      // actor.eps_ladder: env e acts with its own eps_ptr[e]
     if (eps_ptr) eps = eps_ptr[0];
     float s = 0.f;
     for (int e = threadIdx.x; e < E; e += 256) {
         const int ra = (int)(a0_philox_word(seed, stream_a, off_a + (unsigned long long)e) % (uint32_t)A);
         const float u = (float)(a0_philox_word(seed, stream_u, off_u + (unsigned long long)e) >> 8) * 0x1.0p-24f;
-        action[e] = (u > eps) ? greedy[e] : ra;
+        action[e] = (u > (per_env ? eps_ptr[e] : eps)) ? greedy[e] : ra;
         if (qmax) s += qmax[e];
     }
     if (!qs_out) return;
@@ -60,6 +61,28 @@ extern "C" int a0_actor_egreedy_rng(const int* greedy, unsigned long long seed, 
     if (!greedy || !action || E < 1 || A < 1) return a0_fail(A0_EINVAL, "a0_actor_egreedy_rng: bad argument");
     hipLaunchKernelGGL(a0_egreedy_rng_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, greedy, seed, stream_a, stream_u, off_a, off_u, A, eps, E, action, qmax, qs_out, ctrl, eps_ptr);
     return a0_fail_hip((int)hipGetLastError(), "a0_actor_egreedy_rng");
+}
+
+// actor.eps_ladder (Ape-X): env i of N explores with eps^(1 + alpha i / (N - 1)).  The power is formed in double and rounded to fp32 once — a few hundred values
+// once per rollout — so the result does not depend on which float powf the compiler picks; the edges are exact by construction: eps >= 1 (the schedule's all-random
+// warm-up), i == 0 and N <= 1 return eps itself, eps <= 0 (or NaN) returns 0.
+__global__ __launch_bounds__(256) void a0_eps_ladder_kernel(float eps, const float* __restrict__ eps_ptr, float alpha, int E, long long i0, long long n_total,
+                                                             float* __restrict__ eps_vec) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    if (eps_ptr) eps = eps_ptr[0];
+    const long long i = i0 + e;
+    float v;
+    if (!(eps > 0.f)) v = 0.f;
+    else if (eps >= 1.f || i == 0 || n_total <= 1) v = eps;
+    else v = (float)pow((double)eps, 1.0 + (double)alpha * (double)i / (double)(n_total - 1));
+    eps_vec[e] = v;
+}
+
+extern "C" int a0_eps_ladder(float eps, const float* eps_ptr, float alpha, int E, long long i0, long long n_total, float* eps_vec, void* stream) {
+    if (!eps_vec || !(alpha > 0.f) || E < 1 || i0 < 0 || n_total < 1 || i0 + E > n_total) return a0_fail(A0_EINVAL, "a0_eps_ladder: bad argument (alpha > 0, envs [i0, i0 + E) of n_total)");
+    hipLaunchKernelGGL(a0_eps_ladder_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, eps, eps_ptr, alpha, E, i0, n_total, eps_vec);
+    return a0_fail_hip((int)hipGetLastError(), "a0_eps_ladder");
 }
 
 // Ring of the last n (action, reward, done) per env; entry for step t lives at t % n (the per-env body: nstep.h, shared with host_step.hip).

@@ -2,6 +2,11 @@
 // kernel that goes on to encode the NEXT observation in the same launch (a0_actor_step_enc2_kernel, encoder_fused.hip: round 5).
 #pragma once
 #include "synth_env.h"
+// The epsilon env `e` of a launch acts with (include/agent0_hip.h, A0_EPS_PER_ENV): the scalar argument, the device scalar eps_ptr[0], or — actor.eps_ladder — the env's
+// own eps_ptr[e].  The sentinel only moves the address of the load the device scalar already costs; `e` uniform over the wave keeps it a scalar load.
+A0_D float a0_env_eps(float eps, const float* __restrict__ eps_ptr, uint32_t e) {
+    return eps_ptr ? eps_ptr[eps == A0_EPS_PER_ENV ? e : 0u] : eps;
+}
 // One wave finishes fc1 for env `er` from the GEMM's slabs (slab sum + bias + ReLU, in slab order: bit-identical to a0_reduce_bias_act_kernel),
 // evaluates the q head rows staged in `w2s`, the dueling combine, the first maximum and the epsilon-greedy draw.  `raw`: 64 floats of LDS
 // owned by this wave.  Lane 0 returns the action and max_a q; call with all 64 lanes.
@@ -119,7 +124,7 @@ A0_D void a0_actor_qhead_env_body(const a0_qenv_args& P, float* __restrict__ raw
         g += (uint32_t)P.ctrl[A0_CTRL_ENV_STEP]; steps += P.ctrl[A0_CTRL_ACTOR_STEPS]; start += P.ctrl[A0_CTRL_REPLAY_SLOT];
         off_a += (unsigned long long)P.ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)P.ctrl[A0_CTRL_RNG_UNIFORM];
     }
-    if (P.eps_ptr) eps = P.eps_ptr[0];
+    eps = a0_env_eps(eps, P.eps_ptr, e);
     const long long slot = (start + e) % P.cap;
     // the env's Philox draws on the VECTOR unit (every lane the same): on uniform inputs the compiler runs the ten rounds on the scalar unit and keeps their
     // partial products in scalar registers for the rest of the kernel (the source of its scalar-register spills)
@@ -202,7 +207,7 @@ A0_D void a0_actor_dist_tail_wave0(const a0_dtenv_args& P, float* __restrict__ x
     // return and the n-step ring's previous entries (a0_env_commit_prefetch) — the arithmetic behind the action then never waits for memory again
     long long steps = P.steps; unsigned long long off_a = P.off_a, off_u = P.off_u; float eps = P.eps;
     if (P.ctrl) { steps += P.ctrl[A0_CTRL_ACTOR_STEPS]; off_a += (unsigned long long)P.ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)P.ctrl[A0_CTRL_RNG_UNIFORM]; }
-    if (P.eps_ptr) eps = P.eps_ptr[0];
+    eps = a0_env_eps(eps, P.eps_ptr, e);
     a0_env_pre Z;
     if constexpr (ENV) {
         a0_env_commit_prefetch(Z, e, P.E, P.n, steps, P.ep_ret, P.ring_act, P.ring_rew, P.ring_done);

@@ -907,7 +907,7 @@ A0_D void a0_actor_step_enc2_body(const typename TAIL::Args& Q, const a0_step_en
         g += (uint32_t)Q.ctrl[A0_CTRL_ENV_STEP]; steps += Q.ctrl[A0_CTRL_ACTOR_STEPS]; start += Q.ctrl[A0_CTRL_REPLAY_SLOT];
         off_a += (unsigned long long)Q.ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)Q.ctrl[A0_CTRL_RNG_UNIFORM];
     }
-    if (Q.eps_ptr) eps = Q.eps_ptr[0];
+    eps = a0_env_eps(eps, Q.eps_ptr, e);
     const long long slot = (start + e) % Q.cap;
     uint32_t e_v = e;
     asm volatile("" : "+v"(e_v));

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void a0_actor_dist_tail_kernel(const float* __
     }
     if (lane != 0 || e >= E) return;
     if (ctrl) { off_a += (unsigned long long)ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)ctrl[A0_CTRL_RNG_UNIFORM]; }
-    if (eps_ptr) eps = eps_ptr[0];
+    eps = a0_env_eps(eps, eps_ptr, (uint32_t)__builtin_amdgcn_readfirstlane(e));      // one env per wave
     const int ra = (int)(a0_philox_word(seed, stream_a, off_a + (unsigned long long)e) % (uint32_t)A);
     const float u = (float)(a0_philox_word(seed, stream_u, off_u + (unsigned long long)e) >> 8) * 0x1.0p-24f;
     action[e] = (u > eps) ? besta : ra;

@@ -624,7 +624,7 @@ __global__ __launch_bounds__(256) void a0_actor_qhead_kernel(const float* __rest
     __syncthreads();
     if (e >= E) return;
     if (ctrl) { off_a += (unsigned long long)ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)ctrl[A0_CTRL_RNG_UNIFORM]; }
-    if (eps_ptr) eps = eps_ptr[0];
+    eps = a0_env_eps(eps, eps_ptr, (uint32_t)__builtin_amdgcn_readfirstlane(e));      // one env per wave
     int act = 0; float best = 0.f;
     a0_qhead_wave(slabs, slab_stride, nslab, b1, w2s, b2, A, dueling, e, lane, raw[wave], seed, stream_a, stream_u, off_a, off_u, eps, act, best);
     if (lane == 0) { action[e] = act; qmax[e] = best; }

@@ -308,6 +308,10 @@ struct a0_actor {
     a0_env_pool_desc pool{};
     uint8_t* ring_obs = nullptr;
     long long pool_whole = 0;
+    // actor.eps_ladder (a0_actor_set_eps_ladder): env e of a rollout acts with eps_vec[e] = ladder(epsilon, ladder_i0 + e, ladder_n); off: eps_vec is never read
+    float ladder_alpha = 0.f;
+    long long ladder_i0 = 0, ladder_n = 1;
+    float* eps_vec = nullptr;
 };
 
 // the network an actor acts with: the learner's online network, or the actor's own snapshot of it
@@ -432,6 +436,17 @@ extern "C" int a0_actor_attach_pool(a0_actor* a, const a0_env_pool_desc* d) {
     A0_CATCH
 }
 
+extern "C" int a0_actor_set_eps_ladder(a0_actor* a, float alpha, long long i0, long long n_total) {
+    A0_TRY
+    if (!a) return a0_fail(A0_EINVAL, "a0_actor_set_eps_ladder: null handle");
+    if (!(alpha > 0.f)) { a->ladder_alpha = 0.f; return A0_OK; }
+    if (i0 < 0 || n_total < 1 || i0 + a->E > n_total) return a0_fail(A0_EINVAL, "a0_actor_set_eps_ladder: the actor's envs are [i0, i0 + E) of n_total");
+    if (!a->eps_vec) { a->eps_vec = a->mem.alloc<float>(a->E); A0_HIP_THROW(hipDeviceSynchronize()); }
+    a->ladder_alpha = alpha; a->ladder_i0 = i0; a->ladder_n = n_total;
+    return A0_OK;
+    A0_CATCH
+}
+
 extern "C" int a0_actor_detach_pool(a0_actor* a) {
     if (!a) return a0_fail(A0_EINVAL, "a0_actor_detach_pool: null handle");
     a->pool_on = false;
@@ -485,7 +500,7 @@ static int a0_actor_compose(const a0_actor_net& V, void* stream) {
 // Actor._rollout_host over an attached pool (a0_env_pool_desc): the inference of Actor._act_device (the head's tail without an env step), the send, the wait for
 // the workers, the DMA-only upload and one ingest launch per step.  The step's bookkeeping runs ahead of the next step's inference (the Python classes enqueue it
 // after the next send); the kernels and their arguments are the same, so are the bytes.
-static int a0_actor_rollout_pool(a0_actor* a, a0_learner* L, a0_rbuf* R, float epsilon, const a0_actor_net& V, a0_encoder_weights& w, long long start, void* stream) {
+static int a0_actor_rollout_pool(a0_actor* a, a0_learner* L, a0_rbuf* R, float epsilon, const float* eps_vec, const a0_actor_net& V, a0_encoder_weights& w, long long start, void* stream) {
     a0_env_pool_desc& P = a->pool;
     const int E = a->E, A = a->d.A;
     const bool dist = L->d.algo == A0_ALGO_C51 || L->d.algo == A0_ALGO_QR, fqf = L->d.algo == A0_ALGO_FQF, quant = L->d.algo == A0_ALGO_IQN || fqf;
@@ -519,19 +534,19 @@ static int a0_actor_rollout_pool(a0_actor* a, a0_learner* L, a0_rbuf* R, float e
             A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), rows, L->Npad, 512, a->head_slabs, stream));
             const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
             A0_CHECK(a0_actor_quantile_tail(a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, fqf ? a->f_tau_all : nullptr,
-                                            E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr, a->action, qm, stream));
+                                            E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, qm, stream));
         } else if (dist) {
             A0_CHECK(a0_dense_fwd(a->act3, L->feat, V.Wf(), V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
             const int ns = a0_dense_fwd_partial_slabs(E, L->Npad, 512);
             A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), E, L->Npad, 512, a->head_slabs, stream));
             const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
             A0_CHECK(a0_actor_dist_tail(a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, L->d.algo == A0_ALGO_C51 ? 2 : 1,
-                                        L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr,
+                                        L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec,
                                         a->action, qm, stream));
         } else {
             const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
             A0_CHECK(a0_actor_qhead(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0, a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U,
-                                    oa, ou, epsilon, nullptr, nullptr, a->action, qm, stream));
+                                    oa, ou, epsilon, nullptr, eps_vec, a->action, qm, stream));
         }
         A0_CHECK(a0_env_pool_send(a->action, (int*)P.act_dev, E, (long long*)P.ctl_dev, P.step_word | (seq & P.seq_mask), stream));
         A0_CHECK(a0_pool_wait(P, seq));
@@ -573,7 +588,14 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
     // starts with its features in place; the convolution weights do not change inside a rollout, the last step has no next one
     // (not for an actor with its own network — the launch schedule: its rollout runs beside the update block, the critical path there, and a workgroup that holds a CU's
     // LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives: 9.43 -> 9.75 ms)
-    if (a->pool_on) return a0_actor_rollout_pool(a, L, R, epsilon, V, w, start, stream);
+    // actor.eps_ladder: the rollout's per-env epsilons, once; every tail below then reads its env's own entry (off: epsilon and a null pointer, as ever)
+    const float* eps_vec = nullptr;
+    if (a->ladder_alpha > 0.f) {
+        A0_CHECK(a0_eps_ladder(epsilon, nullptr, a->ladder_alpha, E, a->ladder_i0, a->ladder_n, a->eps_vec, stream));
+        eps_vec = a->eps_vec;
+        epsilon = A0_EPS_PER_ENV;
+    }
+    if (a->pool_on) return a0_actor_rollout_pool(a, L, R, epsilon, eps_vec, V, w, start, stream);
     const bool step_enc = !a->own_flat;
     bool feat_ready = false;
     for (int t = 0; t < a->T; ++t) {
@@ -610,14 +632,14 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
             a->g += 1;
             if (step_enc && t + 1 < a->T) {      // (round 6) the tail's workgroups go on to encode their env's new observation: the next step starts with its features
                 A0_CHECK(a0_actor_quantile_tail_env_step_enc(a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, fqf ? a->f_tau_all : nullptr, E, a->rng.seed,
-                                                             STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr, a->action, a->qmax_all + (long long)t * E, a->d.seed,
+                                                             STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed,
                                                              a->d.rank, a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
                                                              a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act,
                                                              R->rew, R->done, a->d.env_task, V.wt, &w, a->act3, stream));
                 feat_ready = true;
             } else
             A0_CHECK(a0_actor_quantile_tail_env_step(a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, fqf ? a->f_tau_all : nullptr, E, a->rng.seed,
-                                                     STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr, a->action, a->qmax_all + (long long)t * E, a->d.seed,
+                                                     STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed,
                                                      a->d.rank, a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
                                                      a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act,
                                                      R->rew, R->done, a->d.env_task, stream));
@@ -638,7 +660,7 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
             if (step_enc && t + 1 < a->T) {
                 A0_CHECK(a0_actor_dist_tail_env_step_enc(a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, L->d.algo == A0_ALGO_C51 ? 2 : 1,
                                                          L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed,
-                                                         STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr, a->action, a->qmax_all + (long long)t * E, a->d.seed, a->d.rank,
+                                                         STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed, a->d.rank,
                                                          a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps, a->d.discount,
                                                          a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
                                                          a->d.env_task, V.wt, &w, a->act3, stream));
@@ -646,7 +668,7 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
             } else
             A0_CHECK(a0_actor_dist_tail_env_step(a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, L->d.algo == A0_ALGO_C51 ? 2 : 1,
                                                  L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed,
-                                                 STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, nullptr, a->action, a->qmax_all + (long long)t * E, a->d.seed, a->d.rank,
+                                                 STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed, a->d.rank,
                                                  a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps, a->d.discount,
                                                  a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
                                                  a->d.env_task, stream));
@@ -660,14 +682,14 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
         a->g += 1;
         if (step_enc && t + 1 < a->T) {
             A0_CHECK(a0_actor_qhead_env_step_enc(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
-                                                 a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, nullptr, a->action, a->qmax_all + (long long)t * E,
+                                                 a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E,
                                                  a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nxt], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
                                                  a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
                                                  a->d.env_task, V.wt, &w, a->act3, stream));
             feat_ready = true;
         } else
         A0_CHECK(a0_actor_qhead_env_step(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
-                                         a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, nullptr, a->action, a->qmax_all + (long long)t * E,
+                                         a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E,
                                          a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nxt], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
                                          a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
                                          a->d.env_task, stream));

@@ -22,7 +22,7 @@ import torch
 from agent0_amd.common.atari_wrappers import make_atari
 from agent0_amd.common.utils import DeviceRng
 from .config import AlgoEnum, ExpConfig
-from .dist import graph_capture_kwargs
+from .dist import eps_ladder_span, graph_capture_kwargs
 from .engine import DeviceLearner, Workspace
 from .model import DeepQNet, layout_from_cfg
 from .replay import ReplayDataset, StageRing, TransitionBlock
@@ -91,6 +91,11 @@ class Actor:
         self.eps_dev = ops.zeros(1)
         self._ctrl_host = torch.zeros(8, dtype=torch.int64).pin_memory()
         self._eps_host = torch.zeros(1).pin_memory()
+        # actor.eps_ladder (Ape-X): a training rollout acts with one epsilon per env, eps^(1 + alpha i / (N - 1)), i and N counted over the whole job; the vector lives
+        # beside eps_dev and is allocated by the first rollout that fills it (``_eps_ladder``) — off, or on an actor that only tests, nothing is
+        self.rank = int(rank)
+        self.ladder_alpha = max(float(cfg.actor.eps_ladder), 0.0)
+        self.eps_vec = None
         self.out_act, self.out_rew, self.out_done = ops.zeros(E, dtype=torch.int32), ops.zeros(E), ops.zeros(E)
         self.atoms = self.model.head.atoms.reshape(-1).contiguous() if self.L.algo == "c51" else None
         self._stage = None
@@ -195,6 +200,16 @@ class Actor:
         ops.actor_egreedy_rng(self.greedy, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U, rng.reserve(rng.STREAM_EGREEDY_A, E),
                               rng.reserve(rng.STREAM_EGREEDY_U, E), L.A, float(epsilon), E, self.action, self.qmax, qs_slot, ctrl, eps_ptr)
 
+    def _eps_ladder(self, epsilon, eps_ptr=None):
+        """actor.eps_ladder: the rollout's per-env epsilons in one launch (a0_eps_ladder; from the device scalar ``eps_ptr`` inside a captured rollout), and what the
+        tails then take in place of ``(epsilon, eps_ptr)``: the per-env sentinel and the vector.  A group passes its envs' slice of it."""
+        from agent0_amd.ops import EPS_PER_ENV
+        i0, n_total = eps_ladder_span(self.rank, self.E)
+        if self.eps_vec is None:
+            self.eps_vec = self.ops.zeros(self.E)
+        self.ops.eps_ladder(epsilon, eps_ptr, self.ladder_alpha, self.E, i0, n_total, self.eps_vec)
+        return EPS_PER_ENV, self.eps_vec
+
     def act(self, epsilon):
         one = self.ops.zeros(1)
         self._act_device(epsilon, one)
@@ -210,6 +225,8 @@ class Actor:
         """The body of Actor.sample's loop (agent.py:48-88), every step enqueued on the stream without touching the host."""
         cfg, ops, E = self.cfg, self.ops, self.E
         R = self.ring_len
+        if self.ladder_alpha > 0 and not test:
+            epsilon, eps_ptr = self._eps_ladder(epsilon, eps_ptr)
         if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq != 0:
             # NoisyLinear.forward composes mu + sigma * epsilon on every call (model.py:54-62), i.e. with the parameters as they are NOW; the
             # composed copies the device keeps were last written before the learner's latest Adam step (or come from a weight snapshot).
@@ -316,6 +333,9 @@ class Actor:
                             self.out_act, self.out_rew, self.out_done, None)
             ops.replay_insert(rp.frames, rp.size, ob, (start + t * E) % rp.size, E, obs0, obs_next, self.out_act, self.out_rew, self.out_done, rp.act, rp.rew, rp.done, None)
 
+        eps_ptr = None
+        if self.ladder_alpha > 0:
+            epsilon, eps_ptr = self._eps_ladder(epsilon)
         if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq != 0:
             self.model._dev.compose_noise()                     # as in _rollout
         pending = None
@@ -323,7 +343,7 @@ class Actor:
             if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0:
                 self.model.reset_noise(rng=self.rng)
             self.action = self._host_actions[t & 1]
-            self._act_device(epsilon, self.qs[t:t + 1], None, None, t)
+            self._act_device(epsilon, self.qs[t:t + 1], None, eps_ptr, t)
             self.envs.step_send(self.action)
             if pending is not None:
                 bookkeeping(*pending)
@@ -337,24 +357,26 @@ class Actor:
             ops.mean_rows(self.qmax_all, T, E, self.qs)
 
     # ------------------------------------------------------------------ grouped host envs: CPU stepping of one group beside the GPU's inference of the other
-    def _group_infer_send(self, g, obs, epsilon, t, offs):
+    def _group_infer_send(self, g, obs, epsilon, t, offs, eps_ptr=None):
         """Actor.act for group ``g`` on its observations (agent.py:25-39), then the actions go to the group's workers without waiting for them.  ``offs``: the step's
         Philox offsets (epsilon-greedy action, uniform, and for iqn the fractions), reserved once for the whole batch; the group takes its envs' part of each.  Every
-        dense GEMM runs with the full batch's split count (``_split_plan``)."""
+        dense GEMM runs with the full batch's split count (``_split_plan``).  ``eps_ptr``: the rollout's per-env epsilons (actor.eps_ladder); the group reads its envs'."""
         L, ops, dev, rng, k, off = self.L, self.ops, self.model._dev, self.rng, g["E"], g["off"]
+        if eps_ptr is not None:
+            eps_ptr = eps_ptr[off:off + k]
         E, ws, sp = self.E, g["ws"], self._splits
         dev.encode(ws, obs, None, self.obs_bytes, 0, k, keep=False)
         qmax = self.qmax_all[t * E + off:t * E + off + k]
         if self.fused_tail:
             (W1, b1), (W2, b2) = dev.wb("fc1"), dev.wb("head")
             ops.actor_qhead_n(ws.act3, k, L.feat, sp["qhead"], W1, b1, W2, b2, L.A, L.dueling, g["scratch"], rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                              offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax)
+                              offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax, None, eps_ptr)
         elif self.dist_tail:
             dev._dense(ws.act3, L.feat, "fc1", ws.h, k, True, splits=sp["fc1"])
             Wh, bh = dev.wb("head")
             ns = ops.dense_fwd_partial_n(ws.h, 512, Wh, k, L.Npad, 512, sp["head"], g["slabs"])
             ops.actor_dist_tail(g["slabs"], ns, bh, L.Npad, L.A, L.T, L.dueling, 2 if L.algo == "c51" else 1, self.atoms, k, rng.seed, rng.STREAM_EGREEDY_A,
-                                rng.STREAM_EGREEDY_U, offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax)
+                                rng.STREAM_EGREEDY_U, offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax, None, eps_ptr)
         else:
             nt = self.n_tau
             if L.algo == "fqf":
@@ -367,7 +389,7 @@ class Actor:
             ns = dev.head_slabs(ws, k, taus, nt, g["slabs"], cos_ready=True, splits=sp)
             _, bh = dev.wb("head")
             ops.actor_quantile_tail(g["slabs"], ns, bh, L.Npad, L.A, nt, L.dueling, mode, aux, k, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                                    offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax)
+                                    offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax, None, eps_ptr)
         g["pool"].step_send(g["action"])
 
     def _rollout_groups(self, epsilon, T, start, bound=True, test=False, stage=None, frames_out=None):
@@ -382,13 +404,16 @@ class Actor:
         iqn = self.quant_slabs and self.L.algo == "iqn"
         reserve = lambda: (rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), rng.reserve(rng.STREAM_TAUS, E * self.n_tau) if iqn else 0)
         noisy, freq = bool(cfg.learner.noisy_net), int(cfg.learner.reset_noise_freq)
+        eps_ptr = None
+        if self.ladder_alpha > 0 and not test:
+            epsilon, eps_ptr = self._eps_ladder(epsilon)
         if noisy and self.steps % freq != 0:
             self.model._dev.compose_noise()                     # as in _rollout
         if noisy and self.steps % freq == 0:
             self.model.reset_noise(rng=self.rng)                # step 0's noise, ahead of its first inference
         offs = reserve()
         for gi, g in enumerate(self.groups):                      # step 0's actions: nothing to overlap with yet
-            self._group_infer_send(g, self.obs[gi], epsilon, 0, offs)
+            self._group_infer_send(g, self.obs[gi], epsilon, 0, offs, eps_ptr)
         for t in range(T):
             nxt_offs = reserve() if t + 1 < T else None
             frames = []
@@ -421,7 +446,7 @@ class Actor:
                     if gi == 0 and noisy and (self.steps + 1) % freq == 0:
                         # NoisyNet: the next step's noise, once, behind every group's inference of this step and ahead of any of the next
                         self.model.reset_noise(rng=self.rng)
-                    self._group_infer_send(g, obs_next, epsilon, t + 1, nxt_offs)
+                    self._group_infer_send(g, obs_next, epsilon, t + 1, nxt_offs, eps_ptr)
             if test:
                 frames_out.append(np.concatenate(frames, axis=0))
             self.steps += 1

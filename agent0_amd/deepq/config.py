@@ -18,6 +18,13 @@ Additions (all default to the reference's behaviour being available):
                    own worker processes and page-locked ring, so that the CPU steps one group while the GPU infers the other (the counterpart of the
                    reference's ``num_actors`` actor processes, launch.py:30-61).  1 = one HostEnvPool.  Every setting gives the same bytes; which one is
                    fastest depends on the emulator's CPU cost per step, so it is the user's choice.  Ignored by the device-resident synthetic env.
+  actor.eps_ladder float, default 0.0 (off; any value <= 0 is off).  alpha > 0: training rollouts explore with one epsilon PER ENVIRONMENT, Ape-X's ladder: env i of
+                   the N environments acts with eps_i = eps^(1 + alpha * i / (N - 1)), eps being the scheduled scalar (so the decay to ``actor.min_eps`` keeps
+                   working; Ape-X's own recipe is ``actor.min_eps=0.4 actor.eps_ladder=7``).  Env 0 keeps eps; while eps >= 1 — the warm-up, where the schedule
+                   starts at 1 + min_eps (quirk Q15) — every env keeps it, so a ladder run is byte-identical to a plain one until eps drops below 1.  i and N
+                   count over the whole job: rank * num_envs + e of world * num_envs under data parallelism, the env's index in the whole vector env for a
+                   grouped host env.  Test rollouts, ``mode=play`` and ``Actor.act`` keep the scalar.  The vector is derived from eps every rollout: a snapshot
+                   does not store it, and the setting may change across a resume like ``actor.min_eps``.
   learner.clip_grad_norm  float, default -1.0 (off; any value <= 0 is off).  > 0: every update scales the gradient Adam steps on — the whole Q-network: conv blocks, fc1,
                    the head, NoisyNet sigmas, the cosine embedding; not the fqf fraction net, which keeps ``max_grad_norm`` and its RMSprop step — by
                    min(1, clip_grad_norm / (norm + 1e-6)), i.e. ``torch.nn.utils.clip_grad_norm_`` with its defaults, and the pre-clip norm is reported as
@@ -146,6 +153,7 @@ class ActorConfig:
     min_eps: float = 0.01
     test_eps: float = 0.001
     env_groups: int = 1
+    eps_ladder: float = 0.0
 
 
 @dataclass

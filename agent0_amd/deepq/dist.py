@@ -18,6 +18,15 @@ def env_world():
     return int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
 
 
+def eps_ladder_span(rank: int, num_envs: int):
+    """actor.eps_ladder counts environments over the whole job: rank r of a data-parallel job of ``world`` ranks with E envs each holds the global envs
+    [r E, (r + 1) E) of world E.  -> (index of the rank's first env, global count)."""
+    world = env_world()[2]
+    if not 0 <= rank < world:
+        raise ValueError(f"actor.eps_ladder: rank {rank} is not one of the job's {world} ranks")
+    return rank * num_envs, world * num_envs
+
+
 def free_port() -> int:
     """A TCP port that is free right now on the loopback interface (for a job's rendezvous)."""
     import socket

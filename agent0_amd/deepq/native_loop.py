@@ -202,6 +202,9 @@ class NativeLoop:
                         {"stream": 0, "block": 1, "chase": 2}[cfg.env_task], int(lc.reset_noise_freq))
         self.actor = C.c_void_p()
         ok(lib.a0_actor_create(C.addressof(ad), C.addressof(self.actor)), "a0_actor_create")
+        if actor.ladder_alpha > 0:      # actor.eps_ladder: the handle fills its own per-env epsilons at the start of every rollout, as Actor._eps_ladder does
+            from .dist import eps_ladder_span
+            ops.actor_set_eps_ladder(self.actor, actor.ladder_alpha, *eps_ladder_span(int(tr.rank), self.E))
         # every workspace now, so that no call of the loop allocates; on the launch schedule the actor gets its OWN copy of the network (launch.py:34-36,58-62) and rolls
         # out into the Trainer's stage ring on the Trainer's actor stream
         self.lp = bool(tr.use_lp)

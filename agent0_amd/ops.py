@@ -151,6 +151,14 @@ class _NoRange:
 _NO_RANGE = _NoRange()
 
 
+EPS_PER_ENV = -1.0      # A0_EPS_PER_ENV (include/agent0_hip.h): with ``eps_ptr`` given, env e of the launch acts with its own eps_ptr[e]
+
+
+def _eps_req(eps, eps_ptr, E: int):
+    """``eps_ptr`` of an action-selection launch: a device scalar, or — ``eps == EPS_PER_ENV`` — one epsilon per env of the launch (actor.eps_ladder)."""
+    return _req(eps_ptr, torch.float32, E if float(eps) == EPS_PER_ENV else 1, "eps_ptr", optional=True)
+
+
 class HipOps:
     name = "hip"
 
@@ -689,7 +697,7 @@ class HipOps:
     def actor_dist_tail(self, slabs, nslab, bias, ld, A, T, dueling, mode, atoms, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl=None, eps_ptr=None):
         check(self.lib.a0_actor_dist_tail(_req(slabs, torch.float32, nslab * E * ld, "slabs"), E * ld, nslab, _req(bias, torch.float32, ld, "bias"), ld, A, T, int(dueling),
                                           mode, _req(atoms, torch.float32, T, "atoms", optional=(mode != 2)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-                                          _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+                                          _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
                                           _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_dist_tail")
 
     def actor_quantile_tail(self, slabs, nslab, bias, ld, A, T, dueling, mode, taus, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl=None, eps_ptr=None):
@@ -697,7 +705,7 @@ class HipOps:
         check(self.lib.a0_actor_quantile_tail(
             _req(slabs, torch.float32, nslab * E * T * ld, "slabs"), E * T * ld, nslab, _req(bias, torch.float32, A + (1 if dueling else 0), "bias"), ld, A, T, int(dueling),
             mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_quantile_tail")
 
     def actor_dist_tail_env_step(self, slabs, nslab, bias, ld, A, T, dueling, mode, atoms, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
@@ -707,7 +715,7 @@ class HipOps:
         check(self.lib.a0_actor_dist_tail_env_step(
             _req(slabs, torch.float32, nslab * E * ld, "slabs"), E * ld, nslab, _req(bias, torch.float32, ld, "bias"), ld, A, T, int(dueling),
             mode, _req(atoms, torch.float32, T, "atoms", optional=(mode != 2)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
             env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
             _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
@@ -724,7 +732,7 @@ class HipOps:
         check(self.lib.a0_actor_dist_tail_env_step_enc(
             _req(slabs, torch.float32, nslab * E * ld, "slabs"), E * ld, nslab, _req(bias, torch.float32, ld, "bias"), ld, A, T, int(dueling),
             mode, _req(atoms, torch.float32, T, "atoms", optional=(mode != 2)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
             env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
             _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
@@ -740,7 +748,7 @@ class HipOps:
         check(self.lib.a0_actor_quantile_tail_env_step(
             _req(slabs, torch.float32, nslab * E * T * ld, "slabs"), E * T * ld, nslab, _req(bias, torch.float32, A + (1 if dueling else 0), "bias"), ld, A, T, int(dueling),
             mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
             env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
             _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
@@ -757,7 +765,7 @@ class HipOps:
         check(self.lib.a0_actor_quantile_tail_env_step_enc(
             _req(slabs, torch.float32, nslab * E * T * ld, "slabs"), E * T * ld, nslab, _req(bias, torch.float32, A + (1 if dueling else 0), "bias"), ld, A, T, int(dueling),
             mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
             env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
             _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
@@ -774,7 +782,7 @@ class HipOps:
         check(self.lib.a0_actor_qhead(_req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
                                       _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
                                       _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
-                                      _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+                                      _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
                                       _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_qhead")
 
     def actor_qhead_n(self, feat, E, K, splits, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl=None, eps_ptr=None):
@@ -783,7 +791,7 @@ class HipOps:
         check(self.lib.a0_actor_qhead_n(_req(feat, torch.float32, E * K, "feat"), E, K, int(splits), _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
                                         _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
                                         _req(scratch, torch.float32, splits * E * 512, "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
-                                        _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+                                        _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
                                         _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"), _stream()), "a0_actor_qhead_n")
 
     def actor_qhead_env_step(self, feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
@@ -795,7 +803,7 @@ class HipOps:
             _req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
             _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
             _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
             env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
             _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
@@ -814,7 +822,7 @@ class HipOps:
             _req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
             _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
             _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
             env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
             _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
@@ -914,7 +922,17 @@ class HipOps:
         check(self.lib.a0_actor_egreedy_rng(_req(greedy, torch.int32, E, "greedy"), seed, stream_a, stream_u, off_a, off_u, A, eps, E,
                                             _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax", optional=True),
                                             _req(qs_out, torch.float32, 1, "qs_out", optional=True), _req(ctrl, torch.int64, 8, "ctrl", optional=True),
-                                            _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True), _stream()), "a0_actor_egreedy_rng")
+                                            _eps_req(eps, eps_ptr, E), _stream()), "a0_actor_egreedy_rng")
+
+    def eps_ladder(self, eps, eps_ptr, alpha, E, i0, n_total, eps_vec):
+        """eps_vec[e] = eps^(1 + alpha (i0 + e) / (n_total - 1)) for e < E (a0_eps_ladder: the power in double, rounded once; eps >= 1 and env 0 keep eps, eps <= 0
+        gives 0); ``eps_ptr``: a device scalar that replaces ``eps`` (a captured rollout)."""
+        check(self.lib.a0_eps_ladder(float(eps), _req(eps_ptr, torch.float32, 1, "eps_ptr", optional=True), float(alpha), int(E), int(i0), int(n_total),
+                                     _req(eps_vec, torch.float32, E, "eps_vec"), _stream()), "a0_eps_ladder")
+
+    def actor_set_eps_ladder(self, actor, alpha, i0, n_total):
+        """actor.eps_ladder for an ``a0_actor`` handle (a0_actor_set_eps_ladder): its rollouts act with one epsilon per env; ``alpha <= 0`` switches it off."""
+        check(self.lib.a0_actor_set_eps_ladder(actor, float(alpha), int(i0), int(n_total)), "a0_actor_set_eps_ladder")
 
     def actor_nstep(self, E, n, steps, gamma, action, reward, terminal, truncated, life_loss, ring_act, ring_rew, ring_done, out_act, out_rew, out_done, ctrl=None):
         check(self.lib.a0_actor_nstep(E, n, steps, gamma, _req(action, torch.int32, E, "action"), _req(reward, torch.float32, E, "reward"),

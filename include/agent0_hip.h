@@ -544,6 +544,11 @@ int a0_actor_snapshot(a0_actor* actor, const a0_learner* learner, void* stream);
 /* (the learner is not const: like the reference's single-process main, the actor acts with the learner's own network object — a NoisyNet actor redraws that
  * network's noise every reset_noise_freq steps from ITS Philox stream 4 and recomposes the effective weights, agent.py:52-53) */
 int a0_actor_rollout(a0_actor* actor, a0_learner* learner, a0_rbuf* replay, float epsilon, void* stream);
+/* actor.eps_ladder for the handle: from now on a0_actor_rollout launches a0_eps_ladder(epsilon, NULL, alpha, E, i0, n_total, vec) once, ahead of its first step, into
+ * an [E] vector the handle owns (allocated by the first call with alpha > 0) and every step's tail reads its env's own entry (A0_EPS_PER_ENV) — device env,
+ * attached pool and the launch schedule's actor stream alike.  alpha <= 0 switches it off again: the rollout's launches and their arguments are those of a handle
+ * that never heard of it.  Derived from `epsilon` every rollout, so no part of a0_actor_state_save. */
+int a0_actor_set_eps_ladder(a0_actor* actor, float alpha, long long i0, long long n_total);
 int a0_actor_collect(a0_actor* actor, float* qs_host, float* returns_host, int max_returns, int* n_returns, void* stream);
 /* Host environments stepped by worker processes (agent0_amd/common/env_pool.py HostEnvPool): while a pool is attached, a0_actor_rollout steps IT instead of the
  * device env.  Per step t: encoder, fc1 + head + the head's tail (a0_actor_qhead / a0_actor_dist_tail / a0_actor_quantile_tail, the full batch's split counts),
@@ -687,6 +692,18 @@ int a0_sumtree_set_from_loss(float* tree, long long cap2, const long long* idx, 
 int a0_sumtree_top_rebuild(float* tree, long long cap2, void* stream);
 
 /* ---------------------------------------------------------------- actor (agent0/deepq/agent.py:25-39,57-73) */
+/* Epsilon of the action-selection entry points below (every one that takes `eps_ptr`): eps_ptr == NULL: the scalar argument `eps`; eps_ptr != NULL: eps_ptr[0], a
+ * device scalar (a captured rollout's epsilon), and `eps` is ignored — unless `eps` is A0_EPS_PER_ENV: then env e of the launch acts with its OWN eps_ptr[e]
+ * (eps_ptr: [E] floats; the index is relative to the pointer, so a launch over envs [off, off + k) of a vector passes vec + off).  What actor.eps_ladder hands in.
+ * CAUTION: beside a device scalar `eps` is therefore no longer a don't-care.  A caller who passes -1.0f there with a one-float eps_ptr makes the kernel read
+ * eps_ptr[1 .. E - 1], past that buffer; the entry points cannot see its length.  Pass any other value (0 will do) beside a device scalar. */
+#define A0_EPS_PER_ENV (-1.0f)
+/* The Ape-X epsilon ladder (actor.eps_ladder = alpha > 0): eps_vec[e] = ladder(eps, i0 + e, n_total) for e < E, where
+ *   ladder(eps, i, N) = eps^(1 + alpha * i / (N - 1))   formed as pow((double)eps, 1.0 + (double)alpha * i / (N - 1)) and rounded to fp32 once,
+ *   = eps, bit for bit, where eps >= 1 (the schedule's all-random warm-up), i == 0 or N <= 1;  = 0 where eps <= 0.
+ * i0 / n_total: the launch's first env in, and the size of, the GLOBAL vector of environments (data parallel: rank * E of world * E).  eps = eps_ptr[0] when
+ * eps_ptr is given (a captured rollout).  One small launch per rollout; alpha <= 0, E < 1, i0 < 0 or i0 + E > n_total: A0_EINVAL. */
+int a0_eps_ladder(float eps, const float* eps_ptr, float alpha, int E, long long i0, long long n_total, float* eps_vec, void* stream);
 int a0_actor_egreedy(const int* greedy, const int* rand_action, const float* u, float eps, int E, int* action,
                      const float* qmax, float* qs_out, void* stream);
 /* Fused actor tail for scalar heads (dqn / mdqn), Actor.act (agent.py:25-39) after the encoder: fc1 (split-K GEMM into `scratch`,
