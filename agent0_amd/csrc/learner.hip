@@ -306,6 +306,14 @@ extern "C" int a0_learner_set_grad_clip(a0_learner* L, double max_norm, float* n
     A0_CATCH
 }
 
+extern "C" int a0_learner_set_target_tau(a0_learner* L, double tau) {
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_target_tau: null handle");
+    if (L->updated) return a0_fail(A0_EINVAL, "a0_learner_set_target_tau: the setting is fixed once the handle has run an update");
+    if (!(tau < 1.0) || !((float)tau < 1.f)) return a0_fail(A0_EINVAL, "a0_learner_set_target_tau: tau >= 1 is the hard copy, which learner.target_update_freq alone gives");
+    L->target_tau = tau > 0.0 && (float)tau > 0.f ? tau : 0.0;
+    return A0_OK;
+}
+
 extern "C" int a0_learner_set_params(a0_learner* L, const float* online_packed, const float* target_packed, void* stream) {
     A0_TRY
     if (!L || !online_packed) return a0_fail(A0_EINVAL, "a0_learner_set_params: null argument");
@@ -385,6 +393,11 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
     if (row_bytes < 2LL * obs) return a0_fail(A0_EINVAL, "a0_learner_update: a replay row holds st || st_next (2 x C x H x W bytes)");
     float* on = L->online; float* tg = L->target;
     a0_encoder_weights w_on = L->enc(on), w_tg = L->enc(tg);
+    L->updated = true;
+    // learner.target_tau (DeviceLearner.apply): the Adam forms get the period 0 — never a hard copy — and a0_target_blend follows whichever tail form the update took
+    const bool soft = L->target_tau > 0.0;
+    const int hard_freq = soft ? 0 : L->d.target_update_freq;
+    auto blend = [&]() -> int { return soft ? a0_target_blend(tg, on, L->n_pad, L->target_tau, L->state, L->d.target_update_freq, 0, &w_tg, L->C, L->wt_tg, stream) : A0_OK; };
     if (L->d.noisy) {
         // BaseLearner.train (agent.py:125-127): reset_noise of the online, then of the target network — ONE Philox fill of the joint buffer (the same draws as two
         // fills: every vector is padded to the offsets' stride of four) — and both networks' effective weights in one launch
@@ -686,7 +699,7 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
     if (fuse_tail)
         A0_CHECK(a0_net_encoder_wgrad_tail(L->net, &w_on, &f_obs, B, L->act1, L->act2, L->d3, L->d2, L->d1, L->grads + L->conv1.off, L->grads + L->conv2.off,
                                            L->grads + L->conv3.off, L->slabs + L->enc_slab_off, &pend, &tail, L->state, L->scalars, L->d.lr, 0.9, 0.999,
-                                           L->d.target_update_freq, stream));
+                                           hard_freq, stream));
     else
     A0_CHECK(a0_net_encoder_wgrad(L->net, &w_on, &f_obs, B, L->act1, L->act2, L->d3, L->d2, L->d1, L->grads + L->conv1.off, L->grads + L->conv2.off, L->grads + L->conv3.off,
                                   L->slabs + L->enc_slab_off, &pend, stream));
@@ -712,18 +725,18 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
     if (fuse_tail) {
         A0_CHECK(a0_update_tail(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, 0.9, 0.999, eps, tg, L->n_pad, &tail, &w_on, L->C, L->wt_on, L->wt_tg, L->loss, B,
                                 L->loss_ring, L->loss_ring_cap, stream));
-        return A0_OK;
+        return blend();
     }
     if (L->clip_max_norm > 0.f) {
         // learner.clip_grad_norm (DeviceLearner.apply): every gradient Adam owns is final here — summed over the ranks behind the join above — so one launch takes
         // its sum of squares and the Adam launch turns it into the norm, the coefficient and the ring entry
         A0_CHECK(a0_grad_norm_partials(L->grads, L->n_adam, L->gnorm_partials, stream));
-        A0_CHECK(a0_adam_step_sync_wt_clip(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, L->d.target_update_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
+        A0_CHECK(a0_adam_step_sync_wt_clip(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, hard_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
                                            L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, L->gnorm_partials, L->clip_max_norm, L->gnorm_ring, L->gnorm_ring_cap, stream));
-        return A0_OK;
+        return blend();
     }
-    A0_CHECK(a0_adam_step_sync_wt(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, L->d.target_update_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
+    A0_CHECK(a0_adam_step_sync_wt(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, hard_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
                                   L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, stream));
-    return A0_OK;
+    return blend();
     A0_CATCH
 }

@@ -70,6 +70,9 @@ struct a0_learner {
     double* gnorm_partials = nullptr;
     float* gnorm_ring = nullptr;
     int gnorm_ring_cap = 0;
+    // ---- soft target updates (a0_learner_set_target_tau): off while target_tau <= 0; `updated`: an update has been issued, the setting is fixed from then on
+    double target_tau = 0.0;
+    bool updated = false;
     // library-owned HBM
     float *online = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *scalars = nullptr, *loss_ring = nullptr;
     float *wt_on = nullptr, *wt_tg = nullptr;

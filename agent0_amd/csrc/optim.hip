@@ -666,6 +666,81 @@ extern "C" int a0_target_sync(float* target, const float* online, long long n, c
     return a0_fail_hip((int)hipGetLastError(), "a0_target_sync");
 }
 
+// ------------------------------------------------------------------------------------------------ soft target updates
+// learner.target_tau: target <- target + tau * (online - target) over [0, n_total) — the whole module, as the hard copy takes it — at the updates where the hard copy
+// would have happened.  The Adam forms in front are called with a target period of 0 ("never sync"), so this launch decides for itself from the step count they have
+// committed by now: state[1] holds the NEW count behind all three tail forms.  When it does not blend, every workgroup returns at once.
+// One rounded subtraction and one fused multiply-add per element, kept out of the compiler's contraction choices (see a0_mul_rounded).
+A0_D float a0_blend1(float t, float p, float tau) {
+    float d;
+    {
+#pragma clang fp contract(off)
+        d = p - t;
+    }
+    asm volatile("" : "+v"(d));
+    return __builtin_fmaf(tau, d, t);
+}
+
+// W: the target's fused-kernel weight copies follow.  The lane that holds a blended convolution weight files it through the update tail's helpers, with a step that
+// writes the target side only (skip: the online copies are not touched; sync: the target's are) — a0_wt_layout stays the only description of the copy layout.
+struct a0_blend_wt { long long o1, o2, o3; int K1, wt4; float* wt_t; };
+template <bool W>
+__global__ __launch_bounds__(256) void a0_target_blend_kernel(float* __restrict__ target, const float* __restrict__ online, long long n_total, float tau,
+                                                              const int* __restrict__ state, int freq, int force, int vec4, a0_blend_wt B) {
+    if (!force && !(freq > 0 && state[1] % freq == 0)) return;
+    a0_tail_args A;
+    const a0_tail_step S{true, true, 0.f, 0.f};
+    if constexpr (W) { A.o1 = B.o1; A.o2 = B.o2; A.o3 = B.o3; A.K1 = B.K1; A.wt4 = B.wt4; A.wt = nullptr; A.wt_t = B.wt_t; }
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    long long done = 0;
+    if (vec4) {                     // both buffers 16-byte aligned: 16 bytes per lane, the same arithmetic per element, and a scalar tail of n_total % 4 floats
+        const long long n4 = n_total >> 2;
+        for (long long j = i; j < n4; j += stride) {
+            a0_f4 tv = ((a0_f4*)target)[j];
+            const a0_f4 pv = ((const a0_f4*)online)[j];
+            tv.x = a0_blend1(tv.x, pv.x, tau); tv.y = a0_blend1(tv.y, pv.y, tau); tv.z = a0_blend1(tv.z, pv.z, tau); tv.w = a0_blend1(tv.w, pv.w, tau);
+            ((a0_f4*)target)[j] = tv;
+            if constexpr (W) {
+                if (A.wt4) a0_tail_wt4(A, S, 4 * j, tv);
+                else { a0_tail_wt1(A, S, 4 * j, tv.x); a0_tail_wt1(A, S, 4 * j + 1, tv.y); a0_tail_wt1(A, S, 4 * j + 2, tv.z); a0_tail_wt1(A, S, 4 * j + 3, tv.w); }
+            }
+        }
+        done = n4 << 2;
+    }
+    for (long long j = done + i; j < n_total; j += stride) {
+        const float t = a0_blend1(target[j], online[j], tau);
+        target[j] = t;
+        if constexpr (W) a0_tail_wt1(A, S, j, t);
+    }
+}
+
+extern "C" int a0_target_blend(float* target, const float* online, long long n_total, double tau, const int* state, int target_update_freq, int force,
+                               const a0_encoder_weights* w_target, int C, float* wt_target, void* stream) {
+    if (!target || !online || n_total < 1 || (!force && !state) || ((((uintptr_t)target) | ((uintptr_t)online)) & 3))
+        return a0_fail(A0_EINVAL, "a0_target_blend: bad argument");
+    const float tau32 = (float)tau;       // rounded to fp32 once
+    if (!(tau > 0.0) || !(tau < 1.0) || !(tau32 > 0.f) || !(tau32 < 1.f)) return a0_fail(A0_EINVAL, "a0_target_blend: tau must lie in (0, 1); tau >= 1 is the hard copy (a0_target_sync)");
+    a0_blend_wt B{0, 0, 0, 0, 0, nullptr};
+    if (wt_target) {
+        if (!w_target || !w_target->w1 || !w_target->w2 || !w_target->w3 || C < 1) return a0_fail(A0_EINVAL, "a0_target_blend: weight copies need the target's encoder weights and C >= 1");
+        if (((uintptr_t)wt_target) & 15) return a0_fail(A0_EINVAL, "a0_target_blend: wt_target must be 16-byte aligned");
+        B.K1 = C * 64; B.wt_t = wt_target;
+        B.o1 = w_target->w1 - target; B.o2 = w_target->w2 - target; B.o3 = w_target->w3 - target;
+        if (B.o1 < 0 || B.o1 + 32LL * B.K1 > n_total || B.o2 < 0 || B.o2 + 64 * 512 > n_total || B.o3 < 0 || B.o3 + 64 * 576 > n_total)
+            return a0_fail(A0_EINVAL, "a0_target_blend: the convolution weights must lie inside target[0, n_total)");
+        B.wt4 = ((B.o1 | B.o2 | B.o3) % 4 == 0) ? 1 : 0;
+    }
+    const int vec4 = ((((uintptr_t)target) | ((uintptr_t)online)) % 16 == 0) ? 1 : 0;
+    long long blocks = ((vec4 ? (n_total + 3) / 4 : n_total) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (wt_target)
+        hipLaunchKernelGGL((a0_target_blend_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, target, online, n_total, tau32, state, target_update_freq, force, vec4, B);
+    else
+        hipLaunchKernelGGL((a0_target_blend_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, target, online, n_total, tau32, state, target_update_freq, force, vec4, B);
+    return a0_fail_hip((int)hipGetLastError(), "a0_target_blend");
+}
+
 // ------------------------------------------------------------------------------------------------ NoisyNet
 // W = mu + sigma * (f(eps_out) x f(eps_in)),  b = mu_b + sigma_b * f(eps_b),  f(x) = sign(x) sqrt|x|
 // (reference agent0/deepq/model.py:54-62,73-87).  Blocks are [W (N*K) | b (N)]; one call handles the rows [r0, r1) that

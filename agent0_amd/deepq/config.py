@@ -30,6 +30,11 @@ Additions (all default to the reference's behaviour being available):
                    min(1, clip_grad_norm / (norm + 1e-6)), i.e. ``torch.nn.utils.clip_grad_norm_`` with its defaults, and the pre-clip norm is reported as
                    ``grad_norm``.  The norm is that of the batch-SUM gradient (the loss is summed over the batch, quirk Q5), after the data-parallel exchange has
                    summed the ranks: a recipe's "10" for a batch-mean loss corresponds to 10 * batch_size here, times the world size under data parallelism.
+  learner.target_tau  float, default 0.0 (off; any value <= 0 is off; >= 1 is refused — that is the hard copy).  0 < tau < 1: the target network is not overwritten
+                   but moves towards the online one, target <- target + tau * (online - target) over the whole module, at exactly the updates where the hard
+                   copy would have happened: every ``learner.target_update_freq`` updates, which keeps its meaning and default (the classical recipe is
+                   ``learner.target_update_freq=1 learner.target_tau=0.005``).  The copy at construction and on checkpoint load stays a hard copy.  No state of
+                   its own: the target is already in every snapshot, and the setting may change across a resume like ``actor.min_eps``.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -121,6 +126,7 @@ class LearnerConfig:
     max_grad_norm: float = -1.0
     clip_grad_norm: float = -1.0
     target_update_freq: int = 500
+    target_tau: float = 0.0
     learner_steps: int = 20
     double_q: bool = False
     dueling_head: bool = False

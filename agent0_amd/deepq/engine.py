@@ -27,6 +27,17 @@ def clip_limit(value) -> float:
     return float(value) if value is not None and value > 0 else -1.0
 
 
+def target_tau_value(value) -> float:
+    """``learner.target_tau`` as the learner uses it: tau when 0 < tau < 1, 0.0 (off) for zero, a negative number or None; tau >= 1 — the hard copy, which
+    ``learner.target_update_freq`` alone gives — is refused."""
+    if value is None or not value > 0:
+        return 0.0
+    tau = float(value)
+    if tau >= 1.0:
+        raise ValueError(f"learner.target_tau={tau!r}: must be below 1 (tau >= 1 is the hard copy: leave learner.target_tau off)")
+    return tau
+
+
 class Workspace:
     """Activations of one forward pass over ``B`` observations (``n_tau`` quantile samples each for IQN/FQF)."""
 
@@ -300,7 +311,7 @@ class DeviceLearner:
 
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
-                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0):
+                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -324,6 +335,9 @@ class DeviceLearner:
         self.clip_grad_norm = clip_limit(clip_grad_norm)
         self.gnorm_partials = ops.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64) if self.clip_grad_norm > 0 else None
         self.gnorm_ring = ops.zeros(1024) if self.clip_grad_norm > 0 else None
+        # learner.target_tau in (0, 1): the Adam forms get the period 0 (never a hard copy) and one launch behind them blends the target towards the online network at
+        # the updates the period names (a0_target_blend).  Off (0.0): apply() issues what it always did.
+        self.target_tau = target_tau_value(target_tau)
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -387,6 +401,21 @@ class DeviceLearner:
     def sync_target(self, force=True):
         self.ops.target_sync(self.target.flat, self.online.flat, self.L.n_params_padded, self.state, force)
         self.target.refresh_wt()
+
+    def _hard_freq(self) -> int:
+        """The target period the Adam forms get: 0 — their "never sync" — while learner.target_tau is on."""
+        return 0 if self.target_tau > 0 else self.target_update_freq
+
+    def _blend_target(self, force=False):
+        """learner.target_tau: one launch behind the update's Adam form; it blends when the committed step count is a multiple of the period (or ``force``) and returns
+        at once otherwise.  The target's weight copies follow when the encoder runs in the fused kernels."""
+        if self.target_tau <= 0:
+            return
+        L, tg = self.L, self.target
+        if tg.fused:
+            self.ops.target_blend(tg.flat, self.online.flat, L.n_params_padded, self.target_tau, self.state, self.target_update_freq, force, tg.encoder_weights(), L.C, tg.wt)
+        else:
+            self.ops.target_blend(tg.flat, self.online.flat, L.n_params_padded, self.target_tau, self.state, self.target_update_freq, force)
 
     def _grad(self, name: str) -> torch.Tensor:
         L = self.L
@@ -465,7 +494,7 @@ class DeviceLearner:
             pend, self._pend = self._pend, None
             if (fuse_tail and self.fused_tail and pend is not None and self.grad_hook is None and self.clip_grad_norm <= 0 and not (L.noisy and pend.n > 0)):
                 self._tail_plan = ops.encoder_wgrad_tail(self.net, on.encoder_weights(), frames, slot, stride, 0, B, ws.act1, ws.act2, ws.d3, ws.d2, ws.d1, g1, g2, g3,
-                                                         self.slabs[self._enc_slab_off:], pend, self.state, self.scalars, self.lr, 0.9, 0.999, self.target_update_freq)
+                                                         self.slabs[self._enc_slab_off:], pend, self.state, self.scalars, self.lr, 0.9, 0.999, self._hard_freq())
                 if L.noisy:
                     self._noisy_sigma_grads()
             elif pend is not None:
@@ -519,16 +548,19 @@ class DeviceLearner:
         return out
 
     def apply(self):
-        """Adam on the flat buffer (NaN-skip and step counter on the device), refresh of the fused kernels' weight copies, target sync."""
+        """Adam on the flat buffer (NaN-skip and step counter on the device), refresh of the fused kernels' weight copies, target sync — with learner.target_tau on, the
+        blend of the target (``_blend_target``) behind whichever Adam form ran."""
         L, ops, on, tg = self.L, self.ops, self.online, self.target
         if L.algo == "fqf":           # unconditional, like the reference's fqf_optimizer.step() in front of the NaN guard (agent.py:139-148)
             blk = L.blocks["frac"]
             ops.rmsprop_step(on.flat[blk.all], self.grads[blk.all], self.rms_sq, blk.size, self.lr / 2e4, 0.95, 1e-5, self.max_grad_norm, self.clip)
         plan, self._tail_plan = self._tail_plan, None
+        hard_freq = self._hard_freq()
         if plan is not None:
             # backward_encoder(fuse_tail=True) left the slab sums and the step's bookkeeping to this launch
             ops.update_tail(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, 0.9, 0.999, self.adam_eps, tg.flat, L.n_params_padded, plan,
                             on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring)
+            self._blend_target()
             return
         tail = self.grads[L.n_params_padded: L.n_params_padded + 1] if self._bucketed_hook() else None
         if self.clip_grad_norm > 0:
@@ -537,19 +569,21 @@ class DeviceLearner:
             ops.grad_norm_partials(self.grads, L.n_adam, self.gnorm_partials)
             if on.fused:
                 ops.adam_step_sync_wt_clip(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                                           self.target_update_freq, tg.flat, L.n_params_padded, tail, on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring,
+                                           hard_freq, tg.flat, L.n_params_padded, tail, on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring,
                                            self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
             else:
                 ops.adam_step_sync_clip(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                                        self.target_update_freq, tg.flat, L.n_params_padded, tail, self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
+                                        hard_freq, tg.flat, L.n_params_padded, tail, self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
+            self._blend_target()
             return
         if on.fused:
             # two launches: Adam with its bookkeeping and the target copy folded in; the online conv copies, mirrored to the target's on a sync
             ops.adam_step_sync_wt(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                                  self.target_update_freq, tg.flat, L.n_params_padded, tail, on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring)
+                                  hard_freq, tg.flat, L.n_params_padded, tail, on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring)
         else:
             ops.adam_step_sync(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                               self.target_update_freq, tg.flat, L.n_params_padded, tail)
+                               hard_freq, tg.flat, L.n_params_padded, tail)
+        self._blend_target()
 
     def _encode_passes(self, frames, slot, sample_stride, passes):
         """passes: [(net, ws, chan_off, keep)] — the encoder forward passes of one update over the same batch.  They are independent of one another (the reference

@@ -103,6 +103,10 @@ class NativeLearner:
         check(self.lib.a0_learner_set_grad_clip(self.h, float(max_norm), _req(norm_ring, torch.float32, 1, "norm_ring", optional=True),
                                                 0 if norm_ring is None else int(norm_ring.numel())), "a0_learner_set_grad_clip")
 
+    def set_target_tau(self, tau):
+        """learner.target_tau through the handle (a0_learner_set_target_tau): before the first update; <= 0 is off, >= 1 is refused."""
+        check(self.lib.a0_learner_set_target_tau(self.h, float(tau)), "a0_learner_set_target_tau")
+
     def grad_norm_ring(self):
         """A copy of the ring of pre-clip gradient norms (A0_PEEK_GRAD_NORM_RING)."""
         ptr, cnt = C.c_void_p(), C.c_longlong()
@@ -527,6 +531,16 @@ class HipOps:
     def target_sync(self, target, online, n, state, force):
         check(self.lib.a0_target_sync(_req(target, torch.float32, n, "target"), _req(online, torch.float32, n, "online"), n,
                                       _req(state, torch.int32, 8, "state", optional=bool(force)), int(force), _stream()), "a0_target_sync")
+
+    def target_blend(self, target, online, n, tau, state, target_freq, force, w_target=None, C_=0, wt_target=None):
+        """learner.target_tau: ``target[:n] += tau * (online[:n] - target[:n])`` in one launch that decides for itself (a0_target_blend): when ``force``, or when
+        ``state[1] % target_freq == 0``.  With ``wt_target`` (and the target's encoder weights ``w_target``) the fused kernels' copies follow the blended target."""
+        ew = None if wt_target is None else self._enc_w(w_target)
+        check(self.lib.a0_target_blend(_req(target, torch.float32, n, "target"), _req(online, torch.float32, n, "online"), n, float(tau),
+                                       _req(state, torch.int32, 8, "state", optional=bool(force)), int(target_freq), int(force),
+                                       None if ew is None else C.addressof(ew), int(C_),
+                                       _req(wt_target, torch.float32, self.conv_wt_floats(C_) if wt_target is not None else 0, "wt_target", optional=True), _stream()),
+              "a0_target_blend")
 
     def noisy_compose(self, mu, sigma, eff, N, K, r0, r1, noise_in, noise_out_w, noise_out_b):
         check(self.lib.a0_noisy_compose(_req(mu, torch.float32, N * K + N, "mu"), _req(sigma, torch.float32, N * K + N, "sigma"), _req(eff, torch.float32, N * K + N, "eff"),

@@ -390,6 +390,17 @@ int a0_adam_step_sync_wt_clip(float* params, const float* grads, float* exp_avg,
 int a0_update_tail(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, const float* scalars2, double beta1, double beta2, double eps,
                    float* target, long long n_total, const a0_update_tail_plan* plan, const a0_encoder_weights* w, int C, float* wt, float* wt_target,
                    const float* loss, int loss_n, float* loss_ring, int ring_cap, void* stream);
+/* Soft (Polyak) target updates (learner.target_tau): target[i] <- fmaf(tau32, fl32(online[i] - target[i]), target[i]) over [0, n_total), tau32 = tau rounded to fp32 once
+ * (0 < tau < 1; tau >= 1 is the hard copy a0_target_sync gives and is refused) — one rounded subtraction and one fused multiply-add, the same bits on every path.
+ * ONE launch, which decides for itself: it blends when force != 0, or when target_update_freq > 0 and state[1] % target_update_freq == 0, and returns at once
+ * otherwise (state may be NULL with force).  Issue it behind an update's Adam form — a0_adam_step_sync, a0_adam_step_sync_wt (with or without _clip) or
+ * a0_net_encoder_wgrad_tail + a0_update_tail — called with target_update_freq = 0: those then never hard-copy, state[4] stays 0 while tau is on, and state[1]
+ * holds the new step count by the time this launch reads it; like the hard copy, the blend also follows a NaN-skipped update whose count is a multiple of the period.
+ * Buffers 16-byte aligned: 16 bytes per lane and a scalar tail of n_total % 4 floats; 4-byte aligned: element by element.  wt_target (optional, 16-byte aligned,
+ * a0_net_conv_wt_floats(C) floats) with w_target, the target's convolution weights inside target[0, n_total): after a blend wt_target holds the bytes
+ * a0_net_conv_wt_refresh would build from the blended target; when the launch does not blend it is not touched.  No scratch, no atomics. */
+int a0_target_blend(float* target, const float* online, long long n_total, double tau, const int* state, int target_update_freq, int force,
+                    const a0_encoder_weights* w_target, int C, float* wt_target, void* stream);
 /* ---------------------------------------------------------------- a whole learner behind one handle (opaque handles, library-owned HBM)
  * BaseLearner (agent.py:97-169) with DQNLearner.train_step (173-190) for scalar heads on 4 x 84 x 84 observations — BASELINE configs[1]: online + target parameters
  * in the packed layout (agent0_amd/deepq/layout.py: conv1 | conv2 | conv3 | fc1 | head, each [W (N x K) | b (N)], head rows padded to a multiple of 32), gradients,
@@ -460,6 +471,11 @@ int a0_learner_set_exchange(a0_learner* learner, long long comm);
  * norm_ring_dev[state[6] % ring_cap] (ring_cap floats the caller owns; NULL: the handle allocates ring_cap slots, 1024 when ring_cap < 1; A0_PEEK_GRAD_NORM_RING
  * returns the ring either way).  max_norm <= 0 switches clipping off again.  Call it between updates, not while one is being captured. */
 int a0_learner_set_grad_clip(a0_learner* learner, double max_norm, float* norm_ring_dev, int ring_cap);
+/* learner.target_tau through the handle: with 0 < tau < 1 every a0_learner_update passes the period 0 to its Adam form and issues a0_target_blend (the handle's
+ * target, its weight copies, desc.target_update_freq) behind it, so the target moves by tau at the updates where it used to be overwritten.  tau <= 0: off, the
+ * update issues what it always did.  tau >= 1: A0_EINVAL.  Accepted before the handle's first update only (A0_EINVAL afterwards); descriptor structs are unchanged.
+ * The forced copies of a0_learner_create* and a0_learner_set_params stay hard copies. */
+int a0_learner_set_target_tau(a0_learner* learner, double tau);
 /* parameters in the packed layout (device pointers, a0_learner_param_floats floats each); target_packed = NULL: target = copy of online (agent.py:100) */
 int a0_learner_set_params(a0_learner* learner, const float* online_packed, const float* target_packed, void* stream);
 /* copies of what the handle holds (any pointer may be NULL): parameters, target parameters, Adam moments (param_floats each), the eight status words */
