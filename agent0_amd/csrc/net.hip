@@ -637,6 +637,35 @@ __global__ __launch_bounds__(512) void a0_actor_qhead_env_kernel(a0_qenv_args P)
     a0_actor_qhead_env_body(P, raw, w2s, &s_chase_cell);
 }
 
+// a0_dense_fwd for the c51 / qr actors' fc1 over pre-split weights: the split GEMM's slabs from a0_actor_fc1_n (the split count a0_dense_fwd takes), then a0_dense_fwd's own
+// reduction launch (slab sum in order + bias + ReLU)
+extern "C" int a0_actor_fc1_dense_ok(int R, int N, int K) {
+    return (a0_actor_fc1_ok(R, N, K) && a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K) > 1) ? 1 : 0;
+}
+extern "C" int a0_actor_fc1_dense(const float* X, int ldx, const unsigned int* planes, const float* b, float* Y, int R, int N, int K, int relu, float* scratch, void* stream) {
+    A0_TRY
+    if (!b || !Y || !scratch || !a0_actor_fc1_dense_ok(R, N, K)) return a0_fail(A0_EINVAL, "a0_actor_fc1_dense: shapes a0_actor_fc1_dense_ok accepts");
+    const int splits = a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K);
+    const int rc = a0_actor_fc1_n(X, ldx, planes, R, N, K, splits, scratch, stream);
+    if (rc != A0_OK) return rc;
+    a0_hip_backend bk{(hipStream_t)stream};
+    bk.reduce_bias_act(scratch, (long long)R * N, splits, b, Y, R, N, relu);
+    return A0_OK;
+    A0_CATCH
+}
+
+// fc1 of a scalar-head actor step: the dedicated kernel over pre-split, fragment-ordered weights (actor_fc1.hip; w1_planes = a0_actor_fc1_planes of W1, or null) where it
+// applies — the same slabs bit for bit — else the general split-K GEMM
+static int a0_actor_fc1_slabs(a0_hip_backend& bk, const float* feat, int K, const float* W1, const unsigned int* w1_planes, int E, int splits, float* scratch) {
+    if (w1_planes && a0_actor_fc1_ok(E, 512, K)) return a0_actor_fc1_n(feat, K, w1_planes, E, 512, K, splits, scratch, (void*)bk.st);
+    a0_mat_src a{feat, K};
+    a0_mat_src bw{W1, K};
+    EpiSlab::Params ep{scratch, (long long)E * 512, 512};
+    bk.tag = A0_TAG_DENSE_FWD;
+    a0_fc1_partial_launch(bk, a, bw, ep, E, 512, K, splits);
+    return A0_OK;
+}
+
 extern "C" long long a0_actor_qhead_scratch(int E, int K) {
     const int splits = a0_fc1_splits(E, 512, K);
     return (long long)splits * E * 512;
@@ -669,12 +698,12 @@ extern "C" int a0_actor_qhead(const float* feat, int E, int K, const float* W1, 
                             qmax, stream);
 }
 
-extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+extern "C" int a0_actor_qhead_env_step_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                                        float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                                        unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
                                        unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
                                        float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
-                                       const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, void* stream) {
+                                       const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, const unsigned int* w1_planes, void* stream) {
     A0_TRY
     if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !action || !qmax || E < 1 || K < 4 || (K & 3) || A < 1 || A + (dueling ? 1 : 0) > 24)
         return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step: bad argument (A + dueling <= 24: the head rows are staged in 48 KB of LDS)");
@@ -684,11 +713,7 @@ extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const fl
     if ((((uintptr_t)obs_in) | ((uintptr_t)obs_out) | ((uintptr_t)obs0) | ((uintptr_t)frames)) & 15) return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step: buffers must be 16-byte aligned");
     a0_hip_backend bk{(hipStream_t)stream};
     const int splits = a0_fc1_splits(E, 512, K);
-    a0_mat_src a{feat, K};
-    a0_mat_src bw{W1, K};
-    EpiSlab::Params ep{scratch, (long long)E * 512, 512};
-    bk.tag = A0_TAG_DENSE_FWD;
-    a0_fc1_partial_launch(bk, a, bw, ep, E, 512, K, splits);
+    { const int rc = a0_actor_fc1_slabs(bk, feat, K, W1, w1_planes, E, splits, scratch); if (rc != A0_OK) return rc; }
     a0_qenv_args P;
     P.slabs = scratch; P.slab_stride = (long long)E * 512; P.nslab = splits; P.b1 = b1; P.W2 = W2; P.b2 = b2; P.A = A; P.dueling = dueling; P.E = E;
     P.rng_seed = seed; P.stream_a = stream_a; P.stream_u = stream_u; P.off_a = off_a; P.off_u = off_u; P.eps = eps; P.ctrl = ctrl; P.eps_ptr = eps_ptr;
@@ -701,16 +726,24 @@ extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const fl
     return A0_OK;
     A0_CATCH
 }
+extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                       float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                       unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                                       unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                                       float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                                       const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, void* stream) {
+    return a0_actor_qhead_env_step_wp(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task, nullptr, stream);
+}
 
 // a0_actor_qhead_env_step whose tail kernel goes on to encode the env's NEW observation (round 5, a0_actor_step_enc2_kernel in encoder_fused.hip): fc1 GEMM over
 // `feat` (this step's features), then one launch for tail + env step + the NEXT step's features into `act3_next` (which may be `feat` itself: the GEMM has read it).
-extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+extern "C" int a0_actor_qhead_env_step_enc_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                                            float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                                            unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
                                            unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
                                            float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
                                            const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
-                                           const float* wt, const a0_encoder_weights* w, float* act3_next, void* stream) {
+                                           const float* wt, const a0_encoder_weights* w, float* act3_next, const unsigned int* w1_planes, void* stream) {
     A0_TRY
     if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !action || !qmax || E < 1 || K != 3136 || A < 1 || A + (dueling ? 1 : 0) > 24)
         return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: bad argument (4 x 84 x 84 observations, A + dueling <= 24)");
@@ -720,11 +753,7 @@ extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, cons
     if ((((uintptr_t)obs_in) | ((uintptr_t)obs_out) | ((uintptr_t)obs0) | ((uintptr_t)frames)) & 15) return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: buffers must be 16-byte aligned");
     a0_hip_backend bk{(hipStream_t)stream};
     const int splits = a0_fc1_splits(E, 512, K);
-    a0_mat_src a{feat, K};
-    a0_mat_src bw{W1, K};
-    EpiSlab::Params ep{scratch, (long long)E * 512, 512};
-    bk.tag = A0_TAG_DENSE_FWD;
-    a0_fc1_partial_launch(bk, a, bw, ep, E, 512, K, splits);
+    { const int rc = a0_actor_fc1_slabs(bk, feat, K, W1, w1_planes, E, splits, scratch); if (rc != A0_OK) return rc; }
     a0_qenv_args P;
     P.slabs = scratch; P.slab_stride = (long long)E * 512; P.nslab = splits; P.b1 = b1; P.W2 = W2; P.b2 = b2; P.A = A; P.dueling = dueling; P.E = E;
     P.rng_seed = seed; P.stream_a = stream_a; P.stream_u = stream_u; P.off_a = off_a; P.off_u = off_u; P.eps = eps; P.ctrl = ctrl; P.eps_ptr = eps_ptr;
@@ -734,6 +763,15 @@ extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, cons
     P.cap = cap; P.start = start_slot % cap; P.r_act = r_act; P.r_rew = r_rew; P.r_done = r_done; P.task = task;
     return a0_actor_step_enc_launch(P, wt, w, act3_next, (hipStream_t)stream);
     A0_CATCH
+}
+extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                           float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                           unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                                           unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                                           float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                                           const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
+                                           const float* wt, const a0_encoder_weights* w, float* act3_next, void* stream) {
+    return a0_actor_qhead_env_step_enc_wp(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task, wt, w, act3_next, nullptr, stream);
 }
 
 // out[t] = mean_e x[t][e]: the per-step mean max-Q of a rollout (agent.py:38,88), all T steps in one launch

@@ -303,6 +303,11 @@ struct a0_actor {
     // online network, NoisyNet buffers included: the reference's train actor SHARES the learner's module there (trainer.py:41-44).
     float *own_flat = nullptr, *own_wt = nullptr, *own_eff = nullptr, *own_noise = nullptr;
     unsigned int* w_planes = nullptr;     // quantile actors (round 6): fc1's weights as bf16 term planes (a0_split_planes), refreshed when a rollout starts and after every NoisyNet compose
+    // scalar and distributional heads: fc1's weights as fragment-ordered bf16 term planes for the per-step kernel of actor_fc1.hip (a0_actor_fc1_planes), refreshed like w_planes;
+    // fc1_planes_on (a0_actor_set_fc1_planes): off = every step keeps the general GEMM (the same bytes; for comparisons)
+    unsigned int* fc1_planes = nullptr;
+    bool fc1_planes_on = true;
+    long long fc1_launches = 0;      // steps whose fc1 ran as a0_actor_fc1_kernel since the handle was created (a0_actor_fc1_launches)
     // an attached host-env pool (a0_actor_attach_pool): the rollout steps it instead of the device env; ring_obs keeps the last n observations for n > 1
     bool pool_on = false;
     a0_env_pool_desc pool{};
@@ -356,6 +361,9 @@ extern "C" int a0_actor_bind(a0_actor* a, const a0_learner* L, int own_network) 
             a->head_slabs = a->mem.alloc<float>((long long)a0_dense_fwd_partial_slabs(E, L->Npad, 512) * E * L->Npad);
             const long long sc = a0_dense_fwd_scratch(E, 512, L->feat);
             a->fwd_scratch = a->mem.alloc<float>(sc > 4 ? sc : 4);
+            if (a0_actor_fc1_dense_ok(E, 512, L->feat)) a->fc1_planes = a->mem.alloc<unsigned int>(a0_actor_fc1_planes_words(512, L->feat), false);
+        } else if (a0_actor_fc1_ok(E, 512, L->feat)) {
+            a->fc1_planes = a->mem.alloc<unsigned int>(a0_actor_fc1_planes_words(512, L->feat), false);
         }
         a->dist_Npad = L->Npad;
         a->bound = true;
@@ -435,6 +443,14 @@ extern "C" int a0_actor_attach_pool(a0_actor* a, const a0_env_pool_desc* d) {
     return A0_OK;
     A0_CATCH
 }
+
+extern "C" int a0_actor_set_fc1_planes(a0_actor* a, int on) {
+    if (!a) return a0_fail(A0_EINVAL, "a0_actor_set_fc1_planes: null handle");
+    a->fc1_planes_on = on != 0;
+    return A0_OK;
+}
+
+extern "C" long long a0_actor_fc1_launches(const a0_actor* a) { return a ? a->fc1_launches : -1; }
 
 extern "C" int a0_actor_set_eps_ladder(a0_actor* a, float alpha, long long i0, long long n_total) {
     A0_TRY
@@ -596,6 +612,12 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
         epsilon = A0_EPS_PER_ENV;
     }
     if (a->pool_on) return a0_actor_rollout_pool(a, L, R, epsilon, eps_vec, V, w, start, stream);
+    // scalar and distributional heads: fc1's weights do not change inside a rollout either (but for a noise reset) — laid out once here for the rollout's T fc1 launches (actor_fc1.hip).
+    // Every rollout start: also what keeps them right after an optimizer step, a0_actor_snapshot, a0_load_snapshot or a checkpoint load
+    const bool fc1p = !quant && a->fc1_planes_on && a->fc1_planes && a->feat == L->feat && (dist ? a0_actor_fc1_dense_ok(E, 512, a->feat) : a0_actor_fc1_ok(E, 512, a->feat));
+    a->fc1_launches += fc1p ? a->T : 0;
+    if (fc1p && !(L->d.noisy && a->steps % freq == 0)) A0_CHECK(a0_actor_fc1_planes(V.Wf(), a->fc1_planes, 512, a->feat, stream));
+    const unsigned int* const w1p = fc1p ? a->fc1_planes : nullptr;
     const bool step_enc = !a->own_flat;
     bool feat_ready = false;
     for (int t = 0; t < a->T; ++t) {
@@ -603,6 +625,7 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
             A0_CHECK(a0_rng_normal(a->rng.seed, 4 /* STREAM_NOISE */, a->rng.reserve(4, L->noise_len), 0.1f, V.noise, L->noise_len, stream));
             A0_CHECK(a0_actor_compose(V, stream));
             if (planes) A0_CHECK(a0_split_planes(V.Wf(), a->w_planes, 512, L->feat, stream));
+            if (fc1p) A0_CHECK(a0_actor_fc1_planes(V.Wf(), a->fc1_planes, 512, a->feat, stream));
         }
         const uint8_t* cur_obs = a->obs[a->cur];
         a0_frames_arg f{cur_obs, nullptr, (long long)a->obs_bytes, 0};
@@ -650,7 +673,8 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
         if (dist) {
             // fc1, the head GEMM's slabs, then ONE launch: slab sum + bias, dueling, expectation over the support, first-max argmax, epsilon-greedy, env step,
             // n-step bookkeeping and the replay row (Actor._dist_tail_args + act_step_commit(kind = "dist"))
-            A0_CHECK(a0_dense_fwd(a->act3, L->feat, V.Wf(), V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
+            if (fc1p) A0_CHECK(a0_actor_fc1_dense(a->act3, L->feat, a->fc1_planes, V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
+            else A0_CHECK(a0_dense_fwd(a->act3, L->feat, V.Wf(), V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
             const int ns = a0_dense_fwd_partial_slabs(E, L->Npad, 512);
             A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), E, L->Npad, 512, a->head_slabs, stream));
             const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
@@ -681,18 +705,18 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
         const int nxt = (a->cur + 1) % a->K;
         a->g += 1;
         if (step_enc && t + 1 < a->T) {
-            A0_CHECK(a0_actor_qhead_env_step_enc(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
+            A0_CHECK(a0_actor_qhead_env_step_enc_wp(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
                                                  a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E,
                                                  a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nxt], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
                                                  a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
-                                                 a->d.env_task, V.wt, &w, a->act3, stream));
+                                                 a->d.env_task, V.wt, &w, a->act3, w1p, stream));
             feat_ready = true;
         } else
-        A0_CHECK(a0_actor_qhead_env_step(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
+        A0_CHECK(a0_actor_qhead_env_step_wp(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
                                          a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E,
                                          a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nxt], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
                                          a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
-                                         a->d.env_task, stream));
+                                         a->d.env_task, w1p, stream));
         a->cur = nxt;
         a->steps += 1;
     }

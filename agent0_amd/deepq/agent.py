@@ -95,6 +95,10 @@ class Actor:
         # beside eps_dev and is allocated by the first rollout that fills it (``_eps_ladder``) — off, or on an actor that only tests, nothing is
         self.rank = int(rank)
         self.ladder_alpha = max(float(cfg.actor.eps_ladder), 0.0)
+        # training rollouts of scalar and c51 / qr heads run fc1 as a0_actor_fc1_kernel over weights laid out once per rollout (``_rollout``; the library's actor handle
+        # likewise, native_loop.py); False keeps the general GEMM in every step — the same bytes, for comparisons.  fc1_launches: steps that took the kernel
+        self.fc1_planes = True
+        self.fc1_launches = 0
         self.eps_vec = None
         self.out_act, self.out_rew, self.out_done = ops.zeros(E, dtype=torch.int32), ops.zeros(E), ops.zeros(E)
         self.atoms = self.model.head.atoms.reshape(-1).contiguous() if self.L.algo == "c51" else None
@@ -140,10 +144,13 @@ class Actor:
         return (self.ws.act3, E, L.feat, W1, b1, W2, b2, L.A, L.dueling, self._qh_scratch, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
                 rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), float(epsilon), self.action, self.qmax_all[t * E:(t + 1) * E], ctrl, eps_ptr)
 
-    def _dist_tail_args(self, epsilon, ctrl, eps_ptr, t):
+    def _dist_tail_args(self, epsilon, ctrl, eps_ptr, t, fc1p=None):
         """fc1 and the head GEMM's slabs (enqueued here), then the arguments of ``ops.actor_dist_tail``."""
         L, ops, E, dev, rng = self.L, self.ops, self.E, self.model._dev, self.rng
-        dev._dense(self.ws.act3, L.feat, "fc1", self.ws.h, E, True)
+        if getattr(self, "_fc1p_on", False) if fc1p is None else fc1p:      # ``_rollout``: fc1 over the planes it laid out (a0_actor_fc1_dense: the same bits)
+            ops.actor_fc1_dense(self.ws.act3, L.feat, dev.actor_fc1_planes, dev.wb("fc1")[1], self.ws.h, E, 512, L.feat, True, dev.scratch(ops.dense_fwd_scratch(E, 512, L.feat)))
+        else:
+            dev._dense(self.ws.act3, L.feat, "fc1", self.ws.h, E, True)
         Wh, bh = dev.wb("head")
         ns = ops.dense_fwd_partial(self.ws.h, 512, Wh, E, L.Npad, 512, self._head_slabs)
         return (self._head_slabs, ns, bh, L.Npad, L.A, L.T, L.dueling, 2 if L.algo == "c51" else 1, self.atoms, E, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
@@ -179,7 +186,7 @@ class Actor:
             ops.actor_qhead(*self._qhead_args(epsilon, ctrl, eps_ptr, t))
             return
         if self.dist_tail:
-            ops.actor_dist_tail(*self._dist_tail_args(epsilon, ctrl, eps_ptr, t))
+            ops.actor_dist_tail(*self._dist_tail_args(epsilon, ctrl, eps_ptr, t, fc1p=False))
             return
         if self.quant_slabs:
             # host envs and test rollouts: the merged step's head and tail without its env step — one tail launch where the generic chain below takes four
@@ -247,12 +254,20 @@ class Actor:
                                and ops.dense_fwd_wplanes_ok(E * self.n_tau, 512, self.L.feat))
         if self._planes_on and not (cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0):
             dev.refresh_fc1_planes()
+        # scalar and c51 / qr actors: the merged step's fc1 as a0_actor_fc1_kernel over weights laid out once here and after every noise reset (the same slabs bit for
+        # bit); ``self.fc1_planes = False`` keeps the general GEMM (comparisons)
+        self._fc1p_on = bool(self.fc1_planes and self.tail_env and bound and not test and hasattr(ops, "actor_fc1_planes")
+                             and (ops.actor_fc1_ok(E, 512, self.L.feat) if self.fused_tail else self.dist_tail and ops.actor_fc1_dense_ok(E, 512, self.L.feat)))
+        if self._fc1p_on and not (cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0):
+            dev.refresh_actor_fc1_planes()
         feat_ready = False
         for t in range(T):
             if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0:
                 self.model.reset_noise(rng=self.rng)
                 if self._planes_on:
                     dev.refresh_fc1_planes()
+                if self._fc1p_on:
+                    dev.refresh_actor_fc1_planes()
             merged = bound and not test and (self.tail_env or (self.quant_tail and self.fused_commit))
             if not feat_ready:
                 self._act_device(epsilon, self.qs[t:t + 1], ctrl, eps_ptr, t, tail=not merged)
@@ -275,7 +290,8 @@ class Actor:
                 enc = (dev.wt, dev.encoder_weights(), self.ws.act3) if (step_enc and t + 1 < T) else None
                 self.obs = self.envs.act_step_commit(targs, self.stat_mask[t * E:(t + 1) * E], self.stat_ret[t * E:(t + 1) * E], self.n, self.steps,
                                                      float(cfg.learner.discount), self.ring_act, self.ring_rew, self.ring_done, obs0, rp, (start + t * E) % rp.size,
-                                                     kind=kind, enc=enc)
+                                                     kind=kind, enc=enc, w1_planes=dev.actor_fc1_planes if (self._fc1p_on and kind == "qhead") else None)
+                self.fc1_launches += 1 if self._fc1p_on else 0
                 feat_ready = enc is not None
                 self.steps += 1
                 continue

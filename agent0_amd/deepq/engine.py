@@ -256,6 +256,14 @@ class DeviceNet:
             self.fc1_planes = torch.empty(self.ops.weight_planes_words(512, self.L.feat), dtype=torch.int32, device=self.flat.device)
         self.ops.split_planes(W, self.fc1_planes, 512, self.L.feat)
 
+    def refresh_actor_fc1_planes(self):
+        """fc1's EFFECTIVE weights as fragment-ordered bf16 term planes (a0_actor_fc1_planes) for the scalar and c51 / qr actors' per-step fc1 (a0_actor_fc1_kernel):
+        refreshed like ``refresh_fc1_planes``, when a rollout starts and after every NoisyNet compose."""
+        W, _ = self.wb("fc1")
+        if getattr(self, "actor_fc1_planes", None) is None:
+            self.actor_fc1_planes = torch.empty(self.ops.actor_fc1_planes_words(512, self.L.feat), dtype=torch.int32, device=self.flat.device)
+        self.ops.actor_fc1_planes(W, self.actor_fc1_planes, 512, self.L.feat)
+
     def head_slabs(self, ws: Workspace, B, taus: torch.Tensor, n_tau: int, slabs: torch.Tensor, cos_ready: bool = False, w_planes: bool = False,
                    splits: Optional[dict] = None) -> int:
         """Quantile heads of a pass that is not differentiated, up to the head GEMM's split-K slabs [ns][B * n_tau][Npad] (the consumer kernel finishes

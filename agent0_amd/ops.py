@@ -365,6 +365,34 @@ class HipOps:
         check(self.lib.a0_dense_fwd_wplanes(_req(X, torch.float32, (R - 1) * ldx + K, "X"), ldx, _req(planes, torch.int32, self.weight_planes_words(N, K), "planes"),
                                             _req(b, torch.float32, N, "b"), _req(Y, torch.float32, R * N, "Y"), R, N, K, int(relu), _stream()), "a0_dense_fwd_wplanes")
 
+    def actor_fc1_planes_words(self, N, K) -> int:
+        return int(self.lib.a0_actor_fc1_planes_words(N, K))
+
+    def actor_fc1_planes(self, W, planes, N, K):
+        """The three bf16 term planes of W [N][K] in MFMA-fragment order for ``actor_fc1`` (a0_actor_fc1_planes); once per change of W."""
+        check(self.lib.a0_actor_fc1_planes(_req(W, torch.float32, N * K, "W"), _req(planes, torch.int32, self.actor_fc1_planes_words(N, K), "planes"), N, K, _stream()),
+              "a0_actor_fc1_planes")
+
+    def actor_fc1_ok(self, R, N, K) -> bool:
+        return bool(self.lib.a0_actor_fc1_ok(R, N, K))
+
+    def actor_fc1(self, X, ldx, planes, R, N, K, slabs, splits=None) -> int:
+        """``dense_fwd_partial`` (``dense_fwd_partial_n`` with ``splits``) for the shapes ``actor_fc1_ok`` accepts, reading the weights as ``actor_fc1_planes``: the same
+        slabs bit for bit (a0_actor_fc1 / a0_actor_fc1_n); returns the slab count."""
+        ns = self.dense_fwd_partial_slabs(R, N, K) if splits is None else int(splits)
+        check(self.lib.a0_actor_fc1_n(_req(X, torch.float32, (R - 1) * ldx + K, "X"), ldx, _req(planes, torch.int32, self.actor_fc1_planes_words(N, K), "planes"), R, N, K, ns,
+                                      _req(slabs, torch.float32, ns * R * N, "slabs"), _stream()), "a0_actor_fc1")
+        return ns
+
+    def actor_fc1_dense_ok(self, R, N, K) -> bool:
+        return bool(self.lib.a0_actor_fc1_dense_ok(R, N, K))
+
+    def actor_fc1_dense(self, X, ldx, planes, b, Y, R, N, K, relu, scratch):
+        """``dense_fwd`` for the shapes ``actor_fc1_dense_ok`` accepts, reading the weights as ``actor_fc1_planes``: the same Y bit for bit (a0_actor_fc1_dense)."""
+        check(self.lib.a0_actor_fc1_dense(_req(X, torch.float32, (R - 1) * ldx + K, "X"), ldx, _req(planes, torch.int32, self.actor_fc1_planes_words(N, K), "planes"),
+                                          _req(b, torch.float32, N, "b"), _req(Y, torch.float32, R * N, "Y"), R, N, K, int(relu),
+                                          _req(scratch, torch.float32, self.dense_fwd_scratch(R, N, K), "scratch"), _stream()), "a0_actor_fc1_dense")
+
     def dense_fwd_mul(self, X, ldx, W, b, M, group, Y, R, N, K, relu):
         check(self.lib.a0_dense_fwd_mul(_req(X, torch.float32, (R - 1) * ldx + K, "X"), ldx, _req(W, torch.float32, N * K, "W"), _req(b, torch.float32, N, "b"),
                                         _req(M, torch.float32, ((R - 1) // group + 1) * N, "M"), group, _req(Y, torch.float32, R * N, "Y"), R, N, K, int(relu), _stream()),
@@ -810,29 +838,11 @@ class HipOps:
 
     def actor_qhead_env_step(self, feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
                              env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
-                             start_slot, r_act, r_rew, r_done, task=0):
+                             start_slot, r_act, r_rew, r_done, task=0, w1_planes=None):
+        """``w1_planes``: ``actor_fc1_planes`` of W1 — fc1 then runs as a0_actor_fc1_kernel where ``actor_fc1_ok`` accepts the step (the same bytes)."""
         nq = A + (1 if dueling else 0)
         nb = E * 4 * 84 * 84
-        check(self.lib.a0_actor_qhead_env_step(
-            _req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
-            _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
-            _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
-            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
-            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
-            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
-            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
-            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
-            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task), _stream()), "a0_actor_qhead_env_step")
-
-    def actor_qhead_env_step_enc(self, feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
-                                 env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
-                                 start_slot, r_act, r_rew, r_done, task=0, wt=None, enc_w=None, act3_next=None):
-        """``actor_qhead_env_step`` whose tail kernel goes on to encode the env's new observation into ``act3_next`` (a0_actor_qhead_env_step_enc): a step in two launches."""
-        nq = A + (1 if dueling else 0)
-        nb = E * 4 * 84 * 84
-        ew = self._enc_w(enc_w)
-        check(self.lib.a0_actor_qhead_env_step_enc(
+        check(self.lib.a0_actor_qhead_env_step_wp(
             _req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
             _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
             _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
@@ -843,7 +853,28 @@ class HipOps:
             _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
             _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
             _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task),
-            _req(wt, torch.float32, self.conv_wt_floats(4), "wt"), C.addressof(ew), _req(act3_next, torch.float32, E * K, "act3_next"), _stream()), "a0_actor_qhead_env_step_enc")
+            _req(w1_planes, torch.int32, self.actor_fc1_planes_words(512, K), "w1_planes", optional=True), _stream()), "a0_actor_qhead_env_step")
+
+    def actor_qhead_env_step_enc(self, feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
+                                 env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
+                                 start_slot, r_act, r_rew, r_done, task=0, wt=None, enc_w=None, act3_next=None, w1_planes=None):
+        """``actor_qhead_env_step`` whose tail kernel goes on to encode the env's new observation into ``act3_next`` (a0_actor_qhead_env_step_enc): a step in two launches."""
+        nq = A + (1 if dueling else 0)
+        nb = E * 4 * 84 * 84
+        ew = self._enc_w(enc_w)
+        check(self.lib.a0_actor_qhead_env_step_enc_wp(
+            _req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
+            _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
+            _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
+            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
+            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
+            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
+            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
+            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
+            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
+            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task),
+            _req(wt, torch.float32, self.conv_wt_floats(4), "wt"), C.addressof(ew), _req(act3_next, torch.float32, E * K, "act3_next"),
+            _req(w1_planes, torch.int32, self.actor_fc1_planes_words(512, K), "w1_planes", optional=True), _stream()), "a0_actor_qhead_env_step_enc")
 
     def mean_rows(self, x, T, E, out):
         check(self.lib.a0_mean_rows(_req(x, torch.float32, T * E, "x"), T, E, _req(out, torch.float32, T, "out"), _stream()), "a0_mean_rows")

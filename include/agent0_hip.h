@@ -206,6 +206,19 @@ int a0_split_planes(const float* W, unsigned int* planes, int N, int K, void* st
 int a0_dense_fwd_wplanes_ok(int R, int N, int K);
 int a0_dense_fwd_wplanes(const float* X, int ldx, const unsigned int* Wplanes, const float* b, float* Y, int R, int N, int K, int relu, void* stream);
 
+/* The actor's per-step fc1 GEMM as a kernel of its own (actor_fc1.hip): a0_actor_fc1_n writes exactly the split-K slabs a0_dense_fwd_partial_n(X, ldx, W, R, N, K, splits,
+ * slabs) writes — same k ranges, same products in the same order: the same bits — for the shapes a0_actor_fc1_ok accepts (N = 512, K % 32 == 0, 1 <= R <= 256, the
+ * six-product split-operand GEMM), reading W as bf16 term planes in MFMA-fragment order: a0_actor_fc1_planes writes them (a0_actor_fc1_planes_words(N, K) 32-bit words;
+ * N % 32 == 0, K % 16 == 0) once per change of W.  splits = a0_dense_fwd_partial_slabs(R, N, K): the scalar-head actors' slabs (a0_actor_qhead*).
+ * a0_actor_fc1_dense: a0_dense_fwd(X, ldx, W, b, Y, R, N, K, relu, scratch) — the c51 / qr actors' fc1 — for the shapes a0_actor_fc1_dense_ok accepts (those of
+ * a0_actor_fc1_ok that a0_dense_fwd runs split): the same slabs into `scratch`, the same reduction launch behind them, the same Y bit for bit. */
+long long a0_actor_fc1_planes_words(int N, int K);
+int a0_actor_fc1_planes(const float* W, unsigned int* planes, int N, int K, void* stream);
+int a0_actor_fc1_ok(int R, int N, int K);
+int a0_actor_fc1_dense_ok(int R, int N, int K);
+int a0_actor_fc1_dense(const float* X, int ldx, const unsigned int* planes, const float* b, float* Y, int R, int N, int K, int relu, float* scratch, void* stream);
+int a0_actor_fc1_n(const float* X, int ldx, const unsigned int* planes, int R, int N, int K, int splits, float* slabs, void* stream);
+
 /* Matrix pipe used by every fp32-operand GEMM above (dense layers, conv2/conv3 weight gradients, unfused conv layers):
  * 1 (default) = bf16 MFMA with both operands split exactly into three bf16 terms, nine products, fp32 accumulation (igemm_x9.h);
  * 0 = fp32 MFMA fmaf chain (igemm.h).  Same results up to the association order of the fp32 additions.  Returns the previous mode;
@@ -565,6 +578,11 @@ int a0_actor_rollout(a0_actor* actor, a0_learner* learner, a0_rbuf* replay, floa
  * attached pool and the launch schedule's actor stream alike.  alpha <= 0 switches it off again: the rollout's launches and their arguments are those of a handle
  * that never heard of it.  Derived from `epsilon` every rollout, so no part of a0_actor_state_save. */
 int a0_actor_set_eps_ladder(a0_actor* actor, float alpha, long long i0, long long n_total);
+/* Scalar heads and c51 / qr: a0_actor_rollout over the device env lays fc1's weights out once per rollout (and after every noise reset) with a0_actor_fc1_planes and runs the steps'
+ * fc1 through a0_actor_fc1 where a0_actor_fc1_ok accepts the shape.  on = 0: the handle keeps the general GEMM in every step — the same bytes (for comparisons). */
+int a0_actor_set_fc1_planes(a0_actor* actor, int on);
+/* steps whose fc1 a0_actor_rollout has run as a0_actor_fc1_kernel since the handle was created */
+long long a0_actor_fc1_launches(const a0_actor* actor);
 int a0_actor_collect(a0_actor* actor, float* qs_host, float* returns_host, int max_returns, int* n_returns, void* stream);
 /* Host environments stepped by worker processes (agent0_amd/common/env_pool.py HostEnvPool): while a pool is attached, a0_actor_rollout steps IT instead of the
  * device env.  Per step t: encoder, fc1 + head + the head's tail (a0_actor_qhead / a0_actor_dist_tail / a0_actor_quantile_tail, the full batch's split counts),
@@ -743,6 +761,13 @@ int a0_actor_qhead_env_step(const float* feat, int E, int K, const float* W1, co
                             unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
                             float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
                             const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, void* stream);
+/* ... with fc1 taken from pre-split weights where a0_actor_fc1_ok accepts the step (w1_planes = a0_actor_fc1_planes of W1, or NULL: the call above): the same bytes */
+int a0_actor_qhead_env_step_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                            float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                            unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                            unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                            float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                            const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, const unsigned int* w1_planes, void* stream);
 /* out[t] = mean over e of x[t][e] (per-step mean max-Q of a rollout, agent.py:38,88) */
 int a0_mean_rows(const float* x, int T, int E, float* out, void* stream);
 
@@ -758,6 +783,14 @@ int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, const float* W1
                                 float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
                                 const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
                                 const float* wt, const a0_encoder_weights* w, float* act3_next, void* stream);
+/* ... with fc1 taken from pre-split weights where a0_actor_fc1_ok accepts the step (w1_planes = a0_actor_fc1_planes of W1, or NULL: the call above): the same bytes */
+int a0_actor_qhead_env_step_enc_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                                unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                                float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                                const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
+                                const float* wt, const a0_encoder_weights* w, float* act3_next, const unsigned int* w1_planes, void* stream);
 /* (round 5) a0_actor_dist_tail_env_step (c51 / qr) whose kernel goes on to encode the env's new observation into act3_next [E][3136], as a0_actor_qhead_env_step_enc
  * does for scalar heads: the same bytes and features as a0_actor_dist_tail_env_step + a0_net_encoder_fwd_fused, one launch and one kernel boundary less per step. */
 int a0_actor_dist_tail_env_step_enc(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
