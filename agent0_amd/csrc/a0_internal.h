@@ -33,6 +33,12 @@ struct a0_hip_error : std::runtime_error {
     catch (const std::exception& e) { return a0_fail(A0_EINVAL, e.what()); } \
     catch (...) { return a0_fail(A0_EINVAL, "unknown C++ exception"); }
 
+// Philox stream ids (agent0_amd/common/utils.py DeviceRng: 1 / 2 epsilon-greedy, 3 quantile fractions, 4 NoisyNet, 5 sum-tree, 6 permutation seeds); 7 = the
+// random shifts of learner.aug_shift (augment.hip), positioned by the update count alone: no running offset, nothing to snapshot
+#define A0_STREAM_AUG 7
+// augment.hip: the range checks of a0_augment_shift (A0_EINVAL with a message that starts with `who`)
+int a0_augment_shift_check(const char* who, int C, int H, int W, int pad, long long row_bytes);
+
 // roctx ranges (core.hip): no-ops unless A0_ROCTX=1
 void a0_trace_push_internal(const char* name);
 void a0_trace_pop_internal();

@@ -56,6 +56,7 @@ extern "C" int a0_learner_create_on(const a0_learner_desc* d, const a0_learner_b
     a0_learner* L = new a0_learner();
     try {
         L->d = *d;
+        L->rng.init(d->seed, 0);      // every learner: learner.aug_shift draws from the seed too (the NoisyNet and quantile branches below set the same value)
         a0_net_desc nd{4, 84, 84};
         if (a0_net_create(&nd, &L->net) != A0_OK) { delete L; return A0_EINVAL; }
         const bool c51 = d->algo == A0_ALGO_C51;
@@ -314,6 +315,18 @@ extern "C" int a0_learner_set_target_tau(a0_learner* L, double tau) {
     return A0_OK;
 }
 
+extern "C" int a0_learner_set_aug_shift(a0_learner* L, int pad) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_aug_shift: null handle");
+    if (pad == 0) { L->aug_pad = 0; return A0_OK; }
+    const long long row = 2LL * L->C * L->H * L->W;
+    A0_CHECK(a0_augment_shift_check("a0_learner_set_aug_shift", L->C, L->H, L->W, pad, row));
+    if (!L->aug_stage) L->aug_stage = L->alloc<uint8_t>((long long)L->d.B * row);
+    L->aug_pad = pad;
+    return A0_OK;
+    A0_CATCH
+}
+
 extern "C" int a0_learner_set_params(a0_learner* L, const float* online_packed, const float* target_packed, void* stream) {
     A0_TRY
     if (!L || !online_packed) return a0_fail(A0_EINVAL, "a0_learner_set_params: null argument");
@@ -394,6 +407,12 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
     float* on = L->online; float* tg = L->target;
     a0_encoder_weights w_on = L->enc(on), w_tg = L->enc(tg);
     L->updated = true;
+    if (L->aug_pad > 0) {
+        // learner.aug_shift (DeviceLearner.forward_dense): the batch is shifted into the stage buffer first, by the draws of update state[6], and every pass below reads
+        // that dense batch; the ring is only read
+        A0_CHECK(a0_augment_shift(frames, slot, row_bytes, L->C, L->H, L->W, L->aug_pad, B, L->rng.seed, L->state, 0, L->aug_stage, stream));
+        frames = L->aug_stage; slot = nullptr; row_bytes = 2LL * obs;
+    }
     // learner.target_tau (DeviceLearner.apply): the Adam forms get the period 0 — never a hard copy — and a0_target_blend follows whichever tail form the update took
     const bool soft = L->target_tau > 0.0;
     const int hard_freq = soft ? 0 : L->d.target_update_freq;

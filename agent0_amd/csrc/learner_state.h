@@ -73,6 +73,9 @@ struct a0_learner {
     // ---- soft target updates (a0_learner_set_target_tau): off while target_tau <= 0; `updated`: an update has been issued, the setting is fixed from then on
     double target_tau = 0.0;
     bool updated = false;
+    // ---- DrQ random shift of the batch (a0_learner_set_aug_shift): off while aug_pad == 0; aug_stage: the dense augmented batch [B][2 * C * H * W], allocated by the first call that switches it on
+    int aug_pad = 0;
+    uint8_t* aug_stage = nullptr;
     // library-owned HBM
     float *online = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *scalars = nullptr, *loss_ring = nullptr;
     float *wt_on = nullptr, *wt_tg = nullptr;

@@ -35,6 +35,14 @@ Additions (all default to the reference's behaviour being available):
                    copy would have happened: every ``learner.target_update_freq`` updates, which keeps its meaning and default (the classical recipe is
                    ``learner.target_update_freq=1 learner.target_tau=0.005``).  The copy at construction and on checkpoint load stays a hard copy.  No state of
                    its own: the target is already in every snapshot, and the setting may change across a resume like ``actor.min_eps``.
+  learner.aug_shift  int, default 0 (off; negative values, values >= min(H, W) of ``obs_shape`` and values above 16 are refused).  p > 0: DrQ's random shift of the
+                   replay batch — every sampled observation is padded by p pixels with edge replication and cropped back at a random offset, one (dy, dx) in
+                   [-p, p]^2 for all planes of an observation, st and st_next of a sample drawn independently; every pass of the update (target, double-Q,
+                   online, conv1's weight gradient) reads the same shifted batch and the ring is never written.  DrQ's value for 84 x 84 frames is 4.  It applies to
+                   the learner's batch only: training rollouts, test rollouts and ``mode=play`` see the frames unshifted, as in DrQ.  The synthetic env's ``block``
+                   and ``chase`` tasks encode their information in position, so no learning claim is made for them.  The draws come from Philox stream 7 of the
+                   learner's seed at the position the device's update count names: no state of its own, nothing new in a snapshot, and the setting may change
+                   across a resume like ``actor.min_eps``.  Not with ``A0_PIPELINE_TARGET=1`` (the separately staged target pass reads the ring).
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -127,6 +135,7 @@ class LearnerConfig:
     clip_grad_norm: float = -1.0
     target_update_freq: int = 500
     target_tau: float = 0.0
+    aug_shift: int = 0
     learner_steps: int = 20
     double_q: bool = False
     dueling_head: bool = False

@@ -38,6 +38,27 @@ def target_tau_value(value) -> float:
     return tau
 
 
+def aug_shift_value(value, obs_shape, pipeline_target: Optional[bool] = None) -> int:
+    """``learner.aug_shift`` as the learner uses it: the pad p of DrQ's random shift, 0 (off) for zero or None.  Refused: a negative or fractional value, p >= min(H, W)
+    of ``obs_shape`` (C, H, W), p > 16 — the kernel's own limits (a0_augment_shift) — and any p > 0 together with ``A0_PIPELINE_TARGET=1`` (``pipeline_target``; None
+    reads the environment): the separately staged target pass reads the ring before the update that shifts the batch exists."""
+    if value is None or value == 0:
+        return 0
+    if int(value) != value or value < 0:
+        raise ValueError(f"learner.aug_shift={value!r}: must be a whole number of pixels >= 0 (0 is off)")
+    p = int(value)
+    H, W = int(obs_shape[-2]), int(obs_shape[-1])
+    if p >= min(H, W):
+        raise ValueError(f"learner.aug_shift={p}: must be below min(H, W) = {min(H, W)} of obs_shape {tuple(obs_shape)}")
+    if p > 16:
+        raise ValueError(f"learner.aug_shift={p}: must be at most 16 (DrQ's value for 84 x 84 frames is 4)")
+    if pipeline_target is None:
+        pipeline_target = os.environ.get("A0_PIPELINE_TARGET", "0") == "1"
+    if pipeline_target:
+        raise ValueError(f"learner.aug_shift={p}: not together with A0_PIPELINE_TARGET=1 (the separately staged target pass reads the unshifted ring)")
+    return p
+
+
 class Workspace:
     """Activations of one forward pass over ``B`` observations (``n_tau`` quantile samples each for IQN/FQF)."""
 
@@ -319,7 +340,7 @@ class DeviceLearner:
 
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
-                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0):
+                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -346,6 +367,17 @@ class DeviceLearner:
         # learner.target_tau in (0, 1): the Adam forms get the period 0 (never a hard copy) and one launch behind them blends the target towards the online network at
         # the updates the period names (a0_target_blend).  Off (0.0): apply() issues what it always did.
         self.target_tau = target_tau_value(target_tau)
+        # learner.aug_shift = p > 0: forward_dense first shifts the batch into aug_stage (a0_augment_shift: Philox stream 7 of aug_rng.seed — the learner's DeviceRng — at
+        # the update count state[6]) and every pass reads that dense batch.  Off (0): no buffer, no launch, and the passes get the arguments they always got.
+        self.aug_shift = aug_shift_value(aug_shift, (L.C, L.H, L.W))
+        self.aug_rng, self.aug_stage = aug_rng, None
+        if self.aug_shift > 0:
+            if not self.online.fused:
+                # adam_step_sync / adam_step_sync_clip, the forms behind the unfused encoder, file no loss mean and so never advance state[6]: every update would repeat update 0's shifts
+                raise ValueError(f"learner.aug_shift={self.aug_shift}: needs observations the fused encoder kernels cover — only their Adam forms advance the update count the shifts are drawn by")
+            if aug_rng is None or not hasattr(ops, "augment_shift"):
+                raise ValueError(f"learner.aug_shift={self.aug_shift}: needs the learner's DeviceRng (aug_rng) and a backend with augment_shift")
+            self.aug_stage = ops.empty(batch_size * 2 * L.C * L.H * L.W, dtype=torch.uint8)
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -715,6 +747,11 @@ class DeviceLearner:
         nxt = self.obs_bytes
         if tstage is not None and not self.target_stage_supported:
             raise ValueError("tstage: this learner's target pass cannot run as a separate stage")
+        if self.aug_shift > 0:
+            if tstage is not None:
+                raise ValueError("tstage: not together with learner.aug_shift (the separately staged target pass has read the unshifted ring)")
+            ops.augment_shift(frames, slot, sample_stride, L.C, L.H, L.W, self.aug_shift, B, self.aug_rng.seed, self.state, 0, self.aug_stage)
+            frames, slot, sample_stride = self.aug_stage, None, 2 * self.obs_bytes
         if L.noisy:
             mods = on.compose_mods() + tg.compose_mods()
             if len(mods) <= 6:

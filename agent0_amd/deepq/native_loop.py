@@ -204,6 +204,8 @@ class NativeLoop:
         ok(lib.a0_actor_create(C.addressof(ad), C.addressof(self.actor)), "a0_actor_create")
         if eng.target_tau > 0:          # learner.target_tau: the handle blends the target behind its Adam form, as DeviceLearner.apply does
             ok(lib.a0_learner_set_target_tau(self.learner, C.c_double(eng.target_tau)), "a0_learner_set_target_tau")
+        if eng.aug_shift > 0:           # learner.aug_shift: the handle shifts the batch into a stage buffer of its own ahead of its passes, as DeviceLearner.forward_dense does
+            ok(lib.a0_learner_set_aug_shift(self.learner, int(eng.aug_shift)), "a0_learner_set_aug_shift")
         if not actor.fc1_planes:        # Actor.fc1_planes = False (comparisons): every step's fc1 on the general GEMM instead of a0_actor_fc1_kernel, as in Actor._rollout
             ok(lib.a0_actor_set_fc1_planes(self.actor, 0), "a0_actor_set_fc1_planes")
         if actor.ladder_alpha > 0:      # actor.eps_ladder: the handle fills its own per-env epsilons at the start of every rollout, as Actor._eps_ladder does

@@ -107,6 +107,10 @@ class NativeLearner:
         """learner.target_tau through the handle (a0_learner_set_target_tau): before the first update; <= 0 is off, >= 1 is refused."""
         check(self.lib.a0_learner_set_target_tau(self.h, float(tau)), "a0_learner_set_target_tau")
 
+    def set_aug_shift(self, pad):
+        """learner.aug_shift through the handle (a0_learner_set_aug_shift): between updates; 0 is off, the kernel's range checks apply to anything else."""
+        check(self.lib.a0_learner_set_aug_shift(self.h, int(pad)), "a0_learner_set_aug_shift")
+
     def grad_norm_ring(self):
         """A copy of the ring of pre-clip gradient norms (A0_PEEK_GRAD_NORM_RING)."""
         ptr, cnt = C.c_void_p(), C.c_longlong()
@@ -1020,6 +1024,13 @@ class HipOps:
 
     def rng_randint(self, seed, stream_id, offset, hi, out, n):
         check(self.lib.a0_rng_randint(seed, stream_id, offset, hi, _req(out, torch.int32, n, "out"), n, _stream()), "a0_rng_randint")
+
+    def augment_shift(self, frames, slot, row_bytes, C_, H, W, pad, B, seed, state, u, out):
+        """learner.aug_shift: the batch ``frames[slot]`` (``slot`` None: rows 0 .. B - 1) shifted into the dense batch ``out`` [B][row_bytes] in one launch
+        (a0_augment_shift); the draws are those of update ``state[6]`` (the learner's status words, read on the device) or, ``state`` None, of update ``u``."""
+        check(self.lib.a0_augment_shift(_req(frames, torch.uint8, B * row_bytes if slot is None else row_bytes, "frames"), _req(slot, torch.int32, B, "slot", optional=True),
+                                        int(row_bytes), int(C_), int(H), int(W), int(pad), int(B), int(seed) & 0xFFFFFFFFFFFFFFFF, _req(state, torch.int32, 8, "state", optional=True),
+                                        int(u), _req(out, torch.uint8, B * row_bytes, "out"), _stream()), "a0_augment_shift")
 
     def rng_normal(self, seed, stream_id, offset, std, out, n):
         check(self.lib.a0_rng_normal(seed, stream_id, offset, std, _req(out, torch.float32, n, "out"), n, _stream()), "a0_rng_normal")

@@ -489,6 +489,13 @@ int a0_learner_set_grad_clip(a0_learner* learner, double max_norm, float* norm_r
  * update issues what it always did.  tau >= 1: A0_EINVAL.  Accepted before the handle's first update only (A0_EINVAL afterwards); descriptor structs are unchanged.
  * The forced copies of a0_learner_create* and a0_learner_set_params stay hard copies. */
 int a0_learner_set_target_tau(a0_learner* learner, double tau);
+/* learner.aug_shift through the handle: with pad > 0 every a0_learner_update first issues a0_augment_shift (the caller's frames / slot / row_bytes, the handle's seed
+ * and state words, so u = state[6]) into a stage buffer of B * 2 * C * H * W bytes that the handle allocates on the first such call, and then runs every pass — the
+ * target and double-Q passes on st_next, the online pass and mdqn's target pass on st, conv1's weight gradient — on that buffer with a NULL slot; the caller's ring is
+ * only read.  pad == 0: off again, the update issues what it always did.  The range checks are a0_augment_shift's, made here against the handle's geometry
+ * (A0_EINVAL); with the setting on, a0_learner_update refuses a row_bytes other than 2 * C * H * W.  Call it between updates, not while one is being captured;
+ * descriptor structs are unchanged, and nothing is added to a snapshot: the update count travels in the state words. */
+int a0_learner_set_aug_shift(a0_learner* learner, int pad);
 /* parameters in the packed layout (device pointers, a0_learner_param_floats floats each); target_packed = NULL: target = copy of online (agent.py:100) */
 int a0_learner_set_params(a0_learner* learner, const float* online_packed, const float* target_packed, void* stream);
 /* copies of what the handle holds (any pointer may be NULL): parameters, target parameters, Adam moments (param_floats each), the eight status words */
@@ -862,6 +869,16 @@ int a0_rng_uniform_ctrl(unsigned long long seed, unsigned int stream_id, unsigne
                         int ctrl_idx, void* stream);
 int a0_rng_normal_ctrl(unsigned long long seed, unsigned int stream_id, unsigned long long offset, float stdv, float* out, long long n,
                        const long long* ctrl, int ctrl_idx, void* stream);
+/* learner.aug_shift: DrQ's random shift of a sampled batch, in one launch.  frames / slot / row_bytes as in a0_learner_update (slot == NULL: rows 0 .. B - 1), a row
+ * being st || st_next of C * H * W bytes each and nothing else (row_bytes == 2 * C * H * W); out: a dense [B][row_bytes] batch.  Every observation is shifted on its
+ * own, all C planes alike: out[c][y][x] = in[c][clamp(y + dy, 0, H - 1)][clamp(x + dx, 0, W - 1)] — a replicate pad by `pad` and a crop at (dy + pad, dx + pad).
+ * The draw: sample b of update u owns words 4 (u B + b) .. + 3 of Philox stream 7 of `seed` (a0_rng_u32's numbering, 64-bit positions): dy(st), dx(st), dy(st_next),
+ * dx(st_next), each word % (2 pad + 1) - pad.  u = state[6] read on the device when state != NULL (the learner's status words: the update count its Adam launch
+ * advances, so a replayed hipGraph moves on by itself), else u_host (>= 0).  A0_EINVAL: pad < 1, pad >= min(H, W), pad > 16, row_bytes != 2 * C * H * W,
+ * C * H * W % 16 != 0 or >= 2^30, frames or out not 16-byte aligned.  `out` must not overlap the rows of `frames` the launch reads: the library cannot detect that,
+ * and the result would depend on the order the workgroups run in.  slot values are not checked either (they index rows of `frames`, as in a0_learner_update). */
+int a0_augment_shift(const uint8_t* frames, const int* slot, long long row_bytes, int C, int H, int W, int pad, int B, unsigned long long seed, const int* state,
+                     long long u_host, uint8_t* out, void* stream);
 /* Synthetic env (oracle/synth_env.c defines it).  `task` selects the reward: A0_ENV_TASK_STREAM = an action-independent stream (P(-1, +1, 0) = .05, .05, .9:
  * the bench workload), A0_ENV_TASK_BLOCK = learnable: +1 when the action equals the quadrant (mod A) of the bright 8x8 block in the newest frame of the
  * observation it was chosen on, -1 for the next class, 0 otherwise (chance level 0, optimum +1 per step).  Terminals / life losses do not depend on it. */
