@@ -233,6 +233,8 @@ struct OpPlanesKC;
 template <> struct a0_x9_plain<OpPlanesKC> { static constexpr bool value = true; };
 template <class EP> struct a0_is_hadamard { static constexpr bool value = false; };
 template <> struct a0_is_hadamard<EpiHadamard> { static constexpr bool value = true; };
+template <class EP> struct a0_is_masked { static constexpr bool value = false; };
+template <> struct a0_is_masked<EpiMaskMat> { static constexpr bool value = true; };
 
 // Cross products of the three-term splits that are formed (NPR): 9 = all of them (every partial product of the fp32 fmaf chain, exactly: the strict mode), 6 = those
 // with term orders i + j <= 2 — a1*b2, a2*b1 and a2*b2 are left out, each below 2^-24 of a*b, i.e. below the rounding the fp32 chain itself applies to every partial SUM
@@ -436,6 +438,34 @@ __device__ __forceinline__ void a0_igemm_x9_body(const typename OA::Params& pa, 
         return;
     }
     const int z = bz;
+    if constexpr (a0_is_masked<EP>::value) {
+        // EpiMaskMat: a store that fetches its own mask value waits for it, and for the store before it — 16 MT NT dependent round trips per lane behind the last MFMA
+        // (profiles/r17_fc1_backward.md).  All mask values are requested first, at clamped (always valid) addresses, so the lane waits once.
+        float mk[MT][NT][16];
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const int y = y0 + wn * (NT * 32) + j * 32 + (lane & 31);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int x = x0 + wm * (MT * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    mk[i][j][r] = EP::mask(pe, x < X ? x : X - 1, y < Y ? y : Y - 1);
+                }
+            }
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const int y = y0 + wn * (NT * 32) + j * 32 + (lane & 31);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int x = x0 + wm * (MT * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    if (x < X && y < Y) EP::store_masked(pe, x, y, acc[i][j][r], mk[i][j][r]);
+                }
+            }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -488,9 +518,10 @@ static inline hipError_t a0_igemm_x9_group_launch(hipStream_t st, int n, const a
     return hipGetLastError();
 }
 
-// Two DIFFERENT GEMMs with the same tile shape and the same number of workgroups in one launch (blockIdx.y picks the body): fc1's data gradient and fc1's weight gradient of
-// a 512-row batch are 392 tiles each on a chip with 512 workgroup slots — alone each leaves a quarter of the slots empty and ends on the CUs that hold two workgroups; together
-// their 784 workgroups keep the slots filled (1.5 rounds instead of 2 x 1).  Same bodies, same tiles: bit-identical results.
+// Two DIFFERENT GEMMs with the same tile shape in one launch (blockIdx.y picks the body): fc1's data gradient and fc1's weight gradient of a 512-row batch.  The launcher's
+// caller picks the tile so that ALL workgroups of the launch are resident at once, one per CU: 128 x 128 on eight waves (two 32 x 32 blocks per wave, 120 KB of LDS) is
+// 100 + 100 workgroups on 256 CUs — one ramp, one prologue and one epilogue per launch, and a quarter fewer LDS fragment reads and a third fewer staged pieces per MFMA
+// than one block per wave (profiles/r17_fc1_backward.md).  Same bodies and, per output element, the same k-ascending MFMAs as on any other tile: bit-identical results.
 template <class OA1, class OB1, class EP1, class OA2, class OB2, class EP2, int WM, int WN, int MT, int NT, int KS = 2, int NPR = 9>
 __global__ __launch_bounds__(WM * WN * 64) void a0_igemm_x9_pair_kernel(typename OA1::Params pa1, typename OB1::Params pb1, typename EP1::Params pe1, int X1, int Y1, int K1, int kc1,
                                                                 int gx1, int gy1, typename OA2::Params pa2, typename OB2::Params pb2, typename EP2::Params pe2, int X2, int Y2,
@@ -509,6 +540,7 @@ static inline hipError_t a0_igemm_x9_pair_launch(hipStream_t st, const typename 
     typedef a0_x9_geom<OA1, OB1, WM, WN, MT, NT, KS> G1;
     typedef a0_x9_geom<OA2, OB2, WM, WN, MT, NT, KS> G2;
     constexpr int LDS = G1::LDS_BYTES > G2::LDS_BYTES ? G1::LDS_BYTES : G2::LDS_BYTES;
+    static_assert(LDS <= 160 * 1024, "a workgroup's tile buffers must fit the 160 KB of LDS");
     const int six = a0_x9_products_now() == 6;
     auto kern = six ? a0_igemm_x9_pair_kernel<OA1, OB1, EP1, OA2, OB2, EP2, WM, WN, MT, NT, KS, 6> : a0_igemm_x9_pair_kernel<OA1, OB1, EP1, OA2, OB2, EP2, WM, WN, MT, NT, KS, 9>;
     static bool configured[2] = {false, false};
@@ -526,7 +558,7 @@ static inline hipError_t a0_igemm_x9_pair_launch(hipStream_t st, const typename 
 }
 
 // The pair above plus a SECOND instance of its second body on a smaller problem (round 5): fc1's data gradient, fc1's weight gradient and the HEAD's weight gradient all
-// depend on the loss kernel's outputs only, and the head's few tiles (8 for a scalar head, 56 for qr's 800 columns) fit into the slots the pair leaves empty — its launch
+// depend on the loss kernel's outputs only, and the head's few tiles (4 of 128 x 128 for a scalar head) fit onto the CUs the pair leaves empty — its launch
 // (6.5 - 10.9 us alone, 20 times per block) disappears.  blockIdx.y names the problem; the third problem's grid column is as long as the pair's, workgroups without a tile
 // of it leave at once.
 template <class OA1, class OB1, class EP1, class OA2, class OB2, class EP2, int WM, int WN, int MT, int NT, int KS = 2, int NPR = 9>
@@ -534,8 +566,8 @@ __global__ __launch_bounds__(WM * WN * 64) void a0_igemm_x9_trio_kernel(typename
                                                                 int gx1, int gy1, typename OA2::Params pa2, typename OB2::Params pb2, typename EP2::Params pe2, int X2, int Y2,
                                                                 int K2, int kc2, int gx2, int gy2, typename OA2::Params pa3, typename OB2::Params pb3, typename EP2::Params pe3,
                                                                 int X3, int Y3, int K3, int kc3, int gx3, int gy3) {
-    // the small problem takes grid row 0: rows are dispatched in order, so its workgroups start with the launch instead of behind the pair's 784 (measured: in the last
-    // row they began when the pair's slots drained and added their whole duration to the launch's tail)
+    // the small problem takes grid row 0: rows are dispatched in order, so its workgroups start with the launch instead of behind the pair's (measured with more
+    // workgroups than CUs: in the last row they began when the pair's slots drained and added their whole duration to the launch's tail)
     if (blockIdx.y == 1) a0_igemm_x9_body<OA1, OB1, EP1, WM, WN, MT, NT, KS, NPR>(pa1, pb1, pe1, X1, Y1, K1, kc1, gx1, gy1);
     else if (blockIdx.y == 2) a0_igemm_x9_body<OA2, OB2, EP2, WM, WN, MT, NT, KS, NPR>(pa2, pb2, pe2, X2, Y2, K2, kc2, gx2, gy2);
     else {
@@ -553,6 +585,7 @@ static inline hipError_t a0_igemm_x9_trio_launch(hipStream_t st, const typename 
     typedef a0_x9_geom<OA1, OB1, WM, WN, MT, NT, KS> G1;
     typedef a0_x9_geom<OA2, OB2, WM, WN, MT, NT, KS> G2;
     constexpr int LDS = G1::LDS_BYTES > G2::LDS_BYTES ? G1::LDS_BYTES : G2::LDS_BYTES;
+    static_assert(LDS <= 160 * 1024, "a workgroup's tile buffers must fit the 160 KB of LDS");
     const int six = a0_x9_products_now() == 6;
     auto kern = six ? a0_igemm_x9_trio_kernel<OA1, OB1, EP1, OA2, OB2, EP2, WM, WN, MT, NT, KS, 6> : a0_igemm_x9_trio_kernel<OA1, OB1, EP1, OA2, OB2, EP2, WM, WN, MT, NT, KS, 9>;
     static bool configured[2] = {false, false};

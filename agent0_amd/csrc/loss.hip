@@ -552,17 +552,23 @@ __global__ __launch_bounds__(256) void a0_dqn_head_loss_slabs_kernel(const float
     __shared__ float dsh[4][32];                   // this row's head gradient (draw), for the fused head data gradient
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int NQ = A + (dueling ? 1 : 0);
-    for (int i = threadIdx.x; i < NQ * 128; i += 256) { ((a0_f4*)wsm)[i] = ((const a0_f4*)W_on)[i]; ((a0_f4*)wsm)[NQ * 128 + i] = ((const a0_f4*)W_tg)[i]; }
     const int b = blockIdx.x * 4 + wave;
     const int br = b < B ? b : B - 1;
+    // everything the tail of the kernel reads is requested here, in front of the slab loads, so that no load waits behind the head reductions: the sample's scalars
+    // (every lane holds them; lane 0 uses them), the head biases (lane a holds row a's) and fc1's bias columns
+    const int ab = act[br];
+    const float rew_b = rew[br], done_b = done[br], wgt_b = wgt[br];
+    const float hb_on = lane < NQ ? b_on[lane] : 0.f, hb_tg = lane < NQ ? b_tg[lane] : 0.f;
+    float b1o[8], b1t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { b1o[i] = b1_on[lane + 64 * i]; b1t[i] = b1_tg[lane + 64 * i]; }
     float ho[8], ht[8], hs[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { ho[i] = 0.f; ht[i] = 0.f; hs[i] = 0.f; }
     const long long ro = (long long)br * 512 + lane;
     // four slabs per trip: every column of the trip is requested before any is added, so 64 (96) loads overlap instead of queueing;
     // the additions stay in slab order
-    auto sum4 = [&](const float* __restrict__ sp, float (&h)[8]) {
-        int z = 0;
+    auto sum4 = [&](const float* __restrict__ sp, float (&h)[8], int z) {
         for (; z + 4 <= nslab; z += 4) {
             float t[4][8];
 #pragma unroll
@@ -582,12 +588,43 @@ __global__ __launch_bounds__(256) void a0_dqn_head_loss_slabs_kernel(const float
             for (int i = 0; i < 8; ++i) h[i] += t[i];
         }
     };
-    sum4(s_on, ho);
-    sum4(s_tg, ht);
-    if (s_sel) sum4(s_sel, hs);
+    // the first four slabs of all three passes are requested together, then the head weights are staged while they are in flight
+    const int z0 = nslab >= 4 ? 4 : 0;
+    float t_on[4][8], t_tg[4][8], t_sel[4][8];
+    if (z0) {
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                t_on[zz][i] = s_on[(long long)zz * slab_stride + ro + 64 * i];
+                t_tg[zz][i] = s_tg[(long long)zz * slab_stride + ro + 64 * i];
+            }
+        if (s_sel) {
+#pragma unroll
+            for (int zz = 0; zz < 4; ++zz)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) t_sel[zz][i] = s_sel[(long long)zz * slab_stride + ro + 64 * i];
+        }
+    }
+    for (int i = threadIdx.x; i < NQ * 128; i += 256) { ((a0_f4*)wsm)[i] = ((const a0_f4*)W_on)[i]; ((a0_f4*)wsm)[NQ * 128 + i] = ((const a0_f4*)W_tg)[i]; }
+    if (z0) {
+#pragma unroll
+        for (int zz = 0; zz < 4; ++zz)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { ho[i] += t_on[zz][i]; ht[i] += t_tg[zz][i]; }
+        if (s_sel) {
+#pragma unroll
+            for (int zz = 0; zz < 4; ++zz)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) hs[i] += t_sel[zz][i];
+        }
+    }
+    sum4(s_on, ho, z0);
+    sum4(s_tg, ht, z0);
+    if (s_sel) sum4(s_sel, hs, z0);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const float bo = b1_on[lane + 64 * i], bt = b1_tg[lane + 64 * i];
+        const float bo = b1o[i], bt = b1t[i];
         float v = ho[i] + bo; ho[i] = v < 0.f ? 0.f : v;
         v = ht[i] + bt; ht[i] = v < 0.f ? 0.f : v;
         v = hs[i] + (MDQN ? bt : bo); hs[i] = v < 0.f ? 0.f : v;
@@ -608,7 +645,8 @@ __global__ __launch_bounds__(256) void a0_dqn_head_loss_slabs_kernel(const float
             st = fmaf(ht[i], w2, st);
         }
         so = a0_wave_sum(so); st = a0_wave_sum(st); ss = a0_wave_sum(ss);
-        if (lane == 0) { raw[wave][0][a] = so + b_on[a]; raw[wave][1][a] = st + b_tg[a]; raw[wave][2][a] = ss + (MDQN ? b_tg[a] : b_on[a]); }
+        const float bo_a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb_on), a)), bt_a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb_tg), a));
+        if (lane == 0) { raw[wave][0][a] = so + bo_a; raw[wave][1][a] = st + bt_a; raw[wave][2][a] = ss + (MDQN ? bt_a : bo_a); }
     }
     if (lane == 0) {
     const int nsel = (s_sel && !MDQN) ? 2 : 1;
@@ -630,20 +668,19 @@ __global__ __launch_bounds__(256) void a0_dqn_head_loss_slabs_kernel(const float
         if (q_tg_out) q_tg_out[(long long)b * A + a] = q(1, a);
         if (MDQN && M.q_sel_out) M.q_sel_out[(long long)b * A + a] = q(2, a);
     }
-    const int ab = act[b];
     float y;
     if (MDQN) {
-        y = a0_mdqn_target([&](int k) { return q(1, k); }, [&](int k) { return q(2, k); }, A, ab, rew[b], done[b], gamma_n, M.tau, M.lo);
+        y = a0_mdqn_target([&](int k) { return q(1, k); }, [&](int k) { return q(2, k); }, A, ab, rew_b, done_b, gamma_n, M.tau, M.lo);
     } else {
         const float qn = q(1, a_star);
-        y = rew[b] + (gamma_n * (1.f - done[b])) * qn;
+        y = rew_b + (gamma_n * (1.f - done_b)) * qn;
     }
     const float d = q(0, ab) - y;
     const float ad = fabsf(d);
     const float l = (ad < 1.f) ? 0.5f * d * d : ad - 0.5f;
     loss[b] = l;
     if (l != l) atomicOr(nan_flag, 1);
-    const float g = wgt[b] * fminf(fmaxf(d, -1.f), 1.f);
+    const float g = wgt_b * fminf(fmaxf(d, -1.f), 1.f);
     float* o = draw + (long long)b * ld;
     for (int c = 0; c < ld; ++c) {
         float out = 0.f;

@@ -825,6 +825,12 @@ extern "C" int a0_dense_dgrad_hadamard(const float* dY, const float* W, const fl
 // a0_dense_dgrad (with the ReLU mask) and the unsplit a0_dense_wgrad of ONE layer — same dY, R x N x K with as many 64 x 64 tiles in the data gradient (R x K) as in the
 // weight gradient (N x K): N == R — as one launch (a0_igemm_x9_pair_kernel).  fc1 of a 512-row batch: dX = (dY W) * (X > 0) into dX, dW = dY^T X (+ bias row sums) into grad.
 // Bit-identical to the two calls.  Shapes: a0_dense_dgrad_wgrad_ok.
+// (the class is stated in the tiles of the single-problem paths it must equal: fewer than 256 tiles of 128 x 64 in the data gradient, so that a0_dense_dgrad runs 64 x 64
+// tiles, and at least 256 tiles of 64 x 64 in the weight gradient, so that a0_dense_wgrad is unsplit; within it the launch's own 128 x 128 tiles number at most
+// 2 x 128 + the head's, and 2 x 100 + 4 for fc1)
+// the tile of the fc1 backward launches (pair and trio): four by two waves of A0_FC1_MT x A0_FC1_NT blocks of 32 x 32
+static constexpr int A0_FC1_MT = 1, A0_FC1_NT = 2;
+static constexpr int A0_FC1_BX = 128 * A0_FC1_MT, A0_FC1_BY = 64 * A0_FC1_NT;
 extern "C" int a0_dense_dgrad_wgrad_ok(int R, int N, int K) {
     const long long b128 = (long long)((R + 127) / 128) * ((K + 63) / 64), b64 = (long long)((N + 63) / 64) * ((K + 63) / 64);
     return (g_gemm_x9 != 0 && g_probe.tag == 0 && R == N && R >= 1 && R <= 1024 && !(N & 3) && !(K & 3) && b128 < 256 && b64 >= 256 && N >= 512 &&
@@ -849,9 +855,11 @@ extern "C" int a0_dense_dgrad_wgrad(const float* dY, const float* W, const float
         A0_HIP_THROW((a0_igemm_x9_pair_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 2, 2, 1, 1>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R)));
         return A0_OK;
     }
-    // 128 x 64 tiles on eight waves (196 + 196 workgroups, one per CU at a time): the same sums as the 64 x 64 tiles of the separate calls (every output element's k loop is the
-    // same sequence of MFMAs), equal on the `main` schedule and ~2 % faster under `launch`, where the rollout's kernels share the chip
-    A0_HIP_THROW((a0_igemm_x9_pair_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 4, 2, 1, 1>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R)));
+    // 128 x 128 tiles on eight waves, two 32 x 32 blocks per wave (A0_FC1_MT x A0_FC1_NT): fc1 of a 512-row batch is 100 + 100 workgroups of 120 KB of LDS, one per CU, ALL
+    // resident at once — the 128 x 64 tile before it needed two rounds of workgroups (196 + 196 on 256 CUs, the second 56 % full) and paid ramp, prologue and epilogue twice
+    // (profiles/r17_fc1_backward.md; the 256 x 64 tile was measured too and is slower).  The same sums as the 64 x 64 tiles of the separate calls: every output element's k
+    // loop is the same sequence of MFMAs, and the bias gradient's 16 partial sums have the same members (BX = 128 on 512 threads, as before).
+    A0_HIP_THROW((a0_igemm_x9_pair_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 4, 2, A0_FC1_MT, A0_FC1_NT>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R)));
     return A0_OK;
     A0_CATCH
 }
@@ -860,26 +868,26 @@ extern "C" int a0_dense_dgrad_wgrad(const float* dY, const float* W, const float
 // final (the head / loss kernel writes them), fc1's data gradient, fc1's weight gradient and the head's weight gradient dW2 = dY2^T X2 (+ bias row sums) into grad2
 // [N2 x K2 | N2] are independent; the head's few tiles ride in the pair's launch (a0_igemm_x9_trio_kernel).  grad2 gets an UNSPLIT sum over the R rows on the bf16 pipe
 // (a0_dense_wgrad splits it into slabs on the fp32 pipe: the same sum up to the association order).  Shapes: a0_dense_dgrad_wgrad_ok(R, N, K), X2 rows of R, ldx2 >= K2.
-// where it pays: heads of at most one row of 128 x 64 tiles (scalar heads: 8 workgroups).  Measured with wider heads in the launch (same box, alternating): c51's 16 tiles
+// where it pays: heads of at most 128 rows over at most 512 columns (scalar heads: four of the launch's 128 x 128 tiles).  Measured with wider heads in the launch
+// (same box, alternating, 128 x 64 tiles): c51's 16 tiles
 // 14.47 - 14.50 -> 14.57 ms, qr's 56 tiles 12.13 -> 12.16 ms — there the fp32-pipe split launch of its own stays; dqn 9.97 -> 9.85 ms, mdqn 11.69 -> 11.60.
 extern "C" int a0_dense_dgrad_wgrad2_ok(int R, int N, int K, int N2, int K2) {
-    return (a0_dense_dgrad_wgrad_ok(R, N, K) && N2 >= 4 && !(N2 & 3) && K2 >= 4 && !(K2 & 3) &&
-            (long long)((N2 + 127) / 128) * ((K2 + 63) / 64) <= 8) ? 1 : 0;
+    return (a0_dense_dgrad_wgrad_ok(R, N, K) && N2 >= 4 && !(N2 & 3) && N2 <= 128 && K2 >= 4 && !(K2 & 3) && K2 <= 512) ? 1 : 0;
 }
 extern "C" int a0_dense_dgrad_wgrad2(const float* dY, const float* W, const float* X, int ldx, float* dX, float* grad, int R, int N, int K,
                                      const float* dY2, const float* X2, int ldx2, float* grad2, int N2, int K2, void* stream) {
     A0_TRY
     if (!dY || !W || !X || !dX || !grad || ldx < K || (ldx & 3) || !a0_dense_dgrad_wgrad_ok(R, N, K)) return a0_fail(A0_EINVAL, "a0_dense_dgrad_wgrad2: shapes a0_dense_dgrad_wgrad_ok accepts");
     if (!dY2 || !X2 || !grad2 || N2 < 4 || (N2 & 3) || K2 < 4 || (K2 & 3) || ldx2 < K2 || (ldx2 & 3) ||
-        (long long)((N2 + 127) / 128) * ((K2 + 63) / 64) > (long long)((R + 127) / 128) * ((K + 63) / 64))
-        return a0_fail(A0_EINVAL, "a0_dense_dgrad_wgrad2: the second layer's weight gradient must have no more 128 x 64 tiles than the first layer's data gradient");
+        (long long)((N2 + A0_FC1_BX - 1) / A0_FC1_BX) * ((K2 + A0_FC1_BY - 1) / A0_FC1_BY) > (long long)((R + A0_FC1_BX - 1) / A0_FC1_BX) * ((K + A0_FC1_BY - 1) / A0_FC1_BY))
+        return a0_fail(A0_EINVAL, "a0_dense_dgrad_wgrad2: the second layer's weight gradient must have no more tiles than the first layer's data gradient");
     a0_mat_src a1{dY, N}, b1{W, K};
     EpiMaskMat::Params e1{dX, X, K};
     a0_mat_src a2{dY, N}, b2{X, ldx};
     EpiWgradSlab::Params e2{grad, 0, K, (long long)N * K};
     a0_mat_src a3{dY2, N2}, b3{X2, ldx2};
     EpiWgradSlab::Params e3{grad2, 0, K2, (long long)N2 * K2};
-    A0_HIP_THROW((a0_igemm_x9_trio_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 4, 2, 1, 1>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R,
+    A0_HIP_THROW((a0_igemm_x9_trio_launch<OpMatKC, OpMatXC, EpiMaskMat, OpMatXC, OpMatXC, EpiWgradSlab, 4, 2, A0_FC1_MT, A0_FC1_NT>((hipStream_t)stream, a1, b1, e1, R, K, N, a2, b2, e2, N, K, R,
                                                                                                                   a3, b3, e3, N2, K2, R)));
     return A0_OK;
     A0_CATCH

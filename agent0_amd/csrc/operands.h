@@ -279,8 +279,9 @@ struct EpiHadamard {
 struct EpiMaskMat {            // dX[x][y] = act[x][y] > 0 ? v : 0   (dense layers)
     static constexpr bool ROWSUM_A = false;
     struct Params { float* dx; const float* act; int ld; };
-    A0_HD static void store(const Params& P, int x, int y, float v, int) {
-        long long i = (long long)x * P.ld + y;
-        P.dx[i] = (P.act[i] > 0.f) ? v : 0.f;
-    }
+    // the store in two halves, so that a kernel can request all of a lane's mask values before its first store (igemm_x9.h); store() is the two in one, for the
+    // fp32 fmaf-chain kernel (igemm.h) and the host emulation
+    A0_HD static float mask(const Params& P, int x, int y) { return P.act[(long long)x * P.ld + y]; }
+    A0_HD static void store_masked(const Params& P, int x, int y, float v, float m) { P.dx[(long long)x * P.ld + y] = (m > 0.f) ? v : 0.f; }
+    A0_HD static void store(const Params& P, int x, int y, float v, int) { store_masked(P, x, y, v, mask(P, x, y)); }
 };
