@@ -61,6 +61,11 @@ class UpdateTailPlan(C.Structure):
     _fields_ = [("seg", ReduceSeg * 8), ("n", C.c_int)]
 
 
+class NetResetSeg(C.Structure):
+    """a0_net_reset_seg: one rule of a network reset — [offset, offset + count) of the flat buffer, kind (0 constant / 1 normal / 2 uniform), scale, keep flag."""
+    _fields_ = [("offset", C.c_longlong), ("count", C.c_longlong), ("kind", C.c_int), ("scale", C.c_float), ("keep", C.c_int)]
+
+
 class EncoderPass(C.Structure):
     _fields_ = [("wt", C.c_void_p), ("w", C.c_void_p), ("f", C.c_void_p), ("B", C.c_int), ("act1", C.c_void_p), ("act2", C.c_void_p), ("act3", C.c_void_p)]
 

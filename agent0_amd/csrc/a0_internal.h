@@ -36,6 +36,8 @@ struct a0_hip_error : std::runtime_error {
 // Philox stream ids (agent0_amd/common/utils.py DeviceRng: 1 / 2 epsilon-greedy, 3 quantile fractions, 4 NoisyNet, 5 sum-tree, 6 permutation seeds); 7 = the
 // random shifts of learner.aug_shift (augment.hip), positioned by the update count alone: no running offset, nothing to snapshot
 #define A0_STREAM_AUG 7
+// 8 = the fresh values of learner.net_reset_freq (optim.hip: a0_net_reset), positioned by (reset number, flat index): no running offset either
+#define A0_STREAM_RESET 8
 // augment.hip: the range checks of a0_augment_shift (A0_EINVAL with a message that starts with `who`)
 int a0_augment_shift_check(const char* who, int C, int H, int W, int pad, long long row_bytes);
 

@@ -315,6 +315,68 @@ extern "C" int a0_learner_set_target_tau(a0_learner* L, double tau) {
     return A0_OK;
 }
 
+// The rule table of a network reset from the handle's block descriptors: NetLayout.reset_segments (agent0_amd/deepq/layout.py), entry for entry.  A fresh weight has
+// the constructor's per-element scale (agent0_amd/deepq/model.py): an orthogonal matrix of gain g has element RMS g / sqrt(max(rows, cols)); a NoisyLinear's mu is
+// uniform in +-1 / sqrt(in), its sigma 0.4 / sqrt(in) (weights) and 0.4 / sqrt(out) (bias).  Returns the number of entries.
+static int a0_learner_reset_table(const a0_learner* L, a0_net_reset_seg* out) {
+    int n = 0;
+    auto add = [&](long long off, long long cnt, int kind, double scale, int keep) { if (cnt > 0) out[n++] = a0_net_reset_seg{off, cnt, kind, (float)scale, keep}; };
+    auto orth = [](double gain, long long rows, long long cols) { return gain / std::sqrt((double)std::max(rows, cols)); };
+    const double g_relu = std::sqrt(2.0);
+    for (const Blk* b : {&L->conv1, &L->conv2, &L->conv3}) {
+        add(b->w(), (long long)b->N * b->K, A0_NET_RESET_NORMAL, orth(g_relu, b->N, b->K), 1);
+        add(b->b(), b->N, A0_NET_RESET_CONST, 0.0, 1);
+    }
+    const long long real = L->Nq + L->V, pad = L->Npad - real;
+    if (L->d.noisy) {
+        const double bf = 1.0 / std::sqrt((double)L->feat), bh = 1.0 / std::sqrt(512.0);
+        add(L->fc1.w(), 512LL * L->feat, A0_NET_RESET_UNIFORM, bf, 0);
+        add(L->fc1.b(), 512, A0_NET_RESET_UNIFORM, bf, 0);
+        add(L->fc1_sigma.w(), 512LL * L->feat, A0_NET_RESET_CONST, 0.4 * bf, 0);
+        add(L->fc1_sigma.b(), 512, A0_NET_RESET_CONST, 0.4 / std::sqrt(512.0), 0);
+        add(L->head.w(), real * 512, A0_NET_RESET_UNIFORM, bh, 0);
+        add(L->head.w() + real * 512, pad * 512, A0_NET_RESET_CONST, 0.0, 0);
+        add(L->head.b(), real, A0_NET_RESET_UNIFORM, bh, 0);
+        add(L->head.b() + real, pad, A0_NET_RESET_CONST, 0.0, 0);
+        add(L->head_sigma.w(), real * 512, A0_NET_RESET_CONST, 0.4 * bh, 0);
+        add(L->head_sigma.w() + real * 512, pad * 512, A0_NET_RESET_CONST, 0.0, 0);
+        add(L->head_sigma.b(), L->Nq, A0_NET_RESET_CONST, 0.4 / std::sqrt((double)L->Nq), 0);
+        add(L->head_sigma.b() + L->Nq, L->V, A0_NET_RESET_CONST, L->V > 0 ? 0.4 / std::sqrt((double)L->V) : 0.0, 0);
+        add(L->head_sigma.b() + real, pad, A0_NET_RESET_CONST, 0.0, 0);
+    } else {
+        add(L->fc1.w(), 512LL * L->feat, A0_NET_RESET_NORMAL, orth(g_relu, 512, L->feat), 0);
+        add(L->fc1.b(), 512, A0_NET_RESET_CONST, 0.0, 0);
+        add(L->head.w(), (long long)L->Nq * 512, A0_NET_RESET_NORMAL, orth(0.01, L->Nq, 512), 0);
+        add(L->head.w() + (long long)L->Nq * 512, (long long)L->V * 512, A0_NET_RESET_NORMAL, orth(1.0, L->V, 512), 0);
+        add(L->head.w() + real * 512, pad * 512, A0_NET_RESET_CONST, 0.0, 0);
+        add(L->head.b(), L->Npad, A0_NET_RESET_CONST, 0.0, 0);
+    }
+    if (L->d.algo == A0_ALGO_IQN || L->d.algo == A0_ALGO_FQF) {
+        add(L->cos.w(), (long long)L->feat * 64, A0_NET_RESET_NORMAL, orth(g_relu, L->feat, 64), 0);
+        add(L->cos.b(), L->feat, A0_NET_RESET_CONST, 0.0, 0);
+    }
+    return n;
+}
+
+extern "C" int a0_learner_set_net_reset(a0_learner* L, int freq, double shrink, unsigned long long seed) {
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_net_reset: null handle");
+    if (L->updated) return a0_fail(A0_EINVAL, "a0_learner_set_net_reset: the setting is fixed once the handle has run an update");
+    if (freq < 0) return a0_fail(A0_EINVAL, "a0_learner_set_net_reset: freq < 0 (0 is off)");
+    if (!(shrink >= 0.0) || !(shrink <= 1.0)) return a0_fail(A0_EINVAL, "a0_learner_set_net_reset: shrink must lie in [0, 1]");
+    L->reset_freq = freq; L->reset_shrink = shrink; L->reset_seed = seed & 0xFFFFFFFFull;
+    L->n_reset_segs = freq > 0 ? a0_learner_reset_table(L, L->reset_segs) : 0;
+    return A0_OK;
+}
+
+extern "C" int a0_learner_net_reset_segs(const a0_learner* L, a0_net_reset_seg* out, int cap) {
+    if (!L || !out || cap < 0) return a0_fail(A0_EINVAL, "a0_learner_net_reset_segs: null argument");
+    a0_net_reset_seg tab[A0_NET_RESET_MAX_SEGS];
+    const int n = a0_learner_reset_table(L, tab);
+    if (n > cap) return a0_fail(A0_EINVAL, "a0_learner_net_reset_segs: cap is smaller than the table (A0_NET_RESET_MAX_SEGS entries always fit)");
+    for (int i = 0; i < n; ++i) out[i] = tab[i];
+    return n;
+}
+
 extern "C" int a0_learner_set_aug_shift(a0_learner* L, int pad) {
     A0_TRY
     if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_aug_shift: null handle");
@@ -416,7 +478,13 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
     // learner.target_tau (DeviceLearner.apply): the Adam forms get the period 0 — never a hard copy — and a0_target_blend follows whichever tail form the update took
     const bool soft = L->target_tau > 0.0;
     const int hard_freq = soft ? 0 : L->d.target_update_freq;
-    auto blend = [&]() -> int { return soft ? a0_target_blend(tg, on, L->n_pad, L->target_tau, L->state, L->d.target_update_freq, 0, &w_tg, L->C, L->wt_tg, stream) : A0_OK; };
+    auto blend_only = [&]() -> int { return soft ? a0_target_blend(tg, on, L->n_pad, L->target_tau, L->state, L->d.target_update_freq, 0, &w_tg, L->C, L->wt_tg, stream) : A0_OK; };
+    // learner.net_reset_freq (DeviceLearner.apply): the update's last launch, behind the blend; it returns at once unless this update's count names a reset
+    auto blend = [&]() -> int {
+        A0_CHECK(blend_only());
+        return L->reset_freq > 0 ? a0_net_reset(on, tg, L->m, L->v, L->n_adam, L->n_pad, L->reset_segs, L->n_reset_segs, L->reset_shrink, L->reset_seed, L->state, L->reset_freq, 0, 0,
+                                                &w_on, L->C, L->wt_on, L->wt_tg, stream) : A0_OK;
+    };
     if (L->d.noisy) {
         // BaseLearner.train (agent.py:125-127): reset_noise of the online, then of the target network — ONE Philox fill of the joint buffer (the same draws as two
         // fills: every vector is padded to the offsets' stride of four) — and both networks' effective weights in one launch

@@ -73,6 +73,11 @@ struct a0_learner {
     // ---- soft target updates (a0_learner_set_target_tau): off while target_tau <= 0; `updated`: an update has been issued, the setting is fixed from then on
     double target_tau = 0.0;
     bool updated = false;
+    // ---- periodic shrink-and-perturb resets (a0_learner_set_net_reset): off while reset_freq == 0; the rule table is built from the block descriptors above
+    int reset_freq = 0, n_reset_segs = 0;
+    double reset_shrink = 1.0;
+    unsigned long long reset_seed = 0;
+    a0_net_reset_seg reset_segs[A0_NET_RESET_MAX_SEGS];
     // ---- DrQ random shift of the batch (a0_learner_set_aug_shift): off while aug_pad == 0; aug_stage: the dense augmented batch [B][2 * C * H * W], allocated by the first call that switches it on
     int aug_pad = 0;
     uint8_t* aug_stage = nullptr;

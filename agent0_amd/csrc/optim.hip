@@ -4,6 +4,7 @@
 // target_update_freq successful updates) without the two host syncs per update the reference pays (quirk Q14):
 // the NaN flag, the step counter and the "sync now" decision all live in a small device-side state block.
 #include "a0_internal.h"
+#include "rng_elem.h"
 #include "update_tail.h"
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 //   [2] skipped       number of updates skipped because of NaN
 //   [3] skip_now      decision for the update in flight (1 = NaN seen, leave the parameters alone)
 //   [4] sync_now      1 if update_steps % target_update_freq == 0 after this update
+//   [7] reset_steps   update_steps at the last network reset (a0_net_reset); Adam's bias corrections count t = max(1, update_steps - reset_steps)
 // scalars (floats): [0] step_size = lr / (1 - b1^t), [1] bc2_sqrt = sqrt(1 - b2^t)
 // extra_flag (optional): a float that is nonzero when ANY data-parallel rank saw a NaN — the sum over ranks of a0_nan_flag_export's
 // output, which travels at the tail of the dense gradient bucket instead of in an all-reduce of its own.
@@ -23,7 +25,7 @@ __global__ void a0_adam_prep_kernel(int* __restrict__ state, float* __restrict__
     const int skip = (state[0] != 0) || (extra_flag && extra_flag[0] != 0.f);
     int steps = state[1];
     if (!skip) steps += 1; else state[2] += 1;
-    const int t = steps > 0 ? steps : 1;
+    const int t = steps - state[7] > 0 ? steps - state[7] : 1;      // state[7]: the count at the last network reset (a0_net_reset), 0 without one
     scal[0] = (float)(lr / (1.0 - pow(b1, (double)t)));
     scal[1] = (float)sqrt(1.0 - pow(b2, (double)t));
     state[1] = steps;
@@ -160,7 +162,7 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
         if (threadIdx.x == 0) {
             const int sk = (state[0] != 0) || (F.extra_flag && F.extra_flag[0] != 0.f);
             const int steps = state[1] + (sk ? 0 : 1);
-            const int t = steps > 0 ? steps : 1;
+            const int t = steps - state[7] > 0 ? steps - state[7] : 1;
             const float ss = (float)(F.lr / (1.0 - pow(F.b1, (double)t))), bc = (float)sqrt(1.0 - pow(F.b2, (double)t));
             const int sy = (F.target_freq > 0 && (steps % F.target_freq) == 0) ? 1 : 0;
             sh_f[0] = ss; sh_f[1] = bc; sh_i[0] = sk; sh_i[1] = sy;
@@ -739,6 +741,173 @@ extern "C" int a0_target_blend(float* target, const float* online, long long n_t
     else
         hipLaunchKernelGGL((a0_target_blend_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, target, online, n_total, tau32, state, target_update_freq, force, vec4, B);
     return a0_fail_hip((int)hipGetLastError(), "a0_target_blend");
+}
+
+// ------------------------------------------------------------------------------------------------ periodic network resets
+// learner.net_reset_freq = N: after an update that was not NaN-skipped and left update_steps a positive multiple of N, the Q-network is re-initialised in ONE launch
+// behind the update's Adam form (and behind a0_target_blend): the head blocks are replaced by fresh values, the encoder blocks keep the share alpha of theirs
+// (shrink and perturb), Adam's moments are zeroed, its bias correction restarts (state[7] <- state[1]), the target becomes a copy of the online network and the
+// lane that holds a convolution weight files it in both networks' weight copies.  On every other update all workgroups return after reading state[1] and state[3].
+// Fresh values: element i at reset k = update_steps / N draws from Philox stream A0_STREAM_RESET of the seed at position k * n_total + i — a function of
+// (seed, k, i) alone; a normal element is a0_rng_normal's value there, a uniform one bound * (2 u - 1) with u a0_rng_uniform's (rng_elem.h).
+struct a0_reset_table { a0_net_reset_seg s[A0_NET_RESET_MAX_SEGS]; int n; };
+struct a0_reset_wt { long long o1, o2, o3; int K1, wt4; float *wt, *wt_t; };
+// the rule of one flat index: kind < 0 outside every segment; keep is the share that survives (alpha32 or 0); end: one past the segment's last index
+struct a0_reset_rule { long long end; int kind; float scale, keep; };
+
+// every lane walks the table in the same order (uniform loads of the by-value table, no indexed access to it); outside every segment `end` is where the next one starts
+A0_D a0_reset_rule a0_reset_find(const a0_reset_table& T, float alpha, long long i, long long n_total) {
+    a0_reset_rule R{n_total, -1, 0.f, 1.f};
+#pragma nounroll
+    for (int s = 0; s < T.n; ++s) {
+        const long long lo = T.s[s].offset, hi = lo + T.s[s].count;
+        if (i >= lo && i < hi) { R.end = hi; R.kind = T.s[s].kind; R.scale = T.s[s].scale; R.keep = T.s[s].keep ? alpha : 0.f; }
+        else if (lo > i && lo < R.end && R.kind < 0) R.end = lo;
+    }
+    return R;
+}
+// 2u - 1 is exact in fp32 (u is a multiple of 2^-24 below 1), then one rounded multiply
+A0_D float a0_reset_uniform(float bound, float u) {
+#pragma clang fp contract(off)
+    return bound * (2.0f * u - 1.0f);
+}
+A0_D float a0_reset_fresh1(const a0_reset_rule& R, unsigned long long seed, unsigned long long pos) {
+    if (R.kind == A0_NET_RESET_NORMAL) return a0_rng_normal_at(seed, A0_STREAM_RESET, pos, R.scale);
+    if (R.kind == A0_NET_RESET_UNIFORM) return a0_reset_uniform(R.scale, a0_rng_uniform_at(seed, A0_STREAM_RESET, pos));
+    return R.scale;
+}
+// four consecutive positions that share one Philox block (pos0 a multiple of four): one block, two Box-Muller pairs — the words a0_philox_word would pick
+A0_D a0_f4 a0_reset_fresh4(const a0_reset_rule& R, unsigned long long seed, unsigned long long pos0) {
+    a0_f4 f;
+    if (R.kind == A0_NET_RESET_CONST) { f.x = f.y = f.z = f.w = R.scale; return f; }
+    const unsigned long long blk = pos0 >> 2;
+    const a0_u4 o = a0_philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), A0_STREAM_RESET, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    if (R.kind == A0_NET_RESET_NORMAL) {
+        f.x = a0_rng_normal_words(o.x, o.y, false, R.scale); f.y = a0_rng_normal_words(o.x, o.y, true, R.scale);
+        f.z = a0_rng_normal_words(o.z, o.w, false, R.scale); f.w = a0_rng_normal_words(o.z, o.w, true, R.scale);
+    } else {
+        f.x = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.x)); f.y = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.y));
+        f.z = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.z)); f.w = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.w));
+    }
+    return f;
+}
+// keep == 0: the fresh value itself; otherwise fmaf(keep, fl32(p - phi), phi) — a0_blend1's form with the fresh value in the target's place
+A0_D float a0_reset_mix(const a0_reset_rule& R, float p, float phi) { return R.keep == 0.f ? phi : a0_blend1(phi, p, R.keep); }
+
+template <bool W>
+__global__ __launch_bounds__(256) void a0_net_reset_kernel(float* __restrict__ p, float* __restrict__ target, float* __restrict__ m, float* __restrict__ v, long long n_adam,
+                                                           long long n_total, a0_reset_table T, float alpha, unsigned long long seed_arg, int* __restrict__ state, int freq,
+                                                           int force, long long k_host, int vec4, a0_reset_wt B) {
+    long long k = k_host;
+    if (!force) {
+        const int steps = state[1];
+        if (state[3] != 0 || !(freq > 0 && steps > 0 && steps % freq == 0)) return;
+        k = steps / freq;
+    }
+    // a fresh optimizer: the three places that derive Adam's step scalars count t from here (nobody reads state[7] during this launch)
+    if (state && blockIdx.x == 0 && threadIdx.x == 0) state[7] = state[1];
+    a0_tail_args A;
+    const a0_tail_step S{false, true, 0.f, 0.f};       // both networks' copies: the target is the online network after a reset
+    if constexpr (W) { A.o1 = B.o1; A.o2 = B.o2; A.o3 = B.o3; A.K1 = B.K1; A.wt4 = B.wt4; A.wt = B.wt; A.wt_t = B.wt_t; }
+    // the seed (32 bits) travels in a vector register: Philox's key schedule of a uniform seed would be hoisted into twenty scalar registers for the whole loop
+    uint32_t seed_v = (uint32_t)seed_arg;
+    asm volatile("" : "+v"(seed_v));
+    const unsigned long long seed = seed_v;
+    const unsigned long long base = (unsigned long long)k * (unsigned long long)n_total;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long groups = (n_total + 3) >> 2;
+    // a lane owns four consecutive elements.  `wide`: the buffers are 16-byte aligned, the four share a Philox block and, with weight copies, a row of a convolution
+    // matrix; where they also lie inside one segment (or between two) they move as 16 bytes.  Everything else — a segment boundary inside the four (the real / pad
+    // boundary of a noisy bias), the tail of n_total % 4 floats, 4-byte-aligned buffers — goes element by element through the same arithmetic.
+    const bool wide = vec4 && (base & 3) == 0 && (!W || A.wt4);
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < groups; j += stride) {
+        const long long e0 = 4 * j;
+        const a0_reset_rule R = a0_reset_find(T, alpha, e0, n_total);
+        if (wide && e0 + 4 <= R.end) {
+            a0_f4 pv = ((a0_f4*)p)[j];
+            if (R.kind >= 0 && R.keep != 1.f) {
+                const a0_f4 f = a0_reset_fresh4(R, seed, base + (unsigned long long)e0);
+                pv.x = a0_reset_mix(R, pv.x, f.x); pv.y = a0_reset_mix(R, pv.y, f.y); pv.z = a0_reset_mix(R, pv.z, f.z); pv.w = a0_reset_mix(R, pv.w, f.w);
+                ((a0_f4*)p)[j] = pv;
+            }
+            ((a0_f4*)target)[j] = pv;
+            if (e0 + 4 <= n_adam) { ((a0_f4*)m)[j] = a0_zero4(); ((a0_f4*)v)[j] = a0_zero4(); }
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (e0 + e < n_adam) { m[e0 + e] = 0.f; v[e0 + e] = 0.f; }
+            }
+            continue;
+        }
+#pragma nounroll
+        for (long long idx = e0; idx < e0 + 4 && idx < n_total; ++idx) {
+            const a0_reset_rule Re = a0_reset_find(T, alpha, idx, n_total);
+            float x = p[idx];
+            if (Re.kind >= 0 && Re.keep != 1.f) { x = a0_reset_mix(Re, x, a0_reset_fresh1(Re, seed, base + (unsigned long long)idx)); p[idx] = x; }
+            target[idx] = x;
+            if (idx < n_adam) { m[idx] = 0.f; v[idx] = 0.f; }
+        }
+    }
+    // the weight copies, in a pass of their own over the convolution blocks: every lane files the parameters it has just written itself (the same lane-to-element map)
+    if constexpr (W) {
+        const long long c_lo = (B.o1 < B.o2 ? (B.o1 < B.o3 ? B.o1 : B.o3) : (B.o2 < B.o3 ? B.o2 : B.o3)) >> 2;
+        long long c_hi = B.o1 + 32LL * B.K1;
+        if (B.o2 + 64 * 512 > c_hi) c_hi = B.o2 + 64 * 512;
+        if (B.o3 + 64 * 576 > c_hi) c_hi = B.o3 + 64 * 576;
+        c_hi = (c_hi + 3) >> 2;
+        for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < c_hi && j < groups; j += stride) {      // the first pass's groups, lane for lane
+            if (j < c_lo) continue;
+            const long long e0 = 4 * j;
+            if (wide && e0 + 4 <= n_total) a0_tail_wt4(A, S, e0, ((const a0_f4*)p)[j]);
+            else {
+#pragma nounroll
+                for (long long idx = e0; idx < e0 + 4 && idx < n_total; ++idx) a0_tail_wt1(A, S, idx, p[idx]);
+            }
+        }
+    }
+}
+
+extern "C" int a0_net_reset(float* params, float* target, float* exp_avg, float* exp_avg_sq, long long n_adam, long long n_total, const a0_net_reset_seg* segs, int n_segs,
+                            double alpha, unsigned long long seed, int* state, int freq, int force, long long k_host, const a0_encoder_weights* w, int C, float* wt,
+                            float* wt_target, void* stream) {
+    if (!params || !target || !exp_avg || !exp_avg_sq || n_adam < 1 || n_total < n_adam || (!force && !state) || freq < 0 || (force && k_host < 0) ||
+        ((((uintptr_t)params) | ((uintptr_t)target) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) & 3))
+        return a0_fail(A0_EINVAL, "a0_net_reset: bad argument");
+    if (!(alpha >= 0.0) || !(alpha <= 1.0)) return a0_fail(A0_EINVAL, "a0_net_reset: alpha must lie in [0, 1]");
+    if (n_segs < 0 || n_segs > A0_NET_RESET_MAX_SEGS || (n_segs > 0 && !segs)) return a0_fail(A0_EINVAL, "a0_net_reset: between 0 and A0_NET_RESET_MAX_SEGS segments");
+    a0_reset_table T;
+    T.n = n_segs;
+    long long at = 0;
+    for (int s = 0; s < A0_NET_RESET_MAX_SEGS; ++s) {
+        if (s >= n_segs) { T.s[s] = a0_net_reset_seg{0, 0, A0_NET_RESET_CONST, 0.f, 0}; continue; }
+        const a0_net_reset_seg& g = segs[s];
+        if (g.offset < at || g.count < 1 || g.offset + g.count > n_adam) return a0_fail(A0_EINVAL, "a0_net_reset: the segments must be ascending, disjoint and inside [0, n_adam)");
+        if (g.kind != A0_NET_RESET_CONST && g.kind != A0_NET_RESET_NORMAL && g.kind != A0_NET_RESET_UNIFORM) return a0_fail(A0_EINVAL, "a0_net_reset: unknown segment kind");
+        if (!(g.scale == g.scale) || g.scale - g.scale != 0.f || (g.keep != 0 && g.keep != 1)) return a0_fail(A0_EINVAL, "a0_net_reset: a segment's scale must be finite and its keep flag 0 or 1");
+        at = g.offset + g.count;
+        T.s[s] = g;
+    }
+    a0_reset_wt B{0, 0, 0, 0, 0, nullptr, nullptr};
+    if (wt || wt_target) {
+        if (!wt || !wt_target || !w || !w->w1 || !w->w2 || !w->w3 || C < 1) return a0_fail(A0_EINVAL, "a0_net_reset: weight copies need wt, wt_target, the online encoder weights and C >= 1");
+        if ((((uintptr_t)wt) | ((uintptr_t)wt_target)) & 15) return a0_fail(A0_EINVAL, "a0_net_reset: wt and wt_target must be 16-byte aligned");
+        B.K1 = C * 64; B.wt = wt; B.wt_t = wt_target;
+        B.o1 = w->w1 - params; B.o2 = w->w2 - params; B.o3 = w->w3 - params;
+        if (B.o1 < 0 || B.o1 + 32LL * B.K1 > n_total || B.o2 < 0 || B.o2 + 64 * 512 > n_total || B.o3 < 0 || B.o3 + 64 * 576 > n_total)
+            return a0_fail(A0_EINVAL, "a0_net_reset: the convolution weights must lie inside params[0, n_total)");
+        B.wt4 = ((B.o1 | B.o2 | B.o3) % 4 == 0) ? 1 : 0;
+    }
+    const int vec4 = ((((uintptr_t)params) | ((uintptr_t)target) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) % 16 == 0) ? 1 : 0;
+    long long blocks = ((n_total + 3) / 4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const float alpha32 = (float)alpha;       // rounded to fp32 once
+    const unsigned long long seed32 = seed & 0xFFFFFFFFull;
+    if (wt)
+        hipLaunchKernelGGL((a0_net_reset_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, target, exp_avg, exp_avg_sq, n_adam, n_total, T, alpha32, seed32,
+                           state, freq, force, k_host, vec4, B);
+    else
+        hipLaunchKernelGGL((a0_net_reset_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, target, exp_avg, exp_avg_sq, n_adam, n_total, T, alpha32, seed32,
+                           state, freq, force, k_host, vec4, B);
+    return a0_fail_hip((int)hipGetLastError(), "a0_net_reset");
 }
 
 // ------------------------------------------------------------------------------------------------ NoisyNet

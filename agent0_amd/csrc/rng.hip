@@ -5,6 +5,7 @@
 // generator in agent0/deepq/model.py:74-76,238); parity tests inject draws instead of comparing streams.
 #include "a0_internal.h"
 #include "philox.h"
+#include "rng_elem.h"
 
 #pragma clang fp contract(off)
 
@@ -19,7 +20,7 @@ __global__ void a0_rng_uniform_kernel(unsigned long long seed, uint32_t stream, 
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (ctrl) offset += (unsigned long long)ctrl[ctrl_idx];
-    out[i] = (float)(a0_philox_word(seed, stream, offset + (unsigned long long)i) >> 8) * 0x1.0p-24f;
+    out[i] = a0_rng_uniform_at(seed, stream, offset + (unsigned long long)i);
 }
 
 __global__ void a0_rng_randint_kernel(unsigned long long seed, uint32_t stream, unsigned long long offset, int hi, int* __restrict__ out, long long n) {
@@ -33,13 +34,7 @@ __global__ void a0_rng_normal_kernel(unsigned long long seed, uint32_t stream, u
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (ctrl) offset += (unsigned long long)ctrl[ctrl_idx];
-    const unsigned long long pos = offset + (unsigned long long)i;
-    const unsigned long long pair = pos & ~1ull;
-    const float u1 = (float)((a0_philox_word(seed, stream, pair) >> 8) + 1u) * 0x1.0p-24f;
-    const float u2 = (float)(a0_philox_word(seed, stream, pair + 1) >> 8) * 0x1.0p-24f;
-    const float rad = sqrtf(-2.0f * logf(u1));
-    const float ang = 6.283185307179586f * u2;
-    out[i] = stdv * rad * ((pos & 1) ? sinf(ang) : cosf(ang));
+    out[i] = a0_rng_normal_at(seed, stream, offset + (unsigned long long)i, stdv);
 }
 
 #define A0_RNG_LAUNCH(kernel, ...)                                                                       \

@@ -67,7 +67,7 @@ A0_D void a0_tail_prep_run(const a0_tail_prep& P) {
     int* const state = P.state;
     const int sk = state[0] != 0;
     const int steps = state[1] + (sk ? 0 : 1);
-    const int t = steps > 0 ? steps : 1;
+    const int t = steps - state[7] > 0 ? steps - state[7] : 1;      // state[7]: the count at the last network reset, 0 without one
     const float ss = (float)(P.lr / (1.0 - pow(P.b1, (double)t))), bc = (float)sqrt(1.0 - pow(P.b2, (double)t));
     const int sy = (P.target_freq > 0 && (steps % P.target_freq) == 0) ? 1 : 0;
     if (sk) state[2] += 1;

@@ -43,6 +43,16 @@ Additions (all default to the reference's behaviour being available):
                    and ``chase`` tasks encode their information in position, so no learning claim is made for them.  The draws come from Philox stream 7 of the
                    learner's seed at the position the device's update count names: no state of its own, nothing new in a snapshot, and the setting may change
                    across a resume like ``actor.min_eps``.  Not with ``A0_PIPELINE_TARGET=1`` (the separately staged target pass reads the ring).
+  learner.net_reset_freq  int, default 0 (off; negative values are refused).  N > 0: after every update that was not NaN-skipped and left ``update_steps`` a positive
+                   multiple of N the Q-network is re-initialised on the device (a0_net_reset, one launch behind the update): fc1, the heads, NoisyNet's mu / sigma and
+                   the cosine embedding get fresh values of the constructor's scale, the encoder (conv1 - conv3) keeps the share ``learner.net_reset_shrink`` of
+                   its values, Adam's moments and bias correction restart, the target becomes a copy of the online network.  The fqf fraction net and its RMSprop
+                   state are left alone.  BBF uses 40000, SR-SPR 20000 / replay ratio.  The fresh values are a function of (the learner's seed, the reset number, the
+                   element): no state of its own, a resumed run resets as the uninterrupted one does.  Adds the statistic ``net_resets``.  Not together with
+                   ``A0_PIPELINE_TARGET=1``.  (The name avoids ``reset_noise_freq``, which is NoisyNet's.)
+  learner.net_reset_shrink  float in [0, 1], default 1.0 (anything else, NaN included, is refused).  The share alpha of the encoder that survives a reset,
+                   p <- alpha * p + (1 - alpha) * fresh: 1.0 leaves the encoder untouched (Nikishin et al. 2022: the last layers only), 0.5 is BBF's and SR-SPR's
+                   shrink-and-perturb, 0 re-initialises it.  Without ``learner.net_reset_freq`` it does nothing.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -136,6 +146,8 @@ class LearnerConfig:
     target_update_freq: int = 500
     target_tau: float = 0.0
     aug_shift: int = 0
+    net_reset_freq: int = 0
+    net_reset_shrink: float = 1.0
     learner_steps: int = 20
     double_q: bool = False
     dueling_head: bool = False

@@ -59,6 +59,26 @@ def aug_shift_value(value, obs_shape, pipeline_target: Optional[bool] = None) ->
     return p
 
 
+def net_reset_value(freq, shrink=1.0, pipeline_target: Optional[bool] = None):
+    """``learner.net_reset_freq`` / ``learner.net_reset_shrink`` as the learner uses them: ``(N, alpha)``, N = 0 (off) for zero or None.  Refused: a negative or
+    fractional N, an alpha outside [0, 1] (NaN included; checked whether or not N is on), and N > 0 together with ``A0_PIPELINE_TARGET=1`` (``pipeline_target``; None
+    reads the environment): the separately staged target pass reads a target network the reset rewrites."""
+    if freq is None:
+        freq = 0
+    if isinstance(freq, bool) or int(freq) != freq or freq < 0:
+        raise ValueError(f"learner.net_reset_freq={freq!r}: must be a whole number of updates >= 0 (0 is off)")
+    alpha = 1.0 if shrink is None else float(shrink)
+    if not (0.0 <= alpha <= 1.0):
+        raise ValueError(f"learner.net_reset_shrink={shrink!r}: must lie in [0, 1] (1 keeps the encoder, 0 re-initialises it)")
+    n = int(freq)
+    if n > 0:
+        if pipeline_target is None:
+            pipeline_target = os.environ.get("A0_PIPELINE_TARGET", "0") == "1"
+        if pipeline_target:
+            raise ValueError(f"learner.net_reset_freq={n}: not together with A0_PIPELINE_TARGET=1 (the separately staged target pass reads a target the reset rewrites)")
+    return n, alpha
+
+
 class Workspace:
     """Activations of one forward pass over ``B`` observations (``n_tau`` quantile samples each for IQN/FQF)."""
 
@@ -340,7 +360,7 @@ class DeviceLearner:
 
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
-                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None):
+                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -378,6 +398,16 @@ class DeviceLearner:
             if aug_rng is None or not hasattr(ops, "augment_shift"):
                 raise ValueError(f"learner.aug_shift={self.aug_shift}: needs the learner's DeviceRng (aug_rng) and a backend with augment_shift")
             self.aug_stage = ops.empty(batch_size * 2 * L.C * L.H * L.W, dtype=torch.uint8)
+        # learner.net_reset_freq = N > 0: apply() ends with one launch more (a0_net_reset) that re-initialises the network after every N-th successful update and returns
+        # at once otherwise.  The fresh values come from Philox stream 8 of the low 32 bits of aug_rng.seed — the learner's DeviceRng, so a loaded snapshot's seed is
+        # followed — unless net_reset_seed names another one (data parallelism: every rank takes rank 0's).  Off (0): no table, no launch.
+        self.net_reset_freq, self.net_reset_shrink = net_reset_value(net_reset_freq, net_reset_shrink)
+        self.net_reset_seed = None
+        self.reset_segs = None
+        if self.net_reset_freq > 0:
+            if aug_rng is None or not hasattr(ops, "net_reset"):
+                raise ValueError(f"learner.net_reset_freq={self.net_reset_freq}: needs the learner's DeviceRng (aug_rng) and a backend with net_reset")
+            self.reset_segs = L.reset_segments()
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -456,6 +486,24 @@ class DeviceLearner:
             self.ops.target_blend(tg.flat, self.online.flat, L.n_params_padded, self.target_tau, self.state, self.target_update_freq, force, tg.encoder_weights(), L.C, tg.wt)
         else:
             self.ops.target_blend(tg.flat, self.online.flat, L.n_params_padded, self.target_tau, self.state, self.target_update_freq, force)
+
+    def reset_seed(self) -> int:
+        """The 32-bit seed of learner.net_reset_freq's fresh values: ``net_reset_seed`` when one was set (rank 0's, under data parallelism), else the low 32 bits of
+        the learner's DeviceRng seed as it stands now."""
+        return int(self.net_reset_seed if self.net_reset_seed is not None else self.aug_rng.seed) & 0xFFFFFFFF
+
+    def _reset_net(self, force=False, k_host=0):
+        """learner.net_reset_freq: the update's last launch, behind the Adam form and the blend; it resets when this update was not NaN-skipped and left the step count
+        a positive multiple of the period (or ``force``, as reset number ``k_host``) and returns at once otherwise."""
+        if self.net_reset_freq <= 0:
+            return
+        L, on, tg = self.L, self.online, self.target
+        if on.fused:
+            self.ops.net_reset(on.flat, tg.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.reset_segs, self.net_reset_shrink, self.reset_seed(), self.state,
+                               self.net_reset_freq, force, k_host, on.encoder_weights(), L.C, on.wt, tg.wt)
+        else:
+            self.ops.net_reset(on.flat, tg.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.reset_segs, self.net_reset_shrink, self.reset_seed(), self.state,
+                               self.net_reset_freq, force, k_host)
 
     def _grad(self, name: str) -> torch.Tensor:
         L = self.L
@@ -589,7 +637,7 @@ class DeviceLearner:
 
     def apply(self):
         """Adam on the flat buffer (NaN-skip and step counter on the device), refresh of the fused kernels' weight copies, target sync — with learner.target_tau on, the
-        blend of the target (``_blend_target``) behind whichever Adam form ran."""
+        blend of the target (``_blend_target``) behind whichever Adam form ran, and with learner.net_reset_freq on the reset launch (``_reset_net``) behind that."""
         L, ops, on, tg = self.L, self.ops, self.online, self.target
         if L.algo == "fqf":           # unconditional, like the reference's fqf_optimizer.step() in front of the NaN guard (agent.py:139-148)
             blk = L.blocks["frac"]
@@ -601,6 +649,7 @@ class DeviceLearner:
             ops.update_tail(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, 0.9, 0.999, self.adam_eps, tg.flat, L.n_params_padded, plan,
                             on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring)
             self._blend_target()
+            self._reset_net()
             return
         tail = self.grads[L.n_params_padded: L.n_params_padded + 1] if self._bucketed_hook() else None
         if self.clip_grad_norm > 0:
@@ -615,6 +664,7 @@ class DeviceLearner:
                 ops.adam_step_sync_clip(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
                                         hard_freq, tg.flat, L.n_params_padded, tail, self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
             self._blend_target()
+            self._reset_net()
             return
         if on.fused:
             # two launches: Adam with its bookkeeping and the target copy folded in; the online conv copies, mirrored to the target's on a sync
@@ -624,6 +674,7 @@ class DeviceLearner:
             ops.adam_step_sync(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
                                hard_freq, tg.flat, L.n_params_padded, tail)
         self._blend_target()
+        self._reset_net()
 
     def _encode_passes(self, frames, slot, sample_stride, passes):
         """passes: [(net, ws, chan_off, keep)] — the encoder forward passes of one update over the same batch.  They are independent of one another (the reference
@@ -747,6 +798,8 @@ class DeviceLearner:
         nxt = self.obs_bytes
         if tstage is not None and not self.target_stage_supported:
             raise ValueError("tstage: this learner's target pass cannot run as a separate stage")
+        if self.net_reset_freq > 0 and tstage is not None:
+            raise ValueError("tstage: not together with learner.net_reset_freq (the separately staged target pass has read a target the reset rewrites)")
         if self.aug_shift > 0:
             if tstage is not None:
                 raise ValueError("tstage: not together with learner.aug_shift (the separately staged target pass has read the unshifted ring)")

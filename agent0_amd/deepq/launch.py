@@ -19,6 +19,21 @@ import sys
 from .dist import env_world, init_process_group, make_grad_hook
 
 
+def broadcast_reset_seed(seed: int, world: int) -> int:
+    """Rank 0's 32-bit reset seed on every rank (a CPU tensor: works over gloo and nccl groups alike)."""
+    seed = int(seed) & 0xFFFFFFFF
+    if world <= 1:
+        return seed
+    import torch
+    import torch.distributed as dist
+
+    box = torch.tensor([seed], dtype=torch.int64)
+    if dist.get_backend() == "nccl":
+        box = box.cuda()
+    dist.broadcast(box, src=0)
+    return int(box.item()) & 0xFFFFFFFF
+
+
 class TrainerNode:
     """One data-parallel replica: reference TrainerNode + its ActorNodes collapsed onto one GPU."""
 
@@ -36,6 +51,17 @@ class TrainerNode:
             dist.broadcast(eng.online.flat, src=0)
             eng.online.refresh_wt()
             eng.sync_target(force=True)
+        self.share_reset_seed(world)
+        self.trainer.on_snapshot_loaded = lambda: self.share_reset_seed(world)
+
+    def share_reset_seed(self, world: int):
+        """learner.net_reset_freq: every rank has its own seed (above), and the replicas must draw the same fresh values — so all of them take rank 0's reset seed,
+        here and again after a ``load_snapshot`` (which brings each rank's own seed back).  One broadcast, no collective per update."""
+        eng = self.trainer.learner.engine
+        if getattr(eng, "net_reset_freq", 0) <= 0:
+            return
+        eng.net_reset_seed = None                      # this rank's own seed as it stands now (a loaded snapshot's, after a load) ...
+        eng.net_reset_seed = broadcast_reset_seed(eng.reset_seed(), world)      # ... replaced by rank 0's; the library's handles are created later and take it from here
 
     def run(self):
         self.trainer.run()

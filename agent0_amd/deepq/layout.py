@@ -125,6 +125,65 @@ class NetLayout:
         return cls(spec.algo, spec.action_dim, spec.dueling, spec.noisy, getattr(spec, "num_atoms", 51), tuple(spec.obs_shape),
                    getattr(spec, "num_cosines", 64), getattr(spec, "F", 32))
 
+    # ------------------------------------------------------------------ learner.net_reset_freq: the rule table of a reset
+    RESET_CONST, RESET_NORMAL, RESET_UNIFORM = 0, 1, 2      # A0_NET_RESET_* (include/agent0_hip.h)
+
+    def reset_segments(self) -> List[Tuple[int, int, int, float, int]]:
+        """(offset, count, kind, scale, keep) rules that tile [0, n_adam): what a network reset (a0_net_reset) draws for every element.  A fresh weight has the
+        constructor's per-element scale (model.py): an orthogonal matrix of gain g has element RMS exactly g / sqrt(max(rows, cols)), so those blocks are normal with
+        that std; a NoisyLinear's mu is uniform in +-1 / sqrt(in), its sigma the constant 0.4 / sqrt(in) (weights) and 0.4 / sqrt(out) (bias); biases of plain layers
+        and padded head rows are zero.  keep = 1 marks the encoder, whose values survive with the share learner.net_reset_shrink.  The fqf fraction net lies behind
+        n_adam and has no entry.  Scales are float64 here and rounded to fp32 once, by the launch; csrc/learner.hip builds the same table for a handle."""
+        import math
+        segs: List[Tuple[int, int, int, float, int]] = []
+        CONST, NORMAL, UNIFORM = self.RESET_CONST, self.RESET_NORMAL, self.RESET_UNIFORM
+
+        def add(off, cnt, kind, scale, keep):
+            if cnt > 0:
+                segs.append((int(off), int(cnt), kind, float(scale), keep))
+
+        def orth(gain, rows, cols):
+            return gain / math.sqrt(float(max(rows, cols)))
+
+        B, g_relu = self.blocks, math.sqrt(2.0)
+        for name in ("conv1", "conv2", "conv3"):
+            b = B[name]
+            add(b.offset, b.N * b.K, NORMAL, orth(g_relu, b.N, b.K), 1)
+            add(b.offset + b.N * b.K, b.N, CONST, 0.0, 1)
+        real = self.Nq + self.V
+        pad = self.Npad - real
+        if self.noisy:
+            bf, bh = 1.0 / math.sqrt(float(self.feat)), 1.0 / math.sqrt(512.0)
+            mu, sg = B["fc1.mu"], B["fc1.sigma"]
+            add(mu.offset, 512 * self.feat, UNIFORM, bf, 0)
+            add(mu.offset + 512 * self.feat, 512, UNIFORM, bf, 0)
+            add(sg.offset, 512 * self.feat, CONST, 0.4 * bf, 0)
+            add(sg.offset + 512 * self.feat, 512, CONST, 0.4 / math.sqrt(512.0), 0)
+            mu, sg = B["head.mu"], B["head.sigma"]
+            wb = self.Npad * 512
+            add(mu.offset, real * 512, UNIFORM, bh, 0)
+            add(mu.offset + real * 512, pad * 512, CONST, 0.0, 0)
+            add(mu.offset + wb, real, UNIFORM, bh, 0)
+            add(mu.offset + wb + real, pad, CONST, 0.0, 0)
+            add(sg.offset, real * 512, CONST, 0.4 * bh, 0)
+            add(sg.offset + real * 512, pad * 512, CONST, 0.0, 0)
+            add(sg.offset + wb, self.Nq, CONST, 0.4 / math.sqrt(float(self.Nq)), 0)
+            add(sg.offset + wb + self.Nq, self.V, CONST, 0.4 / math.sqrt(float(self.V)) if self.V > 0 else 0.0, 0)
+            add(sg.offset + wb + real, pad, CONST, 0.0, 0)
+        else:
+            f, h = B["fc1"], B["head"]
+            add(f.offset, 512 * self.feat, NORMAL, orth(g_relu, 512, self.feat), 0)
+            add(f.offset + 512 * self.feat, 512, CONST, 0.0, 0)
+            add(h.offset, self.Nq * 512, NORMAL, orth(0.01, self.Nq, 512), 0)
+            add(h.offset + self.Nq * 512, self.V * 512, NORMAL, orth(1.0, self.V, 512), 0)
+            add(h.offset + real * 512, pad * 512, CONST, 0.0, 0)
+            add(h.offset + self.Npad * 512, self.Npad, CONST, 0.0, 0)
+        if self.quantile:
+            c = B["cos"]
+            add(c.offset, self.feat * self.num_cosines, NORMAL, orth(g_relu, self.feat, self.num_cosines), 0)
+            add(c.offset + self.feat * self.num_cosines, self.feat, CONST, 0.0, 0)
+        return segs
+
     # ------------------------------------------------------------------ permutations
     def _feat_cols_to_hwc(self, w: torch.Tensor) -> torch.Tensor:
         """[..., 64*H3*W3] with (c,h,w) columns -> (h,w,c) columns."""

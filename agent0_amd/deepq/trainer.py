@@ -310,6 +310,9 @@ class Trainer:
         self._updates_done = None
         self._resume = {"actor": st.get("actor"), "replay": st["replay"], "learner_rng": st["learner_rng"], "pending": pending}
         torch.cuda.synchronize()
+        hook = getattr(self, "on_snapshot_loaded", None)      # launch.TrainerNode: the ranks agree on rank 0's reset seed again (learner.net_reset_freq)
+        if hook is not None:
+            hook()
         return path
 
     # ------------------------------------------------------------------ trainer.py:74-119
@@ -498,10 +501,15 @@ class Trainer:
         return L
 
     def _result(self):
-        """The result dict of trainer.py:111-118; with learner.clip_grad_norm on also ``grad_norm``, the mean pre-clip gradient norm over the last block's updates."""
-        if getattr(self.learner.engine, "gnorm_ring", None) is not None:
-            return dict(self._result_base(), grad_norm=np.mean(self.GNs) if len(self.GNs) > 0 else None)
-        return self._result_base()
+        """The result dict of trainer.py:111-118; with learner.clip_grad_norm on also ``grad_norm``, the mean pre-clip gradient norm over the last block's updates; with
+        learner.net_reset_freq on also ``net_resets`` = update_steps // N."""
+        eng = self.learner.engine
+        out = self._result_base()
+        if getattr(eng, "gnorm_ring", None) is not None:
+            out["grad_norm"] = np.mean(self.GNs) if len(self.GNs) > 0 else None
+        if getattr(eng, "net_reset_freq", 0) > 0:      # learner.net_reset_freq: the resets so far, from the device's step count (one small read per logged iteration)
+            out["net_resets"] = int(eng.state[1]) // eng.net_reset_freq
+        return out
 
     def _result_base(self):
         return dict(
@@ -560,7 +568,9 @@ class Trainer:
                 self.writer.add_scalar(k, v, self.frame_count)
             if self._wandb is not None:
                 self._wandb.log({k: v, "frame": self.frame_count})
-            if k in ["frames", "loss", "qmax", "fps", "grad_norm"] or "return" in k:
+            if k == "net_resets":
+                msg += f"{k}: {v} | "
+            elif k in ["frames", "loss", "qmax", "fps", "grad_norm"] or "return" in k:
                 msg += f"{k}: {v:.2f} | "
         self.logger.info(msg)
 
@@ -575,6 +585,7 @@ class Trainer:
             with open(path, "a", newline="") as f:
                 w = csv.writer(f)
                 cols = PROGRESS_COLUMNS + (("grad_norm",) if "grad_norm" in result else ())      # only with learner.clip_grad_norm on
+                cols = cols + (("net_resets",) if "net_resets" in result else ())               # only with learner.net_reset_freq on
                 if new:
                     w.writerow(cols)
                 w.writerow(["" if result.get(k) is None else result[k] for k in cols])

@@ -107,6 +107,21 @@ class NativeLearner:
         """learner.target_tau through the handle (a0_learner_set_target_tau): before the first update; <= 0 is off, >= 1 is refused."""
         check(self.lib.a0_learner_set_target_tau(self.h, float(tau)), "a0_learner_set_target_tau")
 
+    def set_net_reset(self, freq, shrink, seed):
+        """learner.net_reset_freq / learner.net_reset_shrink through the handle (a0_learner_set_net_reset): before the first update; freq 0 is off; the low 32 bits of
+        ``seed`` position the fresh values."""
+        check(self.lib.a0_learner_set_net_reset(self.h, int(freq), float(shrink), int(seed) & 0xFFFFFFFFFFFFFFFF), "a0_learner_set_net_reset")
+
+    def net_reset_segs(self):
+        """The handle's reset rule table as (offset, count, kind, scale, keep) tuples (a0_learner_net_reset_segs)."""
+        tab = (_abi.NetResetSeg * self.NET_RESET_MAX_SEGS)()
+        n = self.lib.a0_learner_net_reset_segs(self.h, C.addressof(tab), self.NET_RESET_MAX_SEGS)
+        if n < 0:
+            check(n, "a0_learner_net_reset_segs")
+        return [(int(s.offset), int(s.count), int(s.kind), float(s.scale), int(s.keep)) for s in tab[:n]]
+
+    NET_RESET_MAX_SEGS = 32
+
     def set_aug_shift(self, pad):
         """learner.aug_shift through the handle (a0_learner_set_aug_shift): between updates; 0 is off, the kernel's range checks apply to anything else."""
         check(self.lib.a0_learner_set_aug_shift(self.h, int(pad)), "a0_learner_set_aug_shift")
@@ -573,6 +588,25 @@ class HipOps:
                                        None if ew is None else C.addressof(ew), int(C_),
                                        _req(wt_target, torch.float32, self.conv_wt_floats(C_) if wt_target is not None else 0, "wt_target", optional=True), _stream()),
               "a0_target_blend")
+
+    NET_RESET_MAX_SEGS = 32      # A0_NET_RESET_MAX_SEGS (include/agent0_hip.h)
+    NET_RESET_CONST, NET_RESET_NORMAL, NET_RESET_UNIFORM = 0, 1, 2
+
+    def net_reset(self, params, target, exp_avg, exp_avg_sq, n_adam, n_total, segs, alpha, seed, state, freq, force=False, k_host=0, w=None, C_=0, wt=None, wt_target=None):
+        """learner.net_reset_freq: one launch that decides for itself (a0_net_reset) — when ``force`` (reset number ``k_host``), or when ``state[3] == 0`` and
+        ``state[1]`` is a positive multiple of ``freq``: fresh or shrunk parameters by the rule table ``segs`` [(offset, count, kind, scale, keep)], zero moments,
+        ``state[7] = state[1]``, ``target[:n_total] = params[:n_total]`` and, with ``wt`` / ``wt_target`` and the online encoder weights ``w``, both weight copies."""
+        if len(segs) > self.NET_RESET_MAX_SEGS:
+            raise A0Error(f"net_reset: {len(segs)} segments, at most {self.NET_RESET_MAX_SEGS}")
+        tab = (_abi.NetResetSeg * max(1, len(segs)))()
+        for i, (off, cnt, kind, scale, keep) in enumerate(segs):
+            tab[i] = _abi.NetResetSeg(int(off), int(cnt), int(kind), float(scale), int(keep))
+        ew = None if wt is None else self._enc_w(w)
+        nw = self.conv_wt_floats(C_) if wt is not None else 0
+        check(self.lib.a0_net_reset(_req(params, torch.float32, n_total, "params"), _req(target, torch.float32, n_total, "target"), _req(exp_avg, torch.float32, n_adam, "exp_avg"),
+                                    _req(exp_avg_sq, torch.float32, n_adam, "exp_avg_sq"), n_adam, n_total, C.addressof(tab), len(segs), float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    _req(state, torch.int32, 8, "state", optional=bool(force)), int(freq), int(bool(force)), int(k_host), None if ew is None else C.addressof(ew), int(C_),
+                                    _req(wt, torch.float32, nw, "wt", optional=True), _req(wt_target, torch.float32, nw, "wt_target", optional=wt is None), _stream()), "a0_net_reset")
 
     def noisy_compose(self, mu, sigma, eff, N, K, r0, r1, noise_in, noise_out_w, noise_out_b):
         check(self.lib.a0_noisy_compose(_req(mu, torch.float32, N * K + N, "mu"), _req(sigma, torch.float32, N * K + N, "sigma"), _req(eff, torch.float32, N * K + N, "eff"),

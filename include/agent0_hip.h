@@ -360,7 +360,9 @@ int a0_fqf_fraction_loss(const float* q, const float* qh, const float* taus, con
 
 /* ---------------------------------------------------------------- optimizer / target sync (agent.py:102-106,152-161,333-338) */
 /* state: int[8] device block: [0] nan flag (set by losses) [1] update_steps [2] skipped [3] skip_now [4] sync_now [5] scratch of a0_adam_step_sync_wt
- * [6] calls of a0_adam_step_sync_wt with a loss ring (free-running: the ring slot of the next call is state[6] % ring_cap) */
+ * [6] calls of a0_adam_step_sync_wt with a loss ring (free-running: the ring slot of the next call is state[6] % ring_cap)
+ * [7] update_steps at the last network reset (written by a0_net_reset alone; 0 in every run without learner.net_reset_freq).  Every Adam form derives its bias
+ *     corrections from t = max(1, update_steps - state[7]): with the word at 0 that is the update count, as it always was. */
 int a0_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state,
                  float* scalars2, double lr, double beta1, double beta2, double eps, int target_update_freq, void* stream);
 /* a0_adam_step with the target copy of agent.py:160-161 folded into the same pass: when update_steps % target_update_freq == 0 after this
@@ -414,6 +416,34 @@ int a0_update_tail(float* params, float* grads, float* exp_avg, float* exp_avg_s
  * a0_net_conv_wt_refresh would build from the blended target; when the launch does not blend it is not touched.  No scratch, no atomics. */
 int a0_target_blend(float* target, const float* online, long long n_total, double tau, const int* state, int target_update_freq, int force,
                     const a0_encoder_weights* w_target, int C, float* wt_target, void* stream);
+/* Periodic shrink-and-perturb network resets (learner.net_reset_freq / learner.net_reset_shrink; Nikishin et al. 2022, D'Oro et al. 2023, Schwarzer et al. 2023).
+ * ONE launch, which decides for itself: it resets when force != 0 (reset number k = k_host >= 0), or when state[3] == 0 (the update was not NaN-skipped), freq > 0,
+ * state[1] > 0 and state[1] % freq == 0 (k = state[1] / freq); otherwise every workgroup returns after reading those two words (state may be NULL with force).
+ * Issue it behind an update's Adam form — any of those above — and behind a0_target_blend where that is used.  A reset:
+ *  - walks the rule table `segs` (n_segs <= A0_NET_RESET_MAX_SEGS, ascending, disjoint, inside [0, n_adam); passed to the kernel by value).  Element i of a segment
+ *    gets the fresh value phi: kind CONST: `scale`; NORMAL: what a0_rng_normal(seed32, 8, k * n_total + i, scale, ..) writes for that position; UNIFORM:
+ *    scale * (2 u - 1), u what a0_rng_uniform(seed32, 8, k * n_total + i, ..) writes (2 u - 1 is exact, one rounded multiply).  seed32 = seed & 0xFFFFFFFF.  A draw is a
+ *    function of (seed32, k, i) alone: nothing advances, nothing new belongs in a snapshot.
+ *  - keep == 0: params[i] <- phi.  keep == 1: the segment keeps the share alpha (0 <= alpha <= 1, rounded to fp32 once): alpha == 1 leaves the element unread and
+ *    unwritten and draws nothing, alpha == 0 is params[i] <- phi, anything else params[i] <- fmaf(alpha32, fl32(params[i] - phi), phi) (a0_target_blend's arithmetic).
+ *    Elements of [0, n_total) outside every segment (the fqf fraction net behind n_adam) are left alone.
+ *  - exp_avg and exp_avg_sq <- 0 over [0, n_adam); state[7] <- state[1], so that Adam's bias corrections restart at t = 1 with the next update (state != NULL).
+ *  - target[i] <- params[i] over [0, n_total), the hard copy of construction time; with wt / wt_target (both or neither; 16-byte aligned, a0_net_conv_wt_floats(C)
+ *    floats) and w, the ONLINE network's convolution weights inside params[0, n_total), the lane that holds a convolution weight files it in both copies: afterwards
+ *    each holds the bytes a0_net_conv_wt_refresh builds from the new parameters.
+ * All four buffers 16-byte aligned: 16 bytes per lane where four elements lie inside one segment, element by element at a boundary and in the tail of n_total % 4
+ * floats; 4-byte aligned buffers: element by element.  No scratch, no LDS, no atomics. */
+#define A0_NET_RESET_MAX_SEGS 32
+enum { A0_NET_RESET_CONST = 0, A0_NET_RESET_NORMAL = 1, A0_NET_RESET_UNIFORM = 2 };
+typedef struct a0_net_reset_seg {
+    long long offset, count; /* [offset, offset + count) of the flat parameter buffer */
+    int kind;                /* A0_NET_RESET_CONST / _NORMAL / _UNIFORM */
+    float scale;             /* the constant, the standard deviation, the bound */
+    int keep;                /* 1: the segment keeps the share alpha of its values (the encoder); 0: it is replaced */
+} a0_net_reset_seg;
+int a0_net_reset(float* params, float* target, float* exp_avg, float* exp_avg_sq, long long n_adam, long long n_total, const a0_net_reset_seg* segs, int n_segs,
+                 double alpha, unsigned long long seed, int* state, int freq, int force, long long k_host, const a0_encoder_weights* w, int C, float* wt,
+                 float* wt_target, void* stream);
 /* ---------------------------------------------------------------- a whole learner behind one handle (opaque handles, library-owned HBM)
  * BaseLearner (agent.py:97-169) with DQNLearner.train_step (173-190) for scalar heads on 4 x 84 x 84 observations — BASELINE configs[1]: online + target parameters
  * in the packed layout (agent0_amd/deepq/layout.py: conv1 | conv2 | conv3 | fc1 | head, each [W (N x K) | b (N)], head rows padded to a multiple of 32), gradients,
@@ -489,6 +519,13 @@ int a0_learner_set_grad_clip(a0_learner* learner, double max_norm, float* norm_r
  * update issues what it always did.  tau >= 1: A0_EINVAL.  Accepted before the handle's first update only (A0_EINVAL afterwards); descriptor structs are unchanged.
  * The forced copies of a0_learner_create* and a0_learner_set_params stay hard copies. */
 int a0_learner_set_target_tau(a0_learner* learner, double tau);
+/* learner.net_reset_freq / learner.net_reset_shrink through the handle: with freq > 0 every a0_learner_update issues a0_net_reset (the handle's buffers, the rule
+ * table built from its own block descriptors — the one agent0_amd/deepq/layout.py::NetLayout.reset_segments builds — alpha = shrink, the low 32 bits of `seed`) as
+ * its last launch.  freq == 0: off, the update issues what it always did.  freq < 0, or shrink outside [0, 1] (NaN included): A0_EINVAL.  Accepted before the
+ * handle's first update only (A0_EINVAL afterwards); descriptor structs are unchanged.  a0_learner_net_reset_segs copies the table out and returns
+ * the number of entries; a `cap` smaller than that is A0_EINVAL (A0_NET_RESET_MAX_SEGS entries always fit). */
+int a0_learner_set_net_reset(a0_learner* learner, int freq, double shrink, unsigned long long seed);
+int a0_learner_net_reset_segs(const a0_learner* learner, a0_net_reset_seg* out, int cap);
 /* learner.aug_shift through the handle: with pad > 0 every a0_learner_update first issues a0_augment_shift (the caller's frames / slot / row_bytes, the handle's seed
  * and state words, so u = state[6]) into a stage buffer of B * 2 * C * H * W bytes that the handle allocates on the first such call, and then runs every pass — the
  * target and double-Q passes on st_next, the online pass and mdqn's target pass on st, conv1's weight gradient — on that buffer with a NULL slot; the caller's ring is
