@@ -809,21 +809,20 @@ extern "C" int a0_learner_update(a0_learner* L, const uint8_t* frames, const int
         A0_CHECK(a0_rmsprop_step(on + L->frac.off, L->grads + L->frac.off, L->rms_sq, L->frac.size(), L->d.lr / 2e4, 0.95, 1e-5, L->d.max_grad_norm > 0.0 ? L->d.max_grad_norm : -1.0, L->clip, stream));
     // ---- Adam (eps = 1e-2 / B unless given), NaN guard, update counter, target copy every target_update_freq updates, weight-copy refresh (agent.py:102-106,152-161)
     const double eps = L->d.adam_eps > 0.0 ? L->d.adam_eps : 1e-2 / (double)B;
+    const float* dp_flag = dp ? L->grads + L->n_pad : nullptr;
     if (fuse_tail) {
         A0_CHECK(a0_update_tail(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, 0.9, 0.999, eps, tg, L->n_pad, &tail, &w_on, L->C, L->wt_on, L->wt_tg, L->loss, B,
                                 L->loss_ring, L->loss_ring_cap, stream));
-        return blend();
-    }
-    if (L->clip_max_norm > 0.f) {
+    } else if (L->clip_max_norm > 0.f) {
         // learner.clip_grad_norm (DeviceLearner.apply): every gradient Adam owns is final here — summed over the ranks behind the join above — so one launch takes
         // its sum of squares and the Adam launch turns it into the norm, the coefficient and the ring entry
         A0_CHECK(a0_grad_norm_partials(L->grads, L->n_adam, L->gnorm_partials, stream));
-        A0_CHECK(a0_adam_step_sync_wt_clip(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, hard_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
+        A0_CHECK(a0_adam_step_sync_wt_clip(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, hard_freq, tg, L->n_pad, dp_flag, &w_on, L->C,
                                            L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, L->gnorm_partials, L->clip_max_norm, L->gnorm_ring, L->gnorm_ring_cap, stream));
-        return blend();
+    } else {
+        A0_CHECK(a0_adam_step_sync_wt(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, hard_freq, tg, L->n_pad, dp_flag, &w_on, L->C,
+                                      L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, stream));
     }
-    A0_CHECK(a0_adam_step_sync_wt(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, L->d.lr, 0.9, 0.999, eps, hard_freq, tg, L->n_pad, dp ? L->grads + L->n_pad : nullptr, &w_on, L->C,
-                                  L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, stream));
     return blend();
     A0_CATCH
 }

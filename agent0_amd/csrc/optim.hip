@@ -19,38 +19,58 @@
 // scalars (floats): [0] step_size = lr / (1 - b1^t), [1] bc2_sqrt = sqrt(1 - b2^t)
 // extra_flag (optional): a float that is nonzero when ANY data-parallel rank saw a NaN — the sum over ranks of a0_nan_flag_export's
 // output, which travels at the tail of the dense gradient bucket instead of in an all-reduce of its own.
+// The decisions themselves: a0_step_decide / a0_step_publish (update_tail.h).
 __global__ void a0_adam_prep_kernel(int* __restrict__ state, float* __restrict__ scal, double lr, double b1, double b2, int target_freq,
                                     const float* __restrict__ extra_flag) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int skip = (state[0] != 0) || (extra_flag && extra_flag[0] != 0.f);
-    int steps = state[1];
-    if (!skip) steps += 1; else state[2] += 1;
-    const int t = steps - state[7] > 0 ? steps - state[7] : 1;      // state[7]: the count at the last network reset (a0_net_reset), 0 without one
-    scal[0] = (float)(lr / (1.0 - pow(b1, (double)t)));
-    scal[1] = (float)sqrt(1.0 - pow(b2, (double)t));
-    state[1] = steps;
-    state[3] = skip;
-    state[4] = (target_freq > 0 && (steps % target_freq) == 0) ? 1 : 0;   // evaluated even after a skipped step, like the reference
-    state[0] = 0;
+    a0_step_publish(a0_step_decide(state, extra_flag, lr, b1, b2, target_freq), state, scal, true);
+}
+
+// ---- Adam's element.  The library steps a parameter in exactly TWO arithmetic forms, each written out here — fused where __builtin_fmaf says so, rounded products
+// everywhere else — so that no choice of the compiler's contraction can part two kernels that must agree bit for bit (the one-launch tail against the three-launch
+// chain, tests/test_gpu_update_tail.py; a0_adam_step against a0_adam_step_sync, tests/test_gpu_adam_forms.py):
+//   * a0_adam_wide: both moments and the step fused.  Every group of four parameters that moves as 16 bytes: n, n_total multiples of four, every buffer 16-byte aligned.
+//   * a0_adam_scalar: both moments from rounded products plus an add, the step fused.  Everything stepped element by element, and all of a0_adam_step.
+// They differ because that is how the two paths were first compiled, and a buffer's bits must not depend on which kernel steps it; making them one form would
+// change the results of the scalar path.
+struct a0_adam_hyper { float w1, b2, w2, eps; };
+static a0_adam_hyper a0_adam_hyper_of(double beta1, double beta2, double eps) { return a0_adam_hyper{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps}; }
+
+A0_D void a0_adam_wide(float& p, float& m, float& v, float gi, const a0_adam_hyper& H, const a0_step& S) {
+#pragma clang fp contract(off)
+    const float w1 = H.w1, b2 = H.b2, w2 = H.w2;
+    float mi = m, vi = v;
+    mi = __builtin_fmaf(gi - mi, w1, mi);
+    vi = __builtin_fmaf(w2 * gi, gi, vi * b2);
+    const float denom = sqrtf(vi) / S.bc2_sqrt + H.eps;
+    p = __builtin_fmaf(-S.step_size, mi / denom, p);
+    m = mi; v = vi;
+}
+A0_D void a0_adam_scalar(float& p, float& m, float& v, float gi, const a0_adam_hyper& H, const a0_step& S) {
+#pragma clang fp contract(off)
+    const float w1 = H.w1, b2 = H.b2, w2 = H.w2;
+    float mi = m, vi = v;
+    mi = mi + (gi - mi) * w1;
+    vi = vi * b2 + (w2 * gi) * gi;
+    const float denom = sqrtf(vi) / S.bc2_sqrt + H.eps;
+    p = __builtin_fmaf(-S.step_size, mi / denom, p);
+    m = mi; v = vi;
+}
+
+// at most 2048 workgroups of 256 lanes, grid-stride behind that
+static unsigned a0_grid_256(long long items) { const long long b = (items + 255) / 256; return (unsigned)(b > 2048 ? 2048 : b < 1 ? 1 : b); }
+// the 16-byte path of the Adam forms: n, n_total multiples of four and every buffer 16-byte aligned
+static int a0_adam_vec4(const float* params, const float* grads, const float* exp_avg, const float* exp_avg_sq, const float* target, long long n, long long n_total) {
+    return ((n | n_total) % 4 == 0) && ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
 }
 
 __global__ void a0_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                               long long n, const int* __restrict__ state, const float* __restrict__ scal,
-                               float w1, float b2, float w2, float eps) {
-    if (state[3]) return;
-    const float step_size = scal[0], bc2_sqrt = scal[1];
+                               long long n, const int* __restrict__ state, const float* __restrict__ scal, a0_adam_hyper H) {
+    const a0_step S = a0_step_published(state, scal);
+    if (S.skip) return;
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        const float gi = g[i];
-        float mi = m[i], vi = v[i];
-        mi = mi + (gi - mi) * w1;
-        vi = vi * b2 + (w2 * gi) * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - step_size * (mi / denom);
-        m[i] = mi;
-        v[i] = vi;
-    }
+    for (; i < n; i += stride) a0_adam_scalar(p[i], m[i], v[i], g[i], H, S);
 }
 
 extern "C" int a0_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
@@ -58,20 +78,15 @@ extern "C" int a0_adam_step(float* params, const float* grads, float* exp_avg, f
     if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || n < 1) return a0_fail(A0_EINVAL, "a0_adam_step: bad argument");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(a0_adam_prep_kernel, dim3(1), dim3(1), 0, st, state, scalars, lr, beta1, beta2, target_update_freq, (const float*)nullptr);
-    long long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(a0_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, state, scalars,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
+    hipLaunchKernelGGL(a0_adam_kernel, dim3(a0_grid_256(n)), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, state, scalars, a0_adam_hyper_of(beta1, beta2, eps));
     return a0_fail_hip((int)hipGetLastError(), "a0_adam_step");
 }
 
-// Adam with the target copy folded in: when the prep kernel decided "sync now" (update_steps % target_update_freq == 0, agent.py:160-161)
-// every element's NEW value is also written to the target buffer, over [0, n_total) — n_total > n covers blocks Adam does not own (FQF's
-// fraction net).  A skipped (NaN) step leaves the parameters alone but still syncs, like the reference.  == a0_adam_step + a0_target_sync.
-// FOLD: no a0_adam_prep_kernel in front.  Every workgroup derives the step's decisions and scalars itself from state[0] (NaN flag), state[1]
-// (update_steps BEFORE this step) and the data-parallel flag — words nobody writes during this kernel — and workgroup 0 publishes them:
-// state[2..4] as the prep kernel does, the scalars, and the NEW step count in state[5].  state[1] <- state[5] and state[0] <- 0 are
-// committed by the next kernel on the stream (a0_conv_wt_kernel with `commit`), because other workgroups of this one may still have to read them.
+// Adam with the target copy folded in: when the step's decision says "sync now" (update_steps % target_update_freq == 0, agent.py:160-161) every element's NEW
+// value is also written to the target buffer, over [0, n_total) — n_total > n covers blocks Adam does not own (FQF's fraction net).  A skipped (NaN) step leaves the
+// parameters alone but still syncs, like the reference.
+// FOLD: no a0_adam_prep_kernel in front.  Every workgroup derives the step's decisions and scalars itself — from words nobody writes during this kernel — and
+// workgroup 0 publishes them without committing (a0_step_publish).
 struct a0_adam_fold { double lr, b1, b2; int target_freq; const float* extra_flag; int* state_w; float* scal_w; const float* loss; int loss_n; float* loss_ring; int ring_cap; };
 
 // Global gradient-norm clipping (learner.clip_grad_norm; torch.nn.utils.clip_grad_norm_ with its defaults), stage 1: the sum of squares of g[0, n) as
@@ -122,14 +137,26 @@ A0_D float a0_mul_rounded(float a, float b) {
     return r;
 }
 
+// The batch mean of this update's per-sample losses (the Trainer's `loss` statistic, trainer.py:99,111-113) into the ring slot of the free-running call counter
+// state[6], by ONE workgroup of 256 lanes — the same reduction, statement for statement, as a0_mean_rows_kernel, whose launch per update (4.8 us of pure latency)
+// it replaces.  Skipped steps are recorded too (their mean is whatever the loss kernel wrote, NaN included).
+A0_D void a0_loss_mean_to_ring(const float* loss, int loss_n, float* loss_ring, int ring_cap, int* state_w) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int e = threadIdx.x; e < loss_n; e += 256) s += loss[e];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) { const int c = state_w[6]; loss_ring[c % ring_cap] = red[0] / (float)loss_n; state_w[6] = c + 1; }
+}
+
 // stage 2 (CLIP): every workgroup sums the partials in the same order, so all of them step on the same coefficient; workgroup 0 files the norm
 struct a0_adam_clip { const double* partials; float max_norm; float* norm_ring; int ring_cap; };
 template <bool FOLD, bool CLIP>
 __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                     long long n, const int* __restrict__ state, const float* __restrict__ scal,
-                                    float w1, float b2, float w2, float eps, float* __restrict__ target, long long n_total, int vec4, a0_adam_fold F, a0_adam_clip K) {
-    bool skip, sync;
-    float step_size, bc2_sqrt;
+                                    a0_adam_hyper H, float* __restrict__ target, long long n_total, int vec4, a0_adam_fold F, a0_adam_clip K) {
+    a0_step S;
     float coef = 1.f;
     if constexpr (CLIP) {
         // ||g|| = sqrt(sum of the partials), rounded to fp32 once; coef = min(1, max_norm / (||g|| + 1e-6)) in fp32.  The pre-clip norm goes to ring slot
@@ -145,43 +172,23 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
         coef = c < 1.f ? c : 1.f;
     }
     if constexpr (FOLD) {
-        __shared__ float sh_f[2];
-        __shared__ int sh_i[2];
-        // round 4: workgroup 0 also takes the batch mean of this update's per-sample losses (the Trainer's `loss` statistic, trainer.py:99,111-113) into a ring
-        // slot indexed by the free-running call counter state[6] — the same reduction, statement for statement, as a0_mean_rows_kernel, whose launch per update
-        // (4.8 us of pure latency) it replaces; skipped steps are recorded too (their mean is whatever the loss kernel wrote, NaN included)
-        if (blockIdx.x == 0 && F.loss) {
-            __shared__ float red[256];
-            float s = 0.f;
-            for (int e = threadIdx.x; e < F.loss_n; e += 256) s += F.loss[e];
-            red[threadIdx.x] = s;
-            __syncthreads();
-            for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-            if (threadIdx.x == 0) { const int c = F.state_w[6]; F.loss_ring[c % F.ring_cap] = red[0] / (float)F.loss_n; F.state_w[6] = c + 1; }
-        }
+        __shared__ a0_step sh;
+        if (blockIdx.x == 0 && F.loss) a0_loss_mean_to_ring(F.loss, F.loss_n, F.loss_ring, F.ring_cap, F.state_w);
         if (threadIdx.x == 0) {
-            const int sk = (state[0] != 0) || (F.extra_flag && F.extra_flag[0] != 0.f);
-            const int steps = state[1] + (sk ? 0 : 1);
-            const int t = steps - state[7] > 0 ? steps - state[7] : 1;
-            const float ss = (float)(F.lr / (1.0 - pow(F.b1, (double)t))), bc = (float)sqrt(1.0 - pow(F.b2, (double)t));
-            const int sy = (F.target_freq > 0 && (steps % F.target_freq) == 0) ? 1 : 0;
-            sh_f[0] = ss; sh_f[1] = bc; sh_i[0] = sk; sh_i[1] = sy;
-            if (blockIdx.x == 0) {
-                if (sk) F.state_w[2] += 1;
-                F.state_w[3] = sk; F.state_w[4] = sy; F.state_w[5] = steps;
-                F.scal_w[0] = ss; F.scal_w[1] = bc;
-            }
+            sh = a0_step_decide(state, F.extra_flag, F.lr, F.b1, F.b2, F.target_freq);
+            if (blockIdx.x == 0) a0_step_publish(sh, F.state_w, F.scal_w, false);
         }
         __syncthreads();
-        skip = sh_i[0] != 0; sync = sh_i[1] != 0; step_size = sh_f[0]; bc2_sqrt = sh_f[1];
+        S = sh;
     } else {
-        skip = state[3] != 0; sync = state[4] != 0; step_size = scal[0]; bc2_sqrt = scal[1];
+        S = a0_step_published(state, scal);
     }
+    const bool skip = S.skip != 0, sync = S.sync != 0;
     if (skip && !sync) return;
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long stride = (long long)gridDim.x * blockDim.x;
     const long long end = sync ? n_total : n;
-    if (vec4) {                     // n, n_total multiples of four and every buffer 16-byte aligned: 16 bytes per lane, same arithmetic per element
+    if (vec4) {                     // 16 bytes per lane (a0_adam_vec4)
         const long long n4 = n >> 2, end4 = end >> 2;
         for (; i < end4; i += stride) {
             a0_f4 pv = ((a0_f4*)p)[i];
@@ -190,15 +197,7 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
                 a0_f4 mv = ((a0_f4*)m)[i], vv = ((a0_f4*)v)[i];
                 float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float gi = CLIP ? a0_mul_rounded(gp[e], coef) : gp[e];
-                    float mi = mp[e], vi = vp[e];
-                    mi = mi + (gi - mi) * w1;
-                    vi = vi * b2 + (w2 * gi) * gi;
-                    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-                    pp[e] = pp[e] - step_size * (mi / denom);
-                    mp[e] = mi; vp[e] = vi;
-                }
+                for (int e = 0; e < 4; ++e) a0_adam_wide(pp[e], mp[e], vp[e], CLIP ? a0_mul_rounded(gp[e], coef) : gp[e], H, S);
                 ((a0_f4*)p)[i] = pv; ((a0_f4*)m)[i] = mv; ((a0_f4*)v)[i] = vv;
             }
             if (sync) ((a0_f4*)target)[i] = pv;
@@ -208,106 +207,76 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
     for (; i < end; i += stride) {
         float pi = p[i];
         if (i < n && !skip) {
-            const float gi = CLIP ? a0_mul_rounded(g[i], coef) : g[i];
-            float mi = m[i], vi = v[i];
-            mi = mi + (gi - mi) * w1;
-            vi = vi * b2 + (w2 * gi) * gi;
-            const float denom = sqrtf(vi) / bc2_sqrt + eps;
-            pi = pi - step_size * (mi / denom);
+            a0_adam_scalar(pi, m[i], v[i], CLIP ? a0_mul_rounded(g[i], coef) : g[i], H, S);
             p[i] = pi;
-            m[i] = mi;
-            v[i] = vi;
         }
         if (sync) target[i] = pi;
     }
-}
-
-static int a0_adam_sync_plain(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
-                              double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
-                              const float* extra_nan_flag, const a0_adam_clip* clip, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n) return a0_fail(A0_EINVAL, who);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(a0_adam_prep_kernel, dim3(1), dim3(1), 0, st, state, scalars, lr, beta1, beta2, target_update_freq, extra_nan_flag);
-    const int vec4 = ((n | n_total) % 4 == 0) &&
-                     ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
-    long long blocks = ((vec4 ? n_total / 4 : n_total) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    const a0_adam_fold F{0.0, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1};
-    if (clip)
-        hipLaunchKernelGGL((a0_adam_sync_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
-                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, *clip);
-    else
-        hipLaunchKernelGGL((a0_adam_sync_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
-                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, a0_adam_clip{nullptr, 0.f, nullptr, 1});
-    return a0_fail_hip((int)hipGetLastError(), who);
-}
-
-extern "C" int a0_adam_step_sync(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
-                                 double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
-                                 const float* extra_nan_flag, void* stream) {
-    return a0_adam_sync_plain("a0_adam_step_sync: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
-                              extra_nan_flag, nullptr, stream);
 }
 
 static bool a0_clip_args_ok(const double* partials, float max_norm, const float* norm_ring, int norm_ring_cap) {
     return partials && (((uintptr_t)partials) & 7) == 0 && max_norm > 0.f && norm_ring && norm_ring_cap >= 1;
 }
 
-// a0_adam_step_sync on g * min(1, max_norm / (||g|| + 1e-6)), ||g|| from the partials a0_grad_norm_partials left for this gradient buffer
+// The one launcher of the four instantiations.  Plain (wt == nullptr): the one-thread prep kernel in front, == a0_adam_step + a0_target_sync.  Folded (the optimizer
+// tail of a network with fused-kernel weight copies, in TWO launches): Adam with the step's bookkeeping and the loss mean folded in, then the refresh of the online
+// net's weight copies (mirrored into the target's on a sync step), which also commits the step counter; == a0_adam_step_sync + a0_net_conv_wt_refresh_sync.
+// clip (optional): a0_adam_step_sync on g * min(1, max_norm / (||g|| + 1e-6)), ||g|| from the partials a0_grad_norm_partials left for this gradient buffer.
+int a0_conv_wt_refresh_commit(const a0_encoder_weights* w, int C, float* wt, float* wt_target, int* state, hipStream_t st);      // encoder_fused.hip
+struct a0_adam_wt { const a0_encoder_weights* w; int C; float *wt, *wt_target; const float* loss; int loss_n; float* loss_ring; int ring_cap; };
+static int a0_adam_sync_launch(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                               double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                               const float* extra_nan_flag, const a0_adam_wt* wt, const a0_adam_clip* clip, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n || (wt && (!wt->w || !wt->wt || !wt->wt_target || wt->C < 1)))
+        return a0_fail(A0_EINVAL, who);
+    if (wt && wt->loss && (!wt->loss_ring || wt->loss_n < 1 || wt->ring_cap < 1)) return a0_fail(A0_EINVAL, "a0_adam_step_sync_wt: loss statistics need a ring of at least one slot");
+    hipStream_t st = (hipStream_t)stream;
+    a0_adam_fold F{0.0, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 1};
+    if (wt) F = a0_adam_fold{lr, beta1, beta2, target_update_freq, extra_nan_flag, state, scalars, wt->loss, wt->loss_n, wt->loss_ring, wt->ring_cap > 0 ? wt->ring_cap : 1};
+    else hipLaunchKernelGGL(a0_adam_prep_kernel, dim3(1), dim3(1), 0, st, state, scalars, lr, beta1, beta2, target_update_freq, extra_nan_flag);
+    const int vec4 = a0_adam_vec4(params, grads, exp_avg, exp_avg_sq, target, n, n_total);
+    const auto kernel = wt ? (clip ? a0_adam_sync_kernel<true, true> : a0_adam_sync_kernel<true, false>) : (clip ? a0_adam_sync_kernel<false, true> : a0_adam_sync_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(a0_grid_256(vec4 ? n_total / 4 : n_total)), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
+                       a0_adam_hyper_of(beta1, beta2, eps), target, n_total, vec4, F, clip ? *clip : a0_adam_clip{nullptr, 0.f, nullptr, 1});
+    const int e = a0_fail_hip((int)hipGetLastError(), who);
+    return (e != A0_OK || !wt) ? e : a0_conv_wt_refresh_commit(wt->w, wt->C, wt->wt, wt->wt_target, state, st);
+}
+
+extern "C" int a0_adam_step_sync(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
+                                 double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
+                                 const float* extra_nan_flag, void* stream) {
+    return a0_adam_sync_launch("a0_adam_step_sync: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                               extra_nan_flag, nullptr, nullptr, stream);
+}
+
 extern "C" int a0_adam_step_sync_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
                                       double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
                                       const float* extra_nan_flag, const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream) {
     if (!a0_clip_args_ok(partials, max_norm, norm_ring, norm_ring_cap)) return a0_fail(A0_EINVAL, "a0_adam_step_sync_clip: partials, max_norm > 0 and a norm ring of at least one slot");
     const a0_adam_clip clip{partials, max_norm, norm_ring, norm_ring_cap};
-    return a0_adam_sync_plain("a0_adam_step_sync_clip: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
-                              extra_nan_flag, &clip, stream);
-}
-
-// The optimizer tail of a network with fused-kernel weight copies, in TWO launches: Adam with the step's bookkeeping folded in (no one-thread
-// prep kernel in front), then the refresh of the online net's weight copies (mirrored into the target's on a sync step), which also commits
-// the step counter.  Same results as a0_adam_step_sync + a0_net_conv_wt_refresh_sync.
-int a0_conv_wt_refresh_commit(const a0_encoder_weights* w, int C, float* wt, float* wt_target, int* state, hipStream_t st);      // encoder_fused.hip
-static int a0_adam_sync_fold(const char* who, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
-                             double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
-                             const float* extra_nan_flag, const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n,
-                             float* loss_ring, int ring_cap, const a0_adam_clip* clip, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n || !w || !wt || !wt_target || C < 1)
-        return a0_fail(A0_EINVAL, who);
-    if (loss && (!loss_ring || loss_n < 1 || ring_cap < 1)) return a0_fail(A0_EINVAL, "a0_adam_step_sync_wt: loss statistics need a ring of at least one slot");
-    hipStream_t st = (hipStream_t)stream;
-    const int vec4 = ((n | n_total) % 4 == 0) &&
-                     ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
-    long long blocks = ((vec4 ? n_total / 4 : n_total) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    const a0_adam_fold F{lr, beta1, beta2, target_update_freq, extra_nan_flag, state, scalars, loss, loss_n, loss_ring, ring_cap > 0 ? ring_cap : 1};
-    if (clip)
-        hipLaunchKernelGGL((a0_adam_sync_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
-                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, *clip);
-    else
-        hipLaunchKernelGGL((a0_adam_sync_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, (const int*)state, (const float*)scalars,
-                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, target, n_total, vec4, F, a0_adam_clip{nullptr, 0.f, nullptr, 1});
-    int e = a0_fail_hip((int)hipGetLastError(), who);
-    if (e != A0_OK) return e;
-    return a0_conv_wt_refresh_commit(w, C, wt, wt_target, state, st);
+    return a0_adam_sync_launch("a0_adam_step_sync_clip: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                               extra_nan_flag, nullptr, &clip, stream);
 }
 
 extern "C" int a0_adam_step_sync_wt(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
                                     double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
                                     const float* extra_nan_flag, const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n,
                                     float* loss_ring, int ring_cap, void* stream) {
-    return a0_adam_sync_fold("a0_adam_step_sync_wt: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
-                             extra_nan_flag, w, C, wt, wt_target, loss, loss_n, loss_ring, ring_cap, nullptr, stream);
+    const a0_adam_wt fold{w, C, wt, wt_target, loss, loss_n, loss_ring, ring_cap};
+    return a0_adam_sync_launch("a0_adam_step_sync_wt: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                               extra_nan_flag, &fold, nullptr, stream);
 }
 
-// a0_adam_step_sync_wt on the clipped gradient (see a0_adam_step_sync_clip); the norm goes to norm_ring[state[6] % norm_ring_cap], beside the loss mean's slot
+// the norm goes to norm_ring[state[6] % norm_ring_cap], beside the loss mean's slot
 extern "C" int a0_adam_step_sync_wt_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars,
                                          double lr, double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total,
                                          const float* extra_nan_flag, const a0_encoder_weights* w, int C, float* wt, float* wt_target, const float* loss, int loss_n,
                                          float* loss_ring, int ring_cap, const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream) {
     if (!a0_clip_args_ok(partials, max_norm, norm_ring, norm_ring_cap)) return a0_fail(A0_EINVAL, "a0_adam_step_sync_wt_clip: partials, max_norm > 0 and a norm ring of at least one slot");
+    const a0_adam_wt fold{w, C, wt, wt_target, loss, loss_n, loss_ring, ring_cap};
     const a0_adam_clip clip{partials, max_norm, norm_ring, norm_ring_cap};
-    return a0_adam_sync_fold("a0_adam_step_sync_wt_clip: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
-                             extra_nan_flag, w, C, wt, wt_target, loss, loss_n, loss_ring, ring_cap, &clip, stream);
+    return a0_adam_sync_launch("a0_adam_step_sync_wt_clip: bad argument", params, grads, exp_avg, exp_avg_sq, n, state, scalars, lr, beta1, beta2, eps, target_update_freq, target, n_total,
+                               extra_nan_flag, &fold, &clip, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ the update tail in one launch
@@ -318,36 +287,51 @@ extern "C" int a0_adam_step_sync_wt_clip(float* params, const float* grads, floa
 //   * between segments: a0_adam_sync_kernel's body, 1024 parameters per workgroup on the 16-byte path, 256 on the scalar path.
 // The step's decisions were derived one launch earlier (a0_tail_prep_run): state[3], state[4] and the scalars are only read here, so there is nothing to commit and
 // no workgroup waits for another.  The lane that holds a new convolution weight also files it in the fused kernels' copies (the inverse of a0_conv_wt_kernel's gather).
+
+// Where a new convolution weight goes in the fused kernels' copies `wt` (online) / `wt_t` (target): the one description the tail, the blend and the reset share.
+struct a0_wt_sink {
+    long long o1, o2, o3;                       // first weight of conv1 / conv2 / conv3 in the flat buffer
+    int K1, wt4;                                // wt4: o1, o2, o3 multiples of four (four consecutive k of one row per 16-byte lane)
+    float *wt, *wt_t;
+};
+// w: the convolution weights inside base[0, n_total) (`what`: the buffer's name in who's error text); wt may be NULL for a caller that files the target side only
+static int a0_wt_sink_make(a0_wt_sink* S, const char* who, const char* what, const float* base, long long n_total, const a0_encoder_weights* w, int C, float* wt, float* wt_target) {
+    const std::string name(who);
+    if (!w || !w->w1 || !w->w2 || !w->w3 || C < 1 || !wt_target) return a0_fail(A0_EINVAL, (name + ": weight copies need the encoder weights, C >= 1 and the copies' buffers").c_str());
+    if ((((uintptr_t)wt) | ((uintptr_t)wt_target)) & 15) return a0_fail(A0_EINVAL, (name + ": the weight copies must be 16-byte aligned").c_str());
+    *S = a0_wt_sink{w->w1 - base, w->w2 - base, w->w3 - base, C * 64, 0, wt, wt_target};
+    if (S->o1 < 0 || S->o1 + 32LL * S->K1 > n_total || S->o2 < 0 || S->o2 + 64 * 512 > n_total || S->o3 < 0 || S->o3 + 64 * 576 > n_total)
+        return a0_fail(A0_EINVAL, (name + ": the convolution weights must lie inside " + what + "[0, n_total)").c_str());
+    S->wt4 = ((S->o1 | S->o2 | S->o3) % 4 == 0) ? 1 : 0;
+    return A0_OK;
+}
+
 struct a0_tail_region { long long lo, hi; int first_block, seg, vec, pad_; };      // [lo, hi) of the flat buffer; seg < 0: not a slab segment
 struct a0_tail_args {
     float *p, *g, *m, *v, *target;
     long long n, n_total;
     const int* state; const float* scal;
-    float w1, b2, w2, eps;
-    int vec4;                                   // a0_adam_sync_kernel's: n, n_total multiples of four and every buffer 16-byte aligned
+    a0_adam_hyper H;
+    int vec4;                                   // a0_adam_vec4
     a0_reduce_seg seg[8];
     a0_tail_region reg[17];
     int nreg;
     const float* loss; int loss_n; float* loss_ring; int ring_cap; int* state_w;
-    long long o1, o2, o3;                       // first weight of conv1 / conv2 / conv3 in the flat buffer
-    int K1, wt4;                                // wt4: o1, o2, o3 multiples of four (four consecutive k of one row per 16-byte lane)
-    float *wt, *wt_t;
+    a0_wt_sink W;
 };
 
-struct a0_tail_step { bool skip, sync; float step_size, bc2_sqrt; };
-
-A0_D void a0_tail_put16(const a0_tail_args& A, const a0_tail_step& S, long long u16, uint32_t bits) {
-    if (!S.skip) ((uint16_t*)A.wt)[u16] = (uint16_t)bits;
-    if (S.sync) ((uint16_t*)A.wt_t)[u16] = (uint16_t)bits;
+A0_D void a0_tail_put16(const a0_wt_sink& A, bool to_online, bool to_target, long long u16, uint32_t bits) {
+    if (to_online) ((uint16_t*)A.wt)[u16] = (uint16_t)bits;
+    if (to_target) ((uint16_t*)A.wt_t)[u16] = (uint16_t)bits;
 }
-A0_D void a0_tail_put32(const a0_tail_args& A, const a0_tail_step& S, int dw, uint32_t bits) {
-    if (!S.skip) ((uint32_t*)A.wt)[dw] = bits;
-    if (S.sync) ((uint32_t*)A.wt_t)[dw] = bits;
+A0_D void a0_tail_put32(const a0_wt_sink& A, bool to_online, bool to_target, int dw, uint32_t bits) {
+    if (to_online) ((uint32_t*)A.wt)[dw] = bits;
+    if (to_target) ((uint32_t*)A.wt_t)[dw] = bits;
 }
 // dword of term s of weight (n, k) in an a0_wring1 / a0_wring9 segment of N columns: uint4 ((t*N + n)*4 + q)*3 + s holds k = 32t + 8q .. +7; a dword is two consecutive k
 A0_D int a0_tail_term_dword(int N, int n, int k, int s) { return ((((k >> 5) * N + n) * 4 + ((k >> 3) & 3)) * 3 + s) * 4 + ((k >> 1) & 3); }
 // the data-gradient copies of one weight: conv3's flipped taps, conv2's stride phases (see a0_conv_wt_kernel)
-A0_D void a0_tail_wt_dgrad(const a0_tail_args& A, const a0_tail_step& S, const a0_wt_layout& T, bool c3, int co, int k, float w) {
+A0_D void a0_tail_wt_dgrad(const a0_wt_sink& A, bool to_online, bool to_target, const a0_wt_layout& T, bool c3, int co, int k, float w) {
     int base, N, n, kk;
     if (c3) {              // k = (kh*3 + kw)*64 + ci  ->  n = ci, k' = ((2-kh)*3 + (2-kw))*64 + co
         const int cell = k >> 6;
@@ -357,28 +341,28 @@ A0_D void a0_tail_wt_dgrad(const a0_tail_args& A, const a0_tail_step& S, const a
         n = k & 31; kk = ((1 - (kh >> 1)) * 2 + (1 - (kw >> 1))) * 64 + co; base = T.dgrad2x() + ((kh & 1) * 2 + (kw & 1)) * T.n_dgrad2x_phase; N = 32;
     }
 #pragma unroll
-    for (int s = 0; s < 3; ++s) a0_tail_put16(A, S, 2LL * (base + a0_tail_term_dword(N, n, kk, s)) + (kk & 1), a0_bf16_term(w, s));
+    for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * (base + a0_tail_term_dword(N, n, kk, s)) + (kk & 1), a0_bf16_term(w, s));
 }
 // every copy of the weight at flat index idx (new value w): nothing to do outside the three convolution weight blocks
-A0_D void a0_tail_wt1(const a0_tail_args& A, const a0_tail_step& S, long long idx, float w) {
+A0_D void a0_tail_wt1(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, float w) {
     const a0_wt_layout T{A.K1 / 64};
     if (idx >= A.o1 && idx < A.o1 + 32LL * A.K1) {
         const int e = (int)(idx - A.o1), n = e / A.K1, k = e - n * A.K1;
         const float x = w / 255.0f;             // conv1 multiplies raw bytes: the reference's /255 is folded in here
 #pragma unroll
-        for (int s = 0; s < 3; ++s) a0_tail_put16(A, S, 2LL * (T.conv1x() + a0_tail_term_dword(32, n, k, s)) + (k & 1), a0_bf16_term(x, s));
+        for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * (T.conv1x() + a0_tail_term_dword(32, n, k, s)) + (k & 1), a0_bf16_term(x, s));
     } else if ((idx >= A.o2 && idx < A.o2 + 64 * 512) || (idx >= A.o3 && idx < A.o3 + 64 * 576)) {
         const bool c3 = idx >= A.o3 && idx < A.o3 + 64 * 576;
         const int K = c3 ? 576 : 512, e = (int)(idx - (c3 ? A.o3 : A.o2)), n = e / K, k = e - n * K;
         // fp32, a0_wring layout: float ((c*64 + n)*4 + q)*4 + j holds W[n][k = 16c + 4j + q]
-        a0_tail_put32(A, S, (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4 + (k & 3)) * 4 + ((k >> 2) & 3), __float_as_uint(w));
+        a0_tail_put32(A, to_online, to_target, (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4 + (k & 3)) * 4 + ((k >> 2) & 3), __float_as_uint(w));
 #pragma unroll
-        for (int s = 0; s < 3; ++s) a0_tail_put16(A, S, 2LL * ((c3 ? T.conv3x() : T.conv2x()) + a0_tail_term_dword(64, n, k, s)) + (k & 1), a0_bf16_term(w, s));
-        a0_tail_wt_dgrad(A, S, T, c3, n, k, w);
+        for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * ((c3 ? T.conv3x() : T.conv2x()) + a0_tail_term_dword(64, n, k, s)) + (k & 1), a0_bf16_term(w, s));
+        a0_tail_wt_dgrad(A, to_online, to_target, T, c3, n, k, w);
     }
 }
 // four consecutive weights idx .. idx + 3 of one row (idx a multiple of four floats behind its block's start): the terms of four k are 8 adjacent bytes
-A0_D void a0_tail_wt4(const a0_tail_args& A, const a0_tail_step& S, long long idx, const a0_f4& pv) {
+A0_D void a0_tail_wt4(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, const a0_f4& pv) {
     const a0_wt_layout T{A.K1 / 64};
     const float w[4] = {pv.x, pv.y, pv.z, pv.w};
     int base, N, n, k;
@@ -394,24 +378,29 @@ A0_D void a0_tail_wt4(const a0_tail_args& A, const a0_tail_step& S, long long id
     for (int s = 0; s < 3; ++s) {
         const uint2 t{a0_bf16_term(x[0], s) | (a0_bf16_term(x[1], s) << 16), a0_bf16_term(x[2], s) | (a0_bf16_term(x[3], s) << 16)};
         const int dw = base + a0_tail_term_dword(N, n, k, s);          // k a multiple of four: an even dword
-        if (!S.skip) *(uint2*)((uint32_t*)A.wt + dw) = t;
-        if (S.sync) *(uint2*)((uint32_t*)A.wt_t + dw) = t;
+        if (to_online) *(uint2*)((uint32_t*)A.wt + dw) = t;
+        if (to_target) *(uint2*)((uint32_t*)A.wt_t + dw) = t;
     }
     if (c1) return;
     const int ring = (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4) * 4 + ((k >> 2) & 3);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        a0_tail_put32(A, S, ring + 4 * e, __float_as_uint(w[e]));
-        a0_tail_wt_dgrad(A, S, T, c3, n, k + e, w[e]);
+        a0_tail_put32(A, to_online, to_target, ring + 4 * e, __float_as_uint(w[e]));
+        a0_tail_wt_dgrad(A, to_online, to_target, T, c3, n, k + e, w[e]);
     }
 }
 
-// a0_adam_sync_kernel's element, 16-byte form: float4 i of the flat buffer; HAVE_G: the gradient is the sum this lane has just formed
+// four consecutive weights held by one lane
+A0_D void a0_tail_wt_f4(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, const a0_f4& pv) {
+    if (A.wt4) a0_tail_wt4(A, to_online, to_target, idx, pv);
+    else { a0_tail_wt1(A, to_online, to_target, idx, pv.x); a0_tail_wt1(A, to_online, to_target, idx + 1, pv.y); a0_tail_wt1(A, to_online, to_target, idx + 2, pv.z); a0_tail_wt1(A, to_online, to_target, idx + 3, pv.w); }
+}
+
+// a0_adam_sync_kernel's body for float4 i of the flat buffer; HAVE_G: the gradient is the sum this lane has just formed
 template <bool HAVE_G>
-A0_D void a0_tail_adam4(const a0_tail_args& A, const a0_tail_step& S, long long i, a0_f4 gsum) {
+A0_D void a0_tail_adam4(const a0_tail_args& A, const a0_step& S, long long i, a0_f4 gsum) {
     const long long n4 = A.n >> 2, end4 = (S.sync ? A.n_total : A.n) >> 2;
     if ((S.skip && !S.sync) || i >= end4) return;
-    const float w1 = A.w1, b2 = A.b2, w2 = A.w2, eps = A.eps, step_size = S.step_size, bc2_sqrt = S.bc2_sqrt;
     a0_f4 pv = ((a0_f4*)A.p)[i];
     if (i < n4 && !S.skip) {
         a0_f4 gv;
@@ -419,62 +408,32 @@ A0_D void a0_tail_adam4(const a0_tail_args& A, const a0_tail_step& S, long long 
         a0_f4 mv = ((a0_f4*)A.m)[i], vv = ((a0_f4*)A.v)[i];
         float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            // a0_adam_sync_kernel's 16-byte path as it is compiled (v_pk_fma): written out, so that no choice of the compiler's contraction can part the two kernels
-#pragma clang fp contract(off)
-            const float gi = gp[e];
-            float mi = mp[e], vi = vp[e];
-            mi = __builtin_fmaf(gi - mi, w1, mi);
-            vi = __builtin_fmaf(w2 * gi, gi, vi * b2);
-            const float denom = sqrtf(vi) / bc2_sqrt + eps;
-            pp[e] = __builtin_fmaf(-step_size, mi / denom, pp[e]);
-            mp[e] = mi; vp[e] = vi;
-        }
+        for (int e = 0; e < 4; ++e) a0_adam_wide(pp[e], mp[e], vp[e], gp[e], A.H, S);
         ((a0_f4*)A.p)[i] = pv; ((a0_f4*)A.m)[i] = mv; ((a0_f4*)A.v)[i] = vv;
     }
     if (S.sync) ((a0_f4*)A.target)[i] = pv;
-    if (A.wt4) a0_tail_wt4(A, S, 4 * i, pv);
-    else { a0_tail_wt1(A, S, 4 * i, pv.x); a0_tail_wt1(A, S, 4 * i + 1, pv.y); a0_tail_wt1(A, S, 4 * i + 2, pv.z); a0_tail_wt1(A, S, 4 * i + 3, pv.w); }
+    a0_tail_wt_f4(A.W, !S.skip, S.sync, 4 * i, pv);
 }
-// ... and its scalar form
+// ... and for one float
 template <bool HAVE_G>
-A0_D void a0_tail_adam1(const a0_tail_args& A, const a0_tail_step& S, long long i, float gsum) {
+A0_D void a0_tail_adam1(const a0_tail_args& A, const a0_step& S, long long i, float gsum) {
     const long long end = S.sync ? A.n_total : A.n;
     if ((S.skip && !S.sync) || i >= end) return;
-    const float w1 = A.w1, b2 = A.b2, w2 = A.w2, eps = A.eps, step_size = S.step_size, bc2_sqrt = S.bc2_sqrt;
     float pi = A.p[i];
     if (i < A.n && !S.skip) {
-        // a0_adam_sync_kernel's scalar path as it is compiled: both moments from rounded products (v_mul / v_pk_mul, then v_add), the step as one v_fma
-#pragma clang fp contract(off)
-        const float gi = HAVE_G ? gsum : A.g[i];
-        float mi = A.m[i], vi = A.v[i];
-        mi = mi + (gi - mi) * w1;
-        vi = vi * b2 + (w2 * gi) * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        pi = __builtin_fmaf(-step_size, mi / denom, pi);
+        a0_adam_scalar(pi, A.m[i], A.v[i], HAVE_G ? gsum : A.g[i], A.H, S);
         A.p[i] = pi;
-        A.m[i] = mi;
-        A.v[i] = vi;
     }
     if (S.sync) A.target[i] = pi;
-    a0_tail_wt1(A, S, i, pi);
+    a0_tail_wt1(A.W, !S.skip, S.sync, i, pi);
 }
 // a sum leaves as a plain register value, as a loaded gradient would arrive
 A0_D float a0_tail_settle(float r) { asm volatile("" : "+v"(r)); return r; }
 
 __global__ __launch_bounds__(256) void a0_update_tail_kernel(a0_tail_args A) {
     __shared__ a0_f4 red4[8][33];
-    // workgroup 0: the batch mean of this update's per-sample losses into its ring slot, statement for statement as in a0_adam_sync_kernel<true, ...>
-    if (blockIdx.x == 0 && A.loss) {
-        __shared__ float red[256];
-        float s = 0.f;
-        for (int e = threadIdx.x; e < A.loss_n; e += 256) s += A.loss[e];
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-        if (threadIdx.x == 0) { const int c = A.state_w[6]; A.loss_ring[c % A.ring_cap] = red[0] / (float)A.loss_n; A.state_w[6] = c + 1; }
-    }
-    const a0_tail_step S{A.state[3] != 0, A.state[4] != 0, A.scal[0], A.scal[1]};
+    if (blockIdx.x == 0 && A.loss) a0_loss_mean_to_ring(A.loss, A.loss_n, A.loss_ring, A.ring_cap, A.state_w);
+    const a0_step S = a0_step_published(A.state, A.scal);
     int ri = 0;
     for (int k = 1; k < A.nreg; ++k) ri += ((int)blockIdx.x >= A.reg[k].first_block) ? 1 : 0;
     const a0_tail_region R = A.reg[ri];
@@ -511,8 +470,8 @@ __global__ __launch_bounds__(256) void a0_update_tail_kernel(a0_tail_args A) {
         return;
     }
     // scalar path: 32 flat indices per workgroup from R.lo on — the segment's first float, rounded down to a multiple of four where Adam takes its 16-byte form, so
-    // that every aligned group of four parameters is stepped by ONE lane with that form's arithmetic, as a0_adam_sync_kernel would step it (the forms differ in how the
-    // compiler pairs and contracts them); which lane forms an output's sum does not change the sum
+    // that every aligned group of four parameters is stepped by ONE lane with a0_adam_wide, as a0_adam_sync_kernel would step it; which lane forms an
+    // output's sum does not change the sum
     float* red = (float*)red4;                                 // [8][33] floats
     const long long F = R.lo + blk * 32 + c, i = F - (G.out - A.g);
     const bool in = i >= 0 && i < G.count;
@@ -536,20 +495,15 @@ __global__ __launch_bounds__(256) void a0_update_tail_kernel(a0_tail_args A) {
 extern "C" int a0_update_tail(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, const float* scalars, double beta1, double beta2,
                               double eps, float* target, long long n_total, const a0_update_tail_plan* plan, const a0_encoder_weights* w, int C, float* wt, float* wt_target,
                               const float* loss, int loss_n, float* loss_ring, int ring_cap, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n || !plan || plan->n < 0 || plan->n > 8 || !w || !w->w1 ||
-        !w->w2 || !w->w3 || !wt || !wt_target || C < 1)
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scalars || !target || n < 1 || n_total < n || !plan || plan->n < 0 || plan->n > 8 || !wt)
         return a0_fail(A0_EINVAL, "a0_update_tail: bad argument");
     if (loss && (!loss_ring || loss_n < 1 || ring_cap < 1)) return a0_fail(A0_EINVAL, "a0_update_tail: loss statistics need a ring of at least one slot");
     a0_tail_args A;
     A.p = params; A.g = grads; A.m = exp_avg; A.v = exp_avg_sq; A.target = target; A.n = n; A.n_total = n_total;
-    A.state = state; A.scal = scalars; A.w1 = (float)(1.0 - beta1); A.b2 = (float)beta2; A.w2 = (float)(1.0 - beta2); A.eps = (float)eps;
-    A.vec4 = ((n | n_total) % 4 == 0) && ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
+    A.state = state; A.scal = scalars; A.H = a0_adam_hyper_of(beta1, beta2, eps);
+    A.vec4 = a0_adam_vec4(params, grads, exp_avg, exp_avg_sq, target, n, n_total);
     A.loss = loss; A.loss_n = loss_n; A.loss_ring = loss_ring; A.ring_cap = ring_cap > 0 ? ring_cap : 1; A.state_w = state;
-    A.K1 = C * 64; A.wt = wt; A.wt_t = wt_target;
-    A.o1 = w->w1 - params; A.o2 = w->w2 - params; A.o3 = w->w3 - params;
-    if (A.o1 < 0 || A.o1 + 32LL * A.K1 > n_total || A.o2 < 0 || A.o2 + 64 * 512 > n_total || A.o3 < 0 || A.o3 + 64 * 576 > n_total)
-        return a0_fail(A0_EINVAL, "a0_update_tail: the convolution weights must lie inside params");
-    A.wt4 = ((A.o1 | A.o2 | A.o3) % 4 == 0) ? 1 : 0;
+    if (int e = a0_wt_sink_make(&A.W, "a0_update_tail", "params", params, n_total, w, C, wt, wt_target)) return e;
     // the segments in the order of their place in the flat buffer, the ranges between them, and each region's share of the grid
     int order[8];
     for (int k = 0; k < plan->n; ++k) {
@@ -683,16 +637,12 @@ A0_D float a0_blend1(float t, float p, float tau) {
     return __builtin_fmaf(tau, d, t);
 }
 
-// W: the target's fused-kernel weight copies follow.  The lane that holds a blended convolution weight files it through the update tail's helpers, with a step that
-// writes the target side only (skip: the online copies are not touched; sync: the target's are) — a0_wt_layout stays the only description of the copy layout.
-struct a0_blend_wt { long long o1, o2, o3; int K1, wt4; float* wt_t; };
+// W: the target's fused-kernel weight copies follow.  The lane that holds a blended convolution weight files it through the update tail's helpers, on the target
+// side only — a0_wt_layout stays the only description of the copy layout.
 template <bool W>
 __global__ __launch_bounds__(256) void a0_target_blend_kernel(float* __restrict__ target, const float* __restrict__ online, long long n_total, float tau,
-                                                              const int* __restrict__ state, int freq, int force, int vec4, a0_blend_wt B) {
+                                                              const int* __restrict__ state, int freq, int force, int vec4, a0_wt_sink B) {
     if (!force && !(freq > 0 && state[1] % freq == 0)) return;
-    a0_tail_args A;
-    const a0_tail_step S{true, true, 0.f, 0.f};
-    if constexpr (W) { A.o1 = B.o1; A.o2 = B.o2; A.o3 = B.o3; A.K1 = B.K1; A.wt4 = B.wt4; A.wt = nullptr; A.wt_t = B.wt_t; }
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long stride = (long long)gridDim.x * blockDim.x;
     long long done = 0;
@@ -703,17 +653,14 @@ __global__ __launch_bounds__(256) void a0_target_blend_kernel(float* __restrict_
             const a0_f4 pv = ((const a0_f4*)online)[j];
             tv.x = a0_blend1(tv.x, pv.x, tau); tv.y = a0_blend1(tv.y, pv.y, tau); tv.z = a0_blend1(tv.z, pv.z, tau); tv.w = a0_blend1(tv.w, pv.w, tau);
             ((a0_f4*)target)[j] = tv;
-            if constexpr (W) {
-                if (A.wt4) a0_tail_wt4(A, S, 4 * j, tv);
-                else { a0_tail_wt1(A, S, 4 * j, tv.x); a0_tail_wt1(A, S, 4 * j + 1, tv.y); a0_tail_wt1(A, S, 4 * j + 2, tv.z); a0_tail_wt1(A, S, 4 * j + 3, tv.w); }
-            }
+            if constexpr (W) a0_tail_wt_f4(B, false, true, 4 * j, tv);
         }
         done = n4 << 2;
     }
     for (long long j = done + i; j < n_total; j += stride) {
         const float t = a0_blend1(target[j], online[j], tau);
         target[j] = t;
-        if constexpr (W) a0_tail_wt1(A, S, j, t);
+        if constexpr (W) a0_tail_wt1(B, false, true, j, t);
     }
 }
 
@@ -723,23 +670,12 @@ extern "C" int a0_target_blend(float* target, const float* online, long long n_t
         return a0_fail(A0_EINVAL, "a0_target_blend: bad argument");
     const float tau32 = (float)tau;       // rounded to fp32 once
     if (!(tau > 0.0) || !(tau < 1.0) || !(tau32 > 0.f) || !(tau32 < 1.f)) return a0_fail(A0_EINVAL, "a0_target_blend: tau must lie in (0, 1); tau >= 1 is the hard copy (a0_target_sync)");
-    a0_blend_wt B{0, 0, 0, 0, 0, nullptr};
-    if (wt_target) {
-        if (!w_target || !w_target->w1 || !w_target->w2 || !w_target->w3 || C < 1) return a0_fail(A0_EINVAL, "a0_target_blend: weight copies need the target's encoder weights and C >= 1");
-        if (((uintptr_t)wt_target) & 15) return a0_fail(A0_EINVAL, "a0_target_blend: wt_target must be 16-byte aligned");
-        B.K1 = C * 64; B.wt_t = wt_target;
-        B.o1 = w_target->w1 - target; B.o2 = w_target->w2 - target; B.o3 = w_target->w3 - target;
-        if (B.o1 < 0 || B.o1 + 32LL * B.K1 > n_total || B.o2 < 0 || B.o2 + 64 * 512 > n_total || B.o3 < 0 || B.o3 + 64 * 576 > n_total)
-            return a0_fail(A0_EINVAL, "a0_target_blend: the convolution weights must lie inside target[0, n_total)");
-        B.wt4 = ((B.o1 | B.o2 | B.o3) % 4 == 0) ? 1 : 0;
-    }
-    const int vec4 = ((((uintptr_t)target) | ((uintptr_t)online)) % 16 == 0) ? 1 : 0;
-    long long blocks = ((vec4 ? (n_total + 3) / 4 : n_total) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
+    a0_wt_sink B{0, 0, 0, 0, 0, nullptr, nullptr};
     if (wt_target)
-        hipLaunchKernelGGL((a0_target_blend_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, target, online, n_total, tau32, state, target_update_freq, force, vec4, B);
-    else
-        hipLaunchKernelGGL((a0_target_blend_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, target, online, n_total, tau32, state, target_update_freq, force, vec4, B);
+        if (int e = a0_wt_sink_make(&B, "a0_target_blend", "target", target, n_total, w_target, C, nullptr, wt_target)) return e;
+    const int vec4 = ((((uintptr_t)target) | ((uintptr_t)online)) % 16 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(wt_target ? a0_target_blend_kernel<true> : a0_target_blend_kernel<false>, dim3(a0_grid_256(vec4 ? (n_total + 3) / 4 : n_total)), dim3(256), 0, (hipStream_t)stream,
+                       target, online, n_total, tau32, state, target_update_freq, force, vec4, B);
     return a0_fail_hip((int)hipGetLastError(), "a0_target_blend");
 }
 
@@ -751,7 +687,6 @@ extern "C" int a0_target_blend(float* target, const float* online, long long n_t
 // Fresh values: element i at reset k = update_steps / N draws from Philox stream A0_STREAM_RESET of the seed at position k * n_total + i — a function of
 // (seed, k, i) alone; a normal element is a0_rng_normal's value there, a uniform one bound * (2 u - 1) with u a0_rng_uniform's (rng_elem.h).
 struct a0_reset_table { a0_net_reset_seg s[A0_NET_RESET_MAX_SEGS]; int n; };
-struct a0_reset_wt { long long o1, o2, o3; int K1, wt4; float *wt, *wt_t; };
 // the rule of one flat index: kind < 0 outside every segment; keep is the share that survives (alpha32 or 0); end: one past the segment's last index
 struct a0_reset_rule { long long end; int kind; float scale, keep; };
 
@@ -797,18 +732,15 @@ A0_D float a0_reset_mix(const a0_reset_rule& R, float p, float phi) { return R.k
 template <bool W>
 __global__ __launch_bounds__(256) void a0_net_reset_kernel(float* __restrict__ p, float* __restrict__ target, float* __restrict__ m, float* __restrict__ v, long long n_adam,
                                                            long long n_total, a0_reset_table T, float alpha, unsigned long long seed_arg, int* __restrict__ state, int freq,
-                                                           int force, long long k_host, int vec4, a0_reset_wt B) {
+                                                           int force, long long k_host, int vec4, a0_wt_sink B) {
     long long k = k_host;
     if (!force) {
         const int steps = state[1];
         if (state[3] != 0 || !(freq > 0 && steps > 0 && steps % freq == 0)) return;
         k = steps / freq;
     }
-    // a fresh optimizer: the three places that derive Adam's step scalars count t from here (nobody reads state[7] during this launch)
+    // a fresh optimizer: a0_step_decide counts t from here (nobody reads state[7] during this launch)
     if (state && blockIdx.x == 0 && threadIdx.x == 0) state[7] = state[1];
-    a0_tail_args A;
-    const a0_tail_step S{false, true, 0.f, 0.f};       // both networks' copies: the target is the online network after a reset
-    if constexpr (W) { A.o1 = B.o1; A.o2 = B.o2; A.o3 = B.o3; A.K1 = B.K1; A.wt4 = B.wt4; A.wt = B.wt; A.wt_t = B.wt_t; }
     // the seed (32 bits) travels in a vector register: Philox's key schedule of a uniform seed would be hoisted into twenty scalar registers for the whole loop
     uint32_t seed_v = (uint32_t)seed_arg;
     asm volatile("" : "+v"(seed_v));
@@ -819,7 +751,7 @@ __global__ __launch_bounds__(256) void a0_net_reset_kernel(float* __restrict__ p
     // a lane owns four consecutive elements.  `wide`: the buffers are 16-byte aligned, the four share a Philox block and, with weight copies, a row of a convolution
     // matrix; where they also lie inside one segment (or between two) they move as 16 bytes.  Everything else — a segment boundary inside the four (the real / pad
     // boundary of a noisy bias), the tail of n_total % 4 floats, 4-byte-aligned buffers — goes element by element through the same arithmetic.
-    const bool wide = vec4 && (base & 3) == 0 && (!W || A.wt4);
+    const bool wide = vec4 && (base & 3) == 0 && (!W || B.wt4);
     for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < groups; j += stride) {
         const long long e0 = 4 * j;
         const a0_reset_rule R = a0_reset_find(T, alpha, e0, n_total);
@@ -847,7 +779,8 @@ __global__ __launch_bounds__(256) void a0_net_reset_kernel(float* __restrict__ p
             if (idx < n_adam) { m[idx] = 0.f; v[idx] = 0.f; }
         }
     }
-    // the weight copies, in a pass of their own over the convolution blocks: every lane files the parameters it has just written itself (the same lane-to-element map)
+    // the weight copies of BOTH networks (the target is the online network after a reset), in a pass of their own over the convolution blocks: every lane files the
+    // parameters it has just written itself (the same lane-to-element map)
     if constexpr (W) {
         const long long c_lo = (B.o1 < B.o2 ? (B.o1 < B.o3 ? B.o1 : B.o3) : (B.o2 < B.o3 ? B.o2 : B.o3)) >> 2;
         long long c_hi = B.o1 + 32LL * B.K1;
@@ -857,10 +790,10 @@ __global__ __launch_bounds__(256) void a0_net_reset_kernel(float* __restrict__ p
         for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < c_hi && j < groups; j += stride) {      // the first pass's groups, lane for lane
             if (j < c_lo) continue;
             const long long e0 = 4 * j;
-            if (wide && e0 + 4 <= n_total) a0_tail_wt4(A, S, e0, ((const a0_f4*)p)[j]);
+            if (wide && e0 + 4 <= n_total) a0_tail_wt4(B, true, true, e0, ((const a0_f4*)p)[j]);
             else {
 #pragma nounroll
-                for (long long idx = e0; idx < e0 + 4 && idx < n_total; ++idx) a0_tail_wt1(A, S, idx, p[idx]);
+                for (long long idx = e0; idx < e0 + 4 && idx < n_total; ++idx) a0_tail_wt1(B, true, true, idx, p[idx]);
             }
         }
     }
@@ -886,27 +819,16 @@ extern "C" int a0_net_reset(float* params, float* target, float* exp_avg, float*
         at = g.offset + g.count;
         T.s[s] = g;
     }
-    a0_reset_wt B{0, 0, 0, 0, 0, nullptr, nullptr};
+    a0_wt_sink B{0, 0, 0, 0, 0, nullptr, nullptr};
     if (wt || wt_target) {
-        if (!wt || !wt_target || !w || !w->w1 || !w->w2 || !w->w3 || C < 1) return a0_fail(A0_EINVAL, "a0_net_reset: weight copies need wt, wt_target, the online encoder weights and C >= 1");
-        if ((((uintptr_t)wt) | ((uintptr_t)wt_target)) & 15) return a0_fail(A0_EINVAL, "a0_net_reset: wt and wt_target must be 16-byte aligned");
-        B.K1 = C * 64; B.wt = wt; B.wt_t = wt_target;
-        B.o1 = w->w1 - params; B.o2 = w->w2 - params; B.o3 = w->w3 - params;
-        if (B.o1 < 0 || B.o1 + 32LL * B.K1 > n_total || B.o2 < 0 || B.o2 + 64 * 512 > n_total || B.o3 < 0 || B.o3 + 64 * 576 > n_total)
-            return a0_fail(A0_EINVAL, "a0_net_reset: the convolution weights must lie inside params[0, n_total)");
-        B.wt4 = ((B.o1 | B.o2 | B.o3) % 4 == 0) ? 1 : 0;
+        if (!wt) return a0_fail(A0_EINVAL, "a0_net_reset: weight copies need wt and wt_target, both or neither");
+        if (int e = a0_wt_sink_make(&B, "a0_net_reset", "params", params, n_total, w, C, wt, wt_target)) return e;
     }
     const int vec4 = ((((uintptr_t)params) | ((uintptr_t)target) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) % 16 == 0) ? 1 : 0;
-    long long blocks = ((n_total + 3) / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
     const float alpha32 = (float)alpha;       // rounded to fp32 once
     const unsigned long long seed32 = seed & 0xFFFFFFFFull;
-    if (wt)
-        hipLaunchKernelGGL((a0_net_reset_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, target, exp_avg, exp_avg_sq, n_adam, n_total, T, alpha32, seed32,
-                           state, freq, force, k_host, vec4, B);
-    else
-        hipLaunchKernelGGL((a0_net_reset_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, target, exp_avg, exp_avg_sq, n_adam, n_total, T, alpha32, seed32,
-                           state, freq, force, k_host, vec4, B);
+    hipLaunchKernelGGL(wt ? a0_net_reset_kernel<true> : a0_net_reset_kernel<false>, dim3(a0_grid_256((n_total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       params, target, exp_avg, exp_avg_sq, n_adam, n_total, T, alpha32, seed32, state, freq, force, k_host, vec4, B);
     return a0_fail_hip((int)hipGetLastError(), "a0_net_reset");
 }
 

@@ -1,6 +1,6 @@
 // What the one-launch update tail (optim.hip: a0_update_tail_kernel) shares with the kernels it replaces per update: the row-group sums of
 // a0_reduce_segments_kernel (net.hip), the weight-copy layout and the bf16 terms of a0_conv_wt_kernel (encoder_fused.hip), and the one-thread
-// bookkeeping of an optimizer step, which rides in the launch in front of the tail (conv1_wgrad.hip, or a launch of its own).
+// bookkeeping of an optimizer step (a0_step_decide / a0_step_publish), which every Adam form runs and the tail has run in the launch in front of it.
 #pragma once
 #include "a0_defs.h"
 
@@ -59,20 +59,38 @@ A0_HD uint32_t a0_bf16_term(float w, int s) {
     return s == 0 ? hi : s == 1 ? mid : a0_bf16_trunc(r2);
 }
 
-// ---- an optimizer step's bookkeeping, one thread (the arithmetic of a0_adam_prep_kernel and of the folded Adam kernel, optim.hip, and the commit the weight-copy
-// refresh carried): NaN skip, step count, bias corrections, "sync now".  It needs the NaN flag to be final — the loss kernel ran — and nothing else, so it rides
-// in the last launch in front of the tail, whose workgroups then only read state[3], state[4] and the scalars: words nobody writes while they run.
+// ---- an optimizer step's bookkeeping, one thread: NaN skip, step count, bias corrections, "sync now".  a0_step_decide is the only place that derives them; it reads
+// state[0] (NaN flag), state[1] (update_steps BEFORE this step), state[7] (the count at the last network reset, 0 without one) and the optional data-parallel flag.
+struct a0_step { int skip, steps, sync; float step_size, bc2_sqrt; };
+A0_D a0_step a0_step_decide(const int* state, const float* extra_flag, double lr, double b1, double b2, int target_freq) {
+    a0_step S;
+    S.skip = (state[0] != 0) || (extra_flag && extra_flag[0] != 0.f);
+    S.steps = state[1] + (S.skip ? 0 : 1);
+    const int since = S.steps - state[7];
+    const int t = since > 0 ? since : 1;
+    S.step_size = (float)(lr / (1.0 - pow(b1, (double)t)));
+    S.bc2_sqrt = (float)sqrt(1.0 - pow(b2, (double)t));
+    S.sync = (target_freq > 0 && (S.steps % target_freq) == 0) ? 1 : 0;      // evaluated even after a skipped step, like the reference
+    return S;
+}
+// commit: state[1] <- the new count and the NaN flag down.  Without it the new count waits in state[5] for the next kernel on the stream to commit
+// (a0_conv_wt_kernel): the folded Adam kernel publishes while its other workgroups are still reading state[0] and state[1].
+A0_D void a0_step_publish(const a0_step& S, int* state, float* scal, bool commit) {
+    if (S.skip) state[2] += 1;
+    state[3] = S.skip; state[4] = S.sync;
+    scal[0] = S.step_size; scal[1] = S.bc2_sqrt;
+    if (commit) { state[1] = S.steps; state[0] = 0; }
+    else state[5] = S.steps;
+}
+// what a kernel behind a publish steps with: words nobody writes while it runs
+A0_D a0_step a0_step_published(const int* state, const float* scal) { return a0_step{state[3], 0, state[4], scal[0], scal[1]}; }
+
+// The bookkeeping of the one-launch tail needs the NaN flag to be final — the loss kernel ran — and nothing else, so it rides in the last launch in front of the
+// tail (conv1_wgrad.hip, or a launch of its own: net.hip).  It leaves state[5] as the folded form's commit does, so that both tails leave the same status block.
 struct a0_tail_prep { int* state; float* scal; double lr, b1, b2; int target_freq; };
 A0_D void a0_tail_prep_run(const a0_tail_prep& P) {
-    int* const state = P.state;
-    const int sk = state[0] != 0;
-    const int steps = state[1] + (sk ? 0 : 1);
-    const int t = steps - state[7] > 0 ? steps - state[7] : 1;      // state[7]: the count at the last network reset, 0 without one
-    const float ss = (float)(P.lr / (1.0 - pow(P.b1, (double)t))), bc = (float)sqrt(1.0 - pow(P.b2, (double)t));
-    const int sy = (P.target_freq > 0 && (steps % P.target_freq) == 0) ? 1 : 0;
-    if (sk) state[2] += 1;
-    state[3] = sk; state[4] = sy; state[5] = steps;
-    P.scal[0] = ss; P.scal[1] = bc;
-    state[1] = steps; state[0] = 0;
+    const a0_step S = a0_step_decide(P.state, nullptr, P.lr, P.b1, P.b2, P.target_freq);
+    P.state[5] = S.steps;
+    a0_step_publish(S, P.state, P.scal, true);
 }
 #endif

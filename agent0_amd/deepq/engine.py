@@ -643,36 +643,20 @@ class DeviceLearner:
             blk = L.blocks["frac"]
             ops.rmsprop_step(on.flat[blk.all], self.grads[blk.all], self.rms_sq, blk.size, self.lr / 2e4, 0.95, 1e-5, self.max_grad_norm, self.clip)
         plan, self._tail_plan = self._tail_plan, None
-        hard_freq = self._hard_freq()
+        adam = (on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps, self._hard_freq(), tg.flat,
+                L.n_params_padded, self.grads[L.n_params_padded: L.n_params_padded + 1] if self._bucketed_hook() else None)
+        wt = (on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring) if on.fused else ()
         if plan is not None:
             # backward_encoder(fuse_tail=True) left the slab sums and the step's bookkeeping to this launch
-            ops.update_tail(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, 0.9, 0.999, self.adam_eps, tg.flat, L.n_params_padded, plan,
-                            on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring)
-            self._blend_target()
-            self._reset_net()
-            return
-        tail = self.grads[L.n_params_padded: L.n_params_padded + 1] if self._bucketed_hook() else None
-        if self.clip_grad_norm > 0:
+            ops.update_tail(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, 0.9, 0.999, self.adam_eps, tg.flat, L.n_params_padded, plan, *wt)
+        elif self.clip_grad_norm > 0:
             # one launch more: the sum of squares over everything Adam owns (the fqf fraction net lies behind n_adam), taken here — behind the data-parallel
             # exchange — so that every rank derives the same coefficient; the Adam launch finishes the norm, clips and files it (a0_adam_step_sync_clip)
             ops.grad_norm_partials(self.grads, L.n_adam, self.gnorm_partials)
-            if on.fused:
-                ops.adam_step_sync_wt_clip(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                                           hard_freq, tg.flat, L.n_params_padded, tail, on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring,
-                                           self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
-            else:
-                ops.adam_step_sync_clip(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                                        hard_freq, tg.flat, L.n_params_padded, tail, self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
-            self._blend_target()
-            self._reset_net()
-            return
-        if on.fused:
-            # two launches: Adam with its bookkeeping and the target copy folded in; the online conv copies, mirrored to the target's on a sync
-            ops.adam_step_sync_wt(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                                  hard_freq, tg.flat, L.n_params_padded, tail, on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring)
+            (ops.adam_step_sync_wt_clip if on.fused else ops.adam_step_sync_clip)(*adam, *wt, self.gnorm_partials, self.clip_grad_norm, self.gnorm_ring)
         else:
-            ops.adam_step_sync(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps,
-                               hard_freq, tg.flat, L.n_params_padded, tail)
+            # fused: two launches — Adam with its bookkeeping and the target copy folded in; the online conv copies, mirrored to the target's on a sync
+            (ops.adam_step_sync_wt if on.fused else ops.adam_step_sync)(*adam, *wt)
         self._blend_target()
         self._reset_net()
 

@@ -329,13 +329,10 @@ class HipOps:
         """The planned slab sums, Adam, the target copy, the loss mean's ring slot and the fused kernels' weight copies in ONE launch (a0_update_tail): the results of
         ``encoder_wgrad``'s reduction launch followed by ``adam_step_sync_wt``, bit for bit."""
         ew = self._enc_w(w)
-        nw = self.conv_wt_floats(C_)
         check(self.lib.a0_update_tail(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n_total, "grads"), _req(m, torch.float32, n, "m"),
                                       _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
-                                      b1, b2, eps, _req(target, torch.float32, n_total, "target"), n_total, C.addressof(plan), C.addressof(ew), C_,
-                                      _req(wt, torch.float32, nw, "wt"), _req(wt_target, torch.float32, nw, "wt_target"),
-                                      _req(loss, torch.float32, max(loss_n, 1), "loss", optional=True), int(loss_n), _req(loss_ring, torch.float32, 1, "loss_ring", optional=True),
-                                      0 if loss_ring is None else int(loss_ring.numel()), _stream()), "a0_update_tail")
+                                      b1, b2, eps, _req(target, torch.float32, n_total, "target"), n_total, C.addressof(plan),
+                                      *self._fold_args(ew, C_, wt, wt_target, loss, loss_n, loss_ring), _stream()), "a0_update_tail")
 
     # ------------------------------------------------------------------ dense
     def dense_fwd_scratch(self, R, N, K) -> int:
@@ -513,29 +510,38 @@ class HipOps:
                                             _req(dlogits, torch.float32, B * ldl, "dlogits"), _req(logits, torch.float32, B * ldl, "logits"), _stream()), "a0_fqf_fraction_loss")
 
     # ------------------------------------------------------------------ optimizer
+    @staticmethod
+    def _adam_args(params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target=None, n_total=None, extra_nan_flag=None):
+        """The leading arguments every Adam entry point takes; with ``n_total``: also (target, n_total, extra_nan_flag) of the forms that carry the target copy."""
+        a = (_req(params, torch.float32, n if n_total is None else n_total, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
+             _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"), lr, b1, b2, eps, target_freq)
+        if n_total is None:
+            return a
+        return a + (_req(target, torch.float32, n_total, "target"), n_total, _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True))
+
+    def _fold_args(self, ew, C_, wt, wt_target, loss, loss_n, loss_ring):
+        """The weight-copy and loss-ring arguments of the forms that end in the fused kernels' copies (``ew``: the caller keeps the struct alive)."""
+        nw = self.conv_wt_floats(C_)
+        return (C.addressof(ew), C_, _req(wt, torch.float32, nw, "wt"), _req(wt_target, torch.float32, nw, "wt_target"),
+                _req(loss, torch.float32, max(loss_n, 1), "loss", optional=True), int(loss_n), _req(loss_ring, torch.float32, 1, "loss_ring", optional=True),
+                0 if loss_ring is None else int(loss_ring.numel()))
+
+    def _clip_args(self, partials, max_norm, norm_ring):
+        return (_req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), float(max_norm), _req(norm_ring, torch.float32, 1, "norm_ring"), int(norm_ring.numel()))
+
     def adam_step(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq):
-        check(self.lib.a0_adam_step(_req(params, torch.float32, n, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
-                                    _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
-                                    lr, b1, b2, eps, target_freq, _stream()), "a0_adam_step")
+        check(self.lib.a0_adam_step(*self._adam_args(params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq), _stream()), "a0_adam_step")
 
     def adam_step_sync(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag=None):
-        check(self.lib.a0_adam_step_sync(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
-                                         _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
-                                         lr, b1, b2, eps, target_freq, _req(target, torch.float32, n_total, "target"), n_total,
-                                         _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True), _stream()), "a0_adam_step_sync")
+        check(self.lib.a0_adam_step_sync(*self._adam_args(params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag), _stream()),
+              "a0_adam_step_sync")
 
     def adam_step_sync_wt(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag, w, C_, wt, wt_target, loss=None, loss_n=0,
                           loss_ring=None):
         """``loss`` [loss_n] + ``loss_ring``: the Adam launch also writes the batch mean of the per-sample losses to ring slot state[6] % len(ring)."""
         ew = self._enc_w(w)
-        nw = self.conv_wt_floats(C_)
-        check(self.lib.a0_adam_step_sync_wt(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
-                                            _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
-                                            lr, b1, b2, eps, target_freq, _req(target, torch.float32, n_total, "target"), n_total,
-                                            _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True), C.addressof(ew), C_,
-                                            _req(wt, torch.float32, nw, "wt"), _req(wt_target, torch.float32, nw, "wt_target"),
-                                            _req(loss, torch.float32, max(loss_n, 1), "loss", optional=True), int(loss_n), _req(loss_ring, torch.float32, 1, "loss_ring", optional=True),
-                                            0 if loss_ring is None else int(loss_ring.numel()), _stream()), "a0_adam_step_sync_wt")
+        check(self.lib.a0_adam_step_sync_wt(*self._adam_args(params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag),
+                                            *self._fold_args(ew, C_, wt, wt_target, loss, loss_n, loss_ring), _stream()), "a0_adam_step_sync_wt")
 
     GRAD_NORM_PARTIALS = 256      # A0_GRAD_NORM_PARTIALS (include/agent0_hip.h)
 
@@ -546,27 +552,16 @@ class HipOps:
 
     def adam_step_sync_clip(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag, partials, max_norm, norm_ring):
         """``adam_step_sync`` on ``grads * min(1, max_norm / (norm + 1e-6))``, the norm from ``partials``; it is written to norm_ring[state[6] % len(norm_ring)]."""
-        check(self.lib.a0_adam_step_sync_clip(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
-                                              _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
-                                              lr, b1, b2, eps, target_freq, _req(target, torch.float32, n_total, "target"), n_total,
-                                              _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True),
-                                              _req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), float(max_norm), _req(norm_ring, torch.float32, 1, "norm_ring"),
-                                              int(norm_ring.numel()), _stream()), "a0_adam_step_sync_clip")
+        check(self.lib.a0_adam_step_sync_clip(*self._adam_args(params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag),
+                                              *self._clip_args(partials, max_norm, norm_ring), _stream()), "a0_adam_step_sync_clip")
 
     def adam_step_sync_wt_clip(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag, w, C_, wt, wt_target, loss, loss_n,
                                loss_ring, partials, max_norm, norm_ring):
         """``adam_step_sync_wt`` on the clipped gradient (see ``adam_step_sync_clip``); the norm lands in the ring slot of the update's loss mean."""
         ew = self._enc_w(w)
-        nw = self.conv_wt_floats(C_)
-        check(self.lib.a0_adam_step_sync_wt_clip(_req(params, torch.float32, n_total, "params"), _req(grads, torch.float32, n, "grads"), _req(m, torch.float32, n, "m"),
-                                                 _req(v, torch.float32, n, "v"), n, _req(state, torch.int32, 8, "state"), _req(scalars, torch.float32, 2, "scalars"),
-                                                 lr, b1, b2, eps, target_freq, _req(target, torch.float32, n_total, "target"), n_total,
-                                                 _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True), C.addressof(ew), C_,
-                                                 _req(wt, torch.float32, nw, "wt"), _req(wt_target, torch.float32, nw, "wt_target"),
-                                                 _req(loss, torch.float32, max(loss_n, 1), "loss", optional=True), int(loss_n), _req(loss_ring, torch.float32, 1, "loss_ring", optional=True),
-                                                 0 if loss_ring is None else int(loss_ring.numel()),
-                                                 _req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), float(max_norm), _req(norm_ring, torch.float32, 1, "norm_ring"),
-                                                 int(norm_ring.numel()), _stream()), "a0_adam_step_sync_wt_clip")
+        check(self.lib.a0_adam_step_sync_wt_clip(*self._adam_args(params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag),
+                                                 *self._fold_args(ew, C_, wt, wt_target, loss, loss_n, loss_ring), *self._clip_args(partials, max_norm, norm_ring), _stream()),
+              "a0_adam_step_sync_wt_clip")
 
     def nan_flag_export(self, state, out):
         check(self.lib.a0_nan_flag_export(_req(state, torch.int32, 8, "state"), _req(out, torch.float32, 1, "out"), _stream()), "a0_nan_flag_export")

@@ -359,10 +359,14 @@ int a0_fqf_fraction_loss(const float* q, const float* qh, const float* taus, con
                          int ldl, float* loss, float* dlogits, const float* logits, void* stream);
 
 /* ---------------------------------------------------------------- optimizer / target sync (agent.py:102-106,152-161,333-338) */
-/* state: int[8] device block: [0] nan flag (set by losses) [1] update_steps [2] skipped [3] skip_now [4] sync_now [5] scratch of a0_adam_step_sync_wt
+/* state: int[8] device block: [0] nan flag (set by losses) [1] update_steps [2] skipped [3] skip_now [4] sync_now [5] scratch of a0_adam_step_sync_wt (the new
+ * count between its two launches; a0_net_encoder_wgrad_tail leaves the same word)
  * [6] calls of a0_adam_step_sync_wt with a loss ring (free-running: the ring slot of the next call is state[6] % ring_cap)
  * [7] update_steps at the last network reset (written by a0_net_reset alone; 0 in every run without learner.net_reset_freq).  Every Adam form derives its bias
- *     corrections from t = max(1, update_steps - state[7]): with the word at 0 that is the update count, as it always was. */
+ *     corrections from t = max(1, update_steps - state[7]): with the word at 0 that is the update count, as it always was.
+ * Every Adam form below takes the step's decisions — NaN skip, new count, the two bias-correction scalars, "sync now" — from ONE device function
+ * (a0_step_decide, csrc/update_tail.h) and steps a parameter with one of TWO written-out element forms (a0_adam_wide / a0_adam_scalar, csrc/optim.hip): groups of
+ * four that move as 16 bytes take the first, everything stepped element by element — all of a0_adam_step included — the second. */
 int a0_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state,
                  float* scalars2, double lr, double beta1, double beta2, double eps, int target_update_freq, void* stream);
 /* a0_adam_step with the target copy of agent.py:160-161 folded into the same pass: when update_steps % target_update_freq == 0 after this

@@ -538,10 +538,14 @@ def test_freq_zero_is_the_learner_without_the_argument(hip, name, monkeypatch):
         nat.update(*cs.batch(s))
     torch.cuda.synchronize()
     assert not calls, "no launch"
+    # collectable garbage of earlier tests (frames kept alive by caught exceptions hold whole learners) must not be freed in the middle of a measurement
+    import gc
+    gc.collect()
     mem = torch.cuda.memory_allocated()
     more = _engine(cs, net_reset_freq=0, net_reset_shrink=0.5)
     used_off = torch.cuda.memory_allocated() - mem
     del more
+    gc.collect()
     mem = torch.cuda.memory_allocated()
     more = T._engine(cs, FAR)
     assert torch.cuda.memory_allocated() - mem == used_off, "no extra allocation"
