@@ -824,8 +824,12 @@ __global__ __launch_bounds__(64) void a0_c51_loss_kernel(const float* __restrict
     const float p = et / a0_wave_sum(et);
     // Bellman-shifted, clamped support and its fractional bin position
     float tz = rew[b] + (gamma_n * (1.f - done[b])) * (on ? atoms[t] : 0.f);
-    tz = fminf(fmaxf(tz, vmin), vmax);
-    const float bp = (tz - vmin) / delta;
+    tz = tz < vmin ? vmin : tz;                          // comparisons, not fminf / fmaxf: a NaN reward stays NaN and reaches the loss and the flag
+    tz = tz > vmax ? vmax : tz;
+    float bp = (tz - vmin) / delta;
+    bp = bp > (float)(T - 1) ? (float)(T - 1) : bp;      // fl32(delta) may lie below the exact width: vmax itself then lands just above T - 1 and its bin would be T
+    // (a NaN reward: bp is NaN and so are both weights below, which is what carries it to the loss and the flag; the indices then come from the device's
+    // float -> int conversion of NaN, 0, and whatever they were the gather form below only compares them with lane numbers: nothing is addressed by them)
     int lo = (int)floorf(bp), up = (int)ceilf(bp);
     if (up > 0 && lo == up) lo -= 1;
     if (lo < T - 1 && lo == up) up += 1;
@@ -997,8 +1001,10 @@ __global__ __launch_bounds__(256) void a0_c51_head_loss_slabs_kernel(a0_c51hl_ar
     const float et = on ? expf(xt - mxt) : 0.f;
     const float pr = et / a0_wave_sum(et);
     float tz = rew_b + (P.gamma_n * (1.f - done_b)) * atom;
-    tz = fminf(fmaxf(tz, P.vmin), P.vmax);
-    const float bp = (tz - P.vmin) / P.delta;
+    tz = tz < P.vmin ? P.vmin : tz;                      // as in a0_c51_loss_kernel (a NaN reward stays NaN)
+    tz = tz > P.vmax ? P.vmax : tz;
+    float bp = (tz - P.vmin) / P.delta;
+    bp = bp > (float)(T - 1) ? (float)(T - 1) : bp;      // as in a0_c51_loss_kernel (NaN included: the indices are only ever compared, never used as addresses)
     int lo = (int)floorf(bp), up = (int)ceilf(bp);
     if (up > 0 && lo == up) lo -= 1;
     if (lo < T - 1 && lo == up) up += 1;

@@ -203,8 +203,9 @@ class CpuOps:
         p = tgt_logits[: B * A * T].view(B, A, T)[ar, a_star[:B].long()].softmax(-1)
         delta = (vmax - vmin) / (T - 1)
         tz = (rew[:B].view(-1, 1) + (gamma_n * (1 - done[:B].view(-1, 1))) * atoms[:T].view(1, -1)).clamp(vmin, vmax)
-        b = (tz - vmin) / delta
-        lo, up = b.floor().long(), b.ceil().long()
+        b = ((tz - vmin) / delta).clamp(max=T - 1)          # the rounded delta may put vmax just above T - 1 (a0_c51_loss_kernel)
+        bi = torch.nan_to_num(b, nan=0.0)                    # a NaN reward: the kernels' conversion gives index 0, the NaN stays in the weights (and the sample)
+        lo, up = bi.floor().long(), bi.ceil().long()
         lo = torch.where((up > 0) & (lo == up), lo - 1, lo)
         up = torch.where((lo < T - 1) & (lo == up), up + 1, up)
         m = torch.zeros(B, T)

@@ -6,7 +6,8 @@ against the launches it stands for, every output buffer as bit patterns:
     a0_dense_dgrad with the ReLU mask h  ->  dh, on the fp32 fmaf-chain GEMM (a0_gemm_mode 0): dh[k] = fmaf chain over the head's rows in ascending order, which is
     what the fused kernel computes; the split-operand GEMM of the default mode sums six bf16 cross products and agrees to rounding only
 
-at the edges of the kernel's work split: B around its four samples per workgroup, slab counts around its trips of four slabs, one action, the widest head."""
+at the edges of the kernel's work split: B around its four samples per workgroup, slab counts around its trips of four slabs, one action, the widest head
+(A + dueling = 24 both ways: 23 actions with the value stream, 24 without)."""
 import numpy as np
 import pytest
 import torch
@@ -67,7 +68,7 @@ def dgrad_chain(hip, draw, W_on, h, B):
     return dh, dh_x
 
 
-@pytest.mark.parametrize("A,dueling", [(1, False), (1, True), (4, False), (4, True), (18, False), (18, True)])
+@pytest.mark.parametrize("A,dueling", [(1, False), (1, True), (4, False), (4, True), (18, False), (18, True), (23, True), (24, False)])
 def test_dqn_head_loss_from_slabs_is_the_unfused_composition_bit_for_bit(hip, A, dueling):
     worst = 0.0
     for B in BS:
@@ -97,7 +98,7 @@ def test_dqn_head_loss_from_slabs_is_the_unfused_composition_bit_for_bit(hip, A,
     print(f"A={A} dueling={dueling}: dh against the split-operand a0_dense_dgrad differs by at most {worst:.2e} of its scale")
 
 
-@pytest.mark.parametrize("A,dueling", [(1, False), (1, True), (4, False), (4, True), (18, False), (18, True)])
+@pytest.mark.parametrize("A,dueling", [(1, False), (1, True), (4, False), (4, True), (18, False), (18, True), (23, True), (24, False)])
 def test_mdqn_head_loss_from_slabs_is_the_unfused_composition_bit_for_bit(hip, A, dueling):
     """The Munchausen form: the third pass is the TARGET network on the current observation.  h, and the three heads' q values against a0_dqn_head_loss's (the same
     chain); loss and draw against a0_loss_mdqn + a0_dueling_bwd on those q values; dh against a0_dense_dgrad."""
