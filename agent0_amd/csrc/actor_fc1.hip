@@ -16,6 +16,9 @@
 #include "igemm_x9.h"
 #include "a0_internal.h"
 #include "net_impl.h"
+#include "store_policy.h"
+// the eight split-K slabs of a step (store_policy.h): read by the step kernel behind this launch; a lane holds 4 bytes per element
+typedef a0_st_wt a0_fc1_store;       // measured: 0.3 - 0.4 us per launch (profiles/r20_store_policy.md)
 
 constexpr int A0_FC1_RING = 4;      // k tiles (32 k = six fragments per lane) in flight per lane; even: LDS buffer and register slot of a tile follow its ring slot's parity
 
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(256) void a0_actor_fc1_kernel(const float* __restri
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int x = x0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (x < R) out[(long long)x * N] = acc[r];
+        if (x < R) a0_store4<a0_fc1_store>(&out[(long long)x * N], __float_as_uint(acc[r]));
     }
 }
 

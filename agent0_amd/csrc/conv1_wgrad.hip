@@ -17,7 +17,11 @@
 // Every wave owns all 32 output channels x 32 taps (four 16x16 accumulators) for the whole launch; a workgroup adds up its
 // observations in registers and writes one slab [32][256] + bias[32]; the slabs meet in a0_reduce_slabs_kernel (deterministic).
 #include "a0_internal.h"
+#include "store_policy.h"
 #include "update_tail.h"
+// the slabs (store_policy.h), read by the update's tail, 4 bytes per lane and element: written through 0.6 - 2.4 us faster (profiles/r20_store_policy.md).  The frame
+// fetch — rows of the batch the encoder read earlier in the update — measured within the spread with non-temporal loads and is left alone.
+typedef a0_st_wt a0_c1w_store;
 
 #include <cstdint>
 
@@ -179,7 +183,7 @@ __global__ __launch_bounds__(A0W_THREADS) void a0_conv1_wgrad_fused_kernel(a0_c1
         for (int t = 0; t < 2; ++t) {
             const int k = (2 * wave + t) * 16 + r16;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) out[(i * 16 + 4 * q + r) * 256 + k] = acc[i][t][r] / 255.0f;
+            for (int r = 0; r < 4; ++r) a0_store4<a0_c1w_store>(&out[(i * 16 + 4 * q + r) * 256 + k], __float_as_uint(acc[i][t][r] / 255.0f));
         }
     float* red = (float*)smem;
     red[tid] = bsum;

@@ -31,6 +31,9 @@
 // The k-steps of 16 positions cover 80 / 48 of a layer's 81 / 49 positions; the last one runs through one fp32 MFMA (a0q_mma_steps).
 #include "a0_internal.h"
 #include "net_impl.h"
+#include "store_policy.h"
+// the slabs (store_policy.h): read by the update's tail, 4 bytes per lane and element
+typedef a0_st_wt a0_c23w_store;      // measured: 1.0 - 2.3 us per launch (profiles/r20_store_policy.md)
 
 #include <cstdlib>
 
@@ -251,7 +254,7 @@ A0_D void a0q_body(const a0_c23w_args& P, int part, int g, int ngroups, unsigned
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                out[(corow + row) * G::K + kcol[j] + (lane & 31)] = acc[j][r];
+                a0_store4<a0_c23w_store>(&out[(corow + row) * G::K + kcol[j] + (lane & 31)], __float_as_uint(acc[j][r]));
             }
         }
     }

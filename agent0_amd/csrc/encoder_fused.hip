@@ -22,6 +22,7 @@
 #include "a0_internal.h"
 #include "net_tables.h"
 #include "operands.h"
+#include "store_policy.h"
 #include "update_tail.h"
 
 #include <cstdlib>
@@ -729,6 +730,10 @@ A0_D void a0_encoder_fused_x9_body(const a0_fused_args& P, int bid, int nblk) {
 // a0_encoder_fused_x9_body): the same bytes and the same features (tests/test_gpu_trainer.py); a rollout's first step still needs the encoder on its own, and its last
 // step the tail without one.
 #include "actor_tail.h"
+// The step's frame stores (store_policy.h).  The env's replay row, which nobody reads before it is sampled, is written non-temporally: 0.9 us off the step
+// (profiles/r20_store_policy.md).  The env's new stack, which the same env's workgroup reads in the next step, stays plain: with it non-temporal too most of that was
+// lost again.  The pointers are per lane and the scalar file has no room for a buffer resource here, so write-through was not an option.
+typedef a0_st_nt a0_step_row_store;
 // (the encoder's arguments travel as five pointers: the 4 x 84 x 84 geometry is a compile-time constant here, and the two full argument structs together do not fit
 // the scalar registers)
 struct a0_step_enc_args { const float *wt, *b1, *b2, *b3; float* act3; };
@@ -937,7 +942,7 @@ A0_D void a0_actor_step_enc2_body(const typename TAIL::Args& Q, const a0_step_en
         return uint4{w[0], w[1], w[2], w[3]};
     };
     auto put = [&](int c, const uint4 v) {      // channel c of the new observation: global stack, replay row's st_next half, LDS image
-        out16[c * G16] = v; row16[(4 + c) * G16] = v;
+        out16[c * G16] = v; a0_store16<a0_step_row_store>(row16 + (4 + c) * G16, v);
         a0_bytes16_to_img(img, c * G16 + j, v);
     };
     // the frame waves meet each other WITHOUT wave 0 (a workgroup barrier would hold wave 0's latency chain until their staging is done): a counter in LDS
@@ -977,11 +982,11 @@ A0_D void a0_actor_step_enc2_body(const typename TAIL::Args& Q, const a0_step_en
     auto early_stores = [&] {      // everything of the step's frame traffic that does not wait for the action
         if (has_group()) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) row16[c * G16] = keep[c];
+            for (int c = 0; c < 4; ++c) a0_store16<a0_step_row_store>(row16 + c * G16, keep[c]);
             const int nc = !chase ? 4 : (!term ? 3 : 0);
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                if (c < nc) { out16[c * G16] = keep[4 + c]; row16[(4 + c) * G16] = keep[4 + c]; }
+                if (c < nc) { out16[c * G16] = keep[4 + c]; a0_store16<a0_step_row_store>(row16 + (4 + c) * G16, keep[4 + c]); }
         }
     };
     auto mid = [&] {

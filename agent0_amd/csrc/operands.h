@@ -11,6 +11,7 @@
 // All policies are plain C++ so tests/host_emul.cpp can run the same index math on the CPU.
 #pragma once
 #include "a0_defs.h"
+#include "store_policy.h"
 
 enum { A0_KC = 0, A0_XC = 1 };
 
@@ -236,11 +237,14 @@ struct EpiBiasActMul {         // y = act(v + bias[y]) * mul[(x / group)][y]: th
     }
 };
 
+// Cache policy (store_policy.h) of the split-K slabs, which a later kernel sums: a lane holds 4 bytes per element, 32 lanes a 128-byte line.  Written through, fc1's
+// slabs take 1.0 - 2.0 us off their launch (profiles/r20_store_policy.md); fc1's backward launch (EpiMaskMat, EpiWgradSlab) gained nothing repeatable and is left alone.
+typedef a0_st_wt a0_slab_store;
 struct EpiSlab {               // raw partial sums, one slab per z (split-K forward, weight gradients)
     static constexpr bool ROWSUM_A = false;
     struct Params { float* out; long long slab_stride; int ld; };
     A0_HD static void store(const Params& P, int x, int y, float v, int z) {
-        P.out[(long long)z * P.slab_stride + (long long)x * P.ld + y] = v;
+        a0_put_f32<a0_slab_store>(&P.out[(long long)z * P.slab_stride + (long long)x * P.ld + y], v);
     }
 };
 
