@@ -78,6 +78,17 @@ int a0_x9_products_now();      // net.hip: 6 or 9 cross products in the split-op
 struct a0_net_core;
 int a0_conv23_wgrad_fused_launch(const a0_net_core& n, int B, const float* act1, const float* act2, const float* d2, const float* d3, float* slab2, float* slab3,
                                  hipStream_t st);
+// One actor step's tail + synthetic env step in ONE launch, behind the descriptors of actor_step.h (the exported a0_actor_*_env_step* pack them, a0_actor_rollout
+// fills them once per step).  next (optional): the kernel goes on to encode the env's new observation; the *_enc entry points, under whose names the errors then read.
+struct a0_step_draw;
+struct a0_env_commit;
+struct a0_next_enc;
+struct a0_slab_head;
+// net.hip — scalar heads (dqn / mdqn): fc1 over `feat` (w1_planes, optional: a0_actor_fc1_planes of W1), then the tail kernel
+int a0_actor_qhead_env_launch(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling, float* scratch,
+                              const a0_step_draw& draw, const a0_env_commit& env, const a0_next_enc* next, const unsigned int* w1_planes, hipStream_t st);
+// actor_tail.hip — the tails over the head GEMM's slabs (c51 / qr: head.kt = 0, iqn / fqf: head.kt = 1)
+int a0_actor_slab_tail_env_launch(const a0_slab_head& head, int E, const a0_step_draw& draw, const a0_env_commit& env, const a0_next_enc* next, hipStream_t st);
 #endif
 #define A0_TAG_ENCODER_FUSED 12
 #define A0_TAG_ENCODER_DGRAD_FUSED 13

@@ -168,7 +168,7 @@ A0_D void a0_actor_qhead_env_body(const a0_qenv_args& P, float* __restrict__ raw
     }
 }
 
-// ---- the distributional / quantile counterpart (c51, qr; iqn, fqf): a0_actor_dist_tail_env_kernel's body (loss.hip)
+// ---- the distributional / quantile counterpart (c51, qr; iqn, fqf): a0_actor_dist_tail_env_kernel's body (actor_tail.hip)
 A0_D float a0_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -195,7 +195,7 @@ struct a0_dtenv_args {
 };
 // Wave 0's part of the body below: head slab sum, dueling, expectation / quantile mean, first maximum, epsilon-greedy draw, the env's scalar work with the action
 // (and, chase task, the block's new cell into *s_chase_cell_p).  No workgroup barrier inside.  g / slot / x: the step's counter, the replay slot and the env's Philox
-// draw as the body derives them.  ENV = false: the tail alone (a0_actor_quantile_tail_kernel, loss.hip) — the env's fields of P, g, slot, x and s_chase_cell_p are
+// draw as the body derives them.  ENV = false: the tail alone (a0_actor_quantile_tail_kernel, actor_tail.hip) — the env's fields of P, g, slot, x and s_chase_cell_p are
 // not read, and the statements that remain are those of ENV = true.
 template <bool ENV = true>
 A0_D void a0_actor_dist_tail_wave0(const a0_dtenv_args& P, float* __restrict__ xs, int* __restrict__ s_chase_cell_p, uint32_t g, long long slot, const a0_u4& x) {

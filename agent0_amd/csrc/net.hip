@@ -609,6 +609,7 @@ extern "C" int a0_dense_fwd_partial_multi(int n, const float* const* X, int ldx,
 // finishes fc1 (slab sum + bias + ReLU), evaluates the q head (A or A+1 rows of 512), applies the dueling combine, takes the first
 // maximum and makes the epsilon-greedy draw from the actor's Philox streams.  One wave per environment; replaces six launches
 // (reduce, head GEMM, reduce, dueling, select, egreedy) on the actor's critical path.
+#include "actor_step.h"
 #include "actor_tail.h"
 __global__ __launch_bounds__(256) void a0_actor_qhead_kernel(const float* __restrict__ slabs, long long slab_stride, int nslab, const float* __restrict__ b1,
                                                              const float* __restrict__ W2, const float* __restrict__ b2, int A, int dueling, int E,
@@ -698,33 +699,38 @@ extern "C" int a0_actor_qhead(const float* feat, int E, int K, const float* W1, 
                             qmax, stream);
 }
 
+// a0_actor_qhead + a0_env_synth_step_commit: fc1 GEMM over `feat` (this step's features), then ONE launch per env for tail + env step — with `next`, the launch goes on
+// to encode the env's NEW observation (round 5, a0_actor_step_enc2_kernel in encoder_fused.hip) into next->act3_next, which may be `feat` itself: the GEMM has read it
+int a0_actor_qhead_env_launch(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling, float* scratch,
+                              const a0_step_draw& draw, const a0_env_commit& env, const a0_next_enc* next, const unsigned int* w1_planes, hipStream_t st) {
+    A0_TRY
+    if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !draw.action || !draw.qmax || E < 1 || (next ? K != 3136 : (K < 4 || (K & 3))) || A < 1 || A + (dueling ? 1 : 0) > 24)
+        return a0_fail(A0_EINVAL, next ? "a0_actor_qhead_env_step_enc: bad argument (4 x 84 x 84 observations, A + dueling <= 24)"
+                                       : "a0_actor_qhead_env_step: bad argument (A + dueling <= 24: the head rows are staged in 48 KB of LDS)");
+    { const int rc = a0_env_commit_check(env, E, A, next ? "a0_actor_qhead_env_step_enc" : "a0_actor_qhead_env_step"); if (rc != A0_OK) return rc; }
+    a0_hip_backend bk{st};
+    const int splits = a0_fc1_splits(E, 512, K);
+    { const int rc = a0_actor_fc1_slabs(bk, feat, K, W1, w1_planes, E, splits, scratch); if (rc != A0_OK) return rc; }
+    a0_qenv_args P;
+    P.slabs = scratch; P.slab_stride = (long long)E * 512; P.nslab = splits; P.b1 = b1; P.W2 = W2; P.b2 = b2; P.A = A; P.dueling = dueling; P.E = E;
+    a0_step_fill(P, draw, env);
+    if (next) return a0_actor_step_enc_launch(P, next->wt, next->w, next->act3_next, st);
+    hipLaunchKernelGGL(a0_actor_qhead_env_kernel, dim3(E), dim3(512), (size_t)(A + (dueling ? 1 : 0)) * 512 * sizeof(float), st, P);
+    A0_HIP_THROW(hipGetLastError());
+    return A0_OK;
+    A0_CATCH
+}
+
+// (w1_planes: a0_actor_fc1_planes of W1 — fc1 then runs as a0_actor_fc1_kernel where a0_actor_fc1_ok accepts the step; the plain forms pass none)
 extern "C" int a0_actor_qhead_env_step_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                                        float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                                        unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
                                        unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
                                        float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
                                        const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, const unsigned int* w1_planes, void* stream) {
-    A0_TRY
-    if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !action || !qmax || E < 1 || K < 4 || (K & 3) || A < 1 || A + (dueling ? 1 : 0) > 24)
-        return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step: bad argument (A + dueling <= 24: the head rows are staged in 48 KB of LDS)");
-    if (!obs_in || !obs_out || obs_in == obs_out || !ep_ret || !final_mask || !final_ret || !ring_act || !ring_rew || !ring_done || !obs0 || !frames || !r_act ||
-        !r_rew || !r_done || n < 1 || steps < 0 || cap < E || start_slot < 0 || task < A0_ENV_TASK_STREAM || task > A0_ENV_TASK_CHASE || (task == A0_ENV_TASK_CHASE && A < 4))
-        return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step: bad env argument (the chase task needs at least four actions)");
-    if ((((uintptr_t)obs_in) | ((uintptr_t)obs_out) | ((uintptr_t)obs0) | ((uintptr_t)frames)) & 15) return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step: buffers must be 16-byte aligned");
-    a0_hip_backend bk{(hipStream_t)stream};
-    const int splits = a0_fc1_splits(E, 512, K);
-    { const int rc = a0_actor_fc1_slabs(bk, feat, K, W1, w1_planes, E, splits, scratch); if (rc != A0_OK) return rc; }
-    a0_qenv_args P;
-    P.slabs = scratch; P.slab_stride = (long long)E * 512; P.nslab = splits; P.b1 = b1; P.W2 = W2; P.b2 = b2; P.A = A; P.dueling = dueling; P.E = E;
-    P.rng_seed = seed; P.stream_a = stream_a; P.stream_u = stream_u; P.off_a = off_a; P.off_u = off_u; P.eps = eps; P.ctrl = ctrl; P.eps_ptr = eps_ptr;
-    P.action = action; P.qmax = qmax;
-    P.env_seed = env_seed; P.rank = rank; P.g = g; P.obs_in = obs_in; P.obs_out = obs_out; P.ep_ret = ep_ret; P.final_mask = final_mask; P.final_ret = final_ret;
-    P.n = n; P.steps = steps; P.gamma = gamma; P.ring_act = ring_act; P.ring_rew = ring_rew; P.ring_done = ring_done; P.obs0 = obs0; P.frames = frames;
-    P.cap = cap; P.start = start_slot % cap; P.r_act = r_act; P.r_rew = r_rew; P.r_done = r_done; P.task = task;
-    hipLaunchKernelGGL(a0_actor_qhead_env_kernel, dim3(E), dim3(512), (size_t)(A + (dueling ? 1 : 0)) * 512 * sizeof(float), (hipStream_t)stream, P);
-    A0_HIP_THROW(hipGetLastError());
-    return A0_OK;
-    A0_CATCH
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, nullptr, w1_planes, (hipStream_t)stream);
 }
 extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                                        float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
@@ -732,11 +738,11 @@ extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const fl
                                        unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
                                        float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
                                        const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, void* stream) {
-    return a0_actor_qhead_env_step_wp(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task, nullptr, stream);
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, nullptr, nullptr, (hipStream_t)stream);
 }
 
-// a0_actor_qhead_env_step whose tail kernel goes on to encode the env's NEW observation (round 5, a0_actor_step_enc2_kernel in encoder_fused.hip): fc1 GEMM over
-// `feat` (this step's features), then one launch for tail + env step + the NEXT step's features into `act3_next` (which may be `feat` itself: the GEMM has read it).
 extern "C" int a0_actor_qhead_env_step_enc_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                                            float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                                            unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
@@ -744,25 +750,10 @@ extern "C" int a0_actor_qhead_env_step_enc_wp(const float* feat, int E, int K, c
                                            float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
                                            const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
                                            const float* wt, const a0_encoder_weights* w, float* act3_next, const unsigned int* w1_planes, void* stream) {
-    A0_TRY
-    if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !action || !qmax || E < 1 || K != 3136 || A < 1 || A + (dueling ? 1 : 0) > 24)
-        return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: bad argument (4 x 84 x 84 observations, A + dueling <= 24)");
-    if (!obs_in || !obs_out || obs_in == obs_out || !ep_ret || !final_mask || !final_ret || !ring_act || !ring_rew || !ring_done || !obs0 || !frames || !r_act ||
-        !r_rew || !r_done || n < 1 || steps < 0 || cap < E || start_slot < 0 || task < A0_ENV_TASK_STREAM || task > A0_ENV_TASK_CHASE || (task == A0_ENV_TASK_CHASE && A < 4))
-        return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: bad env argument");
-    if ((((uintptr_t)obs_in) | ((uintptr_t)obs_out) | ((uintptr_t)obs0) | ((uintptr_t)frames)) & 15) return a0_fail(A0_EINVAL, "a0_actor_qhead_env_step_enc: buffers must be 16-byte aligned");
-    a0_hip_backend bk{(hipStream_t)stream};
-    const int splits = a0_fc1_splits(E, 512, K);
-    { const int rc = a0_actor_fc1_slabs(bk, feat, K, W1, w1_planes, E, splits, scratch); if (rc != A0_OK) return rc; }
-    a0_qenv_args P;
-    P.slabs = scratch; P.slab_stride = (long long)E * 512; P.nslab = splits; P.b1 = b1; P.W2 = W2; P.b2 = b2; P.A = A; P.dueling = dueling; P.E = E;
-    P.rng_seed = seed; P.stream_a = stream_a; P.stream_u = stream_u; P.off_a = off_a; P.off_u = off_u; P.eps = eps; P.ctrl = ctrl; P.eps_ptr = eps_ptr;
-    P.action = action; P.qmax = qmax;
-    P.env_seed = env_seed; P.rank = rank; P.g = g; P.obs_in = obs_in; P.obs_out = obs_out; P.ep_ret = ep_ret; P.final_mask = final_mask; P.final_ret = final_ret;
-    P.n = n; P.steps = steps; P.gamma = gamma; P.ring_act = ring_act; P.ring_rew = ring_rew; P.ring_done = ring_done; P.obs0 = obs0; P.frames = frames;
-    P.cap = cap; P.start = start_slot % cap; P.r_act = r_act; P.r_rew = r_rew; P.r_done = r_done; P.task = task;
-    return a0_actor_step_enc_launch(P, wt, w, act3_next, (hipStream_t)stream);
-    A0_CATCH
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    const a0_next_enc next{wt, w, act3_next};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, &next, w1_planes, (hipStream_t)stream);
 }
 extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
                                            float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
@@ -771,7 +762,10 @@ extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, cons
                                            float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
                                            const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
                                            const float* wt, const a0_encoder_weights* w, float* act3_next, void* stream) {
-    return a0_actor_qhead_env_step_enc_wp(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task, wt, w, act3_next, nullptr, stream);
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    const a0_next_enc next{wt, w, act3_next};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, &next, nullptr, (hipStream_t)stream);
 }
 
 // out[t] = mean_e x[t][e]: the per-step mean max-Q of a rollout (agent.py:38,88), all T steps in one launch

@@ -10,6 +10,7 @@
 // restate in C++; every device operation is one of the entry points declared above them in include/agent0_hip.h, in the order the Python classes issue
 // them — the rings, parameters and statistics of a run driven through the handles are bit-identical to the Python Trainer's
 // (tests/test_gpu_trainer.py::test_native_handles_run_the_loop_like_the_python_trainer).
+#include "actor_step.h"
 #include "learner_state.h"
 
 #include <chrono>
@@ -633,6 +634,17 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
         feat_ready = false;
         const long long back = (a->steps + 1 < a->n ? a->steps + 1 : a->n) - 1;                 // first observation of the emitted n-step transition
         const uint8_t* obs0 = a->obs[((a->cur - back) % a->K + a->K) % a->K];
+        // what the step's ONE launch for tail + env step carries besides its head (actor_step.h), filled once the branch below has reserved the draw's offsets and counted
+        // the step; and where that launch goes on to encode the env's new observation, so that the next step starts with its features
+        auto draw = [&](unsigned long long oa, unsigned long long ou) {
+            return a0_step_draw{a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E};
+        };
+        auto commit = [&](int nx) {
+            return a0_env_commit{a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps, a->d.discount,
+                                 a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done, a->d.env_task};
+        };
+        const a0_next_enc enc{V.wt, &w, a->act3};
+        const a0_next_enc* const next = step_enc && t + 1 < a->T ? &enc : nullptr;
         if (quant) {
             // Actor._quant_tail_args + act_step_commit(kind = "quantile"): the step's K fractions per env from the actor's Philox stream 3, cosine features, the embedding
             // times the features in the embedding GEMM's epilogue, fc1, the head GEMM's slabs, then ONE launch for slab sum + bias, dueling, the mean over the fractions,
@@ -653,19 +665,9 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
             const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
             const int nx = (a->cur + 1) % a->K;
             a->g += 1;
-            if (step_enc && t + 1 < a->T) {      // (round 6) the tail's workgroups go on to encode their env's new observation: the next step starts with its features
-                A0_CHECK(a0_actor_quantile_tail_env_step_enc(a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, fqf ? a->f_tau_all : nullptr, E, a->rng.seed,
-                                                             STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed,
-                                                             a->d.rank, a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
-                                                             a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act,
-                                                             R->rew, R->done, a->d.env_task, V.wt, &w, a->act3, stream));
-                feat_ready = true;
-            } else
-            A0_CHECK(a0_actor_quantile_tail_env_step(a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, fqf ? a->f_tau_all : nullptr, E, a->rng.seed,
-                                                     STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed,
-                                                     a->d.rank, a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
-                                                     a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act,
-                                                     R->rew, R->done, a->d.env_task, stream));
+            const a0_slab_head head{a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, nullptr, fqf ? a->f_tau_all : nullptr, 1};
+            A0_CHECK(a0_actor_slab_tail_env_launch(head, E, draw(oa, ou), commit(nx), next, (hipStream_t)stream));
+            feat_ready = next != nullptr;
             a->cur = nx;
             a->steps += 1;
             continue;
@@ -681,21 +683,10 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
             const int nx = (a->cur + 1) % a->K;
             a->g += 1;
             if (4LL * ((long long)A * L->T + L->T) * 4 > 160 * 1024) return a0_fail(A0_EINVAL, "a0_actor_rollout: head too wide for the distributional tail kernel");
-            if (step_enc && t + 1 < a->T) {
-                A0_CHECK(a0_actor_dist_tail_env_step_enc(a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, L->d.algo == A0_ALGO_C51 ? 2 : 1,
-                                                         L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed,
-                                                         STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed, a->d.rank,
-                                                         a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps, a->d.discount,
-                                                         a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
-                                                         a->d.env_task, V.wt, &w, a->act3, stream));
-                feat_ready = true;
-            } else
-            A0_CHECK(a0_actor_dist_tail_env_step(a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, L->d.algo == A0_ALGO_C51 ? 2 : 1,
-                                                 L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed,
-                                                 STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E, a->d.seed, a->d.rank,
-                                                 a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps, a->d.discount,
-                                                 a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
-                                                 a->d.env_task, stream));
+            const bool c51 = L->d.algo == A0_ALGO_C51;
+            const a0_slab_head head{a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, c51 ? 2 : 1, c51 ? L->atoms : nullptr, nullptr, 0};
+            A0_CHECK(a0_actor_slab_tail_env_launch(head, E, draw(oa, ou), commit(nx), next, (hipStream_t)stream));
+            feat_ready = next != nullptr;
             a->cur = nx;
             a->steps += 1;
             continue;
@@ -704,19 +695,9 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
         const unsigned long long off_a = a->rng.reserve(STREAM_EGREEDY_A, E), off_u = a->rng.reserve(STREAM_EGREEDY_U, E);
         const int nxt = (a->cur + 1) % a->K;
         a->g += 1;
-        if (step_enc && t + 1 < a->T) {
-            A0_CHECK(a0_actor_qhead_env_step_enc_wp(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
-                                                 a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E,
-                                                 a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nxt], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
-                                                 a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
-                                                 a->d.env_task, V.wt, &w, a->act3, w1p, stream));
-            feat_ready = true;
-        } else
-        A0_CHECK(a0_actor_qhead_env_step_wp(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0,
-                                         a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, off_a, off_u, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E,
-                                         a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nxt], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps,
-                                         a->d.discount, a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done,
-                                         a->d.env_task, w1p, stream));
+        A0_CHECK(a0_actor_qhead_env_launch(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0, a->scratch, draw(off_a, off_u), commit(nxt), next, w1p,
+                                           (hipStream_t)stream));
+        feat_ready = next != nullptr;
         a->cur = nxt;
         a->steps += 1;
     }

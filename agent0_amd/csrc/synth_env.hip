@@ -3,6 +3,7 @@
 // available on the GPU box); honours the obs/reward/terminal/truncated/life_loss/episode-return contract that
 // agent0/deepq/agent.py:55-62,85-88 consumes.  It is NOT Atari.
 #include "a0_internal.h"
+#include "actor_step.h"      // a0_env_commit_check
 
 #pragma clang fp contract(off)
 #include "synth_env.h"
@@ -112,11 +113,9 @@ extern "C" int a0_env_synth_step_commit(unsigned long long seed, unsigned int ra
                                         float* final_mask, float* final_ret, int n, long long steps, double gamma, const int* action, int* ring_act,
                                         float* ring_rew, float* ring_done, const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act,
                                         float* r_rew, float* r_done, int A, int task, const long long* ctrl, void* stream) {
-    if (!obs_in || !obs_out || obs_in == obs_out || !ep_ret || !final_mask || !final_ret || !action || !ring_act || !ring_rew || !ring_done || !obs0 || !frames ||
-        !r_act || !r_rew || !r_done || E < 1 || n < 1 || steps < 0 || cap < E || start_slot < 0 || task < A0_ENV_TASK_STREAM || task > A0_ENV_TASK_CHASE ||
-        (task == A0_ENV_TASK_BLOCK && A < 1) || (task == A0_ENV_TASK_CHASE && A < 4))
-        return a0_fail(A0_EINVAL, "a0_env_synth_step_commit: bad argument");
-    if ((((uintptr_t)obs_in) | ((uintptr_t)obs_out) | ((uintptr_t)obs0) | ((uintptr_t)frames)) & 15) return a0_fail(A0_EINVAL, "a0_env_synth_step_commit: buffers must be 16-byte aligned");
+    if (!action || E < 1 || (task == A0_ENV_TASK_BLOCK && A < 1)) return a0_fail(A0_EINVAL, "a0_env_synth_step_commit: bad argument");
+    const a0_env_commit env{seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    { const int rc = a0_env_commit_check(env, E, A, "a0_env_synth_step_commit"); if (rc != A0_OK) return rc; }
     hipLaunchKernelGGL(a0_env_step_commit_kernel, dim3(2, E), dim3(256), 0, (hipStream_t)stream, seed, rank, E, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n,
                        steps, gamma, action, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot % cap, r_act, r_rew, r_done, ctrl, A, task);
     return a0_fail_hip((int)hipGetLastError(), "a0_env_synth_step_commit");

@@ -182,6 +182,23 @@ def _eps_req(eps, eps_ptr, E: int):
     return _req(eps_ptr, torch.float32, E if float(eps) == EPS_PER_ENV else 1, "eps_ptr", optional=True)
 
 
+def _step_draw(E, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax):
+    """The epsilon-greedy draw of a merged actor step (csrc/actor_step.h: a0_step_draw), as the checked arguments the a0_actor_*_env_step* entry points take."""
+    return (seed, stream_a, stream_u, off_a, off_u, float(eps), _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
+            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"))
+
+
+def _env_commit(E, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot,
+                r_act, r_rew, r_done, task):
+    """The env step, n-step bookkeeping and replay row of a merged actor step (csrc/actor_step.h: a0_env_commit), checked likewise."""
+    nb = E * 4 * 84 * 84
+    return (env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
+            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
+            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
+            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
+            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task))
+
+
 class HipOps:
     name = "hip"
 
@@ -786,67 +803,43 @@ class HipOps:
     def actor_dist_tail_env_step(self, slabs, nslab, bias, ld, A, T, dueling, mode, atoms, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
                                  env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
                                  start_slot, r_act, r_rew, r_done, task=0):
-        nb = E * 4 * 84 * 84
         check(self.lib.a0_actor_dist_tail_env_step(
             _req(slabs, torch.float32, nslab * E * ld, "slabs"), E * ld, nslab, _req(bias, torch.float32, ld, "bias"), ld, A, T, int(dueling),
-            mode, _req(atoms, torch.float32, T, "atoms", optional=(mode != 2)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
-            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
-            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
-            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
-            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
-            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
-            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task), _stream()), "a0_actor_dist_tail_env_step")
+            mode, _req(atoms, torch.float32, T, "atoms", optional=(mode != 2)), E, *_step_draw(E, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax),
+            *_env_commit(E, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot,
+                         r_act, r_rew, r_done, task), _stream()), "a0_actor_dist_tail_env_step")
 
     def actor_dist_tail_env_step_enc(self, slabs, nslab, bias, ld, A, T, dueling, mode, atoms, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
                                      env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
                                      start_slot, r_act, r_rew, r_done, task=0, wt=None, enc_w=None, act3_next=None):
         """``actor_dist_tail_env_step`` whose kernel goes on to encode the env's new observation into ``act3_next`` [E][3136] (a0_actor_dist_tail_env_step_enc)."""
-        nb = E * 4 * 84 * 84
         ew = self._enc_w(enc_w)
         check(self.lib.a0_actor_dist_tail_env_step_enc(
             _req(slabs, torch.float32, nslab * E * ld, "slabs"), E * ld, nslab, _req(bias, torch.float32, ld, "bias"), ld, A, T, int(dueling),
-            mode, _req(atoms, torch.float32, T, "atoms", optional=(mode != 2)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
-            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
-            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
-            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
-            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
-            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
-            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task),
+            mode, _req(atoms, torch.float32, T, "atoms", optional=(mode != 2)), E, *_step_draw(E, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax),
+            *_env_commit(E, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot,
+                         r_act, r_rew, r_done, task),
             _req(wt, torch.float32, self.conv_wt_floats(4), "wt"), C.addressof(ew), _req(act3_next, torch.float32, E * 3136, "act3_next"), _stream()), "a0_actor_dist_tail_env_step_enc")
 
     def actor_quantile_tail_env_step(self, slabs, nslab, bias, ld, A, T, dueling, mode, taus, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
                                      env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
                                      start_slot, r_act, r_rew, r_done, task=0):
-        nb = E * 4 * 84 * 84
         check(self.lib.a0_actor_quantile_tail_env_step(
             _req(slabs, torch.float32, nslab * E * T * ld, "slabs"), E * T * ld, nslab, _req(bias, torch.float32, A + (1 if dueling else 0), "bias"), ld, A, T, int(dueling),
-            mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
-            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
-            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
-            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
-            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
-            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
-            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task), _stream()), "a0_actor_quantile_tail_env_step")
+            mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, *_step_draw(E, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax),
+            *_env_commit(E, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot,
+                         r_act, r_rew, r_done, task), _stream()), "a0_actor_quantile_tail_env_step")
 
     def actor_quantile_tail_env_step_enc(self, slabs, nslab, bias, ld, A, T, dueling, mode, taus, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
                                          env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap,
                                          start_slot, r_act, r_rew, r_done, task=0, wt=None, enc_w=None, act3_next=None):
         """``actor_quantile_tail_env_step`` whose kernel goes on to encode the env's new observation into ``act3_next`` [E][3136] (a0_actor_quantile_tail_env_step_enc)."""
-        nb = E * 4 * 84 * 84
         ew = self._enc_w(enc_w)
         check(self.lib.a0_actor_quantile_tail_env_step_enc(
             _req(slabs, torch.float32, nslab * E * T * ld, "slabs"), E * T * ld, nslab, _req(bias, torch.float32, A + (1 if dueling else 0), "bias"), ld, A, T, int(dueling),
-            mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
-            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
-            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
-            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
-            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
-            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
-            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task),
+            mode, _req(taus, torch.float32, E * (T + 1), "taus", optional=(mode != 3)), E, *_step_draw(E, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax),
+            *_env_commit(E, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot,
+                         r_act, r_rew, r_done, task),
             _req(wt, torch.float32, self.conv_wt_floats(4), "wt"), C.addressof(ew), _req(act3_next, torch.float32, E * 3136, "act3_next"), _stream()), "a0_actor_quantile_tail_env_step_enc")
 
     def actor_qhead_scratch(self, E, K) -> int:
@@ -874,18 +867,12 @@ class HipOps:
                              start_slot, r_act, r_rew, r_done, task=0, w1_planes=None):
         """``w1_planes``: ``actor_fc1_planes`` of W1 — fc1 then runs as a0_actor_fc1_kernel where ``actor_fc1_ok`` accepts the step (the same bytes)."""
         nq = A + (1 if dueling else 0)
-        nb = E * 4 * 84 * 84
         check(self.lib.a0_actor_qhead_env_step_wp(
             _req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
             _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
-            _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
-            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
-            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
-            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
-            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
-            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
-            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task),
+            _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), *_step_draw(E, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax),
+            *_env_commit(E, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot,
+                         r_act, r_rew, r_done, task),
             _req(w1_planes, torch.int32, self.actor_fc1_planes_words(512, K), "w1_planes", optional=True), _stream()), "a0_actor_qhead_env_step")
 
     def actor_qhead_env_step_enc(self, feat, E, K, W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl, eps_ptr,
@@ -893,19 +880,13 @@ class HipOps:
                                  start_slot, r_act, r_rew, r_done, task=0, wt=None, enc_w=None, act3_next=None, w1_planes=None):
         """``actor_qhead_env_step`` whose tail kernel goes on to encode the env's new observation into ``act3_next`` (a0_actor_qhead_env_step_enc): a step in two launches."""
         nq = A + (1 if dueling else 0)
-        nb = E * 4 * 84 * 84
         ew = self._enc_w(enc_w)
         check(self.lib.a0_actor_qhead_env_step_enc_wp(
             _req(feat, torch.float32, E * K, "feat"), E, K, _req(W1, torch.float32, 512 * K, "W1"), _req(b1, torch.float32, 512, "b1"),
             _req(W2, torch.float32, nq * 512, "W2"), _req(b2, torch.float32, nq, "b2"), A, int(dueling),
-            _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), seed, stream_a, stream_u, off_a, off_u, float(eps),
-            _req(ctrl, torch.int64, 8, "ctrl", optional=True), _eps_req(eps, eps_ptr, E),
-            _req(action, torch.int32, E, "action"), _req(qmax, torch.float32, E, "qmax"),
-            env_seed, rank, g, _req(obs_in, torch.uint8, nb, "obs_in"), _req(obs_out, torch.uint8, nb, "obs_out"), _req(ep_ret, torch.float32, E, "ep_ret"),
-            _req(final_mask, torch.float32, E, "final_mask"), _req(final_ret, torch.float32, E, "final_ret"), n, steps, float(gamma),
-            _req(ring_act, torch.int32, n * E, "ring_act"), _req(ring_rew, torch.float32, n * E, "ring_rew"), _req(ring_done, torch.float32, n * E, "ring_done"),
-            _req(obs0, torch.uint8, nb, "obs0"), _req(frames, torch.uint8, cap * 8 * 84 * 84, "frames"), cap, start_slot, _req(r_act, torch.int32, cap, "r_act"),
-            _req(r_rew, torch.float32, cap, "r_rew"), _req(r_done, torch.float32, cap, "r_done"), int(task),
+            _req(scratch, torch.float32, self.actor_qhead_scratch(E, K), "scratch"), *_step_draw(E, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax),
+            *_env_commit(E, env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot,
+                         r_act, r_rew, r_done, task),
             _req(wt, torch.float32, self.conv_wt_floats(4), "wt"), C.addressof(ew), _req(act3_next, torch.float32, E * K, "act3_next"),
             _req(w1_planes, torch.int32, self.actor_fc1_planes_words(512, K), "w1_planes", optional=True), _stream()), "a0_actor_qhead_env_step_enc")
 
