@@ -3,6 +3,7 @@
 #include "a0_internal.h"
 
 #include <cmath>
+#include <memory>
 #include <vector>
 
 struct Blk { long long off; int N, K; long long w() const { return off; } long long b() const { return off + (long long)N * K; } long long size() const { return (long long)N * K + N; } };
@@ -20,8 +21,11 @@ struct a0_host_rng {
 
 struct a0_noise_mod { int block; int r0, r1, in_f; long long off_in, off_w, off_b; };      // block: 0 = fc1, 1 = head; offsets into one network's noise buffer
 
+// Which forward + loss an update runs and which workspaces the handle has, decided once in a0_learner_layout.  Scalar: dqn, mdqn from the fc1 slabs; dist: c51, qr from the head slabs; layerwise: every other qr / mdqn
+enum a0_family { A0_FAM_SCALAR, A0_FAM_DIST, A0_FAM_LAYERWISE, A0_FAM_IQN, A0_FAM_FQF };
+
 struct a0_learner {
-    a0_learner_desc d;
+    a0_learner_desc d; a0_family fam = A0_FAM_SCALAR;
     a0_net* net = nullptr;
     int C = 4, H = 84, W = 84, H1 = 20, W1 = 20, H2 = 9, W2 = 9, feat = 3136, Npad = 32, NQ = 0;
     Blk conv1, conv2, conv3, fc1, head;      // noisy: fc1 / head are the mu blocks
@@ -51,9 +55,7 @@ struct a0_learner {
     float *inner_taus = nullptr, *rms_sq = nullptr, *frac_loss = nullptr, *dfrac = nullptr, *clip = nullptr;
     // ---- dense heads evaluated layer by layer (A0_ALGO_QR, A0_ALGO_MDQN): fc1 output, raw head output, combined head output per pass; dq of the differentiated pass
     struct DWs { float *act3 = nullptr, *h = nullptr, *raw = nullptr, *q = nullptr; } go, gt, gs, gm;      // online on s, target on s', online on s' (double-Q), target on s (mdqn)
-    float *g_dq = nullptr, *qr_taus = nullptr;
-    bool qr_fused = false, mdqn_fused = false;      // round 5: qr from the head GEMMs' slabs (a0_qr_head_loss_slabs), mdqn from the fc1 slabs (a0_mdqn_head_loss_slabs)
-    float* q_cur = nullptr;                         // mdqn: target(obs) [B][A]
+    float *g_dq = nullptr, *qr_taus = nullptr, *q_cur = nullptr;      // q_cur: target(obs) [B][A] of mdqn from the fc1 slabs
     long long slab_off3[3] = {0, 0, 0};
     // effective (W, b) of a dense layer of the online / target network
     const float* Wf(bool tg) const { return d.noisy ? (tg ? eff_tg : eff_on) + eff_fc1.w() : (tg ? target : online) + fc1.w(); }

@@ -1028,20 +1028,27 @@ def test_native_fqf_learner_handle_equals_the_per_kernel_composition(hip, A, due
     nat.close()
 
 
-@pytest.mark.parametrize("algo,A,dueling,double_q,n_step,noisy,B", [("qr", 4, False, False, 1, False, 32), ("qr", 6, True, True, 3, True, 32), ("qr", 4, False, True, 1, False, 512),
-                                                                   ("mdqn", 4, False, False, 1, False, 64), ("mdqn", 18, True, False, 3, True, 32)],
-                         ids=["qr", "qr-duel-double-n3-noisy", "qr-b512", "mdqn", "mdqn-a18-duel-n3-noisy"])
-def test_native_qr_and_mdqn_learner_handles_equal_the_per_kernel_composition(hip, algo, A, dueling, double_q, n_step, noisy, B):
+@pytest.mark.parametrize("algo,A,num_atoms,dueling,double_q,n_step,noisy,B",
+                         [("qr", 4, 200, False, False, 1, False, 32), ("qr", 6, 200, True, True, 3, True, 32), ("qr", 4, 200, False, True, 1, False, 512),
+                          ("mdqn", 4, None, False, False, 1, False, 64), ("mdqn", 18, None, True, False, 3, True, 32),
+                          # the layer-by-layer arm: qr with more than 32 actions, mdqn with A + dueling > 24 (the smallest shapes that leave the fused arms)
+                          ("qr", 33, 8, False, False, 1, False, 16), ("qr", 33, 8, True, True, 3, True, 16),
+                          ("mdqn", 24, None, True, False, 1, False, 16), ("mdqn", 30, None, False, False, 3, True, 16)],
+                         ids=["qr", "qr-duel-double-n3-noisy", "qr-b512", "mdqn", "mdqn-a18-duel-n3-noisy",
+                              "qr-layerwise", "qr-layerwise-duel-double-n3-noisy", "mdqn-layerwise-duel", "mdqn-layerwise-n3-noisy"])
+def test_native_qr_and_mdqn_learner_handles_equal_the_per_kernel_composition(hip, request, algo, A, num_atoms, dueling, double_q, n_step, noisy, B):
     """The reference's remaining learners behind the handle: A0_ALGO_QR (200 fixed quantiles per action, quantile Huber at the midpoints, agent.py:272-293) and
     A0_ALGO_MDQN (Munchausen DQN, agent.py:194-215: the target network also on the current observation), with NoisyNet, dueling, double-Q (qr) and n-step —
     torch.equal to DeviceRng + DeviceLearner.update on losses, parameters, target, Adam moments and status words after each of four updates across a target sync."""
     from agent0_amd.common.utils import DeviceRng
     from agent0_amd.deepq.engine import DeviceLearner
     from agent0_amd.deepq.layout import NetLayout
-    spec = recipe.NetSpec(algo, A, dueling=dueling, noisy=noisy, **({"num_atoms": 200} if algo == "qr" else {}))
+    spec = recipe.NetSpec(algo, A, dueling=dueling, noisy=noisy, **({"num_atoms": num_atoms} if algo == "qr" else {}))
     L = NetLayout.from_spec(spec)
     cap = max(200, B + 40)
     dev = DeviceLearner(hip, L, B, n_step=n_step, double_q=double_q, target_update_freq=3)
+    if "layerwise" in request.node.callspec.id:
+        assert (not dev._qr_fused_ok()) if algo == "qr" else (L.A + dueling > 24), "this case is meant for the layer-by-layer arm (a0_fwd_layerwise)"
     dev.online.load_state_dict(recipe.make_state_dict(spec, 11))
     dev.target.load_state_dict(recipe.make_state_dict(spec, 12))
     seed = 42 + 15485863
