@@ -320,6 +320,37 @@ extern "C" int a0_learner_set_target_tau(a0_learner* L, double tau) {
     return A0_OK;
 }
 
+extern "C" int a0_learner_set_weight_decay(a0_learner* L, double lambda, double* partials_dev) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_weight_decay: null handle");
+    if (L->updated) return a0_fail(A0_EINVAL, "a0_learner_set_weight_decay: the setting is fixed once the handle has run an update");
+    if (lambda != lambda) return a0_fail(A0_EINVAL, "a0_learner_set_weight_decay: lambda is NaN");
+    if (!(lambda > 0.0)) { L->decay_c = 0.0; return A0_OK; }
+    const double c = L->d.lr * lambda;
+    const float c32 = (float)c;
+    char msg[256];
+    if (!(c32 < 1.f)) {
+        snprintf(msg, sizeof msg, "a0_learner_set_weight_decay: lr * lambda = %g * %g = %g must be below 1", L->d.lr, lambda, c);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (!(c32 >= 0x1p-24f)) {
+        snprintf(msg, sizeof msg, "a0_learner_set_weight_decay: lr * lambda = %g * %g = %g is below 2^-24 = %g and would move no fp32 parameter", L->d.lr, lambda, c, 0x1p-24);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (((uintptr_t)partials_dev) & 7) return a0_fail(A0_EINVAL, "a0_learner_set_weight_decay: partials_dev must be 8-byte aligned");
+    if (!partials_dev && !L->decay_own) L->decay_own = L->alloc<double>(A0_GRAD_NORM_PARTIALS, true);
+    L->decay_partials = partials_dev ? partials_dev : L->decay_own;
+    L->decay_c = c;
+    return A0_OK;
+    A0_CATCH
+}
+
+extern "C" int a0_learner_weight_decay_partials(const a0_learner* L, double** partials_dev) {
+    if (!L || !partials_dev) return a0_fail(A0_EINVAL, "a0_learner_weight_decay_partials: null argument");
+    *partials_dev = L->decay_c > 0.0 ? L->decay_partials : nullptr;
+    return A0_OK;
+}
+
 // The rule table of a network reset from the handle's block descriptors: NetLayout.reset_segments (agent0_amd/deepq/layout.py), entry for entry.  A fresh weight has
 // the constructor's per-element scale (agent0_amd/deepq/model.py): an orthogonal matrix of gain g has element RMS g / sqrt(max(rows, cols)); a NoisyLinear's mu is
 // uniform in +-1 / sqrt(in), its sigma 0.4 / sqrt(in) (weights) and 0.4 / sqrt(out) (bias).  Returns the number of entries.
@@ -736,11 +767,12 @@ static int a0_exchange_begin(a0_upd& u) {
 }
 
 // DeviceLearner.backward_encoder(fuse_tail).  The update's tail as one launch: the slab sums wait for the Adam launch — not under data parallelism or clipping, which
-// need the summed gradient first, nor when NoisyNet's sigma gradients wait for deferred dense sums
+// need the summed gradient first, nor under weight decay, whose launch reads the NaN flag the one-launch tail's bookkeeping lowers a launch early, nor when NoisyNet's
+// sigma gradients wait for deferred dense sums
 static int a0_backward_encoder(a0_upd& u) {
     a0_learner* L = u.L; const int B = L->d.B;
     A0_CHECK(a0_net_encoder_dgrad_fused(L->C, L->H, L->W, L->wt_on, L->d3, L->act1, L->act2, B, L->d2, L->d1, u.stream));
-    u.fuse_tail = !u.dp && L->clip_max_norm <= 0.f && !(L->d.noisy && u.pend.n > 0);
+    u.fuse_tail = !u.dp && L->clip_max_norm <= 0.f && L->decay_c <= 0.0 && !(L->d.noisy && u.pend.n > 0);
     if (u.fuse_tail)
         return a0_net_encoder_wgrad_tail(L->net, &u.w_on, &u.f_obs, B, L->act1, L->act2, L->d3, L->d2, L->d1, L->grads + L->conv1.off, L->grads + L->conv2.off,
                                          L->grads + L->conv3.off, L->slabs + L->enc_slab_off, &u.pend, &u.tail, L->state, L->scalars, L->d.lr, 0.9, 0.999, u.hard_freq, u.stream);
@@ -761,7 +793,7 @@ static int a0_exchange_end(a0_upd& u) {
 }
 
 // DeviceLearner.apply: Adam (eps = 1e-2 / B unless given), NaN guard, update counter, target copy every target_update_freq updates, weight-copy refresh
-// (agent.py:102-106,152-161) in one of three forms; then learner.target_tau's blend, which follows whichever form the update took, and learner.net_reset_freq's
+// (agent.py:102-106,152-161) in one of three forms, behind learner.weight_decay's launch; then learner.target_tau's blend, which follows whichever form the update took, and learner.net_reset_freq's
 // reset, the update's last launch, which returns at once unless this update's count names a reset
 static int a0_apply(a0_upd& u, float* loss_out) {
     a0_learner* L = u.L; void* stream = u.stream; const int B = L->d.B; float *on = L->online, *tg = L->target;
@@ -769,6 +801,8 @@ static int a0_apply(a0_upd& u, float* loss_out) {
     if (L->fam == A0_FAM_FQF)      // unconditional, like the reference's fqf_optimizer.step() in front of the NaN guard (agent.py:139-148); lr / 2e4, alpha 0.95, eps 1e-5
         A0_CHECK(a0_rmsprop_step(on + L->frac.off, L->grads + L->frac.off, L->rms_sq, L->frac.size(), L->d.lr / 2e4, 0.95, 1e-5, L->d.max_grad_norm > 0.0 ? L->d.max_grad_norm : -1.0, L->clip, stream));
     const double eps = L->d.adam_eps > 0.0 ? L->d.adam_eps : 1e-2 / (double)B; const float* dp_flag = u.dp ? L->grads + L->n_pad : nullptr;
+    // learner.weight_decay: everything Adam owns shrinks first, unless this update is NaN-skipped; the Adam form behind files the shrunk values' successors
+    if (L->decay_c > 0.0) A0_CHECK(a0_weight_decay(on, L->n_adam, L->decay_c, L->state, dp_flag, L->decay_partials, stream));
     if (u.fuse_tail) {
         A0_CHECK(a0_update_tail(on, L->grads, L->m, L->v, L->n_adam, L->state, L->scalars, 0.9, 0.999, eps, tg, L->n_pad, &u.tail, &u.w_on, L->C, L->wt_on, L->wt_tg, L->loss, B,
                                 L->loss_ring, L->loss_ring_cap, stream));

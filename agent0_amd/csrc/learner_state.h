@@ -75,6 +75,9 @@ struct a0_learner {
     // ---- soft target updates (a0_learner_set_target_tau): off while target_tau <= 0; `updated`: an update has been issued, the setting is fixed from then on
     double target_tau = 0.0;
     bool updated = false;
+    // ---- decoupled weight decay in front of Adam (a0_learner_set_weight_decay): off while decay_c <= 0; decay_c = lr * lambda, rounded to fp32 by a0_weight_decay
+    double decay_c = 0.0;
+    double *decay_partials = nullptr, *decay_own = nullptr;      // where the sums of squares go; the handle's own buffer, once a NULL partials_dev asked for one
     // ---- periodic shrink-and-perturb resets (a0_learner_set_net_reset): off while reset_freq == 0; the rule table is built from the block descriptors above
     int reset_freq = 0, n_reset_segs = 0;
     double reset_shrink = 1.0;

@@ -137,6 +137,63 @@ A0_D float a0_mul_rounded(float a, float b) {
     return r;
 }
 
+// Decoupled weight decay (learner.weight_decay; torch.optim.AdamW's p <- p * (1 - lr * lambda) in front of its Adam step), ONE launch in front of the update's Adam
+// form, in a0_grad_sumsq_kernel's shape: workgroup b owns [b * chunk, (b + 1) * chunk) of p[0, n), shrinks it by c = fl32(lr * lambda) — t = fl32(c * p), then
+// p <- fl32(p - t): one rounded product (a0_mul_rounded) and one rounded subtraction — and writes the sum of the squares of the values it READ to partials[b]
+// (doubles, plain stores, 0 for an empty range): the parameter norm in front of the decay, finished on the host.  The kernel decides "skipped" for itself as
+// a0_step_decide does, from words nobody writes while it runs: the NaN flag state[0], which the Adam form behind lowers, and the optional data-parallel flag.  A
+// skipped update stores no parameter; its partials are written all the same.
+A0_D float a0_decay1(float p, float c) {
+    const float t = a0_mul_rounded(c, p);
+    float r;
+    {
+#pragma clang fp contract(off)
+        r = p - t;
+    }
+    return r;
+}
+__global__ __launch_bounds__(256) void a0_weight_decay_kernel(float* __restrict__ p, long long n, long long chunk, int vec4, float c, const int* __restrict__ state,
+                                                              const float* __restrict__ extra_flag, double* __restrict__ partials) {
+    __shared__ double red[256];
+    const bool skip = (state[0] != 0) || (extra_flag && extra_flag[0] != 0.f);
+    const long long lo = (long long)blockIdx.x * chunk;
+    const long long hi = lo + chunk < n ? lo + chunk : n;
+    double s = 0.0;
+    if (lo < hi) {
+        long long done = 0;
+        if (vec4) {
+            const long long n4 = (hi - lo) >> 2;
+            a0_f4* p4 = (a0_f4*)(p + lo);
+            for (long long j = threadIdx.x; j < n4; j += 256) {
+                a0_f4 x = p4[j];
+                s += (double)x.x * (double)x.x; s += (double)x.y * (double)x.y; s += (double)x.z * (double)x.z; s += (double)x.w * (double)x.w;
+                if (!skip) { x.x = a0_decay1(x.x, c); x.y = a0_decay1(x.y, c); x.z = a0_decay1(x.z, c); x.w = a0_decay1(x.w, c); p4[j] = x; }
+            }
+            done = n4 << 2;
+        }
+        for (long long i = lo + done + threadIdx.x; i < hi; i += 256) {
+            const float x = p[i];
+            s += (double)x * (double)x;
+            if (!skip) p[i] = a0_decay1(x, c);
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+// c: lr * lambda as the caller formed it in double; rounded to fp32 once here.  2^-24 <= fl32(c) < 1: a smaller c moves no fp32 value, c >= 1 is no decay
+extern "C" int a0_weight_decay(float* params, long long n, double c, const int* state, const float* extra_nan_flag, double* partials, void* stream) {
+    if (!params || !state || !partials || n < 1 || (((uintptr_t)params) & 3) || (((uintptr_t)partials) & 7)) return a0_fail(A0_EINVAL, "a0_weight_decay: bad argument");
+    const float c32 = (float)c;
+    if (!(c32 >= 0x1p-24f) || !(c32 < 1.f)) return a0_fail(A0_EINVAL, "a0_weight_decay: c = lr * lambda must lie in [2^-24, 1) as an fp32 number");
+    const long long chunk = ((n + A0_GRAD_NORM_PARTIALS - 1) / A0_GRAD_NORM_PARTIALS + 3) / 4 * 4;
+    hipLaunchKernelGGL(a0_weight_decay_kernel, dim3(A0_GRAD_NORM_PARTIALS), dim3(256), 0, (hipStream_t)stream, params, n, chunk, (((uintptr_t)params) & 15) == 0 ? 1 : 0, c32, state,
+                       extra_nan_flag, partials);
+    return a0_fail_hip((int)hipGetLastError(), "a0_weight_decay");
+}
+
 // The batch mean of this update's per-sample losses (the Trainer's `loss` statistic, trainer.py:99,111-113) into the ring slot of the free-running call counter
 // state[6], by ONE workgroup of 256 lanes — the same reduction, statement for statement, as a0_mean_rows_kernel, whose launch per update (4.8 us of pure latency)
 // it replaces.  Skipped steps are recorded too (their mean is whatever the loss kernel wrote, NaN included).

@@ -53,6 +53,14 @@ Additions (all default to the reference's behaviour being available):
   learner.net_reset_shrink  float in [0, 1], default 1.0 (anything else, NaN included, is refused).  The share alpha of the encoder that survives a reset,
                    p <- alpha * p + (1 - alpha) * fresh: 1.0 leaves the encoder untouched (Nikishin et al. 2022: the last layers only), 0.5 is BBF's and SR-SPR's
                    shrink-and-perturb, 0 re-initialises it.  Without ``learner.net_reset_freq`` it does nothing.
+  learner.weight_decay  float, default 0.0 (off; any value <= 0 is off; NaN is refused).  lambda > 0: decoupled weight decay, ``torch.optim.AdamW(weight_decay=lambda)``:
+                   every update that is not NaN-skipped first shrinks everything Adam owns — the convolutions, fc1, the heads, NoisyNet's mu and sigma, the
+                   cosine embedding, biases included; not the fqf fraction net, which clipping and resets leave alone too — by p <- p - c * p,
+                   c = learning_rate * lambda rounded to fp32 once, and then takes the Adam step on the shrunk values with the gradient computed at the undecayed
+                   ones (a0_weight_decay, one launch in front of the Adam form; the update takes the three-launch tail, as under ``learner.clip_grad_norm``).
+                   BBF and SR-SPR use 0.1.  c >= 1 is refused, and so is 0 < c < 2^-24, which would move no fp32 value.  Masks that exempt biases or sigmas are
+                   not offered.  Adds the statistic ``param_norm``: the L2 norm of everything Adam owns as it stood in front of the decay of the block's last
+                   update.  No state of its own, nothing new in a snapshot, and the setting may change across a resume like ``actor.min_eps``.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -148,6 +156,7 @@ class LearnerConfig:
     aug_shift: int = 0
     net_reset_freq: int = 0
     net_reset_shrink: float = 1.0
+    weight_decay: float = 0.0
     learner_steps: int = 20
     double_q: bool = False
     dueling_head: bool = False

@@ -38,6 +38,29 @@ def target_tau_value(value) -> float:
     return tau
 
 
+WEIGHT_DECAY_MIN_C = 2.0 ** -24      # the smallest lr * lambda, as an fp32 number, that still moves an fp32 parameter
+
+
+def weight_decay_value(value, lr) -> float:
+    """``learner.weight_decay`` as the learner uses it: the per-update coefficient c = fl32(lr * lambda) — formed in double, rounded to fp32 once — when lambda > 0,
+    0.0 (off) for zero, a negative number or None.  Refused: NaN, c >= 1 (the update would wipe or flip the parameters) and 0 < c < 2^-24 (such a c moves no fp32
+    value, and silently doing nothing is worse than an error)."""
+    if value is None:
+        return 0.0
+    lam = float(value)
+    if lam != lam:
+        raise ValueError("learner.weight_decay=nan: must be a number (0.0 or any value <= 0 is off)")
+    if not lam > 0:
+        return 0.0
+    c = float(torch.tensor(float(lr) * lam, dtype=torch.float64).to(torch.float32))
+    if not c < 1.0:
+        raise ValueError(f"learner.weight_decay={lam!r}: learning_rate * weight_decay = {float(lr)!r} * {lam!r} = {float(lr) * lam!r} must be below 1")
+    if c < WEIGHT_DECAY_MIN_C:
+        raise ValueError(f"learner.weight_decay={lam!r}: learning_rate * weight_decay = {float(lr)!r} * {lam!r} = {float(lr) * lam!r} is below 2^-24 = "
+                         f"{WEIGHT_DECAY_MIN_C!r} and would move no fp32 parameter")
+    return c
+
+
 def aug_shift_value(value, obs_shape, pipeline_target: Optional[bool] = None) -> int:
     """``learner.aug_shift`` as the learner uses it: the pad p of DrQ's random shift, 0 (off) for zero or None.  Refused: a negative or fractional value, p >= min(H, W)
     of ``obs_shape`` (C, H, W), p > 16 — the kernel's own limits (a0_augment_shift) — and any p > 0 together with ``A0_PIPELINE_TARGET=1`` (``pipeline_target``; None
@@ -360,7 +383,8 @@ class DeviceLearner:
 
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
-                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0):
+                 mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0,
+                 weight_decay=0.0):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -408,6 +432,16 @@ class DeviceLearner:
             if aug_rng is None or not hasattr(ops, "net_reset"):
                 raise ValueError(f"learner.net_reset_freq={self.net_reset_freq}: needs the learner's DeviceRng (aug_rng) and a backend with net_reset")
             self.reset_segs = L.reset_segments()
+        # learner.weight_decay = lambda > 0: apply() shrinks everything Adam owns by c = fl32(lr * lambda) in one launch in front of the Adam form (a0_weight_decay),
+        # which also leaves the sums of squares of the values it read in wd_partials (the statistic ``param_norm``).  That launch reads the NaN flag the one-launch
+        # tail's bookkeeping would have lowered, so the update takes the three-launch tail, as under clipping.  Off (0.0): no buffer, no launch.
+        self.wd_coef = weight_decay_value(weight_decay, lr)
+        self.weight_decay = float(weight_decay) if self.wd_coef > 0 else 0.0
+        self.wd_partials = None
+        if self.wd_coef > 0:
+            if not hasattr(ops, "weight_decay"):
+                raise ValueError(f"learner.weight_decay={weight_decay!r}: needs a backend with weight_decay")
+            self.wd_partials = ops.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64)
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -571,7 +605,8 @@ class DeviceLearner:
     def backward_encoder(self, fuse_tail: bool = False):
         """d3 -> the three convolution blocks' gradients (flat range [0, L.conv_end)); the second half of the backward pass, on the
         batch of the last forward_dense call.  ``fuse_tail``: apply() follows at once, so the slab sums may be left to its launch (ops.update_tail) — not under a
-        gradient hook or clipping, which need the summed gradient first, nor when NoisyNet's sigma gradients wait for deferred dense sums."""
+        gradient hook or clipping, which need the summed gradient first, nor under weight decay, whose launch reads the NaN flag the one-launch tail lowers early, nor
+        when NoisyNet's sigma gradients wait for deferred dense sums."""
         L, ops, on = self.L, self.ops, self.online
         ws, frames, slot, stride, B = self._bw
         g1, g2, g3 = self.grads[L.blocks["conv1"].all], self.grads[L.blocks["conv2"].all], self.grads[L.blocks["conv3"].all]
@@ -580,7 +615,8 @@ class DeviceLearner:
             # both data gradients per observation in one kernel (LDS-resident d2), then the three weight-gradient GEMMs
             ops.encoder_dgrad_fused(self.net, on.wt, ws.d3, ws.act1, ws.act2, B, ws.d2, ws.d1)
             pend, self._pend = self._pend, None
-            if (fuse_tail and self.fused_tail and pend is not None and self.grad_hook is None and self.clip_grad_norm <= 0 and not (L.noisy and pend.n > 0)):
+            if (fuse_tail and self.fused_tail and pend is not None and self.grad_hook is None and self.clip_grad_norm <= 0 and self.wd_coef <= 0
+                    and not (L.noisy and pend.n > 0)):
                 self._tail_plan = ops.encoder_wgrad_tail(self.net, on.encoder_weights(), frames, slot, stride, 0, B, ws.act1, ws.act2, ws.d3, ws.d2, ws.d1, g1, g2, g3,
                                                          self.slabs[self._enc_slab_off:], pend, self.state, self.scalars, self.lr, 0.9, 0.999, self._hard_freq())
                 if L.noisy:
@@ -636,7 +672,8 @@ class DeviceLearner:
         return out
 
     def apply(self):
-        """Adam on the flat buffer (NaN-skip and step counter on the device), refresh of the fused kernels' weight copies, target sync — with learner.target_tau on, the
+        """Adam on the flat buffer (NaN-skip and step counter on the device), refresh of the fused kernels' weight copies, target sync — with learner.weight_decay on
+        behind the decay launch, with learner.target_tau on, the
         blend of the target (``_blend_target``) behind whichever Adam form ran, and with learner.net_reset_freq on the reset launch (``_reset_net``) behind that."""
         L, ops, on, tg = self.L, self.ops, self.online, self.target
         if L.algo == "fqf":           # unconditional, like the reference's fqf_optimizer.step() in front of the NaN guard (agent.py:139-148)
@@ -646,6 +683,10 @@ class DeviceLearner:
         adam = (on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, self.lr, 0.9, 0.999, self.adam_eps, self._hard_freq(), tg.flat,
                 L.n_params_padded, self.grads[L.n_params_padded: L.n_params_padded + 1] if self._bucketed_hook() else None)
         wt = (on.encoder_weights(), L.C, on.wt, tg.wt, self.loss, self.B, self.loss_ring) if on.fused else ()
+        if self.wd_coef > 0:
+            # learner.weight_decay: everything Adam owns shrinks first, unless this update is NaN-skipped (the launch reads the flags the Adam form behind it reads);
+            # the Adam form then files the weight copies and the target from final values
+            ops.weight_decay(on.flat, L.n_adam, self.wd_coef, self.state, adam[-1], self.wd_partials)
         if plan is not None:
             # backward_encoder(fuse_tail=True) left the slab sums and the step's bookkeeping to this launch
             ops.update_tail(on.flat, self.grads, self.adam_m, self.adam_v, L.n_adam, self.state, self.scalars, 0.9, 0.999, self.adam_eps, tg.flat, L.n_params_padded, plan, *wt)

@@ -204,6 +204,8 @@ class NativeLoop:
         ok(lib.a0_actor_create(C.addressof(ad), C.addressof(self.actor)), "a0_actor_create")
         if eng.target_tau > 0:          # learner.target_tau: the handle blends the target behind its Adam form, as DeviceLearner.apply does
             ok(lib.a0_learner_set_target_tau(self.learner, C.c_double(eng.target_tau)), "a0_learner_set_target_tau")
+        if eng.weight_decay > 0:        # learner.weight_decay: the handle shrinks the parameters in front of its Adam form, as DeviceLearner.apply does, and files the sums of squares in the engine's buffer
+            ok(lib.a0_learner_set_weight_decay(self.learner, C.c_double(eng.weight_decay), p(eng.wd_partials)), "a0_learner_set_weight_decay")
         if eng.net_reset_freq > 0:      # learner.net_reset_freq: the handle ends its update with the reset launch, as DeviceLearner.apply does, on the engine's seed
             ok(lib.a0_learner_set_net_reset(self.learner, int(eng.net_reset_freq), C.c_double(eng.net_reset_shrink), C.c_ulonglong(eng.reset_seed())), "a0_learner_set_net_reset")
         if eng.aug_shift > 0:           # learner.aug_shift: the handle shifts the batch into a stage buffer of its own ahead of its passes, as DeviceLearner.forward_dense does

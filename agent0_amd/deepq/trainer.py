@@ -11,6 +11,7 @@ wandb / tensorboard are used only if importable and enabled (neither ships in th
 from __future__ import annotations
 
 import logging
+import math
 import os
 import time
 
@@ -116,6 +117,7 @@ class Trainer:
         self.num_transitions = cfg.actor.sample_steps * cfg.actor.num_envs
         self.Ls, self.Rs, self.RTs, self.Qs, self.FLs = [], [], [], [], []
         self.GNs = []                                     # learner.clip_grad_norm: the pre-clip gradient norms of the last update block
+        self.PN = None                                    # learner.weight_decay: the parameter norm in front of the decay of the last update block's last update
         self.frame_count = 0
         L = int(cfg.learner.learner_steps)
         self._loss_means = ops.zeros(max(L, 1))
@@ -360,6 +362,8 @@ class Trainer:
             self.Ls.extend(self._block_loss_means(n_upd))                   # the one device->host read of the update block
             if self._gn0 is not None:
                 self.GNs = self._block_grad_norms(self.learner.engine.gnorm_ring.cpu(), n_upd)
+            if getattr(self.learner.engine, "wd_partials", None) is not None:
+                self.PN = self._param_norm(self.learner.engine.wd_partials.cpu())
             # the device's update count (NaN-skipped steps do not count) for the next block's pipelining decision: read here, where the host has just waited
             # for the block anyway, so that the next block can be enqueued behind the rollout without a stop
             self._updates_done = int(self.learner.engine.state[1]) if self._pipeline_candidate() else None
@@ -396,7 +400,15 @@ class Trainer:
                 host[gk] = torch.empty(ring.numel(), dtype=ring.dtype).pin_memory()
             host[gk].copy_(ring, non_blocking=True)
             gn = host[gk]
-        return (n_upd, ring0, host[key], fl, gn)
+        pn = None
+        part = getattr(self.learner.engine, "wd_partials", None)
+        if part is not None:      # learner.weight_decay: the last update's sums of squares travel with the loss means too
+            pk = ("wd_partials", part.numel())
+            if pk not in host:
+                host[pk] = torch.empty(part.numel(), dtype=part.dtype).pin_memory()
+            host[pk].copy_(part, non_blocking=True)
+            pn = host[pk]
+        return (n_upd, ring0, host[key], fl, gn, pn)
 
     def _block_stats_finish(self, handle):
         n_upd, ring0, buf, fl = handle[:4]
@@ -404,6 +416,8 @@ class Trainer:
             return
         if len(handle) > 4 and handle[4] is not None:
             self.GNs = self._block_grad_norms(handle[4], n_upd)
+        if len(handle) > 5 and handle[5] is not None:
+            self.PN = self._param_norm(handle[5])
         if ring0 is None:
             self.Ls.extend(buf[:n_upd].tolist())
         else:
@@ -436,6 +450,15 @@ class Trainer:
             return [float(ring[int(self.learner.engine.state[6]) % cap])]
         n = min(n_upd, cap)
         return [float(ring[(self._gn0 + n_upd - n + i) % cap]) for i in range(n)]
+
+    @staticmethod
+    def _param_norm(partials) -> float:
+        """learner.weight_decay: the decay launch leaves the sums of squares of the parameters it read (a0_weight_decay, one double per workgroup); the norm is
+        finished here — the sum in index order, the square root in double."""
+        total = 0.0
+        for x in partials.tolist():
+            total += x
+        return math.sqrt(total)
 
     def _block_loss_means(self, n_upd: int):
         if getattr(self, "_ring0", None) is None:
@@ -502,13 +525,16 @@ class Trainer:
 
     def _result(self):
         """The result dict of trainer.py:111-118; with learner.clip_grad_norm on also ``grad_norm``, the mean pre-clip gradient norm over the last block's updates; with
-        learner.net_reset_freq on also ``net_resets`` = update_steps // N."""
+        learner.net_reset_freq on also ``net_resets`` = update_steps // N; with learner.weight_decay on also ``param_norm``, the L2 norm of everything Adam owns in
+        front of the decay of the last block's last update."""
         eng = self.learner.engine
         out = self._result_base()
         if getattr(eng, "gnorm_ring", None) is not None:
             out["grad_norm"] = np.mean(self.GNs) if len(self.GNs) > 0 else None
         if getattr(eng, "net_reset_freq", 0) > 0:      # learner.net_reset_freq: the resets so far, from the device's step count (one small read per logged iteration)
             out["net_resets"] = int(eng.state[1]) // eng.net_reset_freq
+        if getattr(eng, "wd_partials", None) is not None:
+            out["param_norm"] = self.PN
         return out
 
     def _result_base(self):
@@ -570,7 +596,7 @@ class Trainer:
                 self._wandb.log({k: v, "frame": self.frame_count})
             if k == "net_resets":
                 msg += f"{k}: {v} | "
-            elif k in ["frames", "loss", "qmax", "fps", "grad_norm"] or "return" in k:
+            elif k in ["frames", "loss", "qmax", "fps", "grad_norm", "param_norm"] or "return" in k:
                 msg += f"{k}: {v:.2f} | "
         self.logger.info(msg)
 
@@ -586,6 +612,7 @@ class Trainer:
                 w = csv.writer(f)
                 cols = PROGRESS_COLUMNS + (("grad_norm",) if "grad_norm" in result else ())      # only with learner.clip_grad_norm on
                 cols = cols + (("net_resets",) if "net_resets" in result else ())               # only with learner.net_reset_freq on
+                cols = cols + (("param_norm",) if "param_norm" in result else ())               # only with learner.weight_decay on
                 if new:
                     w.writerow(cols)
                 w.writerow(["" if result.get(k) is None else result[k] for k in cols])

@@ -107,6 +107,19 @@ class NativeLearner:
         """learner.target_tau through the handle (a0_learner_set_target_tau): before the first update; <= 0 is off, >= 1 is refused."""
         check(self.lib.a0_learner_set_target_tau(self.h, float(tau)), "a0_learner_set_target_tau")
 
+    def set_weight_decay(self, lam, partials=None):
+        """learner.weight_decay through the handle (a0_learner_set_weight_decay): before the first update; <= 0 is off; ``partials`` None: the handle's own buffer."""
+        check(self.lib.a0_learner_set_weight_decay(self.h, float(lam), _req(partials, torch.float64, 256, "partials", optional=True)), "a0_learner_set_weight_decay")
+
+    def weight_decay_partials(self):
+        """A copy of the handle's sums of squares of the last update (a0_learner_weight_decay_partials); None while the setting is off."""
+        ptr = C.c_void_p()
+        check(self.lib.a0_learner_weight_decay_partials(self.h, C.addressof(ptr)), "a0_learner_weight_decay_partials")
+        if not ptr.value:
+            return None
+        view = type("_Partials", (), {"__cuda_array_interface__": {"shape": (256,), "typestr": "<f8", "data": (int(ptr.value), False), "version": 3}})()
+        return torch.as_tensor(view, device="cuda").clone()
+
     def set_net_reset(self, freq, shrink, seed):
         """learner.net_reset_freq / learner.net_reset_shrink through the handle (a0_learner_set_net_reset): before the first update; freq 0 is off; the low 32 bits of
         ``seed`` position the fresh values."""
@@ -566,6 +579,13 @@ class HipOps:
         """Stage 1 of learner.clip_grad_norm: the sum of squares of ``grads[:n]`` as GRAD_NORM_PARTIALS float64 partial sums (a0_grad_norm_partials)."""
         check(self.lib.a0_grad_norm_partials(_req(grads, torch.float32, n, "grads"), n, _req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), _stream()),
               "a0_grad_norm_partials")
+
+    def weight_decay(self, params, n, c, state, extra_nan_flag, partials):
+        """learner.weight_decay: ``params[:n] -= fl32(c * params[:n])`` in one launch in front of the update's Adam form (a0_weight_decay), unless ``state[0]`` or
+        ``extra_nan_flag`` say the update is NaN-skipped; ``partials`` receives the GRAD_NORM_PARTIALS float64 sums of squares of the values read, either way."""
+        check(self.lib.a0_weight_decay(_req(params, torch.float32, n, "params"), n, float(c), _req(state, torch.int32, 8, "state"),
+                                       _req(extra_nan_flag, torch.float32, 1, "extra_nan_flag", optional=True),
+                                       _req(partials, torch.float64, self.GRAD_NORM_PARTIALS, "partials"), _stream()), "a0_weight_decay")
 
     def adam_step_sync_clip(self, params, grads, m, v, n, state, scalars, lr, b1, b2, eps, target_freq, target, n_total, extra_nan_flag, partials, max_norm, norm_ring):
         """``adam_step_sync`` on ``grads * min(1, max_norm / (norm + 1e-6))``, the norm from ``partials``; it is written to norm_ring[state[6] % len(norm_ring)]."""

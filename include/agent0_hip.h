@@ -392,6 +392,16 @@ int a0_adam_step_sync_wt(float* params, const float* grads, float* exp_avg, floa
  * a0_adam_step_sync_clip does not advance state[6]), on NaN-skipped steps too. */
 #define A0_GRAD_NORM_PARTIALS 256
 int a0_grad_norm_partials(const float* grads, long long n, double* partials, void* stream);
+/* Decoupled weight decay in front of Adam (learner.weight_decay; torch.optim.AdamW's p <- p * (1 - lr * lambda)), ONE launch of A0_GRAD_NORM_PARTIALS workgroups,
+ * which decides for itself: the update counts as skipped when state[0] != 0 (the NaN flag, still up: issue this IN FRONT of the update's Adam form — a0_adam_step_sync
+ * or a0_adam_step_sync_wt, with or without _clip; not in front of a0_update_tail, whose bookkeeping has lowered the flag a launch earlier) or when extra_nan_flag
+ * (optional, as the Adam forms take it) is nonzero.  Not skipped: every params[i], i in [0, n), becomes fl32(p - fl32(c32 * p)), c32 = (float)c — one rounded
+ * product, one rounded subtraction, no contraction — so that the Adam form behind steps, and files in the weight copies and the target, the shrunk values.  Skipped:
+ * no parameter is stored.  Either way partials[b] (A0_GRAD_NORM_PARTIALS doubles, 8-byte aligned, a0_grad_norm_partials' split of the range, plain stores, 0 for an
+ * empty range) receives the sum of squares, in double, of the values workgroup b READ: sqrt of their sum is the parameter norm in front of the decay.  params 16-byte
+ * aligned: 16-byte loads and stores; otherwise element by element.  c = lr * lambda formed in double by the caller; A0_EINVAL unless 2^-24 <= c32 < 1 (a smaller
+ * coefficient moves no fp32 value).  No state word is written, no scratch, no atomics. */
+int a0_weight_decay(float* params, long long n, double c, const int* state, const float* extra_nan_flag, double* partials, void* stream);
 int a0_adam_step_sync_clip(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int* state, float* scalars2, double lr,
                            double beta1, double beta2, double eps, int target_update_freq, float* target, long long n_total, const float* extra_nan_flag,
                            const double* partials, float max_norm, float* norm_ring, int norm_ring_cap, void* stream);
@@ -523,6 +533,14 @@ int a0_learner_set_grad_clip(a0_learner* learner, double max_norm, float* norm_r
  * update issues what it always did.  tau >= 1: A0_EINVAL.  Accepted before the handle's first update only (A0_EINVAL afterwards); descriptor structs are unchanged.
  * The forced copies of a0_learner_create* and a0_learner_set_params stay hard copies. */
 int a0_learner_set_target_tau(a0_learner* learner, double tau);
+/* learner.weight_decay through the handle: with lambda > 0 every a0_learner_update issues a0_weight_decay — the handle's online parameters [0, n_adam), i.e.
+ * everything but the fqf fraction net, c = desc.lr * lambda, the data-parallel NaN flag where an exchange is set — behind the fqf RMSprop step and in front of its
+ * Adam form, and takes the three-launch tail as under a0_learner_set_grad_clip.  partials_dev: A0_GRAD_NORM_PARTIALS doubles the caller owns (8-byte aligned), which
+ * receive every update's sums of squares; NULL: the handle allocates them (a0_learner_weight_decay_partials returns the pointer either way, NULL while off).
+ * lambda <= 0: off, the update issues what it always did.  A0_EINVAL: NaN, fl32(lr * lambda) >= 1 or below 2^-24, a misaligned buffer.  Accepted before the
+ * handle's first update only (A0_EINVAL afterwards); descriptor structs are unchanged. */
+int a0_learner_set_weight_decay(a0_learner* learner, double lambda, double* partials_dev);
+int a0_learner_weight_decay_partials(const a0_learner* learner, double** partials_dev);
 /* learner.net_reset_freq / learner.net_reset_shrink through the handle: with freq > 0 every a0_learner_update issues a0_net_reset (the handle's buffers, the rule
  * table built from its own block descriptors — the one agent0_amd/deepq/layout.py::NetLayout.reset_segments builds — alpha = shrink, the low 32 bits of `seed`) as
  * its last launch.  freq == 0: off, the update issues what it always did.  freq < 0, or shrink outside [0, 1] (NaN included): A0_EINVAL.  Accepted before the
