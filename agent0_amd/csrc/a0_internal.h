@@ -89,6 +89,8 @@ int a0_actor_qhead_env_launch(const float* feat, int E, int K, const float* W1, 
                               const a0_step_draw& draw, const a0_env_commit& env, const a0_next_enc* next, const unsigned int* w1_planes, hipStream_t st);
 // actor_tail.hip — the tails over the head GEMM's slabs (c51 / qr: head.kt = 0, iqn / fqf: head.kt = 1)
 int a0_actor_slab_tail_env_launch(const a0_slab_head& head, int E, const a0_step_draw& draw, const a0_env_commit& env, const a0_next_enc* next, hipStream_t st);
+// the same tails without the env step (actor steps over host environments): a0_actor_dist_tail / a0_actor_quantile_tail behind the descriptors
+int a0_actor_slab_tail_launch(const a0_slab_head& head, int E, const a0_step_draw& draw, hipStream_t st);
 #endif
 #define A0_TAG_ENCODER_FUSED 12
 #define A0_TAG_ENCODER_DGRAD_FUSED 13

@@ -107,6 +107,14 @@ __global__ __launch_bounds__(512) void a0_actor_dist_tail_env_kernel(a0_dtenv_ar
     a0_actor_dist_tail_env_body(P, xs, &s_chase_cell);
 }
 
+// the head and draw arguments every slab tail takes, with or without the env step: pointers, ranges, the row width and slab stride of its layout, its two modes
+static bool a0_slab_head_ok(const a0_slab_head& h, int E, const a0_step_draw& draw) {
+    const int A = h.A, T = h.T, other = h.kt ? 3 : 2;
+    return !(!h.slabs || !h.bias || !draw.action || !draw.qmax || E < 1 || A < 1 || T < 1 || h.nslab < 1 ||
+             (h.kt ? h.ld < A + (h.dueling ? 1 : 0) || h.slab_stride < (long long)E * T * h.ld : h.ld < A * T + (h.dueling ? T : 0) || h.slab_stride < (long long)E * h.ld) ||
+             (h.mode != 1 && h.mode != other) || (h.mode == other && !(h.kt ? h.taus : h.atoms)));
+}
+
 // The launcher of the merged step for both slab layouts (a0_internal.h).  head.kt = 0 — c51 / qr: the head GEMM leaves [nslab][E][ld], 160 KB of LDS at most, its width
 // the padded row's where the slab sum runs 16 bytes wide; head.kt = 1 — the quantile networks (iqn: mean over the K sampled quantiles, mode 1; fqf: sum over the F
 // fractions weighted by their widths, mode 3): the head GEMM over E * T rows leaves [nslab][E * T][ld] (a0_dense_fwd_partial), 64 KB at most.  Per env one workgroup sums
@@ -116,11 +124,8 @@ __global__ __launch_bounds__(512) void a0_actor_dist_tail_env_kernel(a0_dtenv_ar
 // an actor step is encoder-less between a rollout's first and last step.
 int a0_actor_slab_tail_env_launch(const a0_slab_head& h, int E, const a0_step_draw& draw, const a0_env_commit& env, const a0_next_enc* next, hipStream_t st) {
     const std::string who = std::string(h.kt ? "a0_actor_quantile_tail_env_step" : "a0_actor_dist_tail_env_step") + (next ? "_enc" : "");
-    const int A = h.A, T = h.T, other = h.kt ? 3 : 2;
-    if (!h.slabs || !h.bias || !draw.action || !draw.qmax || E < 1 || A < 1 || T < 1 || h.nslab < 1 ||
-        (h.kt ? h.ld < A + (h.dueling ? 1 : 0) || h.slab_stride < (long long)E * T * h.ld : h.ld < A * T + (h.dueling ? T : 0) || h.slab_stride < (long long)E * h.ld) ||
-        (h.mode != 1 && h.mode != other) || (h.mode == other && !(h.kt ? h.taus : h.atoms)))
-        return a0_fail(A0_EINVAL, (who + ": bad argument").c_str());
+    const int A = h.A, T = h.T;
+    if (!a0_slab_head_ok(h, E, draw)) return a0_fail(A0_EINVAL, (who + ": bad argument").c_str());
     { const int rc = a0_env_commit_check(env, E, A, who.c_str()); if (rc != A0_OK) return rc; }
     const bool vec4 = !(h.ld & 3) && !(h.slab_stride & 3) && !((((uintptr_t)h.slabs) | ((uintptr_t)h.bias)) & 15);
     const size_t lds = (size_t)(h.kt || (A * T + T) > h.ld || !vec4 ? (A * T + T) : h.ld) * sizeof(float);
@@ -204,41 +209,53 @@ __global__ __launch_bounds__(64) void a0_actor_quantile_tail_kernel(a0_dtenv_arg
     a0_actor_dist_tail_wave0<false>(P, xs, nullptr, 0u, 0, a0_u4{0u, 0u, 0u, 0u});
 }
 
+// The launcher of both slab tails WITHOUT an env step (a0_internal.h): head.kt = 0 — a0_actor_dist_tail_kernel, four envs per workgroup, 160 KB of LDS at most; head.kt = 1 —
+// a0_actor_quantile_tail_kernel, an env per workgroup, 64 KB at most.  The exported a0_actor_dist_tail / a0_actor_quantile_tail pack into it, under whose names its errors
+// read; the actor handle's rollout over a host-env pool calls it with the descriptors it fills for the merged step.
+int a0_actor_slab_tail_launch(const a0_slab_head& h, int E, const a0_step_draw& d, hipStream_t st) {
+    static const char* const MSG[2][4] = {
+        {"a0_actor_dist_tail: bad argument", "a0_actor_dist_tail: head too wide for LDS", "a0_actor_dist_tail: LDS", "a0_actor_dist_tail"},
+        {"a0_actor_quantile_tail: bad argument", "a0_actor_quantile_tail: head too wide for LDS", "a0_actor_quantile_tail: LDS", "a0_actor_quantile_tail"}};
+    const char* const* msg = MSG[h.kt ? 1 : 0];
+    if (!a0_slab_head_ok(h, E, d)) return a0_fail(A0_EINVAL, msg[0]);
+    const int A = h.A, T = h.T;
+    const size_t lds = (size_t)(h.kt ? 1 : 4) * (A * T + T) * sizeof(float);
+    if (lds > (size_t)(h.kt ? 64 : 160) * 1024) return a0_fail(A0_EINVAL, msg[1]);
+    if (h.kt) {
+        a0_dtenv_args P = {};
+        P.slabs = h.slabs; P.slab_stride = h.slab_stride; P.nslab = h.nslab; P.bias = h.bias; P.ld = h.ld; P.A = A; P.T = T; P.dueling = h.dueling; P.mode = h.mode; P.atoms = nullptr; P.E = E;
+        P.rng_seed = d.seed; P.stream_a = d.stream_a; P.stream_u = d.stream_u; P.off_a = d.off_a; P.off_u = d.off_u; P.eps = d.eps; P.ctrl = d.ctrl; P.eps_ptr = d.eps_ptr;
+        P.action = d.action; P.qmax = d.qmax;
+        P.task = A0_ENV_TASK_STREAM;
+        P.kt = 1; P.taus = h.taus;
+        P.vec4 = (!(h.ld & 3) && !(h.slab_stride & 3) && !((((uintptr_t)h.slabs) | ((uintptr_t)h.bias)) & 15)) ? 1 : 0;
+        hipLaunchKernelGGL(a0_actor_quantile_tail_kernel, dim3(E), dim3(64), lds, st, P);
+        return a0_fail_hip((int)hipGetLastError(), msg[3]);
+    }
+    static size_t configured = 0;
+    if (lds > configured) {
+        if (hipFuncSetAttribute((const void*)a0_actor_dist_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return a0_fail(A0_EINVAL, msg[2]);
+        configured = lds;
+    }
+    hipLaunchKernelGGL(a0_actor_dist_tail_kernel, dim3((E + 3) / 4), dim3(256), lds, st, h.slabs, h.slab_stride, h.nslab, h.bias, h.ld, A, T, h.dueling, h.mode, h.atoms, E,
+                       d.seed, d.stream_a, d.stream_u, d.off_a, d.off_u, d.eps, d.ctrl, d.eps_ptr, d.action, d.qmax);
+    return a0_fail_hip((int)hipGetLastError(), msg[3]);
+}
+
+// mode 1: mean over the T sampled quantiles (iqn); mode 3: the fractions' widths from `taus` [E][T + 1] (fqf)
 extern "C" int a0_actor_quantile_tail(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
                                       const float* taus, int E, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                                       unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
-    if (!slabs || !bias || !action || !qmax || E < 1 || A < 1 || T < 1 || nslab < 1 || ld < A + (dueling ? 1 : 0) || slab_stride < (long long)E * T * ld ||
-        (mode != 1 && mode != 3) || (mode == 3 && !taus))
-        return a0_fail(A0_EINVAL, "a0_actor_quantile_tail: bad argument");
-    const size_t lds = (size_t)(A * T + T) * sizeof(float);
-    if (lds > 64 * 1024) return a0_fail(A0_EINVAL, "a0_actor_quantile_tail: head too wide for LDS");
-    a0_dtenv_args P = {};
-    P.slabs = slabs; P.slab_stride = slab_stride; P.nslab = nslab; P.bias = bias; P.ld = ld; P.A = A; P.T = T; P.dueling = dueling; P.mode = mode; P.atoms = nullptr; P.E = E;
-    P.rng_seed = seed; P.stream_a = stream_a; P.stream_u = stream_u; P.off_a = off_a; P.off_u = off_u; P.eps = eps; P.ctrl = ctrl; P.eps_ptr = eps_ptr;
-    P.action = action; P.qmax = qmax;
-    P.task = A0_ENV_TASK_STREAM;
-    P.kt = 1; P.taus = taus;
-    P.vec4 = (!(ld & 3) && !(slab_stride & 3) && !((((uintptr_t)slabs) | ((uintptr_t)bias)) & 15)) ? 1 : 0;
-    hipLaunchKernelGGL(a0_actor_quantile_tail_kernel, dim3(E), dim3(64), lds, (hipStream_t)stream, P);
-    return a0_fail_hip((int)hipGetLastError(), "a0_actor_quantile_tail");
+    const a0_slab_head head{slabs, slab_stride, nslab, bias, ld, A, T, dueling, mode, nullptr, taus, 1};
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    return a0_actor_slab_tail_launch(head, E, draw, (hipStream_t)stream);
 }
 
 // mode 1: mean over the T quantiles (qr); mode 2: C51 expectation with `atoms` [T]
 extern "C" int a0_actor_dist_tail(const float* slabs, long long slab_stride, int nslab, const float* bias, int ld, int A, int T, int dueling, int mode,
                                   const float* atoms, int E, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
                                   unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
-    if (!slabs || !bias || !action || !qmax || E < 1 || A < 1 || T < 1 || nslab < 1 || ld < A * T + (dueling ? T : 0) || slab_stride < (long long)E * ld ||
-        (mode != 1 && mode != 2) || (mode == 2 && !atoms))
-        return a0_fail(A0_EINVAL, "a0_actor_dist_tail: bad argument");
-    const size_t lds = (size_t)4 * (A * T + T) * sizeof(float);
-    if (lds > 160 * 1024) return a0_fail(A0_EINVAL, "a0_actor_dist_tail: head too wide for LDS");
-    static size_t configured = 0;
-    if (lds > configured) {
-        if (hipFuncSetAttribute((const void*)a0_actor_dist_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return a0_fail(A0_EINVAL, "a0_actor_dist_tail: LDS");
-        configured = lds;
-    }
-    hipLaunchKernelGGL(a0_actor_dist_tail_kernel, dim3((E + 3) / 4), dim3(256), lds, (hipStream_t)stream, slabs, slab_stride, nslab, bias, ld, A, T, dueling, mode, atoms, E,
-                       seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax);
-    return a0_fail_hip((int)hipGetLastError(), "a0_actor_dist_tail");
+    const a0_slab_head head{slabs, slab_stride, nslab, bias, ld, A, T, dueling, mode, atoms, nullptr, 0};
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    return a0_actor_slab_tail_launch(head, E, draw, (hipStream_t)stream);
 }

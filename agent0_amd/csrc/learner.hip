@@ -138,8 +138,8 @@ static int a0_ws_common(a0_learner* L, const a0_learner_buffers& U) {
     L->noise = L->alloc<float>(2 * L->noise_len, true);
     // BaseLearner.__init__ builds the online and the target network, and a NoisyLinear draws its first noise when it is built (model.py:44-52): the two
     // networks' first draws come off the learner's stream here, so that the updates' draws continue where the Python classes' do
-    const unsigned long long o = L->rng.reserve(4, L->noise_len);
-    (void)L->rng.reserve(4, L->noise_len);
+    const unsigned long long o = L->rng.reserve(STREAM_NOISE, L->noise_len);
+    (void)L->rng.reserve(STREAM_NOISE, L->noise_len);
     A0_CHECK(a0_rng_normal(L->rng.seed, 4, o, 0.1f, L->noise, 2 * L->noise_len, nullptr));
     A0_HIP_THROW(hipDeviceSynchronize());
     return A0_OK;
@@ -539,7 +539,7 @@ static int a0_upd_prepare(a0_upd& u, const uint8_t* frames, const int* slot, lon
     u.f_next = a0_frames_arg{frames, slot, row_bytes, obs}; u.f_obs = a0_frames_arg{frames, slot, row_bytes, 0};
     if (!L->d.noisy) return A0_OK;
     const long long nn = 2 * L->noise_len;
-    A0_CHECK(a0_rng_normal(L->rng.seed, 4 /* STREAM_NOISE */, L->rng.reserve(4, nn), 0.1f, L->noise, nn, u.stream));
+    A0_CHECK(a0_rng_normal(L->rng.seed, STREAM_NOISE, L->rng.reserve(STREAM_NOISE, nn), 0.1f, L->noise, nn, u.stream));
     return a0_noisy(u, false);
 }
 
@@ -605,9 +605,9 @@ static int a0_fwd_fqf(a0_upd& u) {
 // K, N', N fractions per sample, Philox stream 3)
 static int a0_fwd_iqn(a0_upd& u) {
     a0_learner* L = u.L; void* stream = u.stream; const int B = L->d.B, A = L->d.A, dq = L->d.double_q ? 1 : 0, K = L->d.iqn_K, N = L->d.iqn_N, Nd = L->d.iqn_N_dash;
-    A0_CHECK(a0_rng_uniform(L->rng.seed, 3, L->rng.reserve(3, (long long)B * K), L->t_sel, (long long)B * K, stream));
-    A0_CHECK(a0_rng_uniform(L->rng.seed, 3, L->rng.reserve(3, (long long)B * Nd), L->t_tgt, (long long)B * Nd, stream));
-    A0_CHECK(a0_rng_uniform(L->rng.seed, 3, L->rng.reserve(3, (long long)B * N), L->t_on, (long long)B * N, stream));
+    A0_CHECK(a0_rng_uniform(L->rng.seed, STREAM_TAUS, L->rng.reserve(STREAM_TAUS, (long long)B * K), L->t_sel, (long long)B * K, stream));
+    A0_CHECK(a0_rng_uniform(L->rng.seed, STREAM_TAUS, L->rng.reserve(STREAM_TAUS, (long long)B * Nd), L->t_tgt, (long long)B * Nd, stream));
+    A0_CHECK(a0_rng_uniform(L->rng.seed, STREAM_TAUS, L->rng.reserve(STREAM_TAUS, (long long)B * N), L->t_on, (long long)B * N, stream));
     A0_CHECK(a0_upd_encode(u, {{true, true, L->act3_t, false}, {false, true, dq ? L->act3_s : nullptr, false}, {false, false, L->act3_o, true}}));
     // greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
     a0_learner::QWs& sel = dq ? L->qs : L->qt;

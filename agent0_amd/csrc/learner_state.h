@@ -10,6 +10,8 @@ struct Blk { long long off; int N, K; long long w() const { return off; } long l
 
 static inline long long ceil_to(long long x, long long m) { return (x + m - 1) / m * m; }
 
+// the two Philox streams both the learner and the actor handle draw from (a0_internal.h lists all ids): quantile fractions, NoisyNet noise
+constexpr int STREAM_TAUS = 3, STREAM_NOISE = 4;
 // agent0_amd/common/utils.py DeviceRng: per-stream running offsets, every reservation rounded up to a multiple of four draws
 struct a0_host_rng {
     unsigned long long seed = 0;

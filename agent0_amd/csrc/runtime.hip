@@ -334,6 +334,19 @@ static a0_actor_net a0_actor_view(const a0_actor* a, a0_learner* L) {
     return a0_actor_net{L->online, L->wt_on, L->eff_on, L->noise, L};
 }
 
+// How the actor gets from a step's features to its action: the scalar tail (dqn, mdqn: fc1 and the head inside the tail's launches), or a tail over the head GEMM's
+// split-K slabs with a row per env (c51, qr) or a row per env and fraction (iqn, fqf).  Not the learner's a0_family: a layerwise qr learner still acts through the slab
+// tail.  nt: fractions per env and step (agent.py:25-39 with IQNHead.qval / FQFHead.qval, model.py:253-257,280-284); rows = E * nt, the rows of the head's GEMMs.
+enum a0_actor_kind { A0_ACT_SCALAR, A0_ACT_SLAB_DIST, A0_ACT_SLAB_QUANTILE };
+struct a0_actor_head { a0_actor_kind kind; bool fqf; int nt, rows; };
+static a0_actor_head a0_actor_head_of(const a0_actor* a, const a0_learner* L) {
+    const int algo = L->d.algo;
+    const bool fqf = algo == A0_ALGO_FQF;
+    const a0_actor_kind kind = algo == A0_ALGO_IQN || fqf ? A0_ACT_SLAB_QUANTILE : algo == A0_ALGO_C51 || algo == A0_ALGO_QR ? A0_ACT_SLAB_DIST : A0_ACT_SCALAR;
+    const int nt = fqf ? L->F : kind == A0_ACT_SLAB_QUANTILE ? L->d.iqn_K : 1;
+    return a0_actor_head{kind, fqf, nt, a->E * nt};
+}
+
 // Every workspace a rollout with `learner` needs — the distributional / quantile heads' buffers, sized by the learner's head — and, own_network != 0, the actor's own
 // copy of the network (a0_actor_snapshot fills it).  Call it once at set-up: a0_actor_rollout then neither allocates nor synchronises (an unbound actor is bound at its
 // first rollout, which does both).
@@ -342,12 +355,13 @@ extern "C" int a0_actor_bind(a0_actor* a, const a0_learner* L, int own_network) 
     if (!a || !L) return a0_fail(A0_EINVAL, "a0_actor_bind: null argument");
     if (L->d.A != a->d.A || (L->d.dueling != 0) != (a->d.dueling != 0)) return a0_fail(A0_EINVAL, "a0_actor_bind: actor and learner were created for different heads");
     const int E = a->E;
-    const bool dist = L->d.algo == A0_ALGO_C51 || L->d.algo == A0_ALGO_QR, fqf = L->d.algo == A0_ALGO_FQF, quant = L->d.algo == A0_ALGO_IQN || fqf;
+    const a0_actor_head H = a0_actor_head_of(a, L);
+    const bool fqf = H.fqf;
     if (a->bound && a->dist_Npad != L->Npad) return a0_fail(A0_EINVAL, "a0_actor_bind: this actor was sized for another head");
     if (!a->bound) {
-        const int nt = fqf ? L->F : (quant ? L->d.iqn_K : 1);
-        if (quant) {
-            const long long R = (long long)E * nt;
+        const int nt = H.nt;
+        if (H.kind == A0_ACT_SLAB_QUANTILE) {
+            const long long R = H.rows;
             if (a0_dense_fwd_scratch((int)R, L->feat, 64) != 0) return a0_fail(A0_EINVAL, "a0_actor_bind: E * K rows too few for the embedding kernel this path takes");
             a->h = a->mem.alloc<float>(R * 512);
             a->head_slabs = a->mem.alloc<float>((long long)a0_dense_fwd_partial_slabs((int)R, L->Npad, 512) * R * L->Npad);
@@ -357,7 +371,7 @@ extern "C" int a0_actor_bind(a0_actor* a, const a0_learner* L, int own_network) 
             a->q_taus = a->mem.alloc<float>(ceil_to(R, 4)); a->q_cosx = a->mem.alloc<float>(R * 64); a->q_x = a->mem.alloc<float>(R * L->feat);
             if (fqf) { a->f_logits = a->mem.alloc<float>((long long)E * 32); a->f_tau_all = a->mem.alloc<float>((long long)E * (nt + 1)); }
             if (a0_dense_fwd_wplanes_ok((int)R, 512, L->feat)) a->w_planes = a->mem.alloc<unsigned int>(a0_weight_planes_words(512, L->feat), false);
-        } else if (dist) {
+        } else if (H.kind == A0_ACT_SLAB_DIST) {
             a->h = a->mem.alloc<float>((long long)E * 512);
             a->head_slabs = a->mem.alloc<float>((long long)a0_dense_fwd_partial_slabs(E, L->Npad, 512) * E * L->Npad);
             const long long sc = a0_dense_fwd_scratch(E, 512, L->feat);
@@ -496,9 +510,6 @@ static int a0_pool_wait(const a0_env_pool_desc& P, long long seq) {
     }
 }
 
-// Actor.sample (agent.py:44-90) with the learner's online network: T steps of [encoder, fc1 GEMM, tail + env step + n-step bookkeeping + replay row], the
-// rows written straight into the ring at its write cursor (call a0_rbuf_commit(replay, T * E) afterwards: ReplayDataset.extend), then the per-step mean max-Q.
-// Asynchronous like everything else; a0_actor_collect waits and returns the statistics.
 // the online network's effective weights from its parameters and the noise vectors it currently holds (DeviceNet.compose_noise)
 static int a0_actor_compose(const a0_actor_net& V, void* stream) {
     const a0_learner* L = V.L;
@@ -514,57 +525,174 @@ static int a0_actor_compose(const a0_actor_net& V, void* stream) {
     return a0_noisy_multi(0, L->n_mods, mu, sg, eff, N, K, r0, r1, nin, nw, nb, stream);
 }
 
-// Actor._rollout_host over an attached pool (a0_env_pool_desc): the inference of Actor._act_device (the head's tail without an env step), the send, the wait for
-// the workers, the DMA-only upload and one ingest launch per step.  The step's bookkeeping runs ahead of the next step's inference (the Python classes enqueue it
-// after the next send); the kernels and their arguments are the same, so are the bytes.
-static int a0_actor_rollout_pool(a0_actor* a, a0_learner* L, a0_rbuf* R, float epsilon, const float* eps_vec, const a0_actor_net& V, a0_encoder_weights& w, long long start, void* stream) {
-    a0_env_pool_desc& P = a->pool;
-    const int E = a->E, A = a->d.A;
-    const bool dist = L->d.algo == A0_ALGO_C51 || L->d.algo == A0_ALGO_QR, fqf = L->d.algo == A0_ALGO_FQF, quant = L->d.algo == A0_ALGO_IQN || fqf;
-    const int freq = a->d.reset_noise_freq > 0 ? a->d.reset_noise_freq : 4;
-    const int nt = fqf ? L->F : (quant ? L->d.iqn_K : 1);
-    if (!quant && !dist && A + (a->d.dueling ? 1 : 0) > 24) return a0_fail(A0_EINVAL, "a0_actor_rollout: scalar heads with A + dueling <= 24 actions");
-    for (int t = 0; t < a->T; ++t) {
-        if (L->d.noisy && a->steps % freq == 0) {
-            A0_CHECK(a0_rng_normal(a->rng.seed, 4 /* STREAM_NOISE */, a->rng.reserve(4, L->noise_len), 0.1f, V.noise, L->noise_len, stream));
-            A0_CHECK(a0_actor_compose(V, stream));
+// ---- a0_actor_rollout in stages, named after Actor._rollout (agent0_amd/deepq/agent.py) where it has a name.  a0_roll: what one call reads, decided once in a0_roll_begin.
+struct a0_roll {
+    a0_actor* a; a0_learner* L; a0_rbuf* R; void* stream;
+    a0_actor_net V; a0_encoder_weights w;      // the network the actor acts with, its convolution weights
+    int E; a0_actor_head H; int freq;          // freq: steps between two NoisyNet resets
+    float epsilon; const float* eps_vec;       // actor.eps_ladder: A0_EPS_PER_ENV and the per-env epsilons; off: the caller's epsilon and a null pointer, as ever
+    long long start;                           // the ring's write cursor when the rollout starts
+    bool planes, fc1p;                         // which laid-out copies of fc1's weights this rollout reads (w_planes, fc1_planes): none over a pool
+    bool step_enc;                             // the tail's launch of step t also encodes the env's new observation for step t + 1
+    bool noise_due() const { return L->d.noisy && a->steps % freq == 0; }      // agent.py:52-53: self.model.reset_noise() every reset_noise_freq steps
+};
+
+// part 1: the argument checks, what no step of the rollout could run (refused before anything is launched), the workspaces, the network, the epsilons
+static int a0_roll_begin(a0_roll& r, a0_actor* a, a0_learner* L, a0_rbuf* R, float epsilon, void* stream) {
+    if (!a || !L || !R) return a0_fail(A0_EINVAL, "a0_actor_rollout: null argument");
+    if (L->d.A != a->d.A || (L->d.dueling != 0) != (a->d.dueling != 0) || R->obs_bytes != a->obs_bytes || R->size < a->E)
+        return a0_fail(A0_EINVAL, "a0_actor_rollout: actor, learner and replay were created for different shapes");
+    r.a = a; r.L = L; r.R = R; r.stream = stream;
+    r.E = a->E; r.H = a0_actor_head_of(a, L);
+    r.freq = a->d.reset_noise_freq > 0 ? a->d.reset_noise_freq : 4;
+    if (r.H.kind == A0_ACT_SCALAR && a->d.A + (a->d.dueling ? 1 : 0) > 24) return a0_fail(A0_EINVAL, "a0_actor_rollout: scalar heads with A + dueling <= 24 actions");
+    // (over a pool the tail's own launcher refuses the same width, under its own name)
+    if (r.H.kind == A0_ACT_SLAB_DIST && !a->pool_on && 4LL * ((long long)a->d.A * L->T + L->T) * 4 > 160 * 1024)
+        return a0_fail(A0_EINVAL, "a0_actor_rollout: head too wide for the distributional tail kernel");
+    if (!a->bound || a->dist_Npad != L->Npad) A0_CHECK(a0_actor_bind(a, L, 0));      // (a host that wants no allocation after set-up binds there)
+    r.V = a0_actor_view(a, L);
+    r.w = L->enc(r.V.flat);
+    r.start = R->written % R->size;
+    r.planes = r.fc1p = false;
+    // scalar, c51 / qr and quantile heads alike (Actor._rollout): a step's ONE launch for tail + env step goes on to encode the env's new observation, so that step t + 1
+    // starts with its features in place; the convolution weights do not change inside a rollout, the last step has no next one
+    // (not for an actor with its own network — the launch schedule: its rollout runs beside the update block, the critical path there, and a workgroup that holds a CU's
+    // LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives: 9.43 -> 9.75 ms)
+    r.step_enc = !a->pool_on && !a->own_flat;
+    // NoisyLinear.forward composes mu + sigma * eps with the parameters as they are NOW (model.py:54-62): a rollout that does not start on a noise reset
+    // recomposes the copies once (agent0_amd/deepq/agent.py Actor._rollout)
+    if (L->d.noisy && !r.noise_due()) A0_CHECK(a0_actor_compose(r.V, stream));
+    // actor.eps_ladder: the rollout's per-env epsilons, once; every tail then reads its env's own entry
+    r.epsilon = epsilon; r.eps_vec = nullptr;
+    if (a->ladder_alpha > 0.f) {
+        A0_CHECK(a0_eps_ladder(epsilon, nullptr, a->ladder_alpha, r.E, a->ladder_i0, a->ladder_n, a->eps_vec, stream));
+        r.eps_vec = a->eps_vec;
+        r.epsilon = A0_EPS_PER_ENV;
+    }
+    return A0_OK;
+}
+
+// fc1's weights do not change inside a rollout (but for a noise reset): laid out once at the start of a device-env rollout.  Quantile actors (round 6): bf16 term planes
+// for the rollout's GEMMs of E * K rows, split here instead of in every tile of every GEMM; scalar and c51 / qr actors: fragment-ordered planes for the T launches of
+// actor_fc1.hip.  The same exact terms, the same bits.  Every rollout start: also what keeps them right after an optimizer step, a0_actor_snapshot, a0_load_snapshot
+// or a checkpoint load.  (A rollout that starts on a noise reset lays them out there, behind its compose.)
+static int a0_roll_layout_planes(a0_roll& r) {
+    a0_actor* a = r.a; const a0_learner* L = r.L;
+    const bool quant = r.H.kind == A0_ACT_SLAB_QUANTILE;
+    r.planes = quant && a->w_planes && a0_dense_fwd_wplanes_ok(r.H.rows, 512, L->feat);
+    r.fc1p = !quant && a->fc1_planes_on && a->fc1_planes && a->feat == L->feat &&
+             (r.H.kind == A0_ACT_SLAB_DIST ? a0_actor_fc1_dense_ok(r.E, 512, a->feat) : a0_actor_fc1_ok(r.E, 512, a->feat));
+    a->fc1_launches += r.fc1p ? a->T : 0;
+    if (r.noise_due()) return A0_OK;
+    if (r.planes) A0_CHECK(a0_split_planes(r.V.Wf(), a->w_planes, 512, L->feat, r.stream));
+    if (r.fc1p) A0_CHECK(a0_actor_fc1_planes(r.V.Wf(), a->fc1_planes, 512, a->feat, r.stream));
+    return A0_OK;
+}
+
+// self.model.reset_noise() from the ACTOR's stream, where a step is due one: fresh noise vectors, the composed weights, and every laid-out copy of them this rollout reads
+static int a0_roll_noise_reset(a0_roll& r) {
+    if (!r.noise_due()) return A0_OK;
+    a0_actor* a = r.a; const a0_learner* L = r.L;
+    A0_CHECK(a0_rng_normal(a->rng.seed, STREAM_NOISE, a->rng.reserve(STREAM_NOISE, L->noise_len), 0.1f, r.V.noise, L->noise_len, r.stream));
+    A0_CHECK(a0_actor_compose(r.V, r.stream));
+    if (r.planes) A0_CHECK(a0_split_planes(r.V.Wf(), a->w_planes, 512, L->feat, r.stream));
+    if (r.fc1p) A0_CHECK(a0_actor_fc1_planes(r.V.Wf(), a->fc1_planes, 512, a->feat, r.stream));
+    return A0_OK;
+}
+
+// From the step's features (act3) to the head GEMM's split-K slabs, described in *head for the tail; scalar heads have no such chain (fc1 and the head run inside
+// their tail's launches) and leave *head alone.  Quantile (Actor._quant_tail_args): the step's fractions — fqf: the fraction net on the features, no draws
+// (FQFHead.prop_taus, model.py:268-278); iqn: nt per env from the actor's Philox stream STREAM_TAUS — with their cosine features in the same launch (round 6), the
+// embedding times the features in the embedding GEMM's epilogue, then fc1 and the head partial over E * nt rows.  c51 / qr (Actor._dist_tail_args): fc1 and the head
+// partial over E rows.  fc1 reads laid-out weights where the rollout has them (a0_roll_layout_planes).
+static int a0_roll_head(a0_roll& r, a0_slab_head* head) {
+    if (r.H.kind == A0_ACT_SCALAR) return A0_OK;
+    a0_actor* a = r.a; const a0_learner* L = r.L; const a0_actor_net& V = r.V; void* stream = r.stream;
+    const int E = r.E, nt = r.H.nt, rows = r.H.rows, dueling = a->d.dueling ? 1 : 0;
+    const bool quant = r.H.kind == A0_ACT_SLAB_QUANTILE, fqf = r.H.fqf, c51 = L->d.algo == A0_ALGO_C51;
+    const float* x = a->act3;      // fc1's input
+    if (quant) {
+        const float* on = V.flat;
+        if (fqf) {
+            A0_CHECK(a0_dense_fwd(a->act3, L->feat, on + L->frac.w(), on + L->frac.b(), a->f_logits, E, 32, L->feat, 0, a->fwd_scratch, stream));
+            A0_CHECK(a0_fqf_taus_cos(a->f_logits, 32, a->f_tau_all, a->q_taus, a->q_cosx, 64, E, nt, stream));
+        } else {
+            A0_CHECK(a0_tau_cos_features(a->rng.seed, STREAM_TAUS, a->rng.reserve(STREAM_TAUS, rows), nullptr, 0, a->q_taus, a->q_cosx, rows, 64, stream));
         }
+        A0_CHECK(a0_dense_fwd_mul(a->q_cosx, 64, on + L->cos.w(), on + L->cos.b(), a->act3, nt, a->q_x, rows, L->feat, 64, 1, stream));
+        x = a->q_x;
+    }
+    if (r.planes) A0_CHECK(a0_dense_fwd_wplanes(x, L->feat, a->w_planes, V.bf(), a->h, rows, 512, L->feat, 1, stream));
+    else if (r.fc1p) A0_CHECK(a0_actor_fc1_dense(x, L->feat, a->fc1_planes, V.bf(), a->h, rows, 512, L->feat, 1, a->fwd_scratch, stream));
+    else A0_CHECK(a0_dense_fwd(x, L->feat, V.Wf(), V.bf(), a->h, rows, 512, L->feat, 1, a->fwd_scratch, stream));
+    const int ns = a0_dense_fwd_partial_slabs(rows, L->Npad, 512);
+    A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), rows, L->Npad, 512, a->head_slabs, stream));
+    if (quant) *head = a0_slab_head{a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, a->d.A, nt, dueling, fqf ? 3 : 1, nullptr, fqf ? a->f_tau_all : nullptr, 1};
+    else *head = a0_slab_head{a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, a->d.A, L->T, dueling, c51 ? 2 : 1, c51 ? L->atoms : nullptr, nullptr, 0};
+    return A0_OK;
+}
+
+// step t's epsilon-greedy draw: its two offsets in the actor's Philox streams (reserved behind the step's fractions), where the action and max_a q go
+static a0_step_draw a0_roll_draw(a0_roll& r, int t) {
+    a0_actor* a = r.a;
+    const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, r.E), ou = a->rng.reserve(STREAM_EGREEDY_U, r.E);
+    return a0_step_draw{a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, r.epsilon, nullptr, r.eps_vec, a->action, a->qmax_all + (long long)t * r.E};
+}
+
+// Actor._rollout on the device env: T steps of [encoder unless the step before left the features, the head's chain, ONE launch for the tail (slab sum + bias, dueling,
+// action values, first-max argmax, epsilon-greedy) + env step + n-step bookkeeping + replay row (+ the next step's encoder)] (actor_step.h, act_step_commit)
+static int a0_roll_device(a0_roll& r) {
+    a0_actor* a = r.a; a0_learner* L = r.L; a0_rbuf* R = r.R; const a0_actor_net& V = r.V;
+    const int E = r.E;
+    A0_CHECK(a0_roll_layout_planes(r));
+    bool feat_ready = false;
+    for (int t = 0; t < a->T; ++t) {
+        A0_CHECK(a0_roll_noise_reset(r));
+        const uint8_t* cur_obs = a->obs[a->cur];
+        a0_frames_arg f{cur_obs, nullptr, (long long)a->obs_bytes, 0};
+        if (!feat_ready) A0_CHECK(a0_net_encoder_fwd_fused(L->C, L->H, L->W, V.wt, &r.w, &f, E, nullptr, nullptr, a->act3, r.stream));
+        a0_slab_head head{};
+        A0_CHECK(a0_roll_head(r, &head));
+        const a0_step_draw draw = a0_roll_draw(r, t);
+        const long long back = (a->steps + 1 < a->n ? a->steps + 1 : a->n) - 1;                 // first observation of the emitted n-step transition
+        const uint8_t* obs0 = a->obs[((a->cur - back) % a->K + a->K) % a->K];
+        const int nx = (a->cur + 1) % a->K;
+        const a0_env_commit env{a->d.seed, a->d.rank, a->g + 1, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps, a->d.discount,
+                                a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (r.start + (long long)t * E) % R->size, R->act, R->rew, R->done, a->d.env_task};
+        const a0_next_enc enc{V.wt, &r.w, a->act3};
+        const a0_next_enc* const next = r.step_enc && t + 1 < a->T ? &enc : nullptr;
+        if (r.H.kind == A0_ACT_SCALAR)
+            A0_CHECK(a0_actor_qhead_env_launch(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), a->d.A, a->d.dueling ? 1 : 0, a->scratch, draw, env, next,
+                                               r.fc1p ? a->fc1_planes : nullptr, (hipStream_t)r.stream));
+        else A0_CHECK(a0_actor_slab_tail_env_launch(head, E, draw, env, next, (hipStream_t)r.stream));
+        a->g += 1; a->cur = nx; a->steps += 1;
+        feat_ready = next != nullptr;
+    }
+    return A0_OK;
+}
+
+// Actor._rollout_host over an attached pool (a0_env_pool_desc): the inference of Actor._act_device (the head's chain and its tail without an env step), the send, the
+// wait for the workers, the DMA-only upload and one ingest launch per step.  The step's bookkeeping runs ahead of the next step's inference (the Python classes enqueue
+// it after the next send); the kernels and their arguments are the same, so are the bytes.
+static int a0_roll_pool(a0_roll& r) {
+    a0_actor* a = r.a; a0_learner* L = r.L; a0_rbuf* R = r.R; const a0_actor_net& V = r.V; void* stream = r.stream;
+    a0_env_pool_desc& P = a->pool;
+    const int E = r.E;
+    for (int t = 0; t < a->T; ++t) {
+        A0_CHECK(a0_roll_noise_reset(r));
         const long long seq = P.seq + 1;
         const int half = (int)(seq & 1);
         const uint8_t* cur = (const uint8_t*)P.obs_dev[half ^ 1];
         uint8_t* nxt = (uint8_t*)P.obs_dev[half];
         a0_frames_arg f{cur, nullptr, (long long)a->obs_bytes, 0};
-        A0_CHECK(a0_net_encoder_fwd_fused(L->C, L->H, L->W, V.wt, &w, &f, E, nullptr, nullptr, a->act3, stream));
-        float* qm = a->qmax_all + (long long)t * E;
-        if (quant) {
-            const int rows = E * nt;
-            const float* on = V.flat;
-            if (fqf) {
-                A0_CHECK(a0_dense_fwd(a->act3, L->feat, on + L->frac.w(), on + L->frac.b(), a->f_logits, E, 32, L->feat, 0, a->fwd_scratch, stream));
-                A0_CHECK(a0_fqf_taus_cos(a->f_logits, 32, a->f_tau_all, a->q_taus, a->q_cosx, 64, E, nt, stream));
-            } else {
-                A0_CHECK(a0_tau_cos_features(a->rng.seed, 3 /* STREAM_TAUS */, a->rng.reserve(3, rows), nullptr, 0, a->q_taus, a->q_cosx, rows, 64, stream));
-            }
-            A0_CHECK(a0_dense_fwd_mul(a->q_cosx, 64, on + L->cos.w(), on + L->cos.b(), a->act3, nt, a->q_x, rows, L->feat, 64, 1, stream));
-            A0_CHECK(a0_dense_fwd(a->q_x, L->feat, V.Wf(), V.bf(), a->h, rows, 512, L->feat, 1, a->fwd_scratch, stream));
-            const int ns = a0_dense_fwd_partial_slabs(rows, L->Npad, 512);
-            A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), rows, L->Npad, 512, a->head_slabs, stream));
-            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
-            A0_CHECK(a0_actor_quantile_tail(a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, fqf ? a->f_tau_all : nullptr,
-                                            E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, qm, stream));
-        } else if (dist) {
-            A0_CHECK(a0_dense_fwd(a->act3, L->feat, V.Wf(), V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
-            const int ns = a0_dense_fwd_partial_slabs(E, L->Npad, 512);
-            A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), E, L->Npad, 512, a->head_slabs, stream));
-            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
-            A0_CHECK(a0_actor_dist_tail(a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, L->d.algo == A0_ALGO_C51 ? 2 : 1,
-                                        L->d.algo == A0_ALGO_C51 ? L->atoms : nullptr, E, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec,
-                                        a->action, qm, stream));
-        } else {
-            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
-            A0_CHECK(a0_actor_qhead(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0, a->scratch, a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U,
-                                    oa, ou, epsilon, nullptr, eps_vec, a->action, qm, stream));
-        }
+        A0_CHECK(a0_net_encoder_fwd_fused(L->C, L->H, L->W, V.wt, &r.w, &f, E, nullptr, nullptr, a->act3, stream));
+        a0_slab_head head{};
+        A0_CHECK(a0_roll_head(r, &head));
+        const a0_step_draw d = a0_roll_draw(r, t);
+        if (r.H.kind == A0_ACT_SCALAR)
+            A0_CHECK(a0_actor_qhead(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), a->d.A, a->d.dueling ? 1 : 0, a->scratch, d.seed, d.stream_a, d.stream_u, d.off_a, d.off_u,
+                                    d.eps, d.ctrl, d.eps_ptr, d.action, d.qmax, stream));
+        else A0_CHECK(a0_actor_slab_tail_launch(head, E, d, (hipStream_t)stream));
         A0_CHECK(a0_env_pool_send(a->action, (int*)P.act_dev, E, (long long*)P.ctl_dev, P.step_word | (seq & P.seq_mask), stream));
         A0_CHECK(a0_pool_wait(P, seq));
         int whole = 0;
@@ -572,136 +700,24 @@ static int a0_actor_rollout_pool(a0_actor* a, a0_learner* L, a0_rbuf* R, float e
                                     (const uint8_t*)P.obs_host[half], nullptr, nxt, E, P.nstack, P.frame_bytes, &whole, stream));
         a->pool_whole += whole;
         A0_CHECK(a0_host_step_ingest(cur, (const uint8_t*)P.new_dev, (const float*)P.scal_dev[half], nxt, E, P.nstack, P.frame_bytes, P.use_life_loss, a->action, a->n, a->n,
-                                     a->steps, a->d.discount, a->ring_act, a->ring_rew, a->ring_done, a->ring_obs, R->frames, R->size, (start + (long long)t * E) % R->size,
+                                     a->steps, a->d.discount, a->ring_act, a->ring_rew, a->ring_done, a->ring_obs, R->frames, R->size, (r.start + (long long)t * E) % R->size,
                                      R->act, R->rew, R->done, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, nullptr, stream));
         P.seq = seq;
         a->steps += 1;
     }
-    return a0_mean_rows(a->qmax_all, a->T, E, a->qs, stream);
+    return A0_OK;
 }
 
+// Actor.sample (agent.py:44-90) with the learner's online network, or the actor's own snapshot of it: T steps, the rows written straight into the ring at its write
+// cursor (call a0_rbuf_commit(replay, T * E) afterwards: ReplayDataset.extend), then the per-step mean max-Q.  Asynchronous like everything else; a0_actor_collect waits
+// and returns the statistics.
 extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float epsilon, void* stream) {
     A0_TRY
     a0_trace_scope range("rollout");
-    if (!a || !L || !R) return a0_fail(A0_EINVAL, "a0_actor_rollout: null argument");
-    if (L->d.A != a->d.A || (L->d.dueling != 0) != (a->d.dueling != 0) || R->obs_bytes != a->obs_bytes || R->size < a->E)
-        return a0_fail(A0_EINVAL, "a0_actor_rollout: actor, learner and replay were created for different shapes");
-    const int E = a->E, A = a->d.A;
-    const bool dist = L->d.algo == A0_ALGO_C51 || L->d.algo == A0_ALGO_QR, fqf = L->d.algo == A0_ALGO_FQF, quant = L->d.algo == A0_ALGO_IQN || fqf;
-    const int freq = a->d.reset_noise_freq > 0 ? a->d.reset_noise_freq : 4;
-    const int nt = fqf ? L->F : (quant ? L->d.iqn_K : 1);  // fractions per env and step (agent.py:25-39 with IQNHead.qval / FQFHead.qval, model.py:253-257,280-284)
-    if (!a->bound || a->dist_Npad != L->Npad) A0_CHECK(a0_actor_bind(a, L, 0));      // (a host that wants no allocation after set-up binds there)
-    const a0_actor_net V = a0_actor_view(a, L);
-    const long long start = R->written % R->size;
-    a0_encoder_weights w = L->enc(V.flat);
-    // NoisyLinear.forward composes mu + sigma * eps with the parameters as they are NOW (model.py:54-62): a rollout that does not start on a noise reset
-    // recomposes the copies once (agent0_amd/deepq/agent.py Actor._rollout)
-    if (L->d.noisy && a->steps % freq != 0) A0_CHECK(a0_actor_compose(V, stream));
-    // quantile actors (round 6): fc1's weight operand as term planes for the rollout's 80 GEMMs of E * K rows — split once here (and after every noise reset below)
-    // instead of in every tile of every GEMM; the same exact terms, the same bits
-    const bool planes = quant && a->w_planes && a0_dense_fwd_wplanes_ok(E * nt, 512, L->feat);
-    if (planes && !(L->d.noisy && a->steps % freq == 0)) A0_CHECK(a0_split_planes(V.Wf(), a->w_planes, 512, L->feat, stream));
-    // scalar heads (Actor._rollout): the tail + env-step launch of step t also encodes the env's new observation (a0_actor_qhead_env_step_enc), so that step t + 1
-    // starts with its features in place; the convolution weights do not change inside a rollout, the last step has no next one
-    // (not for an actor with its own network — the launch schedule: its rollout runs beside the update block, the critical path there, and a workgroup that holds a CU's
-    // LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives: 9.43 -> 9.75 ms)
-    // actor.eps_ladder: the rollout's per-env epsilons, once; every tail below then reads its env's own entry (off: epsilon and a null pointer, as ever)
-    const float* eps_vec = nullptr;
-    if (a->ladder_alpha > 0.f) {
-        A0_CHECK(a0_eps_ladder(epsilon, nullptr, a->ladder_alpha, E, a->ladder_i0, a->ladder_n, a->eps_vec, stream));
-        eps_vec = a->eps_vec;
-        epsilon = A0_EPS_PER_ENV;
-    }
-    if (a->pool_on) return a0_actor_rollout_pool(a, L, R, epsilon, eps_vec, V, w, start, stream);
-    // scalar and distributional heads: fc1's weights do not change inside a rollout either (but for a noise reset) — laid out once here for the rollout's T fc1 launches (actor_fc1.hip).
-    // Every rollout start: also what keeps them right after an optimizer step, a0_actor_snapshot, a0_load_snapshot or a checkpoint load
-    const bool fc1p = !quant && a->fc1_planes_on && a->fc1_planes && a->feat == L->feat && (dist ? a0_actor_fc1_dense_ok(E, 512, a->feat) : a0_actor_fc1_ok(E, 512, a->feat));
-    a->fc1_launches += fc1p ? a->T : 0;
-    if (fc1p && !(L->d.noisy && a->steps % freq == 0)) A0_CHECK(a0_actor_fc1_planes(V.Wf(), a->fc1_planes, 512, a->feat, stream));
-    const unsigned int* const w1p = fc1p ? a->fc1_planes : nullptr;
-    const bool step_enc = !a->own_flat;
-    bool feat_ready = false;
-    for (int t = 0; t < a->T; ++t) {
-        if (L->d.noisy && a->steps % freq == 0) {      // agent.py:52-53: self.model.reset_noise() every reset_noise_freq steps, from the ACTOR's stream
-            A0_CHECK(a0_rng_normal(a->rng.seed, 4 /* STREAM_NOISE */, a->rng.reserve(4, L->noise_len), 0.1f, V.noise, L->noise_len, stream));
-            A0_CHECK(a0_actor_compose(V, stream));
-            if (planes) A0_CHECK(a0_split_planes(V.Wf(), a->w_planes, 512, L->feat, stream));
-            if (fc1p) A0_CHECK(a0_actor_fc1_planes(V.Wf(), a->fc1_planes, 512, a->feat, stream));
-        }
-        const uint8_t* cur_obs = a->obs[a->cur];
-        a0_frames_arg f{cur_obs, nullptr, (long long)a->obs_bytes, 0};
-        if (!feat_ready) A0_CHECK(a0_net_encoder_fwd_fused(L->C, L->H, L->W, V.wt, &w, &f, E, nullptr, nullptr, a->act3, stream));
-        feat_ready = false;
-        const long long back = (a->steps + 1 < a->n ? a->steps + 1 : a->n) - 1;                 // first observation of the emitted n-step transition
-        const uint8_t* obs0 = a->obs[((a->cur - back) % a->K + a->K) % a->K];
-        // what the step's ONE launch for tail + env step carries besides its head (actor_step.h), filled once the branch below has reserved the draw's offsets and counted
-        // the step; and where that launch goes on to encode the env's new observation, so that the next step starts with its features
-        auto draw = [&](unsigned long long oa, unsigned long long ou) {
-            return a0_step_draw{a->rng.seed, STREAM_EGREEDY_A, STREAM_EGREEDY_U, oa, ou, epsilon, nullptr, eps_vec, a->action, a->qmax_all + (long long)t * E};
-        };
-        auto commit = [&](int nx) {
-            return a0_env_commit{a->d.seed, a->d.rank, a->g, cur_obs, a->obs[nx], a->ep_ret, a->stat_mask + (long long)t * E, a->stat_ret + (long long)t * E, a->n, a->steps, a->d.discount,
-                                 a->ring_act, a->ring_rew, a->ring_done, obs0, R->frames, R->size, (start + (long long)t * E) % R->size, R->act, R->rew, R->done, a->d.env_task};
-        };
-        const a0_next_enc enc{V.wt, &w, a->act3};
-        const a0_next_enc* const next = step_enc && t + 1 < a->T ? &enc : nullptr;
-        if (quant) {
-            // Actor._quant_tail_args + act_step_commit(kind = "quantile"): the step's K fractions per env from the actor's Philox stream 3, cosine features, the embedding
-            // times the features in the embedding GEMM's epilogue, fc1, the head GEMM's slabs, then ONE launch for slab sum + bias, dueling, the mean over the fractions,
-            // first-max argmax, epsilon-greedy, env step, n-step bookkeeping and the replay row
-            const int rows = E * nt;
-            const float* on = V.flat;
-            if (fqf) {      // FQFHead.prop_taus (model.py:268-278): the fraction net on the step's features; no draws
-                A0_CHECK(a0_dense_fwd(a->act3, L->feat, on + L->frac.w(), on + L->frac.b(), a->f_logits, E, 32, L->feat, 0, a->fwd_scratch, stream));
-                A0_CHECK(a0_fqf_taus_cos(a->f_logits, 32, a->f_tau_all, a->q_taus, a->q_cosx, 64, E, nt, stream));       // (round 6) + the cosine features of the tau_hats
-            } else {       // (round 6) the draw and its cosine features in one launch
-                A0_CHECK(a0_tau_cos_features(a->rng.seed, 3 /* STREAM_TAUS */, a->rng.reserve(3, rows), nullptr, 0, a->q_taus, a->q_cosx, rows, 64, stream));
-            }
-            A0_CHECK(a0_dense_fwd_mul(a->q_cosx, 64, on + L->cos.w(), on + L->cos.b(), a->act3, nt, a->q_x, rows, L->feat, 64, 1, stream));
-            if (planes) A0_CHECK(a0_dense_fwd_wplanes(a->q_x, L->feat, a->w_planes, V.bf(), a->h, rows, 512, L->feat, 1, stream));
-            else A0_CHECK(a0_dense_fwd(a->q_x, L->feat, V.Wf(), V.bf(), a->h, rows, 512, L->feat, 1, a->fwd_scratch, stream));
-            const int ns = a0_dense_fwd_partial_slabs(rows, L->Npad, 512);
-            A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), rows, L->Npad, 512, a->head_slabs, stream));
-            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
-            const int nx = (a->cur + 1) % a->K;
-            a->g += 1;
-            const a0_slab_head head{a->head_slabs, (long long)rows * L->Npad, ns, V.bh(), L->Npad, A, nt, a->d.dueling ? 1 : 0, fqf ? 3 : 1, nullptr, fqf ? a->f_tau_all : nullptr, 1};
-            A0_CHECK(a0_actor_slab_tail_env_launch(head, E, draw(oa, ou), commit(nx), next, (hipStream_t)stream));
-            feat_ready = next != nullptr;
-            a->cur = nx;
-            a->steps += 1;
-            continue;
-        }
-        if (dist) {
-            // fc1, the head GEMM's slabs, then ONE launch: slab sum + bias, dueling, expectation over the support, first-max argmax, epsilon-greedy, env step,
-            // n-step bookkeeping and the replay row (Actor._dist_tail_args + act_step_commit(kind = "dist"))
-            if (fc1p) A0_CHECK(a0_actor_fc1_dense(a->act3, L->feat, a->fc1_planes, V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
-            else A0_CHECK(a0_dense_fwd(a->act3, L->feat, V.Wf(), V.bf(), a->h, E, 512, L->feat, 1, a->fwd_scratch, stream));
-            const int ns = a0_dense_fwd_partial_slabs(E, L->Npad, 512);
-            A0_CHECK(a0_dense_fwd_partial(a->h, 512, V.Wh(), E, L->Npad, 512, a->head_slabs, stream));
-            const unsigned long long oa = a->rng.reserve(STREAM_EGREEDY_A, E), ou = a->rng.reserve(STREAM_EGREEDY_U, E);
-            const int nx = (a->cur + 1) % a->K;
-            a->g += 1;
-            if (4LL * ((long long)A * L->T + L->T) * 4 > 160 * 1024) return a0_fail(A0_EINVAL, "a0_actor_rollout: head too wide for the distributional tail kernel");
-            const bool c51 = L->d.algo == A0_ALGO_C51;
-            const a0_slab_head head{a->head_slabs, (long long)E * L->Npad, ns, V.bh(), L->Npad, A, L->T, a->d.dueling ? 1 : 0, c51 ? 2 : 1, c51 ? L->atoms : nullptr, nullptr, 0};
-            A0_CHECK(a0_actor_slab_tail_env_launch(head, E, draw(oa, ou), commit(nx), next, (hipStream_t)stream));
-            feat_ready = next != nullptr;
-            a->cur = nx;
-            a->steps += 1;
-            continue;
-        }
-        if (A + (a->d.dueling ? 1 : 0) > 24) return a0_fail(A0_EINVAL, "a0_actor_rollout: scalar heads with A + dueling <= 24 actions");
-        const unsigned long long off_a = a->rng.reserve(STREAM_EGREEDY_A, E), off_u = a->rng.reserve(STREAM_EGREEDY_U, E);
-        const int nxt = (a->cur + 1) % a->K;
-        a->g += 1;
-        A0_CHECK(a0_actor_qhead_env_launch(a->act3, E, a->feat, V.Wf(), V.bf(), V.Wh(), V.bh(), A, a->d.dueling ? 1 : 0, a->scratch, draw(off_a, off_u), commit(nxt), next, w1p,
-                                           (hipStream_t)stream));
-        feat_ready = next != nullptr;
-        a->cur = nxt;
-        a->steps += 1;
-    }
-    return a0_mean_rows(a->qmax_all, a->T, E, a->qs, stream);
+    a0_roll r;
+    A0_CHECK(a0_roll_begin(r, a, L, R, epsilon, stream));
+    A0_CHECK(a->pool_on ? a0_roll_pool(r) : a0_roll_device(r));
+    return a0_mean_rows(a->qmax_all, a->T, r.E, a->qs, stream);
     A0_CATCH
 }
 

@@ -3,7 +3,10 @@ the function's reporting name, before any HIP call: the pointers here are small 
 
 The two `_wp` forms report under the names of the plain forms they serve.  Check order: head arguments, then the env commit, then the 16-byte alignment of the
 observation buffers, then the head's width against LDS.  The env commit has thirteen pointers (obs_in, obs_out, ep_ret, final_mask, final_ret, the three n-step
-rings, obs0, frames and the replay row's three arrays); each is tried null."""
+rings, obs0, frames and the replay row's three arrays); each is tried null.
+
+The three tails WITHOUT an env step (a0_actor_dist_tail, a0_actor_quantile_tail, a0_actor_qhead: the actor steps over host environments) take the head and the draw
+alone and are held to the same: every pointer null, every range at its edge, the head's width against LDS, each under the function's own name."""
 import pytest
 
 EINVAL = -1
@@ -120,3 +123,61 @@ def test_head_argument_is_reported_before_env_argument(lib, fn):
     head = dict(K=6) if FUNCS[fn][1] == "scalar" else dict(nslab=0)
     msg = _refused(lib, fn, obs_in=None, n=0, **head)
     assert "bad argument" in msg and "env argument" not in msg
+
+
+# ---------------------------------------------------------------------------------------------- the tails without an env step
+TAILS = {"a0_actor_dist_tail": "dist", "a0_actor_quantile_tail": "quantile", "a0_actor_qhead": "scalar"}
+SLAB_TAILS = [f for f, v in TAILS.items() if v != "scalar"]
+
+
+def _tail_refused(lib, fn, **bad):
+    """Calls the tail `fn` (head arguments, the draw, the stream) with its valid arguments overridden by `bad`; asserts A0_EINVAL under its own name and returns the message."""
+    from agent0_amd import _abi
+    family = TAILS[fn]
+    a = dict(_scalar_head() if family == "scalar" else _slab_head(family == "quantile"))
+    a.update(DRAW)
+    a["stream"] = None
+    assert set(bad) <= set(a), bad
+    a.update(bad)
+    assert getattr(lib, fn)(*a.values()) == EINVAL, (fn, bad)
+    msg = _abi.last_error()
+    assert msg.startswith(fn + ":"), (fn, bad, msg)
+    return msg
+
+
+def _tail_cases(fn):
+    if TAILS[fn] == "scalar":      # K: a multiple of 4; A + dueling rows of 512 floats in 48 KB of LDS  (E and K below 1 are not tried: a0_actor_qhead sizes fc1's split from
+        # them in front of a0_actor_qhead_n's check)
+        return [{p: None} for p in ("feat", "W1", "b1", "W2", "b2", "scratch", "action", "qmax")] + [dict(K=6), dict(A=0), dict(A=24, dueling=1), dict(A=25, dueling=0)]
+    q = TAILS[fn] == "quantile"
+    ld_min, ld_min_duel = (4, 5) if q else (20, 25)
+    return [{p: None} for p in ("slabs", "bias", "action", "qmax")] + [dict(E=0), dict(A=0), dict(T=0), dict(nslab=0), dict(ld=ld_min - 1, dueling=0),
+                                                                          dict(ld=ld_min_duel - 1, dueling=1), dict(slab_stride=(3 * 5 * 24 if q else 3 * 24) - 1), dict(mode=0),
+                                                                          dict(mode=2 if q else 3), dict(mode=4), dict(aux=None)]
+
+
+@pytest.mark.parametrize("fn,bad", [(f, b) for f in TAILS for b in _tail_cases(f)], ids=lambda v: v if isinstance(v, str) else ",".join(f"{k}={x}" for k, x in v.items()))
+def test_tail_without_env_step_arguments(lib, fn, bad):
+    assert "bad argument" in _tail_refused(lib, fn, **bad)
+
+
+@pytest.mark.parametrize("fn", SLAB_TAILS)
+def test_tail_without_env_step_takes_the_other_mode_without_its_table(lib, fn):
+    """mode 1 (qr, iqn: a plain mean) needs neither atoms nor taus: with them null the call gets past the argument check and is refused for its width"""
+    wide = dict(T=3277, slab_stride=3 * 3277 * 24) if TAILS[fn] == "quantile" else dict(T=2049, ld=4 * 2049, slab_stride=3 * 4 * 2049)
+    assert _tail_refused(lib, fn, mode=1, aux=None, **wide) == fn + ": head too wide for LDS"
+
+
+@pytest.mark.parametrize("fn", SLAB_TAILS)
+def test_tail_without_env_step_head_too_wide_for_lds(lib, fn):
+    if TAILS[fn] == "quantile":
+        bad = dict(A=4, T=3277, slab_stride=3 * 3277 * 24)                 # a workgroup per env: (A * T + T) * 4 bytes = 65 540 > 64 KiB
+    else:
+        bad = dict(A=4, T=2049, ld=4 * 2049, slab_stride=3 * 4 * 2049)     # four envs per workgroup: 4 * (A * T + T) * 4 bytes = 163 920 > 160 KiB
+    assert _tail_refused(lib, fn, **bad) == fn + ": head too wide for LDS"
+
+
+@pytest.mark.parametrize("fn", SLAB_TAILS)
+def test_tail_without_env_step_reports_an_argument_before_the_width(lib, fn):
+    wide = dict(T=3277, slab_stride=3 * 3277 * 24) if TAILS[fn] == "quantile" else dict(T=2049, ld=4 * 2049, slab_stride=3 * 4 * 2049)
+    assert _tail_refused(lib, fn, nslab=0, **wide) == fn + ": bad argument"
