@@ -105,20 +105,22 @@ class DeviceSynthVecEnv:
         return self._obs[nxt]
 
     def act_step_commit(self, tail_args, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, replay, start_slot, kind: str = "qhead", enc=None, w1_planes=None):
-        """``step_commit`` with the actor's tail in the same launch: ``tail_args`` are the arguments of ``ops.actor_qhead`` (``kind="qhead"``: scalar heads,
-        a0_actor_qhead_env_step), of ``ops.actor_dist_tail`` (``"dist"``: c51 / qr, a0_actor_dist_tail_env_step) or of the quantile tail (``"quantile"``:
-        iqn / fqf, a0_actor_quantile_tail_env_step), all ending in action, qmax, ctrl, eps_ptr; the action chosen there is the one this step takes.
+        """``step_commit`` with the actor's tail in the same launch.  ``tail_args``: what ``Actor._roll_head`` returns — the leading arguments of ``ops.actor_qhead``
+        (``kind="qhead"``: scalar heads, a0_actor_qhead_env_step), ``ops.actor_dist_tail`` (``"dist"``: c51 / qr) or ``ops.actor_quantile_tail`` (``"quantile"``: iqn /
+        fqf) — followed by ``Actor._draw_args``: seed, stream_a, stream_u, off_a, off_u, epsilon, action, qmax, ctrl, eps_ptr; the action chosen there is the one this
+        step takes.  ``enc`` = (wt, encoder weights, act3): the launch goes on to encode the new observation — the next step's features (a0_actor_*_env_step_enc).
         ``w1_planes`` (``kind="qhead"``): fc1's weights as ``ops.actor_fc1_planes`` for the step's fc1 launch."""
         self.g += 1
         nxt = (self._cur + 1) % len(self._obs)
         common = (self.seed, self.rank, self.g, self._obs[self._cur], self._obs[nxt], self.ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0,
                   replay.frames, replay.size, start_slot, replay.act, replay.rew, replay.done)
-        extra = {"w1_planes": w1_planes} if (kind == "qhead" and w1_planes is not None) else {}
-        if enc is not None:      # (wt, encoder weights, act3): the same launch goes on to encode the new observation — the next step's features (a0_actor_*_env_step_enc)
-            {"qhead": self.ops.actor_qhead_env_step_enc, "dist": self.ops.actor_dist_tail_env_step_enc, "quantile": self.ops.actor_quantile_tail_env_step_enc}[kind](
-                *tail_args, *common, task=self.task, wt=enc[0], enc_w=enc[1], act3_next=enc[2], **extra)
-        else:
-            {"qhead": self.ops.actor_qhead_env_step, "dist": self.ops.actor_dist_tail_env_step, "quantile": self.ops.actor_quantile_tail_env_step}[kind](*tail_args, *common, task=self.task, **extra)
+        ops = self.ops
+        launch = {("qhead", False): ops.actor_qhead_env_step, ("dist", False): ops.actor_dist_tail_env_step, ("quantile", False): ops.actor_quantile_tail_env_step,
+                  ("qhead", True): ops.actor_qhead_env_step_enc, ("dist", True): ops.actor_dist_tail_env_step_enc, ("quantile", True): ops.actor_quantile_tail_env_step_enc}[kind, enc is not None]
+        extra = {} if enc is None else {"wt": enc[0], "enc_w": enc[1], "act3_next": enc[2]}
+        if kind == "qhead" and w1_planes is not None:
+            extra["w1_planes"] = w1_planes
+        launch(*tail_args, *common, task=self.task, **extra)
         self._cur = nxt
         return self._obs[nxt]
 

@@ -525,7 +525,7 @@ static int a0_actor_compose(const a0_actor_net& V, void* stream) {
     return a0_noisy_multi(0, L->n_mods, mu, sg, eff, N, K, r0, r1, nin, nw, nb, stream);
 }
 
-// ---- a0_actor_rollout in stages, named after Actor._rollout (agent0_amd/deepq/agent.py) where it has a name.  a0_roll: what one call reads, decided once in a0_roll_begin.
+// ---- a0_actor_rollout in stages; Actor (agent0_amd/deepq/agent.py) has the same under the same names (_roll_begin, _roll_layout_planes, _roll_noise_reset, _roll_head, _roll_draw).  a0_roll: what one call reads, decided once in a0_roll_begin.
 struct a0_roll {
     a0_actor* a; a0_learner* L; a0_rbuf* R; void* stream;
     a0_actor_net V; a0_encoder_weights w;      // the network the actor acts with, its convolution weights
@@ -560,7 +560,7 @@ static int a0_roll_begin(a0_roll& r, a0_actor* a, a0_learner* L, a0_rbuf* R, flo
     // LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives: 9.43 -> 9.75 ms)
     r.step_enc = !a->pool_on && !a->own_flat;
     // NoisyLinear.forward composes mu + sigma * eps with the parameters as they are NOW (model.py:54-62): a rollout that does not start on a noise reset
-    // recomposes the copies once (agent0_amd/deepq/agent.py Actor._rollout)
+    // recomposes the copies once (agent0_amd/deepq/agent.py Actor._roll_begin)
     if (L->d.noisy && !r.noise_due()) A0_CHECK(a0_actor_compose(r.V, stream));
     // actor.eps_ladder: the rollout's per-env epsilons, once; every tail then reads its env's own entry
     r.epsilon = epsilon; r.eps_vec = nullptr;
@@ -601,9 +601,9 @@ static int a0_roll_noise_reset(a0_roll& r) {
 }
 
 // From the step's features (act3) to the head GEMM's split-K slabs, described in *head for the tail; scalar heads have no such chain (fc1 and the head run inside
-// their tail's launches) and leave *head alone.  Quantile (Actor._quant_tail_args): the step's fractions — fqf: the fraction net on the features, no draws
+// their tail's launches) and leave *head alone.  Actor._roll_head is its twin.  Quantile: the step's fractions — fqf: the fraction net on the features, no draws
 // (FQFHead.prop_taus, model.py:268-278); iqn: nt per env from the actor's Philox stream STREAM_TAUS — with their cosine features in the same launch (round 6), the
-// embedding times the features in the embedding GEMM's epilogue, then fc1 and the head partial over E * nt rows.  c51 / qr (Actor._dist_tail_args): fc1 and the head
+// embedding times the features in the embedding GEMM's epilogue, then fc1 and the head partial over E * nt rows.  c51 / qr: fc1 and the head
 // partial over E rows.  fc1 reads laid-out weights where the rollout has them (a0_roll_layout_planes).
 static int a0_roll_head(a0_roll& r, a0_slab_head* head) {
     if (r.H.kind == A0_ACT_SCALAR) return A0_OK;

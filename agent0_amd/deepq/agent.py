@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import os
 
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import numpy as np
@@ -37,6 +38,40 @@ def _ops_from(cfg, ops=None):
     return ops
 
 
+class _Part:
+    """Envs [off, off + E) of the batch with the buffers their steps use: the whole batch (``off`` = 0; the actor's own ``ws``, ``action``, ``ring_*`` and ``out_*``
+    are these fields), or one group of a grouped host env with its ``pool``.  ``scratch``: a0_actor_qhead's fc1 slabs (scalar heads); ``slabs``: the head GEMM's
+    (every other one-kernel tail); ``ring_obs``: the last observations of an n-step window, where the env does not keep them itself."""
+
+    def __init__(self, actor, off, E, action, scratch, slabs, pool=None):
+        ops, n = actor.ops, actor.n
+        self.off, self.E, self.action, self.scratch, self.slabs, self.pool = off, E, action, scratch, slabs, pool
+        self.ws = Workspace(ops, actor.L, E, actor.n_tau)
+        self.ring_act, self.ring_rew, self.ring_done = ops.zeros(n * E, dtype=torch.int32), ops.zeros(n * E), ops.zeros(n * E)
+        self.out_act, self.out_rew, self.out_done = ops.zeros(E, dtype=torch.int32), ops.zeros(E), ops.zeros(E)
+        self.ring_obs = ops.zeros(actor.ring_len * E * actor.obs_bytes, dtype=torch.uint8) if (n > 1 and not actor.env_history) else None
+
+
+@dataclass
+class _Roll:
+    """What the stages of one rollout read (the handle's a0_roll, runtime.hip).  ``sample_async`` fills the first block; ``_roll_begin`` decides the second, and a
+    context in which it is left off (``act``, host envs, groups, test rollouts) runs every step on the general launches."""
+    epsilon: float                               # actor.eps_ladder: the per-env sentinel, with the vector in ``eps_ptr``
+    eps_ptr: Optional[torch.Tensor] = None
+    ctrl: Optional[torch.Tensor] = None          # a captured rollout: the device control block, and the device scalar epsilon in ``eps_ptr``
+    T: int = 1
+    start: int = 0                               # the ring's write cursor when the rollout starts
+    bound: bool = False
+    test: bool = False
+    stage: Optional[dict] = None                 # where an unbound rollout leaves its rows, where a test rollout leaves its frames
+    frames_out: Optional[list] = None
+    splits: Optional[dict] = None                # a grouped env: the full batch's split-K counts (``_split_plan``); None: every GEMM takes its shape's own
+    merged: bool = False                         # tail + env step + n-step bookkeeping + replay row in ONE launch (``act_step_commit``)
+    step_enc: bool = False                       # ... which also encodes the env's new observation for step t + 1
+    planes: bool = False                         # quantile heads: fc1 reads the term planes of ``refresh_fc1_planes``
+    fc1p: bool = False                           # scalar and c51 / qr heads: fc1 reads the planes of ``refresh_actor_fc1_planes``
+
+
 class Actor:
     def __init__(self, cfg: ExpConfig, model: Optional[DeepQNet] = None, replay: Optional[ReplayDataset] = None, ops=None, rank: int = 0, envs=None):
         self.cfg = cfg
@@ -52,13 +87,10 @@ class Actor:
         self.n = int(cfg.learner.n_step_q)
         self.steps = 0
         self.obs_bytes = self.L.C * self.L.H * self.L.W
-        n_tau = self.L.F if self.L.algo == "fqf" else (cfg.learner.iqn.K if self.L.algo == "iqn" else 1)
-        self.n_tau = n_tau
-        self.ws = Workspace(ops, self.L, E, n_tau)
+        n_tau = self.n_tau = self.L.F if self.L.algo == "fqf" else (cfg.learner.iqn.K if self.L.algo == "iqn" else 1)
         self.taus = ops.empty(E * n_tau) if self.L.algo == "iqn" else None
-        self.greedy, self.rand_a, self.action = ops.zeros(E, dtype=torch.int32), ops.zeros(E, dtype=torch.int32), ops.zeros(E, dtype=torch.int32)
-        self.u, self.qmax = ops.zeros(E), ops.zeros(E)
-        T = max(int(cfg.actor.sample_steps), int(cfg.actor.test_steps) if False else int(cfg.actor.sample_steps))
+        self.greedy, self.qmax = ops.zeros(E, dtype=torch.int32), ops.zeros(E)
+        T = int(cfg.actor.sample_steps)
         self.qs = ops.zeros(T)
         # scalar heads take the fused tail (fc1 slabs -> q -> dueling -> argmax -> epsilon-greedy in one kernel, a0_actor_qhead)
         self.fused_tail = self.L.algo in ("dqn", "mdqn") and self.L.feat % 4 == 0 and self.L.A + (1 if self.L.dueling else 0) <= 24
@@ -72,19 +104,21 @@ class Actor:
         self.quant_slabs = self.L.algo in ("iqn", "fqf") and ops.dense_fwd_scratch(E * n_tau, self.L.feat, self.L.num_cosines) == 0
         if self.quant_slabs:
             self._head_slabs = ops.empty(ops.dense_fwd_partial_slabs(E * n_tau, self.L.Npad, 512) * E * n_tau * self.L.Npad)
-        self.qmax_all = ops.zeros(T * E) if (self.fused_tail or self.dist_tail or self.quant_slabs) else None
+        self.one_tail = self.fused_tail or self.dist_tail or self.quant_slabs      # the head has a one-kernel tail (``_roll_head`` / ``_roll_tail``); else the generic chain
+        self.qmax_all = ops.zeros(T * E) if self.one_tail else None
         self._qh_scratch = ops.empty(ops.actor_qhead_scratch(E, self.L.feat)) if self.fused_tail else None
         self.stat_mask, self.stat_ret = ops.zeros(T * E), ops.zeros(T * E)
-        self.ring_act, self.ring_rew, self.ring_done = ops.zeros(self.n * E, dtype=torch.int32), ops.zeros(self.n * E), ops.zeros(self.n * E)
         # observation ring for n-step: holds the last n observations; its length divides sample_steps when possible so that the
         # slot pattern of a rollout repeats (required for hipGraph replay)
-        T_ = int(cfg.actor.sample_steps)
-        self.ring_len = next((r for r in range(self.n, 2 * self.n + 1) if T_ % r == 0), self.n)
+        self.ring_len = next((r for r in range(self.n, 2 * self.n + 1) if T % r == 0), self.n)
         # a device env that keeps its own observation history needs no copy at all: n + 1 (or the next divisor of the rollout length) buffers
         self.env_history = self.n > 1 and hasattr(self.envs, "set_history")
         if self.env_history:
-            self.envs.set_history(next((r for r in range(self.n + 1, 2 * self.n + 3) if T_ % r == 0), self.n + 1))
-        self.ring_obs = ops.zeros(self.ring_len * E * self.obs_bytes, dtype=torch.uint8) if (self.n > 1 and not self.env_history) else None
+            self.envs.set_history(next((r for r in range(self.n + 1, 2 * self.n + 3) if T % r == 0), self.n + 1))
+        # the whole batch as a part; the attribute names the loop, the snapshots and the tests read stay
+        p = self.whole = _Part(self, 0, E, ops.zeros(E, dtype=torch.int32), self._qh_scratch, self._head_slabs)
+        self.ws, self.action, self.ring_obs = p.ws, p.action, p.ring_obs
+        self.ring_act, self.ring_rew, self.ring_done, self.out_act, self.out_rew, self.out_done = p.ring_act, p.ring_rew, p.ring_done, p.out_act, p.out_rew, p.out_done
         self.use_graph = True
         self._graph, self._graph_warm = None, 0
         self.ctrl = ops.zeros(8, dtype=torch.int64)
@@ -95,34 +129,26 @@ class Actor:
         # beside eps_dev and is allocated by the first rollout that fills it (``_eps_ladder``) — off, or on an actor that only tests, nothing is
         self.rank = int(rank)
         self.ladder_alpha = max(float(cfg.actor.eps_ladder), 0.0)
-        # training rollouts of scalar and c51 / qr heads run fc1 as a0_actor_fc1_kernel over weights laid out once per rollout (``_rollout``; the library's actor handle
-        # likewise, native_loop.py); False keeps the general GEMM in every step — the same bytes, for comparisons.  fc1_launches: steps that took the kernel
+        # training rollouts of scalar and c51 / qr heads run fc1 as a0_actor_fc1_kernel over weights laid out once per rollout (``_roll_layout_planes``; the library's
+        # actor handle likewise, native_loop.py); False keeps the general GEMM in every step — the same bytes, for comparisons.  fc1_launches: steps that took the kernel
         self.fc1_planes = True
         self.fc1_launches = 0
         self.eps_vec = None
-        self.out_act, self.out_rew, self.out_done = ops.zeros(E, dtype=torch.int32), ops.zeros(E), ops.zeros(E)
         self.atoms = self.model.head.atoms.reshape(-1).contiguous() if self.L.algo == "c51" else None
         self._stage = None
+        self._host_actions = None                    # ``_rollout_host``: the action buffer and its alternate
         self.fused_commit = hasattr(self.envs, "step_commit") and (self.obs_bytes == 4 * 84 * 84)
         # scalar heads on the synthetic env: the tail and the env step share one launch (a0_actor_qhead_env_step)
         self.tail_env = (self.fused_tail or self.dist_tail) and self.fused_commit and hasattr(self.envs, "act_step_commit") and os.environ.get("A0_TAIL_ENV", "1") != "0"      # 0: tuning aid (same bytes)
         # a host env split into groups (env_pool.HostEnvGroups): per-group workspaces and n-step state; the CPU steps one group while the GPU infers the other
-        self.groups = None
+        self.groups, self._splits = None, None
         if hasattr(self.envs, "pools"):
-            if not (self.fused_tail or self.dist_tail or self.quant_slabs):
+            if not self.one_tail:
                 raise ValueError("a grouped host env needs a head with a one-kernel actor tail (scalar: A + dueling <= 24; c51 / qr: the head's outputs in LDS); use one group")
-            self._splits = self._split_plan()
-            rows = E * n_tau if self.quant_slabs else E
-            self.groups = []
-            for pool, off in zip(self.envs.pools, self.envs.offsets):
-                k = pool.E
-                g = dict(pool=pool, off=off, E=k, ws=Workspace(ops, self.L, k, n_tau), action=self.action[off:off + k],
-                         ring_act=ops.zeros(self.n * k, dtype=torch.int32), ring_rew=ops.zeros(self.n * k), ring_done=ops.zeros(self.n * k),
-                         out_act=ops.zeros(k, dtype=torch.int32), out_rew=ops.zeros(k), out_done=ops.zeros(k),
-                         scratch=ops.empty(self._splits["qhead"] * k * 512) if self.fused_tail else None,
-                         slabs=ops.empty(self._splits["head"] * k * (rows // E) * self.L.Npad) if not self.fused_tail else None,
-                         ring_obs=ops.zeros(self.ring_len * k * self.obs_bytes, dtype=torch.uint8) if self.n > 1 else None)
-                self.groups.append(g)
+            sp = self._splits = self._split_plan()
+            self.groups = [_Part(self, off, pool.E, self.action[off:off + pool.E], ops.empty(sp["qhead"] * pool.E * 512) if self.fused_tail else None,
+                                 None if self.fused_tail else ops.empty(sp["head"] * pool.E * (n_tau if self.quant_slabs else 1) * self.L.Npad), pool)
+                           for pool, off in zip(self.envs.pools, self.envs.offsets)]
 
     def _split_plan(self) -> dict:
         """The split-K counts of the actor step's dense GEMMs at the FULL batch (E rows, E * n_tau for the quantile heads).  A group of k envs runs its GEMMs with
@@ -137,75 +163,10 @@ class Actor:
             plan["frac"] = dev.dense_splits("frac", E)
         return plan
 
-    # ------------------------------------------------------------------ agent.py:25-39
-    def _qhead_args(self, epsilon, ctrl, eps_ptr, t):
-        L, E, dev, rng = self.L, self.E, self.model._dev, self.rng
-        (W1, b1), (W2, b2) = dev.wb("fc1"), dev.wb("head")
-        return (self.ws.act3, E, L.feat, W1, b1, W2, b2, L.A, L.dueling, self._qh_scratch, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), float(epsilon), self.action, self.qmax_all[t * E:(t + 1) * E], ctrl, eps_ptr)
-
-    def _dist_tail_args(self, epsilon, ctrl, eps_ptr, t, fc1p=None):
-        """fc1 and the head GEMM's slabs (enqueued here), then the arguments of ``ops.actor_dist_tail``."""
-        L, ops, E, dev, rng = self.L, self.ops, self.E, self.model._dev, self.rng
-        if getattr(self, "_fc1p_on", False) if fc1p is None else fc1p:      # ``_rollout``: fc1 over the planes it laid out (a0_actor_fc1_dense: the same bits)
-            ops.actor_fc1_dense(self.ws.act3, L.feat, dev.actor_fc1_planes, dev.wb("fc1")[1], self.ws.h, E, 512, L.feat, True, dev.scratch(ops.dense_fwd_scratch(E, 512, L.feat)))
-        else:
-            dev._dense(self.ws.act3, L.feat, "fc1", self.ws.h, E, True)
-        Wh, bh = dev.wb("head")
-        ns = ops.dense_fwd_partial(self.ws.h, 512, Wh, E, L.Npad, 512, self._head_slabs)
-        return (self._head_slabs, ns, bh, L.Npad, L.A, L.T, L.dueling, 2 if L.algo == "c51" else 1, self.atoms, E, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), float(epsilon), self.action, self.qmax_all[t * E:(t + 1) * E], ctrl, eps_ptr)
-
-    def _quant_tail_args(self, epsilon, ctrl, eps_ptr, t, w_planes=None):
-        """The quantile head up to the head GEMM's slabs (enqueued here), then the arguments of ``ops.actor_quantile_tail_env_step`` (and of ``ops.actor_quantile_tail``,
-        which takes them up to ``eps_ptr``).  ``w_planes=False``: fc1 from its weights, not from the term planes a training rollout keeps (``_rollout``)."""
-        L, ops, E, dev, rng = self.L, self.ops, self.E, self.model._dev, self.rng
-        fused_cos = hasattr(ops, "tau_cos_features")      # round 6: the fractions and their cosine features in one launch
-        if L.algo == "fqf":
-            dev.fqf_taus(self.ws, E, with_cos=fused_cos)
-            taus, aux, mode = self.ws.tau_hat, self.ws.tau_all, 3
-        else:
-            if fused_cos:
-                rng.uniform_cos(rng.STREAM_TAUS, self.taus, self.ws.cosx, E * self.n_tau, L.num_cosines)
-            else:
-                rng.uniform(rng.STREAM_TAUS, self.taus, E * self.n_tau)
-            taus, aux, mode = self.taus, None, 1
-        ns = dev.head_slabs(self.ws, E, taus, self.n_tau, self._head_slabs, cos_ready=fused_cos,
-                            w_planes=getattr(self, "_planes_on", False) if w_planes is None else w_planes)
-        _, bh = dev.wb("head")
-        return (self._head_slabs, ns, bh, L.Npad, L.A, self.n_tau, L.dueling, mode, aux, E, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), float(epsilon), self.action, self.qmax_all[t * E:(t + 1) * E], ctrl, eps_ptr)
-
-    def _act_device(self, epsilon: float, qs_slot: Optional[torch.Tensor], ctrl=None, eps_ptr=None, t: int = 0, tail: bool = True):
-        """``tail=False``: the encoder only — the caller runs the tail together with the env step (``_qhead_args`` / ``_dist_tail_args``)."""
-        L, ops, E, dev = self.L, self.ops, self.E, self.model._dev
-        dev.encode(self.ws, self.obs, None, self.obs_bytes, 0, E, keep=False)
-        if not tail:
-            return
-        if self.fused_tail:
-            ops.actor_qhead(*self._qhead_args(epsilon, ctrl, eps_ptr, t))
-            return
-        if self.dist_tail:
-            ops.actor_dist_tail(*self._dist_tail_args(epsilon, ctrl, eps_ptr, t, fc1p=False))
-            return
-        if self.quant_slabs:
-            # host envs and test rollouts: the merged step's head and tail without its env step — one tail launch where the generic chain below takes four
-            ops.actor_quantile_tail(*self._quant_tail_args(epsilon, ctrl, eps_ptr, t, w_planes=False))
-            return
-        if L.algo == "fqf":
-            dev.fqf_taus(self.ws, E)
-            dev.head(self.ws, E, self.ws.tau_hat, L.F)
-        elif L.algo == "iqn":
-            self.rng.uniform(self.rng.STREAM_TAUS, self.taus, E * self.n_tau)
-            dev.head(self.ws, E, self.taus, self.n_tau)
-        else:
-            dev.head(self.ws, E)
-        dev.select(self.ws, E, self.n_tau, self.greedy, qmax=self.qmax, atoms=self.atoms)
-        # the reference draws randint(0, A, E) and then rand(E) (agent.py:29-36): both come from their own Philox stream, generated
-        # inside the selection kernel
-        rng = self.rng
-        ops.actor_egreedy_rng(self.greedy, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U, rng.reserve(rng.STREAM_EGREEDY_A, E),
-                              rng.reserve(rng.STREAM_EGREEDY_U, E), L.A, float(epsilon), E, self.action, self.qmax, qs_slot, ctrl, eps_ptr)
+    # ------------------------------------------------------------------ the stages of a rollout, named after the actor handle's (a0_roll_*, runtime.hip)
+    def _noise_due(self, steps) -> bool:
+        """agent.py:52-53: ``self.model.reset_noise()`` every reset_noise_freq steps."""
+        return bool(self.cfg.learner.noisy_net) and steps % self.cfg.learner.reset_noise_freq == 0
 
     def _eps_ladder(self, epsilon, eps_ptr=None):
         """actor.eps_ladder: the rollout's per-env epsilons in one launch (a0_eps_ladder; from the device scalar ``eps_ptr`` inside a captured rollout), and what the
@@ -217,256 +178,286 @@ class Actor:
         self.ops.eps_ladder(epsilon, eps_ptr, self.ladder_alpha, self.E, i0, n_total, self.eps_vec)
         return EPS_PER_ENV, self.eps_vec
 
+    def _roll_begin(self, roll: _Roll):
+        """The epsilons, the composed weights, and which launches the rollout's steps take."""
+        cfg, ops, dev, L = self.cfg, self.ops, self.model._dev, self.L
+        if self.ladder_alpha > 0 and not roll.test:
+            roll.epsilon, roll.eps_ptr = self._eps_ladder(roll.epsilon, roll.eps_ptr)
+        if cfg.learner.noisy_net and not self._noise_due(self.steps):
+            # NoisyLinear.forward composes mu + sigma * epsilon on every call (model.py:54-62), i.e. with the parameters as they are NOW; the
+            # composed copies the device keeps were last written before the learner's latest Adam step (or come from a weight snapshot).
+            # A rollout that does not start on a noise reset recomposes them once (with the default sample_steps = 80 it always does).
+            dev.compose_noise()
+        # a training rollout on the device env: the tail of every one-kernel head shares its launch with the env step
+        roll.merged = roll.bound and not roll.test and bool(self.tail_env or (self.quant_tail and self.fused_commit))
+        # round 5: that launch of step t also ENCODES the env's new observation (a0_actor_*_env_step_enc) — the next step starts with its features in place, and a
+        # scalar-head step is two launches (fc1 GEMM | tail + env step + next encoder) instead of three.  The convolution weights do not change inside a rollout
+        # (NoisyNet touches the dense layers only), the last step has no next one.
+        fused_84 = dev.fused and (L.C, L.H, L.W) == (4, 84, 84)
+        # not on the launch schedule (the rollout into a stage ring): there the rollout runs BESIDE the update block, which is the critical path, and a
+        # workgroup that holds a CU's LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives (9.43 -> 9.75 ms)
+        launch_schedule = isinstance(self.replay, StageRing)
+        roll.step_enc = roll.merged and fused_84 and not launch_schedule
+        # quantile actors (round 6): fc1's weight operand as bf16 term planes for the rollout's T GEMMs of E * K rows, split once per rollout and after every noise
+        # reset (a0_split_planes; the same exact terms the GEMM forms per tile, hence the same bits)
+        roll.planes = roll.merged and self.quant_tail and bool(ops.dense_fwd_wplanes_ok(self.E * self.n_tau, 512, L.feat))
+        # scalar and c51 / qr actors: the merged step's fc1 as a0_actor_fc1_kernel over weights laid out likewise (the same slabs bit for bit);
+        # ``self.fc1_planes = False`` keeps the general GEMM (comparisons)
+        roll.fc1p = roll.merged and self.fc1_planes and self.tail_env and bool(ops.actor_fc1_ok(self.E, 512, L.feat) if self.fused_tail
+                                                                                else ops.actor_fc1_dense_ok(self.E, 512, L.feat))
+
+    def _roll_layout_planes(self, roll: _Roll, at_start: bool = True):
+        """The laid-out copies of fc1's weights this rollout reads: at its start (unless a noise reset is due there: it lays them out behind its compose), after every reset."""
+        if at_start and self._noise_due(self.steps):
+            return
+        if roll.planes:
+            self.model._dev.refresh_fc1_planes()
+        if roll.fc1p:
+            self.model._dev.refresh_actor_fc1_planes()
+
+    def _roll_noise_reset(self, roll: _Roll, steps):
+        """``self.model.reset_noise()`` where step ``steps`` is due one: fresh noise, the composed weights, the laid-out copies of them."""
+        if self._noise_due(steps):
+            self.model.reset_noise(rng=self.rng)
+            self._roll_layout_planes(roll, at_start=False)
+
+    def _roll_draw(self):
+        """One step's Philox offsets, claimed ONCE for the whole batch: (seed, the two epsilon-greedy streams, their offsets, the offset of iqn's E * n_tau fractions
+        where a one-kernel tail draws them).  The reference draws randint(0, A, E) and then rand(E) (agent.py:29-36): each from its own stream, inside the kernel."""
+        rng, E = self.rng, self.E
+        sa, su = rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U
+        return (rng.seed, sa, su, rng.reserve(sa, E), rng.reserve(su, E), rng.reserve(rng.STREAM_TAUS, E * self.n_tau) if (self.quant_slabs and self.L.algo == "iqn") else 0)
+
+    def _draw_args(self, part: _Part, roll: _Roll, draw, t):
+        """What every tail ends in — seed, stream_a, stream_u, off_a, off_u, epsilon, action, qmax, ctrl, eps_ptr — for ``part``: env e's draws lie at the step's
+        offsets + e whatever part it is in, its max-Q at row t of ``qmax_all``, its epsilon (actor.eps_ladder) at e of the vector."""
+        seed, sa, su, off_a, off_u, _ = draw
+        lo, hi = part.off, part.off + part.E
+        eps_ptr = roll.eps_ptr if (roll.eps_ptr is None or part.E == self.E) else roll.eps_ptr[lo:hi]
+        return (seed, sa, su, off_a + lo, off_u + lo, float(roll.epsilon), part.action, self.qmax_all[t * self.E + lo:t * self.E + hi], roll.ctrl, eps_ptr)
+
+    def _roll_head(self, part: _Part, roll: _Roll, draw):
+        """From ``part.ws.act3`` to what the tail reads (a0_roll_head): enqueues the chain and returns the tail's leading arguments.  Scalar heads have no chain (fc1 and
+        the head run inside the tail's launches).  c51 / qr: fc1 and the head GEMM's slabs.  Quantile: the fractions — fqf: the fraction net on the part's own features,
+        no draws; iqn: the part's rows of the step's draws — with their cosine features in the same launch (round 6), the embedding times the features, fc1 and the
+        head GEMM's slabs over E * n_tau rows.  Split counts: ``roll.splits`` (a group: the full batch's) or the shape's own; fc1 from laid-out weights where
+        ``roll`` says so."""
+        L, ops, dev, rng, ws, k, nt = self.L, self.ops, self.model._dev, self.rng, part.ws, part.E, self.n_tau
+        sp = roll.splits or {}
+        if self.fused_tail:
+            (W1, b1), (W2, b2) = dev.wb("fc1"), dev.wb("head")
+            return (ws.act3, k, L.feat, W1, b1, W2, b2, L.A, L.dueling, part.scratch)
+        if self.dist_tail:
+            if roll.fc1p:      # a0_actor_fc1_dense: the same bits
+                ops.actor_fc1_dense(ws.act3, L.feat, dev.actor_fc1_planes, dev.wb("fc1")[1], ws.h, k, 512, L.feat, True, dev.scratch(ops.dense_fwd_scratch(k, 512, L.feat)))
+            else:
+                dev._dense(ws.act3, L.feat, "fc1", ws.h, k, True, splits=sp.get("fc1"))
+            Wh, bh = dev.wb("head")
+            ns = ops.dense_fwd_partial_n(ws.h, 512, Wh, k, L.Npad, 512, sp["head"], part.slabs) if sp else ops.dense_fwd_partial(ws.h, 512, Wh, k, L.Npad, 512, part.slabs)
+            return (part.slabs, ns, bh, L.Npad, L.A, L.T, L.dueling, 2 if L.algo == "c51" else 1, self.atoms, k)
+        if L.algo == "fqf":
+            dev.fqf_taus(ws, k, with_cos=True, splits=sp.get("frac"))
+            taus, aux, mode = ws.tau_hat, ws.tau_all, 3
+        else:
+            # env e's n_tau fractions are draws [base + e n_tau, base + (e + 1) n_tau) whatever part it is in; a captured rollout adds ctrl[A0_CTRL_RNG_TAUS]
+            ops.tau_cos_features(rng.seed, rng.STREAM_TAUS, draw[5] + part.off * nt, ws.taus, ws.cosx, k * nt, L.num_cosines, ctrl=rng.ctrl, ctrl_idx=rng.CTRL_INDEX[rng.STREAM_TAUS])
+            taus, aux, mode = ws.taus, None, 1
+        ns = dev.head_slabs(ws, k, taus, nt, part.slabs, cos_ready=True, w_planes=roll.planes, splits=roll.splits)
+        _, bh = dev.wb("head")
+        return (part.slabs, ns, bh, L.Npad, L.A, nt, L.dueling, mode, aux, k)
+
+    def _roll_tail(self, part: _Part, roll: _Roll, draw, t):
+        """The head's chain and its tail without an env step (host envs, groups, test and unbound rollouts, ``act``): one tail launch."""
+        ops, head, args = self.ops, self._roll_head(part, roll, draw), self._draw_args(part, roll, draw, t)
+        if self.fused_tail and roll.splits is not None:
+            ops.actor_qhead_n(*head[:3], roll.splits["qhead"], *head[3:], *args)
+        elif self.fused_tail:
+            ops.actor_qhead(*head, *args)
+        elif self.dist_tail:
+            ops.actor_dist_tail(*head, *args)
+        else:
+            ops.actor_quantile_tail(*head, *args)
+
+    def _act_device(self, part: _Part, obs, roll: _Roll, draw, t: int = 0, qs_slot: Optional[torch.Tensor] = None, tail: bool = True):
+        """Actor.act for ``part`` on its observations (agent.py:25-39).  ``tail=False``: the encoder only — the caller runs the tail together with the env step."""
+        L, ops, E, dev, ws = self.L, self.ops, self.E, self.model._dev, part.ws
+        dev.encode(ws, obs, None, self.obs_bytes, 0, part.E, keep=False)
+        if not tail:
+            return
+        if self.one_tail:
+            self._roll_tail(part, roll, draw, t)
+            return
+        # heads no one-kernel tail accepts (the whole batch only): head with its reduction, first-max selection, the epsilon-greedy draw
+        if L.algo == "fqf":
+            dev.fqf_taus(ws, E)
+            dev.head(ws, E, ws.tau_hat, L.F)
+        elif L.algo == "iqn":
+            self.rng.uniform(self.rng.STREAM_TAUS, self.taus, E * self.n_tau)
+            dev.head(ws, E, self.taus, self.n_tau)
+        else:
+            dev.head(ws, E)
+        dev.select(ws, E, self.n_tau, self.greedy, qmax=self.qmax, atoms=self.atoms)
+        ops.actor_egreedy_rng(self.greedy, *draw[:5], L.A, float(roll.epsilon), E, part.action, self.qmax, qs_slot, roll.ctrl, roll.eps_ptr)
+
+    def _obs0(self, part: _Part, cur_obs, steps):
+        """The first observation of the n-step transition that step ``steps`` emits; where the env keeps no history, ``cur_obs`` first goes into the part's ring."""
+        if self.n == 1:
+            return cur_obs
+        count = min(steps + 1, self.n)
+        if self.env_history:
+            return self.envs.history(count - 1)
+        R, nb = self.ring_len, part.E * self.obs_bytes
+        slot, oldest = steps % R, (steps - (count - 1)) % R
+        part.ring_obs[slot * nb:(slot + 1) * nb].copy_(cur_obs)
+        return part.ring_obs[oldest * nb:(oldest + 1) * nb]
+
+    def _commit_rows(self, part: _Part, roll: _Roll, t, steps, action, obs0, obs_next, reward, terminal, truncated, info):
+        """Step ``t``'s rows of ``part`` leave the actor: the n-step window (agent.py:63-81), then the ring's slots [start + t E + off, ...) or the same rows of the stage
+        (a test rollout keeps the window and emits nothing)."""
+        ops, k, ob = self.ops, part.E, self.obs_bytes
+        ops.actor_nstep(k, self.n, steps, float(self.cfg.learner.discount), action, reward, terminal, truncated, info.get("life_loss"),
+                        part.ring_act, part.ring_rew, part.ring_done, part.out_act, part.out_rew, part.out_done, roll.ctrl)
+        if roll.test:
+            return
+        row = t * self.E + part.off
+        if roll.bound:
+            rp = self.replay
+            ops.replay_insert(rp.frames, rp.size, ob, (roll.start + row) % rp.size, k, obs0, obs_next, part.out_act, part.out_rew, part.out_done, rp.act, rp.rew, rp.done, roll.ctrl)
+        else:
+            st, sl = roll.stage, slice(row, row + k)
+            st["obs"][sl].copy_(obs0.view(k, -1)); st["obs_next"][sl].copy_(obs_next.view(k, -1))
+            st["act"][sl].copy_(part.out_act); st["rew"][sl].copy_(part.out_rew); st["done"][sl].copy_(part.out_done)
+
+    # ------------------------------------------------------------------ agent.py:25-39
     def act(self, epsilon):
         one = self.ops.zeros(1)
-        self._act_device(epsilon, one)
-        if self.fused_tail or self.dist_tail or self.quant_slabs:
+        self._act_device(self.whole, self.obs, _Roll(epsilon), self._roll_draw(), qs_slot=one)
+        if self.one_tail:
             self.ops.mean_rows(self.qmax_all, 1, self.E, one)
         return self.action.cpu().numpy().astype(np.int64), float(one[0])
 
     def reset(self):
         self.obs, _ = self.envs.reset()
 
-    # ------------------------------------------------------------------ agent.py:44-90
-    def _rollout(self, epsilon, T, start, bound, test, stage, frames_out, ctrl=None, eps_ptr=None):
+    # ------------------------------------------------------------------ agent.py:44-90: four loops, each the ORDER in which it issues the stages
+    def _rollout(self, roll: _Roll):
         """The body of Actor.sample's loop (agent.py:48-88), every step enqueued on the stream without touching the host."""
-        cfg, ops, E = self.cfg, self.ops, self.E
-        R = self.ring_len
-        if self.ladder_alpha > 0 and not test:
-            epsilon, eps_ptr = self._eps_ladder(epsilon, eps_ptr)
-        if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq != 0:
-            # NoisyLinear.forward composes mu + sigma * epsilon on every call (model.py:54-62), i.e. with the parameters as they are NOW; the
-            # composed copies the device keeps were last written before the learner's latest Adam step (or come from a weight snapshot).
-            # A rollout that does not start on a noise reset recomposes them once (with the default sample_steps = 80 it always does).
-            self.model._dev.compose_noise()
-        # round 5: for scalar and distributional heads the tail + env-step launch of step t also ENCODES the env's new observation (a0_actor_qhead_env_step_enc /
-        # a0_actor_dist_tail_env_step_enc) — the next step starts with its features in place, and a scalar-head step is two launches (fc1 GEMM | tail + env step + next
-        # encoder) instead of three.  The convolution weights do not change inside a rollout (NoisyNet touches the dense layers only), the last step has no next one.
-        dev = self.model._dev
-        step_enc = ((self.tail_env and (self.fused_tail or self.dist_tail) or (self.quant_tail and self.fused_commit and hasattr(ops, "actor_quantile_tail_env_step_enc")))
-                    and bound and not test and dev.fused and (self.L.C, self.L.H, self.L.W) == (4, 84, 84) and hasattr(ops, "actor_qhead_env_step_enc")
-                    # not on the launch schedule (the rollout into a stage ring): there the rollout runs BESIDE the update block, which is the critical path, and a
-                    # workgroup that holds a CU's LDS from the tail to the end of the encoder takes more from the block than the saved boundary gives (9.43 -> 9.75 ms)
-                    and not isinstance(self.replay, StageRing))
-        # quantile actors (round 6): fc1's weight operand as bf16 term planes for the rollout's T GEMMs of E * K rows, split once here and after every noise reset
-        # (a0_split_planes; the same exact terms the GEMM forms per tile, hence the same bits)
-        self._planes_on = bool(self.quant_tail and bound and not test and self.fused_commit and hasattr(ops, "dense_fwd_wplanes")
-                               and ops.dense_fwd_wplanes_ok(E * self.n_tau, 512, self.L.feat))
-        if self._planes_on and not (cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0):
-            dev.refresh_fc1_planes()
-        # scalar and c51 / qr actors: the merged step's fc1 as a0_actor_fc1_kernel over weights laid out once here and after every noise reset (the same slabs bit for
-        # bit); ``self.fc1_planes = False`` keeps the general GEMM (comparisons)
-        self._fc1p_on = bool(self.fc1_planes and self.tail_env and bound and not test and hasattr(ops, "actor_fc1_planes")
-                             and (ops.actor_fc1_ok(E, 512, self.L.feat) if self.fused_tail else self.dist_tail and ops.actor_fc1_dense_ok(E, 512, self.L.feat)))
-        if self._fc1p_on and not (cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0):
-            dev.refresh_actor_fc1_planes()
+        cfg, ops, E, dev, part, rp = self.cfg, self.ops, self.E, self.model._dev, self.whole, self.replay
+        T, gamma = roll.T, float(cfg.learner.discount)
+        self._roll_begin(roll)
+        self._roll_layout_planes(roll)
         feat_ready = False
         for t in range(T):
-            if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0:
-                self.model.reset_noise(rng=self.rng)
-                if self._planes_on:
-                    dev.refresh_fc1_planes()
-                if self._fc1p_on:
-                    dev.refresh_actor_fc1_planes()
-            merged = bound and not test and (self.tail_env or (self.quant_tail and self.fused_commit))
+            self._roll_noise_reset(roll, self.steps)
+            draw = self._roll_draw()
             if not feat_ready:
-                self._act_device(epsilon, self.qs[t:t + 1], ctrl, eps_ptr, t, tail=not merged)
-            cur_obs = self.obs
-            if self.n > 1 and self.env_history:
-                obs0 = self.envs.history(min(self.steps + 1, self.n) - 1)         # first observation of the emitted n-step transition
-            elif self.n > 1:
-                slot = self.steps % R
-                self.ring_obs[slot * E * self.obs_bytes:(slot + 1) * E * self.obs_bytes].copy_(cur_obs)
-                count = min(self.steps + 1, self.n)
-                oldest = (self.steps - (count - 1)) % R
-                obs0 = self.ring_obs[oldest * E * self.obs_bytes:(oldest + 1) * E * self.obs_bytes]
-            else:
-                obs0 = cur_obs
-            if merged:
-                # fc1's tail (head, argmax, epsilon-greedy) and the env step + n-step bookkeeping + replay row in ONE launch
-                rp = self.replay
+                self._act_device(part, self.obs, roll, draw, t, self.qs[t:t + 1], tail=not roll.merged)
+            obs0 = self._obs0(part, self.obs, self.steps)
+            mask, ret = self.stat_mask[t * E:(t + 1) * E], self.stat_ret[t * E:(t + 1) * E]
+            if roll.merged:
+                # the head's chain, then its tail (head, argmax, epsilon-greedy) and the env step + n-step bookkeeping + replay row in ONE launch
                 kind = "qhead" if self.fused_tail else ("dist" if self.dist_tail else "quantile")
-                targs = {"qhead": self._qhead_args, "dist": self._dist_tail_args, "quantile": self._quant_tail_args}[kind](epsilon, ctrl, eps_ptr, t)
-                enc = (dev.wt, dev.encoder_weights(), self.ws.act3) if (step_enc and t + 1 < T) else None
-                self.obs = self.envs.act_step_commit(targs, self.stat_mask[t * E:(t + 1) * E], self.stat_ret[t * E:(t + 1) * E], self.n, self.steps,
-                                                     float(cfg.learner.discount), self.ring_act, self.ring_rew, self.ring_done, obs0, rp, (start + t * E) % rp.size,
-                                                     kind=kind, enc=enc, w1_planes=dev.actor_fc1_planes if (self._fc1p_on and kind == "qhead") else None)
-                self.fc1_launches += 1 if self._fc1p_on else 0
+                targs = self._roll_head(part, roll, draw) + self._draw_args(part, roll, draw, t)
+                enc = (dev.wt, dev.encoder_weights(), part.ws.act3) if (roll.step_enc and t + 1 < T) else None
+                self.obs = self.envs.act_step_commit(targs, mask, ret, self.n, self.steps, gamma, part.ring_act, part.ring_rew, part.ring_done, obs0, rp,
+                                                     (roll.start + t * E) % rp.size, kind=kind, enc=enc,
+                                                     w1_planes=dev.actor_fc1_planes if (roll.fc1p and kind == "qhead") else None)
+                self.fc1_launches += 1 if roll.fc1p else 0
                 feat_ready = enc is not None
                 self.steps += 1
                 continue
-            if bound and not test and self.fused_commit:
+            if roll.bound and not roll.test and self.fused_commit:
                 # env step, n-step bookkeeping and the replay row in one launch (synthetic env)
-                rp = self.replay
-                obs_next = self.envs.step_commit(self.action, self.stat_mask[t * E:(t + 1) * E], self.stat_ret[t * E:(t + 1) * E], self.n, self.steps,
-                                                 float(cfg.learner.discount), self.ring_act, self.ring_rew, self.ring_done, obs0, rp, (start + t * E) % rp.size, ctrl)
+                self.obs = self.envs.step_commit(part.action, mask, ret, self.n, self.steps, gamma, part.ring_act, part.ring_rew, part.ring_done, obs0, rp,
+                                                 (roll.start + t * E) % rp.size, roll.ctrl)
                 self.steps += 1
-                self.obs = obs_next
                 continue
-            obs_next, reward, terminal, truncated, info = self.envs.step(self.action, final_mask=self.stat_mask[t * E:(t + 1) * E],
-                                                                         final_ret=self.stat_ret[t * E:(t + 1) * E], ctrl=ctrl)
-            ops.actor_nstep(E, self.n, self.steps, float(cfg.learner.discount), self.action, reward, terminal, truncated, info.get("life_loss"),
-                            self.ring_act, self.ring_rew, self.ring_done, self.out_act, self.out_rew, self.out_done, ctrl)
+            obs_next, reward, terminal, truncated, info = self.envs.step(part.action, final_mask=mask, final_ret=ret, ctrl=roll.ctrl)
+            self._commit_rows(part, roll, t, self.steps, part.action, obs0, obs_next, reward, terminal, truncated, info)
             self.steps += 1
-            if test:
-                frames_out.append(obs_next.view(E, self.L.C, self.L.H, self.L.W)[:4, -1:].cpu().numpy())
-            elif bound:
-                rp = self.replay
-                ops.replay_insert(rp.frames, rp.size, self.obs_bytes, (start + t * E) % rp.size, E, obs0, obs_next, self.out_act, self.out_rew, self.out_done,
-                                  rp.act, rp.rew, rp.done, ctrl)
-            else:
-                sl = slice(t * E, (t + 1) * E)
-                stage["obs"][sl].copy_(obs0.view(E, -1)); stage["obs_next"][sl].copy_(obs_next.view(E, -1))
-                stage["act"][sl].copy_(self.out_act); stage["rew"][sl].copy_(self.out_rew); stage["done"][sl].copy_(self.out_done)
+            if roll.test:
+                roll.frames_out.append(obs_next.view(E, self.L.C, self.L.H, self.L.W)[:4, -1:].cpu().numpy())
             self.obs = obs_next
-        if self.fused_tail or self.dist_tail or self.quant_slabs:
+        if self.one_tail:
             ops.mean_rows(self.qmax_all, T, E, self.qs)          # per-step mean max-Q (agent.py:38,88), all steps at once
 
     # ------------------------------------------------------------------ host envs (env_pool.HostEnvPool): nothing but inference between two env steps
-    def _rollout_host(self, epsilon, T, start):
+    def _rollout_host(self, roll: _Roll):
         """Actor.sample's loop (agent.py:48-88) over a host env that takes its actions without waiting (``step_send`` / ``step_recv``).  What lies between "the
         workers have finished step t" and "the workers see the actions of step t + 1" is the upload and Actor.act alone: the bookkeeping of step t (n-step window,
         replay row, episode statistics: agent.py:63-88) is enqueued AFTER the actions of step t + 1 have been sent and runs while the workers step.  Same kernels on
         the same inputs in an order that respects every dependency — the bytes of ``_rollout`` (tests/test_gpu_trainer.py::test_host_env_pool_matches_device_env);
         the action buffer alternates between two tensors because step t's n-step update reads its actions after step t + 1's have been chosen."""
-        cfg, ops, E, rp = self.cfg, self.ops, self.E, self.replay
-        R, ob, gamma = self.ring_len, self.obs_bytes, float(cfg.learner.discount)
-        if getattr(self, "_host_actions", None) is None:
+        ops, E, part = self.ops, self.E, self.whole
+        if self._host_actions is None:
             self._host_actions = (self.action, ops.zeros(E, dtype=torch.int32))
 
         def bookkeeping(t, steps, action, cur_obs, obs_next, reward, terminal, truncated, info):
             sl = slice(t * E, (t + 1) * E)
             self.stat_mask[sl].copy_(info["final_mask"], non_blocking=True)
             self.stat_ret[sl].copy_(info["final_ret"], non_blocking=True)
-            if self.n > 1:
-                slot = steps % R
-                self.ring_obs[slot * E * ob:(slot + 1) * E * ob].copy_(cur_obs)
-                oldest = (steps - (min(steps + 1, self.n) - 1)) % R
-                obs0 = self.ring_obs[oldest * E * ob:(oldest + 1) * E * ob]
-            else:
-                obs0 = cur_obs
-            ops.actor_nstep(E, self.n, steps, gamma, action, reward, terminal, truncated, info.get("life_loss"), self.ring_act, self.ring_rew, self.ring_done,
-                            self.out_act, self.out_rew, self.out_done, None)
-            ops.replay_insert(rp.frames, rp.size, ob, (start + t * E) % rp.size, E, obs0, obs_next, self.out_act, self.out_rew, self.out_done, rp.act, rp.rew, rp.done, None)
+            self._commit_rows(part, roll, t, steps, action, self._obs0(part, cur_obs, steps), obs_next, reward, terminal, truncated, info)
 
-        eps_ptr = None
-        if self.ladder_alpha > 0:
-            epsilon, eps_ptr = self._eps_ladder(epsilon)
-        if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq != 0:
-            self.model._dev.compose_noise()                     # as in _rollout
+        self._roll_begin(roll)
         pending = None
-        for t in range(T):
-            if cfg.learner.noisy_net and self.steps % cfg.learner.reset_noise_freq == 0:
-                self.model.reset_noise(rng=self.rng)
-            self.action = self._host_actions[t & 1]
-            self._act_device(epsilon, self.qs[t:t + 1], None, eps_ptr, t)
-            self.envs.step_send(self.action)
+        for t in range(roll.T):
+            self._roll_noise_reset(roll, self.steps)
+            part.action = self._host_actions[t & 1]
+            self._act_device(part, self.obs, roll, self._roll_draw(), t, self.qs[t:t + 1])
+            self.envs.step_send(part.action)
             if pending is not None:
                 bookkeeping(*pending)
             obs_next, reward, terminal, truncated, info = self.envs.step_recv()
-            pending = (t, self.steps, self.action, self.obs, obs_next, reward, terminal, truncated, info)
+            pending = (t, self.steps, part.action, self.obs, obs_next, reward, terminal, truncated, info)
             self.steps += 1
             self.obs = obs_next
         bookkeeping(*pending)
-        self.action = self._host_actions[0]
-        if self.fused_tail or self.dist_tail or self.quant_slabs:
-            ops.mean_rows(self.qmax_all, T, E, self.qs)
+        part.action = self._host_actions[0]
+        if self.one_tail:
+            ops.mean_rows(self.qmax_all, roll.T, E, self.qs)
 
     # ------------------------------------------------------------------ grouped host envs: CPU stepping of one group beside the GPU's inference of the other
-    def _group_infer_send(self, g, obs, epsilon, t, offs, eps_ptr=None):
-        """Actor.act for group ``g`` on its observations (agent.py:25-39), then the actions go to the group's workers without waiting for them.  ``offs``: the step's
-        Philox offsets (epsilon-greedy action, uniform, and for iqn the fractions), reserved once for the whole batch; the group takes its envs' part of each.  Every
-        dense GEMM runs with the full batch's split count (``_split_plan``).  ``eps_ptr``: the rollout's per-env epsilons (actor.eps_ladder); the group reads its envs'."""
-        L, ops, dev, rng, k, off = self.L, self.ops, self.model._dev, self.rng, g["E"], g["off"]
-        if eps_ptr is not None:
-            eps_ptr = eps_ptr[off:off + k]
-        E, ws, sp = self.E, g["ws"], self._splits
-        dev.encode(ws, obs, None, self.obs_bytes, 0, k, keep=False)
-        qmax = self.qmax_all[t * E + off:t * E + off + k]
-        if self.fused_tail:
-            (W1, b1), (W2, b2) = dev.wb("fc1"), dev.wb("head")
-            ops.actor_qhead_n(ws.act3, k, L.feat, sp["qhead"], W1, b1, W2, b2, L.A, L.dueling, g["scratch"], rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                              offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax, None, eps_ptr)
-        elif self.dist_tail:
-            dev._dense(ws.act3, L.feat, "fc1", ws.h, k, True, splits=sp["fc1"])
-            Wh, bh = dev.wb("head")
-            ns = ops.dense_fwd_partial_n(ws.h, 512, Wh, k, L.Npad, 512, sp["head"], g["slabs"])
-            ops.actor_dist_tail(g["slabs"], ns, bh, L.Npad, L.A, L.T, L.dueling, 2 if L.algo == "c51" else 1, self.atoms, k, rng.seed, rng.STREAM_EGREEDY_A,
-                                rng.STREAM_EGREEDY_U, offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax, None, eps_ptr)
-        else:
-            nt = self.n_tau
-            if L.algo == "fqf":
-                dev.fqf_taus(ws, k, with_cos=True, splits=sp["frac"])          # the fractions come from the group's own features: no draws
-                taus, aux, mode = ws.tau_hat, ws.tau_all, 3
-            else:
-                # the group's rows of the step's E * K fraction draws: env e's K fractions are draws [base + e K, base + (e + 1) K) whatever group it is in
-                ops.tau_cos_features(rng.seed, rng.STREAM_TAUS, offs[2] + off * nt, ws.taus, ws.cosx, k * nt, L.num_cosines)
-                taus, aux, mode = ws.taus, None, 1
-            ns = dev.head_slabs(ws, k, taus, nt, g["slabs"], cos_ready=True, splits=sp)
-            _, bh = dev.wb("head")
-            ops.actor_quantile_tail(g["slabs"], ns, bh, L.Npad, L.A, nt, L.dueling, mode, aux, k, rng.seed, rng.STREAM_EGREEDY_A, rng.STREAM_EGREEDY_U,
-                                    offs[0] + off, offs[1] + off, float(epsilon), g["action"], qmax, None, eps_ptr)
-        g["pool"].step_send(g["action"])
-
-    def _rollout_groups(self, epsilon, T, start, bound=True, test=False, stage=None, frames_out=None):
+    def _rollout_groups(self, roll: _Roll):
         """Actor.sample's loop (agent.py:48-88) over a grouped host env: while group A's worker processes step their envs, the GPU runs Actor.act for group B,
         and vice versa (the overlap the reference gets from ``num_actors`` actor processes, launch.py:30-61).  Every env sees exactly what it would see in
         a one-group rollout — its own observations, the epsilon-greedy (and iqn fraction) draws at its own offset of the step's Philox block, its own n-step window,
         the same NoisyNet noise — and group g's transitions of step t land in the ring slots [start + t E + off_g, ...): the same bytes in the same order
-        (tests/test_gpu_trainer.py, tests/test_gpu_host_env_groups.py).  ``test``: no n-step bookkeeping and no rows, the first four envs' newest frames per step
-        into ``frames_out``; ``bound=False`` (and not ``test``): the rows go to ``stage`` at the same positions."""
-        cfg, ops, E, rng, rp = self.cfg, self.ops, self.E, self.rng, self.replay
-        R, gamma, ob = self.ring_len, float(cfg.learner.discount), self.obs_bytes
-        iqn = self.quant_slabs and self.L.algo == "iqn"
-        reserve = lambda: (rng.reserve(rng.STREAM_EGREEDY_A, E), rng.reserve(rng.STREAM_EGREEDY_U, E), rng.reserve(rng.STREAM_TAUS, E * self.n_tau) if iqn else 0)
-        noisy, freq = bool(cfg.learner.noisy_net), int(cfg.learner.reset_noise_freq)
-        eps_ptr = None
-        if self.ladder_alpha > 0 and not test:
-            epsilon, eps_ptr = self._eps_ladder(epsilon)
-        if noisy and self.steps % freq != 0:
-            self.model._dev.compose_noise()                     # as in _rollout
-        if noisy and self.steps % freq == 0:
-            self.model.reset_noise(rng=self.rng)                # step 0's noise, ahead of its first inference
-        offs = reserve()
+        (tests/test_gpu_trainer.py, tests/test_gpu_host_env_groups.py).  ``roll.test``: no n-step bookkeeping and no rows, the first four envs' newest frames per step
+        into ``roll.frames_out``; unbound (and not a test): the rows go to ``roll.stage`` at the same positions.  A step's Philox offsets are claimed once for the
+        whole batch and every group takes its envs' part of each; every dense GEMM runs with the full batch's split count (``roll.splits``)."""
+        E, T = self.E, roll.T
+
+        def infer_send(g, obs, draw, t):                          # Actor.act for group g, then its actions go to its workers without waiting for them
+            self._act_device(g, obs, roll, draw, t)
+            g.pool.step_send(g.action)
+
+        self._roll_begin(roll)
+        self._roll_noise_reset(roll, self.steps)                  # step 0's noise, ahead of its first inference
+        draw = self._roll_draw()
         for gi, g in enumerate(self.groups):                      # step 0's actions: nothing to overlap with yet
-            self._group_infer_send(g, self.obs[gi], epsilon, 0, offs, eps_ptr)
+            infer_send(g, self.obs[gi], draw, 0)
         for t in range(T):
-            nxt_offs = reserve() if t + 1 < T else None
+            nxt_draw = self._roll_draw() if t + 1 < T else None
             frames = []
             for gi, g in enumerate(self.groups):
-                k, off = g["E"], g["off"]
+                k, off = g.E, g.off
                 cur_obs = self.obs[gi]
                 sl = slice(t * E + off, t * E + off + k)
-                obs_next, reward, terminal, truncated, info = g["pool"].step_recv(self.stat_mask[sl], self.stat_ret[sl])      # waits for THIS group's workers only
-                if test:
-                    if off < 4:                                     # the newest frame of the first four envs (agent.py / trainer.py:131-132), gathered over the groups
-                        frames.append(obs_next.view(k, self.L.C, self.L.H, self.L.W)[:4 - off, -1:].cpu().numpy())
-                else:
-                    if self.n > 1:
-                        slot = self.steps % R
-                        g["ring_obs"][slot * k * ob:(slot + 1) * k * ob].copy_(cur_obs)
-                        oldest = (self.steps - (min(self.steps + 1, self.n) - 1)) % R
-                        obs0 = g["ring_obs"][oldest * k * ob:(oldest + 1) * k * ob]
-                    else:
-                        obs0 = cur_obs
-                    ops.actor_nstep(k, self.n, self.steps, gamma, g["action"], reward, terminal, truncated, info.get("life_loss"), g["ring_act"], g["ring_rew"],
-                                    g["ring_done"], g["out_act"], g["out_rew"], g["out_done"], None)
-                    if bound:
-                        ops.replay_insert(rp.frames, rp.size, ob, (start + t * E + off) % rp.size, k, obs0, obs_next, g["out_act"], g["out_rew"], g["out_done"],
-                                          rp.act, rp.rew, rp.done, None)
-                    else:
-                        stage["obs"][sl].copy_(obs0.view(k, -1)); stage["obs_next"][sl].copy_(obs_next.view(k, -1))
-                        stage["act"][sl].copy_(g["out_act"]); stage["rew"][sl].copy_(g["out_rew"]); stage["done"][sl].copy_(g["out_done"])
+                obs_next, reward, terminal, truncated, info = g.pool.step_recv(self.stat_mask[sl], self.stat_ret[sl])      # waits for THIS group's workers only
+                if not roll.test:
+                    self._commit_rows(g, roll, t, self.steps, g.action, self._obs0(g, cur_obs, self.steps), obs_next, reward, terminal, truncated, info)
+                elif off < 4:                                       # the newest frame of the first four envs (agent.py / trainer.py:131-132), gathered over the groups
+                    frames.append(obs_next.view(k, self.L.C, self.L.H, self.L.W)[:4 - off, -1:].cpu().numpy())
                 self.obs[gi] = obs_next
-                if nxt_offs is not None:                            # the next step's actions for this group, while the other group's workers are stepping
-                    if gi == 0 and noisy and (self.steps + 1) % freq == 0:
+                if nxt_draw is not None:                            # the next step's actions for this group, while the other group's workers are stepping
+                    if gi == 0:
                         # NoisyNet: the next step's noise, once, behind every group's inference of this step and ahead of any of the next
-                        self.model.reset_noise(rng=self.rng)
-                    self._group_infer_send(g, obs_next, epsilon, t + 1, nxt_offs, eps_ptr)
-            if test:
-                frames_out.append(np.concatenate(frames, axis=0))
+                        self._roll_noise_reset(roll, self.steps + 1)
+                    infer_send(g, obs_next, nxt_draw, t + 1)
+            if roll.test:
+                roll.frames_out.append(np.concatenate(frames, axis=0))
             self.steps += 1
-        ops.mean_rows(self.qmax_all, T, E, self.qs)
+        self.ops.mean_rows(self.qmax_all, T, E, self.qs)
 
     def _graph_eligible(self, T, bound, test, state_dict) -> bool:
         cfg = self.cfg
@@ -477,14 +468,14 @@ class Actor:
         rng = self.rng
         return {"g": self.envs.g, "steps": self.steps, "slot": self.replay.write_cursor(), "rng": dict(rng.offsets), "cur": self.envs._cur}
 
-    def _rollout_graphed(self, epsilon, T, start):
+    def _rollout_graphed(self, roll: _Roll):
         """One hipGraph launch per rollout: the 80 x ~10 launches are captured once; counters that keep advancing (env step, n-step
         index, Philox offsets, replay cursor) reach the kernels through a device control block, epsilon through a device scalar."""
-        rng, rp = self.rng, self.replay
+        rng, rp, epsilon, T, start = self.rng, self.replay, roll.epsilon, roll.T, roll.start
         if self._graph is None:
             if self._graph_warm < 2:                     # eager first: lazy allocations (workspaces, scratch) happen here
                 self._graph_warm += 1
-                self._rollout(epsilon, T, start, True, False, None, None)
+                self._rollout(roll)
                 return
             self._ctrl_host.zero_(); self.ctrl.zero_(); self._eps_host[0] = float(epsilon); self.eps_dev.copy_(self._eps_host)
             rng.ctrl = self.ctrl
@@ -492,7 +483,7 @@ class Actor:
             graph = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
             with torch.cuda.graph(graph, **graph_capture_kwargs()):
-                self._rollout(epsilon, T, start, True, False, None, None, ctrl=self.ctrl, eps_ptr=self.eps_dev)
+                self._rollout(replace(roll, ctrl=self.ctrl, eps_ptr=self.eps_dev))
             rng.ctrl = None                              # the captured kernels hold the pointer; eager rollouts must not add stale deltas
             after = self._snapshot()
             assert after["cur"] == base["cur"]
@@ -540,14 +531,15 @@ class Actor:
                                     "act": ops.zeros(T * E, dtype=torch.int32), "rew": ops.zeros(T * E), "done": ops.zeros(T * E)}
         start = self.replay.write_cursor() if bound else 0
         frames_out = []
+        roll = _Roll(epsilon, T=T, start=start, bound=bound, test=test, stage=st, frames_out=frames_out, splits=self._splits)
         if self.groups is not None:
-            self._rollout_groups(epsilon, T, start, bound, test, st, frames_out)
+            self._rollout_groups(roll)
         elif self._graph_eligible(T, bound, test, state_dict):
-            self._rollout_graphed(epsilon, T, start)
+            self._rollout_graphed(roll)
         elif bound and hasattr(self.envs, "step_send") and os.environ.get("A0_HOST_ROLLOUT", "1") != "0":      # 0: the step-by-step order of _rollout (same bytes; a tuning aid)
-            self._rollout_host(epsilon, T, start)
+            self._rollout_host(roll)
         else:
-            self._rollout(epsilon, T, start, bound, test, st, frames_out)
+            self._rollout(roll)
         done_ev = torch.cuda.Event()
         done_ev.record()
         return (T, bound, test, st, start, frames_out, done_ev)
