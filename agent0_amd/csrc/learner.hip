@@ -527,7 +527,7 @@ static int a0_noisy(a0_upd& u, bool sigma_grads) {
 }
 static int a0_sigma_grads(a0_upd& u) { return a0_noisy(u, true); }
 
-// In front of DeviceLearner.forward_dense.  learner.aug_shift: the batch is shifted into the stage buffer first, by the draws of update state[6], and every pass reads
+// DeviceLearner._upd_prepare, in front of every family's forward.  learner.aug_shift: the batch is shifted into the stage buffer first, by the draws of update state[6], and every pass reads
 // that dense batch; the ring is only read.  NoisyNet, BaseLearner.train (agent.py:125-127): reset_noise of the online, then of the target network — ONE Philox fill of
 // the joint buffer (the same draws as two fills: every vector is padded to the offsets' stride of four) — and both networks' effective weights in one launch
 static int a0_upd_prepare(a0_upd& u, const uint8_t* frames, const int* slot, long long row_bytes) {
@@ -543,7 +543,7 @@ static int a0_upd_prepare(a0_upd& u, const uint8_t* frames, const int* slot, lon
     return a0_noisy(u, false);
 }
 
-// The passes' encoders as ONE launch in the order given (a pass without act3 is left out); `keep`: the differentiated pass, whose act1 / act2 the encoder backward reads
+// DeviceLearner._upd_encode: the passes' encoders as ONE launch in the order given (a pass without act3 is left out); `keep`: the differentiated pass, whose act1 / act2 the encoder backward reads
 struct a0_enc_sel { bool target, next; float* act3; bool keep; };
 static int a0_upd_encode(a0_upd& u, const a0_enc_sel (&sel)[3]) {
     a0_learner* L = u.L;
@@ -554,7 +554,7 @@ static int a0_upd_encode(a0_upd& u, const a0_enc_sel (&sel)[3]) {
     return a0_net_encoder_fwd_fused_multi(L->C, L->H, L->W, np, passes, u.stream);
 }
 
-// engine.py's layer-by-layer path (qr, mdqn): the passes' encoders in one launch, then per pass fc1, head, dueling combine; the loss leaves dq in g_dq
+// DeviceLearner._fwd_layerwise (qr, mdqn; the Python side also takes the wide dqn head there, which this handle refuses): the passes' encoders in one launch, then per pass fc1, head, dueling combine; the loss leaves dq in g_dq
 static int a0_fwd_layerwise(a0_upd& u) {
     a0_learner* L = u.L; void* stream = u.stream; const int B = L->d.B, A = L->d.A, T = L->T, dq = L->d.double_q ? 1 : 0;
     if (L->d.algo == A0_ALGO_MDQN) {       // the third pass is the target network on the CURRENT observation (agent.py:202-204)
@@ -574,7 +574,7 @@ static int a0_fwd_layerwise(a0_upd& u) {
     return a0_loss_quantile_huber(L->go.q, (long long)A * T, 1, T, L->y, L->qr_taus, 0, u.act, u.wgt, B, T, T, L->loss, L->g_dq, L->state, stream);
 }
 
-// FQFLearner.train_step (agent.py:334-388) in the order of agent0_amd/deepq/engine.py's fqf path
+// FQFLearner.train_step (agent.py:334-388) in the order of DeviceLearner._fwd_fqf (agent0_amd/deepq/engine.py)
 static int a0_fwd_fqf(a0_upd& u) {
     a0_learner* L = u.L; void* stream = u.stream; const int B = L->d.B, A = L->d.A, F = L->F, dq = L->d.double_q ? 1 : 0;
     A0_CHECK(a0_upd_encode(u, {{false, false, L->act3_o, true}, {true, true, L->act3_t, false}, {false, true, dq ? L->act3_s : nullptr, false}}));
@@ -601,7 +601,7 @@ static int a0_fwd_fqf(a0_upd& u) {
     return a0_dense_wgrad(L->dfrac, L->act3_o, L->feat, L->grads + L->frac.off, B, 32, L->feat, L->slabs, stream);
 }
 
-// IQNLearner.train_step (agent.py:296-331) in the order of agent0_amd/deepq/engine.py's iqn path.  The update's three tau draws first (BaseLearner.train_batch:
+// IQNLearner.train_step (agent.py:296-331) in the order of DeviceLearner._fwd_iqn (agent0_amd/deepq/engine.py).  The update's three tau draws first (BaseLearner.train_batch:
 // K, N', N fractions per sample, Philox stream 3)
 static int a0_fwd_iqn(a0_upd& u) {
     a0_learner* L = u.L; void* stream = u.stream; const int B = L->d.B, A = L->d.A, dq = L->d.double_q ? 1 : 0, K = L->d.iqn_K, N = L->d.iqn_N, Nd = L->d.iqn_N_dash;
@@ -620,7 +620,7 @@ static int a0_fwd_iqn(a0_upd& u) {
     return a0_loss_quantile_huber(L->qo.q, (long long)N * A, A, 1, L->y, L->t_on, N, u.act, u.wgt, B, N, Nd, L->loss, L->qo.dq, L->state, stream);
 }
 
-// C51Learner.train_step (agent.py:218-268) / QRLearner.train_step (agent.py:272-293), in the order of agent0_amd/deepq/engine.py's c51 / qr path: the three encoder
+// C51Learner.train_step (agent.py:218-268) / QRLearner.train_step (agent.py:272-293), in the order of DeviceLearner._fwd_dist (agent0_amd/deepq/engine.py): the three encoder
 // passes in one launch; the online fc1 over [s ; s'] rows as ONE GEMM and the target's, their slabs finished by one reduction launch; the two head GEMMs; and one
 // launch for everything behind them (slab sums, dueling, greedy next action, projection, cross entropy, head gradient)
 static int a0_fwd_dist(a0_upd& u) {
@@ -668,7 +668,7 @@ static int a0_fwd_dist(a0_upd& u) {
                                   L->q_o, L->q_t, L->m_proj, L->a_star, L->state, stream);
 }
 
-// dqn (agent.py:173-190) and mdqn from the fc1 slabs (193-215): the target pass on s', a third pass (the online network on s' under double-Q; mdqn: the TARGET network
+// DeviceLearner._fwd_scalar — dqn (agent.py:173-190) and mdqn from the fc1 slabs (193-215): the target pass on s', a third pass (the online network on s' under double-Q; mdqn: the TARGET network
 // on the CURRENT observation, agent.py:202-204) and the online pass on s as ONE encoder launch, their fc1 GEMMs (split-K slabs), then the heads of both networks,
 // dueling, argmax, Huber loss, head gradient and the head's backward-data pass in one launch
 static int a0_fwd_scalar(a0_upd& u) {

@@ -161,6 +161,7 @@ class DeviceNet:
         self.fused = bool(ops.fused_supported(L.C, L.H, L.W))
         self.fused_dgrad = self.fused and bool(ops.dgrad_fused_supported(L.C, L.H, L.W))
         self.wt = ops.zeros(ops.conv_wt_floats(L.C)) if self.fused else None
+        self.fc1_planes = self.actor_fc1_planes = None       # the actor's laid-out copies of fc1's weights (refresh_fc1_planes / refresh_actor_fc1_planes allocate them)
 
     def adopt_noise_buf(self, buf: torch.Tensor):
         """Move the noise vectors into ``buf`` (noise_len floats of a buffer the caller owns): the learner puts its two networks' vectors back to back, in
@@ -316,7 +317,7 @@ class DeviceNet:
         """fc1's EFFECTIVE weights as bf16 term planes (a0_split_planes) for ``head_slabs(.., w_planes=True)``: the actor refreshes them when a rollout starts and after
         every NoisyNet compose, and reuses them for the rollout's GEMMs of E * K rows (same exact terms as the GEMM would form per tile: same bits)."""
         W, _ = self.wb("fc1")
-        if getattr(self, "fc1_planes", None) is None:
+        if self.fc1_planes is None:
             self.fc1_planes = torch.empty(self.ops.weight_planes_words(512, self.L.feat), dtype=torch.int32, device=self.flat.device)
         self.ops.split_planes(W, self.fc1_planes, 512, self.L.feat)
 
@@ -324,7 +325,7 @@ class DeviceNet:
         """fc1's EFFECTIVE weights as fragment-ordered bf16 term planes (a0_actor_fc1_planes) for the scalar and c51 / qr actors' per-step fc1 (a0_actor_fc1_kernel):
         refreshed like ``refresh_fc1_planes``, when a rollout starts and after every NoisyNet compose."""
         W, _ = self.wb("fc1")
-        if getattr(self, "actor_fc1_planes", None) is None:
+        if self.actor_fc1_planes is None:
             self.actor_fc1_planes = torch.empty(self.ops.actor_fc1_planes_words(512, self.L.feat), dtype=torch.int32, device=self.flat.device)
         self.ops.actor_fc1_planes(W, self.actor_fc1_planes, 512, self.L.feat)
 
@@ -378,8 +379,20 @@ class DeviceNet:
             ops.select_action(ws.q, n_tau * L.A, 1, L.A, B, L.A, n_tau, MODE_FQF, ws.tau_all, a_star, qsel, qmax)
 
 
+class _Upd:
+    """One update's per-call context (the handle's ``a0_upd``): the batch as every pass reads it (``_upd_prepare`` re-points it at the shifted copy under
+    learner.aug_shift; ``backward_encoder`` reads it again), and what the family's forward left: ``have_draw`` / ``have_dh`` — the loss launch wrote the head
+    output's gradient / the head's data gradient itself — and fqf's fraction loss."""
+    __slots__ = ("frames", "slot", "stride", "act", "rew", "done", "wgt", "rand", "tstage", "have_draw", "have_dh", "frac")
+
+    def __init__(self, frames, slot, stride, act, rew, done, wgt, rand, tstage):
+        self.frames, self.slot, self.stride, self.act, self.rew, self.done, self.wgt, self.rand, self.tstage = frames, slot, stride, act, rew, done, wgt, rand, tstage
+        self.have_draw, self.have_dh, self.frac = False, False, None
+
+
 class DeviceLearner:
     """Online + target network, gradients, Adam / RMSprop state and the per-algorithm update."""
+    SHAPE_PREDICATES = ("dense_fwd_partial_multi_ok", "dense_dgrad_wgrad_ok", "dense_dgrad_wgrad_ok2", "dense_dgrad_wgrad2_ok", "dense_dgrad_hadamard_ok")
 
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
@@ -450,7 +463,9 @@ class DeviceLearner:
         self.K, self.N, self.N_dash = K, N, N_dash
         self.max_grad_norm = max_grad_norm
         self.mdqn_tau, self.mdqn_lo = float(mdqn_tau), float(mdqn_lo)
+        self.family = self._family()
         B = batch_size
+        self.ws_m = self.atoms = self._fc1_slabs = self._q_cur = self._dist_buf = None
         if L.quantile:
             n_on = N if L.algo == "iqn" else L.F
             n_tg = N_dash if L.algo == "iqn" else L.F
@@ -477,6 +492,14 @@ class DeviceLearner:
         if L.algo == "c51":
             self.atoms = torch.linspace(self.vmin, self.vmax, L.T).to(ops.device)
             self.m_proj = ops.empty(B * L.T)
+        if self.family == "scalar":
+            # the passes' fc1 split-K slabs, which the head / loss kernel finishes: online on s, target on s', and the third pass's (double-Q; mdqn)
+            n = ops.dense_fwd_partial_slabs(B, 512, L.feat) * B * 512
+            self._fc1_slabs = [ops.empty(n) for _ in range(3 if double_q or L.algo == "mdqn" else 2)]
+            self._q_cur = ops.empty(B * L.A) if L.algo == "mdqn" else None
+        elif self.family == "dist":
+            self._ws_dist()
+        self._tst = {}         # A0_PIPELINE_TARGET=1: the separately staged target pass's buffers, per parity (``_tstage_buf``)
         self.a_star = ops.zeros(B, dtype=torch.int32)
         self.loss = ops.empty(B)
         n_slab = max(ops.encoder_bwd_scratch(self.net, B),
@@ -489,14 +512,15 @@ class DeviceLearner:
         # Round 4: without a gradient hook the dense layers' slab reductions ride in the encoder weight gradients' reduction launch (a0_pending_reduce: one launch less
         # per update, same sums) — their slabs then have to survive until that launch, so the encoder's get a region of their own behind them
         self._enc_slab_off, self._defer_dense = 0, False
-        if hasattr(ops, "pending_reduce") and self.online.fused and self.online.fused_dgrad and os.environ.get("A0_DEFER_DENSE_REDUCE", "1") != "0":
+        if self.online.fused and self.online.fused_dgrad and os.environ.get("A0_DEFER_DENSE_REDUCE", "1") != "0":
             self._enc_slab_off, self._defer_dense = ops.dense_wgrad_multi_scratch(shapes), True
             n_slab = max(n_slab, self._enc_slab_off + ops.encoder_bwd_scratch(self.net, B))
         self._pend = None
-        # the update's tail as one launch (ops.update_tail: slab sums, Adam, target copy, weight copies); a backend without it composes the three launches
-        self.fused_tail = self._defer_dense and hasattr(ops, "update_tail")
-        self.fused_tail_reason = "one-launch update tail" if self.fused_tail else "three-launch update tail: the backend has no update_tail or the encoder is not fused"
-        self._tail_plan = None
+        # the update's tail as one launch (ops.update_tail: slab sums, Adam, target copy, weight copies); without the deferred sums the three launches are composed
+        self.fused_tail = self._defer_dense
+        self._tail_plan = self._upd = None
+        # the grouped / paired launches' shape predicates, looked up once: HipOps and CpuOps have all five (a test holds them to the names); a backend without such a launch answers no
+        self._ok = {n: getattr(ops, n, lambda *shape: False) for n in self.SHAPE_PREDICATES}
         self.slabs = ops.empty(n_slab)
         self.obs_bytes = L.C * L.H * L.W
         self.grad_hook = None       # data parallelism: callable(grads, state) run between backward and the optimizer (dist.GradAllReduce)
@@ -516,10 +540,8 @@ class DeviceLearner:
         if self.target_tau <= 0:
             return
         L, tg = self.L, self.target
-        if tg.fused:
-            self.ops.target_blend(tg.flat, self.online.flat, L.n_params_padded, self.target_tau, self.state, self.target_update_freq, force, tg.encoder_weights(), L.C, tg.wt)
-        else:
-            self.ops.target_blend(tg.flat, self.online.flat, L.n_params_padded, self.target_tau, self.state, self.target_update_freq, force)
+        self.ops.target_blend(tg.flat, self.online.flat, L.n_params_padded, self.target_tau, self.state, self.target_update_freq, force,
+                              *((tg.encoder_weights(), L.C, tg.wt) if tg.fused else ()))
 
     def reset_seed(self) -> int:
         """The 32-bit seed of learner.net_reset_freq's fresh values: ``net_reset_seed`` when one was set (rank 0's, under data parallelism), else the low 32 bits of
@@ -532,12 +554,8 @@ class DeviceLearner:
         if self.net_reset_freq <= 0:
             return
         L, on, tg = self.L, self.online, self.target
-        if on.fused:
-            self.ops.net_reset(on.flat, tg.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.reset_segs, self.net_reset_shrink, self.reset_seed(), self.state,
-                               self.net_reset_freq, force, k_host, on.encoder_weights(), L.C, on.wt, tg.wt)
-        else:
-            self.ops.net_reset(on.flat, tg.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.reset_segs, self.net_reset_shrink, self.reset_seed(), self.state,
-                               self.net_reset_freq, force, k_host)
+        self.ops.net_reset(on.flat, tg.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.reset_segs, self.net_reset_shrink, self.reset_seed(), self.state,
+                           self.net_reset_freq, force, k_host, *((on.encoder_weights(), L.C, on.wt, tg.wt) if on.fused else ()))
 
     def _grad(self, name: str) -> torch.Tensor:
         L = self.L
@@ -557,18 +575,18 @@ class DeviceLearner:
         # the data gradients first, then every dense weight gradient with ONE slab reduction
         wg = [(ws.draw, ws.h, 512, self._grad("head"), R, L.Npad, 512)]
         if not have_dh:
-            if hasattr(ops, "dense_dgrad_wgrad_ok2") and ops.dense_dgrad_wgrad_ok2(R, L.Npad, 512):
+            if self._ok["dense_dgrad_wgrad_ok2"](R, L.Npad, 512):
                 # round 5: a distributional head's data gradient (64 tiles) and weight gradient (32 - 104 tiles) side by side in one launch
                 ops.dense_dgrad_wgrad(ws.draw, Wh, ws.h, 512, ws.dh, self._grad("head"), R, L.Npad, 512)
                 wg = []
             else:
                 ops.dense_dgrad(ws.draw, Wh, ws.h, ws.dh, R, L.Npad, 512)
         if not L.quantile:
-            if wg and hasattr(ops, "dense_dgrad_wgrad2") and ops.dense_dgrad_wgrad2_ok(R, 512, L.feat, L.Npad, 512):
+            if wg and self._ok["dense_dgrad_wgrad2_ok"](R, 512, L.feat, L.Npad, 512):
                 # round 5: ... and the head's weight gradient, which waits for the loss kernel only, in the same launch (its few tiles fill slots the pair leaves empty)
                 ops.dense_dgrad_wgrad2(ws.dh, Wf, ws.act3, L.feat, ws.d3, self._grad("fc1"), R, 512, L.feat, ws.draw, ws.h, 512, self._grad("head"), L.Npad, 512)
                 wg = []
-            elif hasattr(ops, "dense_dgrad_wgrad") and ops.dense_dgrad_wgrad_ok(R, 512, L.feat):
+            elif self._ok["dense_dgrad_wgrad_ok"](R, 512, L.feat):
                 # fc1's data gradient and weight gradient — 392 tiles each at R = 512 — as ONE launch that keeps the chip's workgroup slots filled (bit-identical)
                 ops.dense_dgrad_wgrad(ws.dh, Wf, ws.act3, L.feat, ws.d3, self._grad("fc1"), R, 512, L.feat)
             else:
@@ -577,7 +595,7 @@ class DeviceLearner:
         else:
             n = ws.n_tau
             wg.append((ws.dh, ws.x, L.feat, self._grad("fc1"), R, 512, L.feat))
-            if hasattr(ops, "dense_dgrad_hadamard") and ops.dense_dgrad_hadamard_ok(R, 512, L.feat, n):
+            if self._ok["dense_dgrad_hadamard_ok"](R, 512, L.feat, n):
                 # round 6: dx = dh W never reaches HBM — the embedding product's backward runs in the data-gradient GEMM's epilogue
                 ops.dense_dgrad_hadamard(ws.dh, Wf, ws.emb, ws.act3, ws.demb, ws.d3, R, 512, L.feat, n)
             else:
@@ -608,7 +626,8 @@ class DeviceLearner:
         gradient hook or clipping, which need the summed gradient first, nor under weight decay, whose launch reads the NaN flag the one-launch tail lowers early, nor
         when NoisyNet's sigma gradients wait for deferred dense sums."""
         L, ops, on = self.L, self.ops, self.online
-        ws, frames, slot, stride, B = self._bw
+        u, ws, B = self._upd, self.ws_o, self.B
+        frames, slot, stride = u.frames, u.slot, u.stride
         g1, g2, g3 = self.grads[L.blocks["conv1"].all], self.grads[L.blocks["conv2"].all], self.grads[L.blocks["conv3"].all]
         self._tail_plan = None
         if on.fused and on.fused_dgrad:
@@ -701,18 +720,6 @@ class DeviceLearner:
         self._blend_target()
         self._reset_net()
 
-    def _encode_passes(self, frames, slot, sample_stride, passes):
-        """passes: [(net, ws, chan_off, keep)] — the encoder forward passes of one update over the same batch.  They are independent of one another (the reference
-        runs them one after the other, agent.py:176-181 / 222-231): on the fused split-operand kernel they go out as ONE launch (a0_net_encoder_fwd_fused_multi)."""
-        L, ops, B = self.L, self.ops, self.B
-        multi = len(passes) > 1 and self.online.fused and (L.C, L.H, L.W) == (4, 84, 84) and hasattr(ops, "encoder_fwd_fused_multi")
-        if not multi:
-            for net, ws, chan_off, keep in passes:
-                net.encode(ws, frames, slot, sample_stride, chan_off, B, keep=keep)
-            return
-        ops.encoder_fwd_fused_multi(self.net, [(net.wt, net.encoder_weights(), frames, slot, sample_stride, chan_off, B, ws.act1 if keep else None, ws.act2 if keep else None, ws.act3)
-                                               for net, ws, chan_off, keep in passes])
-
     # ------------------------------------------------------------------ the target network's pass as a stage of its own
     @property
     def target_stage_supported(self) -> bool:
@@ -720,13 +727,9 @@ class DeviceLearner:
         previous update's gradients, so the Trainer may run it for batch k + 1 on a second stream while update k is in flight — for the paths whose
         tail consumes the target's fc1 slabs (dqn's and c51's fused heads) and without NoisyNet (whose per-update noise draws are ordered on the host)."""
         L = self.L
-        if L.noisy or not self.online.fused:
-            return False
-        return (L.algo == "dqn" and L.A + (1 if L.dueling else 0) <= 24) or (L.algo == "c51" and hasattr(self.ops, "c51_head_loss_slabs"))
+        return not L.noisy and self.online.fused and ((L.algo == "dqn" and self.family == "scalar") or L.algo == "c51")
 
     def _tstage_buf(self, p: int):
-        if getattr(self, "_tst", None) is None:
-            self._tst = {}
         if p not in self._tst:
             ns = self.ops.dense_fwd_partial_slabs(self.B, 512, self.L.feat)
             self._tst[p] = (self.ops.empty(self.B * self.L.feat), self.ops.empty(ns * self.B * 512))
@@ -743,58 +746,139 @@ class DeviceLearner:
     def _qr_fused_ok(self) -> bool:
         """QR's head path from the GEMM slabs to the loss in one launch (a0_qr_head_loss_slabs): the staged head outputs of a sample must fit in LDS."""
         L, ops = self.L, self.ops
-        if not hasattr(ops, "qr_head_loss_slabs"):
-            return False
         R_on = 2 * self.B if self.double_q else self.B
         return (L.A <= 32 and (3 * L.Npad + (L.T + 3) // 4 * 4) * 4 <= 150 * 1024 and L.Npad % 4 == 0
                 and max(ops.dense_fwd_partial_slabs(R_on, L.Npad, 512), ops.dense_fwd_partial_slabs(self.B, L.Npad, 512)) <= 8)
 
-    def _dist_heads_to_slabs(self, frames, slot, sample_stride, tstage):
-        """The distributional learners' passes (online on s, online on s' under double-Q, target on s': agent.py:219-231 / 272-280) up to the head GEMMs' split-K slabs:
-        the encoders as one launch, the fc1 GEMMs as one grouped launch (the online passes' rows interleaved into one [splits][R_on][512] buffer), ONE reduction launch
-        (bias + ReLU), the head GEMMs as one grouped launch.  Returns (buffers, online head slab count, target head slab count, R_on); buffers["hs_on"] holds rows
-        [0, B) = s and, under double-Q, rows [B, 2B) = s'."""
+    # ------------------------------------------------------------------ the family: decided once, with its buffers
+    def _family(self) -> str:
+        """Which forward ``forward_dense`` runs, decided once like the handle's ``a0_family`` (learner_state.h): "scalar" — dqn and mdqn with A + dueling <= 24, from the
+        fc1 slabs to the loss in one launch; "dist" — c51, and qr where ``_qr_fused_ok``; "iqn"; "fqf"; "layerwise" — the rest, layer by layer: qr and mdqn beyond those
+        limits and — the one difference: the handle refuses it — the wide dqn head."""
+        L = self.L
+        if L.algo in ("iqn", "fqf"):
+            return L.algo
+        if L.algo in ("dqn", "mdqn"):
+            return "scalar" if L.A + (1 if L.dueling else 0) <= 24 else "layerwise"
+        if L.algo not in ("c51", "qr"):
+            raise NotImplementedError(f"algo {L.algo} has no device learner yet")
+        return "dist" if L.algo == "c51" or self._qr_fused_ok() else "layerwise"
+
+    def _ws_dist(self):
+        """The dist family's buffers (a0_ws_dist): the online network's features of s and (double-Q) of s' lie back to back, and so do their fc1 slabs, h and head
+        slabs — R_on = B or 2B rows — because fc1 and the head run over both as ONE GEMM each (same weights).  ``ws_o.act3`` and ``ws_o.h`` (h(s) of the online
+        network: what the backward pass reads) and ``ws_s.act3`` are views into them."""
         L, ops, B = self.L, self.ops, self.B
-        on, tg = self.online, self.target
-        wo, wt, wsel = self.ws_o, self.ws_t, self.ws_s
-        nxt = self.obs_bytes
-        dq_ = self.double_q
-        ns = ops.dense_fwd_partial_slabs(B, 512, L.feat)
-        R_on = 2 * B if dq_ else B
-        ns_on = ops.dense_fwd_partial_slabs(R_on, 512, L.feat)
-        if getattr(self, "_c51_buf", None) is None:
-            nh_on, nh_tg = ops.dense_fwd_partial_slabs(R_on, L.Npad, 512), ops.dense_fwd_partial_slabs(B, L.Npad, 512)
-            self._c51_buf = dict(fc1_on=ops.empty(ns_on * R_on * 512), fc1_tg=ops.empty(ns * B * 512), h_on=ops.empty(R_on * 512), act3_on=ops.empty(R_on * L.feat),
-                                 hs_on=ops.empty(nh_on * R_on * L.Npad), hs_tg=ops.empty(nh_tg * B * L.Npad), R_on=R_on)
-            wo.h = self._c51_buf["h_on"][: B * 512]                  # h(s) of the online network: what the backward pass reads
-            # the online network's features of s and (double-Q) of s' back to back: fc1 and the head run over both as ONE GEMM each (same weights)
-            wo.act3 = self._c51_buf["act3_on"][: B * L.feat]
-            if dq_:
-                wsel.act3 = self._c51_buf["act3_on"][B * L.feat:]
-        buf = self._c51_buf
+        R_on = 2 * B if self.double_q else B
+        ns, ns_on = ops.dense_fwd_partial_slabs(B, 512, L.feat), ops.dense_fwd_partial_slabs(R_on, 512, L.feat)
+        nh_on, nh_tg = ops.dense_fwd_partial_slabs(R_on, L.Npad, 512), ops.dense_fwd_partial_slabs(B, L.Npad, 512)
+        buf = self._dist_buf = dict(fc1_on=ops.empty(ns_on * R_on * 512), fc1_tg=ops.empty(ns * B * 512), h_on=ops.empty(R_on * 512), act3_on=ops.empty(R_on * L.feat),
+                                    hs_on=ops.empty(nh_on * R_on * L.Npad), hs_tg=ops.empty(nh_tg * B * L.Npad), R_on=R_on)
+        self.ws_o.h, self.ws_o.act3 = buf["h_on"][: B * 512], buf["act3_on"][: B * L.feat]
+        if self.double_q:
+            self.ws_s.act3 = buf["act3_on"][B * L.feat:]
+
+    # ------------------------------------------------------------------ forward_dense's stages, under the names of the handle's (csrc/learner.hip)
+    def _upd_prepare(self, u: _Upd):
+        """In front of every forward: what a separately staged target pass cannot go with, learner.aug_shift's shift of the batch into the stage buffer — every pass
+        then reads that dense batch — and NoisyNet's compose of both networks' effective weights."""
+        L, ops, on, tg = self.L, self.ops, self.online, self.target
+        if u.tstage is not None and not self.target_stage_supported:
+            raise ValueError("tstage: this learner's target pass cannot run as a separate stage")
+        if self.net_reset_freq > 0 and u.tstage is not None:
+            raise ValueError("tstage: not together with learner.net_reset_freq (the separately staged target pass has read a target the reset rewrites)")
+        if self.aug_shift > 0:
+            if u.tstage is not None:
+                raise ValueError("tstage: not together with learner.aug_shift (the separately staged target pass has read the unshifted ring)")
+            ops.augment_shift(u.frames, u.slot, u.stride, L.C, L.H, L.W, self.aug_shift, self.B, self.aug_rng.seed, self.state, 0, self.aug_stage)
+            u.frames, u.slot, u.stride = self.aug_stage, None, 2 * self.obs_bytes
+        if L.noisy:
+            mods = on.compose_mods() + tg.compose_mods()
+            if len(mods) <= 6:
+                ops.noisy_multi(False, mods)            # both networks' effective weights in one launch
+            else:
+                on.compose_noise()
+                tg.compose_noise()
+
+    def _upd_encode(self, u: _Upd, *sel):
+        """sel: up to three ``(net, ws, next, keep)`` or None (a pass this update does not have) — the encoder forward passes of one update over the same batch, on the
+        next or the current observation; ``keep``: the differentiated pass, whose act1 / act2 the encoder backward reads.  They are independent of one another (the
+        reference runs them one after the other, agent.py:176-181 / 222-231): on the fused split-operand kernel they go out, in the order given, as ONE launch
+        (a0_net_encoder_fwd_fused_multi)."""
+        L, B = self.L, self.B
+        passes = [(net, ws, self.obs_bytes if nxt else 0, keep) for net, ws, nxt, keep in filter(None, sel)]
+        if len(passes) > 1 and self.online.fused and (L.C, L.H, L.W) == (4, 84, 84):
+            self.ops.encoder_fwd_fused_multi(self.net, [(net.wt, net.encoder_weights(), u.frames, u.slot, u.stride, chan_off, B, ws.act1 if keep else None,
+                                                         ws.act2 if keep else None, ws.act3) for net, ws, chan_off, keep in passes])
+            return
+        for net, ws, chan_off, keep in passes:
+            net.encode(ws, u.frames, u.slot, u.stride, chan_off, B, keep=keep)
+
+    def _fwd_scalar(self, u: _Upd):
+        """dqn (agent.py:173-190) and mdqn (193-215) from the fc1 slabs: the target pass on s' (unless ``tstage`` left it), a third pass — the online network on s'
+        under double-Q; mdqn: the TARGET network on the CURRENT observation (agent.py:202-204) — and the online pass on s as one encoder launch, their fc1 GEMMs, and
+        one kernel that finishes fc1 from the GEMMs' split-K slabs and runs heads, loss, head gradient and the head's backward-data pass (a0_dqn_head_loss_slabs /
+        a0_mdqn_head_loss_slabs): only fc1 runs as a GEMM, and there are no reduction launches."""
+        L, ops, B, on, tg = self.L, self.ops, self.B, self.online, self.target
+        wo, wt, sl = self.ws_o, self.ws_t, self._fc1_slabs
+        mdqn, staged = L.algo == "mdqn", u.tstage is not None
+        (Wo, bo), (Wt, bt) = on.wb("head"), tg.wb("head")
         (Wf_o, bf_o), (Wf_t, bf_t) = on.wb("fc1"), tg.wb("fc1")
-        (Wh_o, _), (Wh_t, _) = on.wb("head"), tg.wb("head")
+        w3, W3 = (self.ws_m, Wf_t) if mdqn else (self.ws_s, Wf_o)        # the third pass: ws_s is None without double-Q
+        third = w3 is not None
+        ns = ops.dense_fwd_partial_slabs(B, 512, L.feat)
+        s_tg = sl[1]
+        self._upd_encode(u, None if staged else (tg, wt, True, False), (tg if mdqn else on, w3, not mdqn, False) if third else None, (on, wo, False, True))
+        if not staged and self._ok["dense_fwd_partial_multi_ok"](len(sl), B, 512, L.feat):
+            # the passes' fc1 GEMMs as ONE launch: together they fill the chip with a half / a third of the splits each would need alone
+            ns = ops.dense_fwd_partial_multi([wo.act3, wt.act3] + ([w3.act3] if third else []), L.feat, [Wf_o, Wf_t] + ([W3] if third else []), B, 512, L.feat, sl)
+        else:
+            if staged:
+                s_tg = self._tstage_buf(u.tstage)[1]
+            else:
+                ops.dense_fwd_partial(wt.act3, L.feat, Wf_t, B, 512, L.feat, s_tg)
+            if third:
+                ops.dense_fwd_partial(w3.act3, L.feat, W3, B, 512, L.feat, sl[2])
+            ops.dense_fwd_partial(wo.act3, L.feat, Wf_o, B, 512, L.feat, sl[0])
+        if mdqn:
+            ops.mdqn_head_loss_slabs(sl[0], s_tg, sl[2], ns, bf_o, bf_t, wo.h, Wo, bo, Wt, bt, L.A, L.dueling, L.Npad, u.act, u.rew, u.done, u.wgt,
+                                     self.gamma_n, self.mdqn_tau, self.mdqn_lo, B, self.loss, wo.q, wt.q, self._q_cur, wo.draw, self.state, wo.dh)
+        else:
+            ops.dqn_head_loss_slabs(sl[0], s_tg, sl[2] if third else None, ns, bf_o, bf_t, wo.h, Wo, bo, Wt, bt,
+                                    L.A, L.dueling, L.Npad, u.act, u.rew, u.done, u.wgt, self.gamma_n, B, self.loss, wo.q, wt.q, wo.draw, self.state, wo.dh)
+        u.have_draw = u.have_dh = True           # draw, and the head's backward-data pass: dh is written by the same kernel
+
+    def _fwd_dist(self, u: _Upd):
+        """c51 (agent.py:218-268) and qr where ``_qr_fused_ok`` (272-293).  The passes (online on s, online on s' under double-Q, target on s') up to the head GEMMs'
+        split-K slabs: the encoders as one launch, the fc1 GEMMs as one grouped launch (the online passes' rows interleaved into one [splits][R_on][512] buffer), ONE
+        reduction launch (bias + ReLU), the head GEMMs as one grouped launch — buf["hs_on"] holds rows [0, B) = s and, under double-Q, rows [B, 2B) = s'.  Then one
+        launch for everything behind them (a0_c51_head_loss_slabs: slab sums, dueling, greedy next action, projection + cross entropy, head gradient;
+        a0_qr_head_loss_slabs: the quantile Huber loss in its place)."""
+        L, ops, B, on, tg, buf = self.L, self.ops, self.B, self.online, self.target, self._dist_buf
+        wo, wt, wsel, dq_, R_on = self.ws_o, self.ws_t, self.ws_s, self.double_q, self._dist_buf["R_on"]
+        staged = u.tstage is not None
+        ns, ns_on = ops.dense_fwd_partial_slabs(B, 512, L.feat), ops.dense_fwd_partial_slabs(R_on, 512, L.feat)
+        (Wf_o, bf_o), (Wf_t, bf_t) = on.wb("fc1"), tg.wb("fc1")
+        (Wh_o, bh_o), (Wh_t, bh_t) = on.wb("head"), tg.wb("head")
         s_tg = buf["fc1_tg"]
-        self._encode_passes(frames, slot, sample_stride, ([(tg, wt, nxt, False)] if tstage is None else []) + ([(on, wsel, nxt, False)] if dq_ else []) + [(on, wo, 0, True)])
+        self._upd_encode(u, None if staged else (tg, wt, True, False), (on, wsel, True, False) if dq_ else None, (on, wo, False, True))
         npass = 3 if dq_ else 2
-        grouped = (tstage is None and hasattr(ops, "dense_fwd_partial_multi") and ops.dense_fwd_partial_multi_ok(npass, B, 512, L.feat)
-                   and ops.dense_fwd_partial_multi_ok(npass, B, L.Npad, 512))
+        grouped = not staged and self._ok["dense_fwd_partial_multi_ok"](npass, B, 512, L.feat) and self._ok["dense_fwd_partial_multi_ok"](npass, B, L.Npad, 512)
         if grouped:
-            # the passes (online on s, online on s' under double-Q, target on s') are GEMMs of one shape each for fc1 and for the head: ONE grouped launch per layer,
-            # the online passes' rows interleaved into the [splits][R_on][N] buffers the reduction and the loss kernel read
+            # the passes are GEMMs of one shape each for fc1 and for the head: ONE grouped launch per layer, the online passes' rows interleaved into the
+            # [splits][R_on][N] buffers the reduction and the loss kernel read
             a3, f1 = buf["act3_on"], buf["fc1_on"]
             Xs = [a3[: B * L.feat]] + ([a3[B * L.feat:]] if dq_ else []) + [wt.act3]
             sl = [f1] + ([f1[B * 512:]] if dq_ else []) + [s_tg]
             st = [R_on * 512] * (npass - 1) + [B * 512]
             ns_on = ns = ops.dense_fwd_partial_multi(Xs, L.feat, [Wf_o] * (npass - 1) + [Wf_t], B, 512, L.feat, sl, st)
         else:
-            if tstage is None:
-                ops.dense_fwd_partial(wt.act3, L.feat, Wf_t, B, 512, L.feat, s_tg)
+            if staged:
+                s_tg = self._tstage_buf(u.tstage)[1]
             else:
-                s_tg = self._tstage_buf(tstage)[1]
+                ops.dense_fwd_partial(wt.act3, L.feat, Wf_t, B, 512, L.feat, s_tg)
             ops.dense_fwd_partial(buf["act3_on"], L.feat, Wf_o, R_on, 512, L.feat, buf["fc1_on"])
-        layers = [(buf["fc1_on"], ns_on, bf_o, buf["h_on"], R_on), (s_tg, ns, bf_t, wt.h, B)]
-        ops.reduce_bias_act_multi(layers, 512, True)
+        ops.reduce_bias_act_multi([(buf["fc1_on"], ns_on, bf_o, buf["h_on"], R_on), (s_tg, ns, bf_t, wt.h, B)], 512, True)
         if grouped:
             h, hs = buf["h_on"], buf["hs_on"]
             Xs = [h[: B * 512]] + ([h[B * 512:]] if dq_ else []) + [wt.h]
@@ -804,7 +888,84 @@ class DeviceLearner:
         else:
             nh_on = ops.dense_fwd_partial(buf["h_on"], 512, Wh_o, R_on, L.Npad, 512, buf["hs_on"])
             nh_tg = ops.dense_fwd_partial(wt.h, 512, Wh_t, B, L.Npad, 512, buf["hs_tg"])
-        return buf, nh_on, nh_tg, R_on
+        head = (buf["hs_on"], nh_on, R_on, buf["hs_tg"], nh_tg, B if dq_ else -1, bh_o, bh_t, L.Npad, L.A, L.T, L.dueling, u.act, u.rew, u.done, u.wgt)
+        if L.algo == "c51":
+            ops.c51_head_loss_slabs(*head, self.atoms, self.gamma_n, self.vmin, self.vmax, B, self.loss, wo.draw, self.state, q_on=wo.q, q_tg=wt.q, m_out=self.m_proj,
+                                    a_star=self.a_star)
+        else:
+            ops.qr_head_loss_slabs(*head, self.qr_taus, self.gamma_n, B, self.loss, wo.draw, self.state, q_on=wo.q, q_tg=wt.q, a_star=self.a_star)
+        u.have_draw = True
+
+    def _fwd_layerwise(self, u: _Upd):
+        """Layer by layer — per pass fc1, head, dueling combine; the loss leaves dq: the wide dqn head, qr and mdqn where the one-launch paths do not take them."""
+        L, ops, B, on, tg = self.L, self.ops, self.B, self.online, self.target
+        wo, wt, wsel = self.ws_o, self.ws_t, self.ws_s
+        if L.algo == "mdqn":
+            # target net on the next AND on the current observation (agent.py:202-204), online net on the current one: one launch
+            self._upd_encode(u, (tg, wt, True, False), (tg, self.ws_m, False, False), (on, wo, False, True))
+            tg.head(wt, B)
+            tg.head(self.ws_m, B)
+            on.head(wo, B)
+            ops.loss_mdqn(wo.q, wt.q, self.ws_m.q, L.A, u.act, u.rew, u.done, u.wgt, self.gamma_n, self.mdqn_tau, self.mdqn_lo, B, self.loss, wo.dq, self.state)
+            return
+        sel, ws_sel = (on, wsel) if self.double_q else (tg, wt)      # the network that selects the next action, and the pass it does so from
+        self._upd_encode(u, (tg, wt, True, False), (on, wsel, True, False) if self.double_q else None, (on, wo, False, True))
+        tg.head(wt, B)
+        if self.double_q:
+            on.head(wsel, B)
+        sel.select(ws_sel, B, 1, self.a_star)
+        on.head(wo, B)
+        if L.algo == "dqn":
+            ops.loss_dqn(wo.q, wt.q, L.A, u.act, self.a_star, u.rew, u.done, u.wgt, self.gamma_n, B, self.loss, wo.dq, self.state)
+        else:
+            ops.quantile_target(wt.q, L.A * L.T, 1, L.T, self.a_star, u.rew, u.done, self.gamma_n, B, L.T, self.y)
+            wo.dq.zero_()
+            ops.loss_quantile_huber(wo.q, L.A * L.T, 1, L.T, self.y, self.qr_taus, 0, u.act, u.wgt, B, L.T, L.T, self.loss, wo.dq, self.state)
+
+    def _fwd_iqn(self, u: _Upd):
+        """IQNLearner.train_step (agent.py:296-331); ``u.rand``: [taus_K [B*K], taus_N' [B*N'], taus_N [B*N]] in the reference's draw order."""
+        L, ops, B, on, tg = self.L, self.ops, self.B, self.online, self.target
+        wo, wt, wsel = self.ws_o, self.ws_t, self.ws_s
+        (t_sel, t_tgt, t_on), (K, Nd, N) = u.rand, (self.K, self.N_dash, self.N)
+        sel, ws_sel = (on, wsel) if self.double_q else (tg, wt)      # greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
+        self._upd_encode(u, (tg, wt, True, False), (on, wsel, True, False) if self.double_q else None, (on, wo, False, True))
+        sel.head(ws_sel, B, t_sel, K)
+        sel.select(ws_sel, B, K, self.a_star)
+        tg.head(wt, B, t_tgt, Nd)
+        ops.quantile_target(wt.q, Nd * L.A, L.A, 1, self.a_star, u.rew, u.done, self.gamma_n, B, Nd, self.y)
+        on.head(wo, B, t_on, N)
+        wo.dq.zero_()
+        ops.loss_quantile_huber(wo.q, N * L.A, L.A, 1, self.y, t_on, N, u.act, u.wgt, B, N, Nd, self.loss, wo.dq, self.state)
+
+    def _fwd_fqf(self, u: _Upd):
+        """FQFLearner.train_step (agent.py:334-388); ``u.rand`` (parity tests only): fractions evaluated elsewhere, written over the fraction net's own (see
+        ``forward_dense``).  Leaves the fraction loss in ``u.frac``."""
+        L, ops, B, on, tg, F = self.L, self.ops, self.B, self.online, self.target, self.L.F
+        wo, wt, wsel, wf = self.ws_o, self.ws_t, self.ws_s, self.ws_f
+
+        def taus(net, ws, k):
+            net.fqf_taus(ws, B)
+            if u.rand is not None:
+                ws.tau_all[: B * (F + 1)].copy_(u.rand[2 * k].reshape(-1)); ws.tau_hat[: B * F].copy_(u.rand[2 * k + 1].reshape(-1))
+        sel, ws_sel = (on, wsel) if self.double_q else (tg, wt)      # greedy next action at the selecting network's own fractions
+        self._upd_encode(u, (on, wo, False, True), (tg, wt, True, False), (on, wsel, True, False) if self.double_q else None)
+        taus(on, wo, 0)
+        on.head(wo, B, wo.tau_hat, F)
+        taus(sel, ws_sel, 1)
+        sel.head(ws_sel, B, ws_sel.tau_hat, F)
+        sel.select(ws_sel, B, F, self.a_star)
+        tg.head(wt, B, wo.tau_hat, F)           # quirk Q16: target evaluated at the ONLINE tau-hats
+        ops.quantile_target(wt.q, F * L.A, L.A, 1, self.a_star, u.rew, u.done, self.gamma_n, B, F, self.y)
+        wo.dq.zero_()
+        ops.loss_quantile_huber(wo.q, F * L.A, L.A, 1, self.y, wo.tau_hat, F, u.act, u.wgt, B, F, F, self.loss, wo.dq, self.state)
+        # fraction loss: q at the interior taus (no grad), its gradient w.r.t. the fraction logits, RMSprop
+        ops.fqf_inner_taus(wo.tau_all, wf.taus, B, F)                      # taus[:, 1:-1] -> [B][F-1]
+        on.head(wf, B, wf.taus, F - 1, feat=wo.act3)
+        ops.fqf_fraction_loss(wf.q, wo.q, wo.tau_all, u.act, u.wgt, B, F, L.A, L.Fpad, self.frac_loss, self.dfrac_logits, wo.frac_logits)
+        ops.dense_wgrad(self.dfrac_logits, wo.act3, L.feat, self.grads[L.blocks["frac"].all], B, L.Fpad, L.feat, self.slabs)
+        # the fraction net's RMSprop step (agent.py:140-147) runs in apply(): nothing in this update reads the fraction net again, and
+        # under data parallelism its gradient has then been reduced with the dense bucket like every other block
+        u.frac = self.frac_loss
 
     def forward_dense(self, frames, slot, sample_stride, act, rew, done, wgt, rand: Optional[List[torch.Tensor]] = None, tstage: Optional[int] = None):
         """Forward passes, losses and the dense half of the backward pass (every gradient but the convolution blocks', which
@@ -818,172 +979,11 @@ class DeviceLearner:
         so that both sides evaluate q(tau) at bit-identical fractions; the fraction net still runs (its logits feed the fraction loss).
         Returns the per-sample loss tensor (device) — and for FQF also the fraction loss.
         """
-        L, ops, B = self.L, self.ops, self.B
-        on, tg = self.online, self.target
-        nxt = self.obs_bytes
-        if tstage is not None and not self.target_stage_supported:
-            raise ValueError("tstage: this learner's target pass cannot run as a separate stage")
-        if self.net_reset_freq > 0 and tstage is not None:
-            raise ValueError("tstage: not together with learner.net_reset_freq (the separately staged target pass has read a target the reset rewrites)")
-        if self.aug_shift > 0:
-            if tstage is not None:
-                raise ValueError("tstage: not together with learner.aug_shift (the separately staged target pass has read the unshifted ring)")
-            ops.augment_shift(frames, slot, sample_stride, L.C, L.H, L.W, self.aug_shift, B, self.aug_rng.seed, self.state, 0, self.aug_stage)
-            frames, slot, sample_stride = self.aug_stage, None, 2 * self.obs_bytes
-        if L.noisy:
-            mods = on.compose_mods() + tg.compose_mods()
-            if len(mods) <= 6:
-                ops.noisy_multi(False, mods)            # both networks' effective weights in one launch
-            else:
-                on.compose_noise()
-                tg.compose_noise()
-        algo = L.algo
-        wo, wt, wsel = self.ws_o, self.ws_t, self.ws_s
-        frac = None
-        have_draw = have_dh = False
-        if algo == "mdqn" and L.A + (1 if L.dueling else 0) <= 24 and hasattr(ops, "mdqn_head_loss_slabs"):
-            # round 5: dqn's path with the Munchausen target (a0_mdqn_head_loss_slabs) — the three passes' encoders in one launch, their fc1 GEMMs in one grouped launch,
-            # and one kernel from the fc1 slabs to loss, head gradient and dh.  The third pass is the TARGET network on the current observation (agent.py:202-204).
-            wm = self.ws_m
-            (Wo, bo), (Wt, bt) = on.wb("head"), tg.wb("head")
-            ns = ops.dense_fwd_partial_slabs(B, 512, L.feat)
-            if getattr(self, "_fc1_slabs", None) is None or self._fc1_slabs[0].numel() < ns * B * 512:
-                self._fc1_slabs = [ops.empty(ns * B * 512) for _ in range(3)]
-                self._q_cur = ops.empty(B * L.A)
-            (Wf_o, bf_o), (Wf_t, bf_t) = on.wb("fc1"), tg.wb("fc1")
-            self._encode_passes(frames, slot, sample_stride, [(tg, wt, nxt, False), (tg, wm, 0, False), (on, wo, 0, True)])
-            if hasattr(ops, "dense_fwd_partial_multi") and ops.dense_fwd_partial_multi_ok(3, B, 512, L.feat):
-                ns = ops.dense_fwd_partial_multi([wo.act3, wt.act3, wm.act3], L.feat, [Wf_o, Wf_t, Wf_t], B, 512, L.feat, self._fc1_slabs[:3])
-            else:
-                ops.dense_fwd_partial(wt.act3, L.feat, Wf_t, B, 512, L.feat, self._fc1_slabs[1])
-                ops.dense_fwd_partial(wm.act3, L.feat, Wf_t, B, 512, L.feat, self._fc1_slabs[2])
-                ops.dense_fwd_partial(wo.act3, L.feat, Wf_o, B, 512, L.feat, self._fc1_slabs[0])
-            ops.mdqn_head_loss_slabs(self._fc1_slabs[0], self._fc1_slabs[1], self._fc1_slabs[2], ns, bf_o, bf_t, wo.h, Wo, bo, Wt, bt, L.A, L.dueling, L.Npad, act, rew, done, wgt,
-                                     self.gamma_n, self.mdqn_tau, self.mdqn_lo, B, self.loss, wo.q, wt.q, self._q_cur, wo.draw, self.state, wo.dh)
-            have_dh = True
-            have_draw = True
-        elif algo == "mdqn":
-            wm = self.ws_m
-            # target net on the next AND on the current observation (agent.py:202-204), online net on the current one: one launch
-            self._encode_passes(frames, slot, sample_stride, [(tg, wt, nxt, False), (tg, wm, 0, False), (on, wo, 0, True)])
-            tg.head(wt, B)
-            tg.head(wm, B)
-            on.head(wo, B)
-            ops.loss_mdqn(wo.q, wt.q, wm.q, L.A, act, rew, done, wgt, self.gamma_n, self.mdqn_tau, self.mdqn_lo, B, self.loss, wo.dq, self.state)
-        elif algo == "dqn" and L.A + (1 if L.dueling else 0) <= 24:
-            # heads, loss and head gradient in one kernel that also finishes fc1 from the GEMMs' split-K slabs (a0_dqn_head_loss_slabs):
-            # only fc1 runs as a GEMM, and there are no reduction launches
-            (Wo, bo), (Wt, bt) = on.wb("head"), tg.wb("head")
-            ns = ops.dense_fwd_partial_slabs(B, 512, L.feat)
-            if getattr(self, "_fc1_slabs", None) is None or self._fc1_slabs[0].numel() < ns * B * 512:
-                self._fc1_slabs = [ops.empty(ns * B * 512) for _ in range(3 if self.double_q else 2)]
-            (Wf_o, bf_o), (Wf_t, bf_t) = on.wb("fc1"), tg.wb("fc1")
-            s_tg = self._fc1_slabs[1]
-            self._encode_passes(frames, slot, sample_stride, ([(tg, wt, nxt, False)] if tstage is None else []) + ([(on, wsel, nxt, False)] if self.double_q else []) + [(on, wo, 0, True)])
-            n_fc1 = 3 if self.double_q else 2
-            if tstage is None and hasattr(ops, "dense_fwd_partial_multi") and ops.dense_fwd_partial_multi_ok(n_fc1, B, 512, L.feat):
-                # the passes' fc1 GEMMs as ONE launch: together they fill the chip with a half / a third of the splits each would need alone
-                ns = ops.dense_fwd_partial_multi([wo.act3, wt.act3] + ([wsel.act3] if self.double_q else []), L.feat, [Wf_o, Wf_t] + ([Wf_o] if self.double_q else []),
-                                                 B, 512, L.feat, self._fc1_slabs[:n_fc1])
-            else:
-                if tstage is None:
-                    ops.dense_fwd_partial(wt.act3, L.feat, Wf_t, B, 512, L.feat, s_tg)
-                else:
-                    s_tg = self._tstage_buf(tstage)[1]
-                if self.double_q:
-                    ops.dense_fwd_partial(wsel.act3, L.feat, Wf_o, B, 512, L.feat, self._fc1_slabs[2])
-                ops.dense_fwd_partial(wo.act3, L.feat, Wf_o, B, 512, L.feat, self._fc1_slabs[0])
-            ops.dqn_head_loss_slabs(self._fc1_slabs[0], s_tg, self._fc1_slabs[2] if self.double_q else None, ns, bf_o, bf_t, wo.h, Wo, bo, Wt, bt,
-                                    L.A, L.dueling, L.Npad, act, rew, done, wgt, self.gamma_n, B, self.loss, wo.q, wt.q, wo.draw, self.state, wo.dh)
-            have_dh = True           # ... and the head's backward-data pass: dh is written by the same kernel
-            have_draw = True
-        elif algo == "c51" and hasattr(ops, "c51_head_loss_slabs"):
-            # three fc1 GEMMs (their split-K slabs finished by ONE reduction launch), the online head as ONE GEMM over [s ; s'] rows, the target head, and
-            # one launch for everything behind them (a0_c51_head_loss_slabs: slab sums, dueling, greedy next action, projection + cross entropy, head gradient)
-            buf, nh_on, nh_tg, R_on = self._dist_heads_to_slabs(frames, slot, sample_stride, tstage)
-            _, bh_o = on.wb("head")
-            _, bh_t = tg.wb("head")
-            ops.c51_head_loss_slabs(buf["hs_on"], nh_on, R_on, buf["hs_tg"], nh_tg, B if self.double_q else -1, bh_o, bh_t, L.Npad, L.A, L.T, L.dueling, act, rew, done, wgt,
-                                    self.atoms, self.gamma_n, self.vmin, self.vmax, B, self.loss, wo.draw, self.state, q_on=wo.q, q_tg=wt.q, m_out=self.m_proj,
-                                    a_star=self.a_star)
-            have_draw = True
-        elif algo == "qr" and self._qr_fused_ok():
-            # round 5: the same layer structure as c51 (grouped fc1 GEMMs, one reduction launch, grouped head GEMMs) and ONE launch from the head slabs to the
-            # quantile Huber loss and the head gradient (a0_qr_head_loss_slabs; agent.py:272-293)
-            buf, nh_on, nh_tg, R_on = self._dist_heads_to_slabs(frames, slot, sample_stride, tstage)
-            _, bh_o = on.wb("head")
-            _, bh_t = tg.wb("head")
-            ops.qr_head_loss_slabs(buf["hs_on"], nh_on, R_on, buf["hs_tg"], nh_tg, B if self.double_q else -1, bh_o, bh_t, L.Npad, L.A, L.T, L.dueling, act, rew, done, wgt,
-                                   self.qr_taus, self.gamma_n, B, self.loss, wo.draw, self.state, q_on=wo.q, q_tg=wt.q, a_star=self.a_star)
-            have_draw = True
-        elif algo in ("dqn", "c51", "qr"):
-            self._encode_passes(frames, slot, sample_stride, [(tg, wt, nxt, False)] + ([(on, wsel, nxt, False)] if self.double_q else []) + [(on, wo, 0, True)])
-            tg.head(wt, B)
-            if self.double_q:
-                on.head(wsel, B)
-                on.select(wsel, B, 1, self.a_star, atoms=getattr(self, "atoms", None))
-            else:
-                tg.select(wt, B, 1, self.a_star, atoms=getattr(self, "atoms", None))
-            on.head(wo, B)
-            if algo == "dqn":
-                ops.loss_dqn(wo.q, wt.q, L.A, act, self.a_star, rew, done, wgt, self.gamma_n, B, self.loss, wo.dq, self.state)
-            elif algo == "c51":
-                ops.loss_c51(wo.q, wt.q, L.A, L.T, act, self.a_star, rew, done, wgt, self.atoms, self.gamma_n, self.vmin, self.vmax, B,
-                             self.loss, wo.dq, self.m_proj, self.state)
-            else:
-                ops.quantile_target(wt.q, L.A * L.T, 1, L.T, self.a_star, rew, done, self.gamma_n, B, L.T, self.y)
-                wo.dq.zero_()
-                ops.loss_quantile_huber(wo.q, L.A * L.T, 1, L.T, self.y, self.qr_taus, 0, act, wgt, B, L.T, L.T, self.loss, wo.dq, self.state)
-        elif algo == "iqn":
-            t_sel, t_tgt, t_on = rand
-            K, Nd, N = self.K, self.N_dash, self.N
-            self._encode_passes(frames, slot, sample_stride, [(tg, wt, nxt, False)] + ([(on, wsel, nxt, False)] if self.double_q else []) + [(on, wo, 0, True)])
-            if self.double_q:
-                on.head(wsel, B, t_sel, K)
-                on.select(wsel, B, K, self.a_star)
-            else:
-                tg.head(wt, B, t_sel, K)
-                tg.select(wt, B, K, self.a_star)
-            tg.head(wt, B, t_tgt, Nd)
-            ops.quantile_target(wt.q, Nd * L.A, L.A, 1, self.a_star, rew, done, self.gamma_n, B, Nd, self.y)
-            on.head(wo, B, t_on, N)
-            wo.dq.zero_()
-            ops.loss_quantile_huber(wo.q, N * L.A, L.A, 1, self.y, t_on, N, act, wgt, B, N, Nd, self.loss, wo.dq, self.state)
-        elif algo == "fqf":
-            F = L.F
-            def taus(net, ws, k):
-                net.fqf_taus(ws, B)
-                if rand is not None:
-                    ws.tau_all[: B * (F + 1)].copy_(rand[2 * k].reshape(-1)); ws.tau_hat[: B * F].copy_(rand[2 * k + 1].reshape(-1))
-            self._encode_passes(frames, slot, sample_stride, [(on, wo, 0, True), (tg, wt, nxt, False)] + ([(on, wsel, nxt, False)] if self.double_q else []))
-            taus(on, wo, 0)
-            on.head(wo, B, wo.tau_hat, F)
-            if self.double_q:
-                taus(on, wsel, 1)
-                on.head(wsel, B, wsel.tau_hat, F)
-                on.select(wsel, B, F, self.a_star)
-            else:
-                taus(tg, wt, 1)
-                tg.head(wt, B, wt.tau_hat, F)
-                tg.select(wt, B, F, self.a_star)
-            tg.head(wt, B, wo.tau_hat, F)           # quirk Q16: target evaluated at the ONLINE tau-hats
-            ops.quantile_target(wt.q, F * L.A, L.A, 1, self.a_star, rew, done, self.gamma_n, B, F, self.y)
-            wo.dq.zero_()
-            ops.loss_quantile_huber(wo.q, F * L.A, L.A, 1, self.y, wo.tau_hat, F, act, wgt, B, F, F, self.loss, wo.dq, self.state)
-            # fraction loss: q at the interior taus (no grad), its gradient w.r.t. the fraction logits, RMSprop
-            wf = self.ws_f
-            ops.fqf_inner_taus(wo.tau_all, wf.taus, B, F)                      # taus[:, 1:-1] -> [B][F-1]
-            on.head(wf, B, wf.taus, F - 1, feat=wo.act3)
-            ops.fqf_fraction_loss(wf.q, wo.q, wo.tau_all, act, wgt, B, F, L.A, L.Fpad, self.frac_loss, self.dfrac_logits, wo.frac_logits)
-            gfr = self.grads[L.blocks["frac"].all]
-            ops.dense_wgrad(self.dfrac_logits, wo.act3, L.feat, gfr, B, L.Fpad, L.feat, self.slabs)
-            # the fraction net's RMSprop step (agent.py:140-147) runs in apply(): nothing in this update reads the fraction net again, and
-            # under data parallelism its gradient has then been reduced with the dense bucket like every other block
-            frac = self.frac_loss
-        else:
-            raise NotImplementedError(f"algo {algo} has no device learner yet")
-        self._backward_dense(wo, B, have_draw, have_dh)
-        self._bw = (wo, frames, slot, sample_stride, B)
+        u = self._upd = _Upd(frames, slot, sample_stride, act, rew, done, wgt, rand, tstage)
+        self._upd_prepare(u)
+        {"scalar": self._fwd_scalar, "dist": self._fwd_dist, "layerwise": self._fwd_layerwise, "iqn": self._fwd_iqn, "fqf": self._fwd_fqf}[self.family](u)
+        self._backward_dense(self.ws_o, self.B, u.have_draw, u.have_dh)
         if self._bucketed_hook():      # the NaN flag rides at the tail of the dense gradient bucket
-            ops.nan_flag_export(self.state, self.grads[L.n_params_padded: L.n_params_padded + 1])
-        return (self.loss, frac) if frac is not None else self.loss
+            self.ops.nan_flag_export(self.state, self.grads[self.L.n_params_padded: self.L.n_params_padded + 1])
+        u.act = u.rew = u.done = u.wgt = u.rand = None      # backward_encoder reads the batch (frames, slot, stride) again, nothing else
+        return (self.loss, u.frac) if u.frac is not None else self.loss

@@ -379,6 +379,22 @@ class CpuOps:
     def dense_fwd_partial_slabs(self, R, N, K) -> int:
         return 1
 
+    # the grouped / paired launches' shape predicates: this backend has none of those launches, so the learner composes the single ones
+    def dense_fwd_partial_multi_ok(self, n, R, N, K) -> bool:
+        return False
+
+    def dense_dgrad_wgrad_ok(self, R, N, K) -> bool:
+        return False
+
+    def dense_dgrad_wgrad_ok2(self, R, N, K) -> bool:
+        return False
+
+    def dense_dgrad_wgrad2_ok(self, R, N, K, N2, K2) -> bool:
+        return False
+
+    def dense_dgrad_hadamard_ok(self, R, N, K, n) -> bool:
+        return False
+
     def dense_fwd_partial(self, X, ldx, W, R, N, K, slabs):
         self.dense_fwd(X, ldx, W, torch.zeros(N), slabs, R, N, K, False, self.empty(max(self.dense_fwd_scratch(R, N, K), 1)))
         return 1

@@ -444,6 +444,65 @@ def test_full_size_check_machinery_on_the_small_geometry(ops, name):
     assert all(n > 0 for _, n, _ in stats.values())
 
 
+# the layer-by-layer family's wide dqn head (A + dueling = 25, the smallest): the one arm no handle-equals-composition case reaches (the handle refuses it)
+WIDE_DQN = {"a24-duel": (NetSpec("dqn", 24, dueling=True), Hyper(double_q=False, n_step=1)), "a25-double-n3": (NetSpec("dqn", 25), Hyper(double_q=True, n_step=3))}
+
+
+@pytest.mark.parametrize("case", list(WIDE_DQN))
+def test_wide_dqn_update_at_real_geometry(ops, case):
+    """The wide dqn head at 84x84, B = 32 — the smallest batch at which check_update_full_size's cap of 1e-4 differing ReLU decisions still permits one
+    in fc1 (40, 16, 10 and 1 in conv1, conv2, conv3, fc1; none differ on this backend).  On the GPU the fused encoder, the deferred dense reductions and
+    the one-launch tail run behind this arm only at this geometry (tests/test_gpu_engine.py::test_wide_dqn_update_at_real_geometry)."""
+    spec, hp = WIDE_DQN[case]
+    check_update_full_size(ops, spec, hp, 32)
+
+
+FAMILIES = [(NetSpec("dqn", 24, obs_shape=TINY), "scalar"), (NetSpec("dqn", 24, dueling=True, obs_shape=TINY), "layerwise"),
+            (NetSpec("mdqn", 23, dueling=True, obs_shape=TINY), "scalar"), (NetSpec("mdqn", 24, dueling=True, obs_shape=TINY), "layerwise"),
+            (NetSpec("c51", 3, num_atoms=51, obs_shape=TINY), "dist"), (NetSpec("qr", 4, num_atoms=200, obs_shape=TINY), "dist"),
+            (NetSpec("qr", 33, num_atoms=8, obs_shape=TINY), "layerwise"), (NetSpec("iqn", 9, obs_shape=TINY), "iqn"), (NetSpec("fqf", 4, obs_shape=TINY), "fqf")]
+
+
+@pytest.mark.parametrize("spec,family", FAMILIES, ids=[f"{s.algo}-a{s.action_dim}{'-duel' if s.dueling else ''}" for s, _ in FAMILIES])
+def test_learner_family(ops, spec, family):
+    """DeviceLearner.family, decided once at creation: the tag forward_dense dispatches on (a0_family on the handle's side).  The target pass as a stage of
+    its own needs the fused encoder, which this backend does not have."""
+    dev = DeviceLearner(ops, NetLayout.from_spec(spec), 8)
+    assert dev.family == family
+    assert dev.target_stage_supported is False
+
+
+class _NoShapePredicates:
+    """A backend that has neither the grouped / paired launches nor their shape predicates: CpuOps with the five predicates hidden."""
+    HIDDEN = ("dense_fwd_partial_multi_ok", "dense_dgrad_wgrad_ok", "dense_dgrad_wgrad_ok2", "dense_dgrad_wgrad2_ok", "dense_dgrad_hadamard_ok")
+
+    def __init__(self, ops):
+        self._ops = ops
+
+    def __getattr__(self, name):
+        if name in self.HIDDEN:
+            raise AttributeError(name)
+        return getattr(self._ops, name)
+
+
+def test_both_backends_have_every_shape_predicate_under_its_name():
+    """A predicate renamed or misspelt on one side would not fail any equality test — the single launches are bit-identical — it would only cost speed: so the
+    names the learner looks up are held to both backends here."""
+    from agent0_amd.ops import HipOps
+    assert _NoShapePredicates.HIDDEN == DeviceLearner.SHAPE_PREDICATES
+    for name in DeviceLearner.SHAPE_PREDICATES:
+        assert callable(getattr(HipOps, name, None)) and callable(getattr(CpuOps, name, None)), name
+
+
+@pytest.mark.parametrize("name,B,dq,n", [("dqn_duel", 8, True, 3), ("c51", 8, False, 1), ("iqn", 6, False, 1)])
+def test_update_on_a_backend_without_the_shape_predicates(ops, name, B, dq, n):
+    """The learner looks the predicates of the grouped / paired launches up once; a backend without them gets the single launches (scalar, dist and quantile
+    families: every place a predicate is asked) and the update still matches the oracle."""
+    bare = _NoShapePredicates(ops)
+    assert not any(hasattr(bare, p) for p in bare.HIDDEN)
+    check_update(bare, name, B, dq, n)
+
+
 @pytest.mark.parametrize("name,dq,n", [("iqn", False, 1), ("fqf_duel", True, 3)])
 def test_quantile_update_through_the_kept_embedding_launch(name, dq, n):
     """The differentiated pass of the quantile heads through dense_fwd_mul_keep (the embedding kept for the backward pass and its product with

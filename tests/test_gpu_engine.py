@@ -324,6 +324,15 @@ def test_update_full_size(hip, algo, A, dq, n, duel, noisy):
             {k: {"differ": int(v[0]), "of": int(v[1]), "largest_preactivation_rel": float(v[2])} for k, v in stats.items()})
 
 
+@pytest.mark.parametrize("case", list(E.WIDE_DQN))
+def test_wide_dqn_update_at_real_geometry(hip, case):
+    """The layer-by-layer family with a wide dqn head (A + dueling = 25) at 84x84, B = 32: the fused encoder, the deferred dense reductions and the one-launch
+    tail behind the arm that test_update reaches at 36x36 only and that the handle refuses (tests/test_engine_emul.py::test_wide_dqn_update_at_real_geometry)."""
+    spec, hp = E.WIDE_DQN[case]
+    stats = E.check_update_full_size(hip, spec, hp, 32)
+    print({k: (v[0], v[1], f"{v[2]:.1e}") for k, v in stats.items()})
+
+
 @pytest.mark.parametrize("name", ["fqf", "fqf_duel", "fqf_duel_a18"])
 def test_fqf_update_with_device_fractions(hip, name):
     """The un-injected FQF update at the small geometry: the device's own a0_fqf_taus -> cos -> head -> loss -> gradient chain against
@@ -1048,7 +1057,7 @@ def test_native_qr_and_mdqn_learner_handles_equal_the_per_kernel_composition(hip
     cap = max(200, B + 40)
     dev = DeviceLearner(hip, L, B, n_step=n_step, double_q=double_q, target_update_freq=3)
     if "layerwise" in request.node.callspec.id:
-        assert (not dev._qr_fused_ok()) if algo == "qr" else (L.A + dueling > 24), "this case is meant for the layer-by-layer arm (a0_fwd_layerwise)"
+        assert dev.family == "layerwise", "this case is meant for the layer-by-layer arm (a0_fwd_layerwise)"
     dev.online.load_state_dict(recipe.make_state_dict(spec, 11))
     dev.target.load_state_dict(recipe.make_state_dict(spec, 12))
     seed = 42 + 15485863
