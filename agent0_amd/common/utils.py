@@ -35,6 +35,16 @@ def set_random_seed(seed: int) -> None:
     torch.manual_seed(np.random.randint(int(1e6)))
 
 
+def pinned_copy(cache: dict, name: str, src: torch.Tensor) -> torch.Tensor:
+    """``src`` on its way into a page-locked host buffer of its size and type, kept in ``cache`` under ``(name, numel)``: the copy is enqueued on the current
+    stream and not waited for — the caller reads the buffer after an event or a synchronize of its own."""
+    key = (name, src.numel())
+    if key not in cache:
+        cache[key] = torch.empty(src.numel(), dtype=src.dtype).pin_memory()
+    cache[key].copy_(src, non_blocking=True)
+    return cache[key]
+
+
 class DeviceRng:
     """Philox streams on the device (agent0_amd/csrc/rng.hip).  Every consumer owns a stream id and a running offset,
     so a run is reproducible from (seed, rank) alone and ranks never share draws."""

@@ -15,13 +15,13 @@ from __future__ import annotations
 import os
 
 from dataclasses import dataclass, replace
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from agent0_amd.common.atari_wrappers import make_atari
-from agent0_amd.common.utils import DeviceRng
+from agent0_amd.common.utils import DeviceRng, pinned_copy
 from .config import AlgoEnum, ExpConfig
 from .dist import eps_ladder_span, graph_capture_kwargs
 from .engine import DeviceLearner, Workspace
@@ -70,6 +70,17 @@ class _Roll:
     step_enc: bool = False                       # ... which also encodes the env's new observation for step t + 1
     planes: bool = False                         # quantile heads: fc1 reads the term planes of ``refresh_fc1_planes``
     fc1p: bool = False                           # scalar and c51 / qr heads: fc1 reads the planes of ``refresh_actor_fc1_planes``
+
+
+class Pending(NamedTuple):
+    """A rollout that has been issued and not yet collected (``sample_async`` -> ``block_of`` / ``stats_async`` / ``sample_finish``)."""
+    T: int
+    bound: bool                                  # the rows go straight into the actor's replay (or stage) ring, from ``start`` on
+    test: bool
+    st: Optional[dict]                           # where an unbound rollout leaves its rows
+    start: int
+    frames_out: list
+    done_ev: torch.cuda.Event                    # recorded behind the rollout's last launch
 
 
 class Actor:
@@ -136,6 +147,7 @@ class Actor:
         self.eps_vec = None
         self.atoms = self.model.head.atoms.reshape(-1).contiguous() if self.L.algo == "c51" else None
         self._stage = None
+        self._stat_host = {}                         # ``stats_async``: its page-locked buffers
         self._host_actions = None                    # ``_rollout_host``: the action buffer and its alternate
         self.fused_commit = hasattr(self.envs, "step_commit") and (self.obs_bytes == 4 * 84 * 84)
         # scalar heads on the synthetic env: the tail and the env step share one launch (a0_actor_qhead_env_step)
@@ -542,7 +554,7 @@ class Actor:
             self._rollout(roll)
         done_ev = torch.cuda.Event()
         done_ev.record()
-        return (T, bound, test, st, start, frames_out, done_ev)
+        return Pending(T, bound, test, st, start, frames_out, done_ev)
 
     def block_of(self, pending) -> TransitionBlock:
         """The TransitionBlock of a rollout that has been issued (``sample_async``) but not necessarily finished: what ``replay.extend`` needs is
@@ -569,16 +581,9 @@ class Actor:
     def stats_async(self, pending):
         """The statistics of an issued rollout on their way to page-locked host buffers, stream-ordered behind it (and ahead of the next rollout, which reuses the
         device buffers); ``stats_finish`` waits for exactly these copies, not for whatever was enqueued afterwards."""
-        T = pending[0]
+        T = pending.T
         n = T * self.E
-        host = self.__dict__.setdefault("_stat_host", {})
-        out = []
-        for name, src in (("qs", self.qs[:T]), ("mask", self.stat_mask[:n]), ("ret", self.stat_ret[:n])):
-            key = (name, src.numel())
-            if key not in host:
-                host[key] = torch.empty(src.numel(), dtype=src.dtype).pin_memory()
-            host[key].copy_(src, non_blocking=True)
-            out.append(host[key])
+        out = [pinned_copy(self._stat_host, name, src) for name, src in (("qs", self.qs[:T]), ("mask", self.stat_mask[:n]), ("ret", self.stat_ret[:n]))]
         ev = torch.cuda.Event()
         ev.record()
         return (ev, out)
@@ -632,7 +637,7 @@ class Actor:
         """The handle of a rollout that had been issued ahead when the snapshot was taken and whose rows and statistics the loaded state holds."""
         ev = torch.cuda.Event()
         ev.record()
-        return (int(self.cfg.actor.sample_steps), True, False, None, int(start), [], ev)
+        return Pending(int(self.cfg.actor.sample_steps), True, False, None, int(start), [], ev)
 
     def close(self):
         self.envs.close()

@@ -83,9 +83,12 @@ class _Batch(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("idx", "slot", "act", "rew", "done", "prio", "weights")]
 
 
+NOT_WRAPPERS = frozenset({"epsilon_fn", "on_snapshot_loaded"})      # instance-level callables that are the Trainer's own: the schedule, launch.TrainerNode's hook
+
+
 def _wrapped(obj) -> bool:
     """An instance-level function on one of the hot-loop objects: a test harness intercepting calls (tests/test_gpu_trace.py)."""
-    return any(type(v).__name__ in ("function", "method") for k, v in vars(obj).items() if k != "epsilon_fn")
+    return any(type(v).__name__ in ("function", "method") for k, v in vars(obj).items() if k not in NOT_WRAPPERS)
 
 
 def hook_ok(hook) -> bool:
@@ -122,14 +125,14 @@ def eligible(tr) -> Optional[str]:
             return "dqn handle: A + dueling <= 24"
     elif algo in ("iqn", "fqf"):
         # the merged quantile tail (device env) or, on a host pool, the quantile tail without the env step (Actor.quant_slabs)
-        tail = getattr(actor, "quant_slabs", False) if isinstance(actor.envs, HostEnvPool) else getattr(actor, "quant_tail", False)
+        tail = actor.quant_slabs if isinstance(actor.envs, HostEnvPool) else actor.quant_tail
         if cfg.action_dim + (1 if lc.dueling_head else 0) > 32 or not tail:
             return "quantile handles: A + dueling <= 32, the merged quantile tail"
     elif algo == "qr":
-        if not getattr(tr.actors[1], "dist_tail", False):
+        if not actor.dist_tail:
             return "qr handle: the distributional tail kernel"
     elif algo == "mdqn":
-        if not getattr(tr.actors[1], "fused_tail", False):
+        if not actor.fused_tail:
             return "mdqn handle: A + dueling <= 24"
     elif algo != "c51":
         return f"no handle for {algo}"
@@ -139,7 +142,7 @@ def eligible(tr) -> Optional[str]:
     if rp.use_sumtree and lc.batch_size > 1024:
         return "prioritized batches above 1024"
     eng = tr.learner.engine
-    if not (eng.online.fused and eng.online.fused_dgrad) or tr.ops.gemm_mode() != 1 or not getattr(eng, "_defer_dense", False):
+    if not (eng.online.fused and eng.online.fused_dgrad) or tr.ops.gemm_mode() != 1 or not eng._defer_dense:
         return "a tuning mode of the Python composition"
     if lc.learner_steps > eng.loss_ring.numel():
         return "block longer than the loss ring"
@@ -153,7 +156,7 @@ def eligible(tr) -> Optional[str]:
 class NativeLoop:
     def __init__(self, tr):
         self.tr = tr
-        self.learner = self.rbuf = self.actor = None        # close() destroys whatever exists, also when a later create call fails
+        self.learner = self.rbuf = self.actor = self.stage = None        # close() destroys whatever exists, also when a later create call fails
         self.lib, self.ok = _abi.load(), _abi.check
         try:
             self._create(tr)
@@ -227,7 +230,6 @@ class NativeLoop:
             self._pool_desc = pool_desc(self.pool)
             ok(lib.a0_actor_attach_pool(self.actor, C.addressof(self._pool_desc)), "a0_actor_attach_pool")
             self._pool_whole = 0
-        self.stage = None
         if self.lp:
             sg = tr.stage
             sd = _RbufDesc(int(sg.size), int(sg.obs_bytes), min(self.B, int(sg.size)), 0, float(rc.alpha), float(rc.eps), float(rc.beta0), int(cfg.trainer.total_steps), int(cfg.seed) + 7)
@@ -267,16 +269,29 @@ class NativeLoop:
         actor.obs = pool._obs[pool.seq & 1]
 
     def _commit(self, st):
+        self.ok(self.lib.a0_rbuf_commit(self.rbuf, self.T * self.E, st), "a0_rbuf_commit")
+        self._book()
+
+    def _book(self):
+        """A rollout's rows have entered the ring (``_commit``, or the launch schedule's a0_rbuf_extend_from): the frame count and the ReplayDataset's counters follow
+        (its buffers ARE the handle's), and the sampler's beta."""
         tr, rp = self.tr, self.tr.replay
         n = self.T * self.E
-        self.ok(self.lib.a0_rbuf_commit(self.rbuf, n, st), "a0_rbuf_commit")
         tr.frame_count += n
-        rp.written += n                                   # the ReplayDataset's counters follow (its buffers ARE the handle's)
+        rp.written += n
         rp.top = min(rp.top + n, rp.size)
         if self.prio:
             beta = C.c_double()
             self.ok(self.lib.a0_rbuf_info(self.rbuf, None, None, C.addressof(beta)), "a0_rbuf_info")
             rp.beta = beta.value
+
+    def _collect_wait(self, stream):
+        """Waits for the rollout on ``stream`` and takes its statistics into ``_qs`` / ``_rs`` (a0_actor_collect synchronises that stream)."""
+        self.ok(self.lib.a0_actor_collect(self.actor, self._qs, self._rs, self.T * self.E, C.addressof(self._nret), stream), "a0_actor_collect")
+
+    def _collect(self):
+        """The statistics the last collect call left: per-step mean max-Q and the finished episodes' returns."""
+        self.tr._collect(np.ctypeslib.as_array(self._rs)[: self._nret.value].tolist(), np.ctypeslib.as_array(self._qs).tolist())
 
     # the three links of one update (trainer.py:81-104) — kept apart so that a parity harness can stand between them (tests/test_gpu_trace.py walks this very path
     # against the CPU oracle link by link)
@@ -297,16 +312,17 @@ class NativeLoop:
     def _priority(self, st):
         self.ok(self.lib.a0_rbuf_update_priority(self.rbuf, self.loss_ptr, self.tr.learner.engine.state.data_ptr(), st), "a0_rbuf_update_priority")
 
-    def _block(self, st) -> int:
+    def _block(self, st):
+        """The update block (Trainer._block): -> its statistics record.  The Adam launch writes the block's batch-mean losses to ring slots ring0 .. ring0 + n - 1 and,
+        with learner.clip_grad_norm on, the pre-clip gradient norms beside them."""
         tr, lib, ok = self.tr, self.lib, self.ok
         cfg = tr.cfg
-        tr._gn0, tr.GNs = None, []
+        blk = tr._block_open(on_ring=True)
         if int(lib.a0_rbuf_len(self.rbuf)) <= cfg.trainer.training_start_steps:
-            return 0
-        ln = tr.learner
+            return blk
         n = int(cfg.learner.learner_steps)
-        if self.fqf and tr._floss_means.numel() < n:
-            tr._loss_means, tr._floss_means = tr.ops.zeros(n), tr.ops.zeros(n)
+        if self.fqf:
+            tr._mean_buffers(n)
         with tr.ops.range("update_block"):
             for i in range(n):
                 b = self._sample(i, n, st)
@@ -316,12 +332,11 @@ class NativeLoop:
                 if self.fqf:                              # the `fraction_loss` statistic (trainer.py:99-101): batch mean of the update's fraction losses
                     ok(lib.a0_learner_get_frac_loss(self.learner, self._floss.data_ptr(), st), "a0_learner_get_frac_loss")
                     tr.ops.mean_rows(self._floss, 1, self.B, tr._floss_means[i:i + 1])
-        tr._gn0 = tr._gnorm_ring_start()                  # ... and, with learner.clip_grad_norm on, the pre-clip gradient norms beside them
-        tr._ring0 = ln.updates_issued                     # the Adam launch wrote the block's batch-mean losses to ring slots ring0 .. ring0 + n - 1
-        ln.updates_issued += n
+        tr.learner.updates_issued += n
+        blk.n_upd, blk.has_frac = n, self.fqf
         if self.prio and not self.flat:
             tr.replay._top_stale = True                   # the handle defers the tree's top levels to its next sample; ReplayDataset.tree brings them up to date for other readers
-        return n
+        return blk
 
     # ------------------------------------------------------------------ Trainer.run_iteration
     def run_iteration(self, prefetch: bool = False):
@@ -332,21 +347,15 @@ class NativeLoop:
             self._rollout(st)
         self._pending_rollout = False
         self._commit(st)
-        n_upd = self._block(st)
-        blk = tr._block_stats_async(n_upd, self.fqf and n_upd > 0)      # loss ring (+ fraction-loss means) -> page-locked buffers, stream-ordered behind the block
+        blk = tr._stats(self._block(st), defer=True)      # loss ring (+ fraction-loss means) -> page-locked buffers, stream-ordered behind the block
         ok(lib.a0_actor_collect_begin(self.actor, st), "a0_actor_collect_begin")
         if prefetch:
             self._rollout(st)                             # the next iteration's rollout before the host waits for this one's statistics
             self._pending_rollout = True
         ok(lib.a0_actor_collect_end(self.actor, self._qs, self._rs, self.T * self.E, C.addressof(self._nret)), "a0_actor_collect_end")
-        tr._block_stats_finish(blk)
-        tr.Qs.extend(np.ctypeslib.as_array(self._qs).tolist())
-        tr.Rs.extend(np.ctypeslib.as_array(self._rs)[: self._nret.value].tolist())
-        result = tr._result()
-        if not prefetch:
-            torch.cuda.synchronize()
-        result.update(fps=tr.num_transitions / (time.time() - tic))
-        return result
+        blk.finish(tr)
+        self._collect()
+        return tr._close(tic, None if prefetch else torch.cuda.synchronize)
 
     # ------------------------------------------------------------------ the launch schedule (Trainer.run_iteration_lp; launch.py:30-63)
     def _snapshot_lp(self):
@@ -382,36 +391,22 @@ class NativeLoop:
         if self._lp_pending is None:
             self._lp_pending = self._rollout_lp(*self._snapshot_lp())          # launch.py:32-37 primes the pipeline before the loop
         # wait for the rollout in flight and take its statistics (a0_actor_collect synchronises the ACTOR stream)
-        ok(lib.a0_actor_collect(self.actor, self._qs, self._rs, self.T * self.E, C.addressof(self._nret), tr.actor_stream.cuda_stream), "a0_actor_collect")
-        start = self._lp_pending
-        qs, rs = np.ctypeslib.as_array(self._qs).tolist(), np.ctypeslib.as_array(self._rs)[: self._nret.value].tolist()
-        eps, ev = self._snapshot_lp()                    # the next rollout acts with the weights and the epsilon of NOW
+        self._collect_wait(tr.actor_stream.cuda_stream)
+        snap = self._snapshot_lp()                       # the next rollout acts with the weights and the epsilon of NOW
         # Trainer.step: extend (the finished rollout's rows from the stage into the ring), then the update block
-        n = self.T * self.E
-        ok(lib.a0_rbuf_extend_from(self.rbuf, self.stage, start, n, st), "a0_rbuf_extend_from")
-        rp = tr.replay
-        tr.frame_count += n
-        rp.written += n
-        rp.top = min(rp.top + n, rp.size)
-        if self.prio:
-            beta = C.c_double()
-            ok(lib.a0_rbuf_info(self.rbuf, None, None, C.addressof(beta)), "a0_rbuf_info")
-            rp.beta = beta.value
-        tr.Qs.extend(qs)
-        tr.Rs.extend(rs)
-        n_upd = self._block(st)
-        blk = tr._block_stats_async(n_upd, self.fqf and n_upd > 0)
-        self._lp_pending = self._rollout_lp(eps, ev)     # ... and runs beside the block
+        ok(lib.a0_rbuf_extend_from(self.rbuf, self.stage, self._lp_pending, self.T * self.E, st), "a0_rbuf_extend_from")
+        self._book()
+        self._collect()
+        blk = tr._stats(self._block(st), defer=True)
+        self._lp_pending = self._rollout_lp(*snap)       # ... and runs beside the block
         torch.cuda.current_stream().synchronize()        # the update block (and the statistics' copies behind it); the next rollout keeps running on the actor stream
-        tr._block_stats_finish(blk)
-        result = tr._result()
-        result.update(fps=tr.num_transitions / (time.time() - tic))
-        return result
+        blk.finish(tr)
+        return tr._close(tic)
 
     def drain_lp(self):
         """The rollout still in flight when the run ends: waited for and dropped, like Trainer.final does for the Python actor's."""
         if self.lp and self._lp_pending is not None:
-            self.ok(self.lib.a0_actor_collect(self.actor, self._qs, self._rs, self.T * self.E, C.addressof(self._nret), self.tr.actor_stream.cuda_stream), "a0_actor_collect")
+            self._collect_wait(self.tr.actor_stream.cuda_stream)
             self._lp_pending = None
 
     # ------------------------------------------------------------------ resumable snapshots (Trainer.save_snapshot / load_snapshot; deepq/snapshot.py)
@@ -479,9 +474,8 @@ class NativeLoop:
             st = torch.cuda.current_stream().cuda_stream
             self._pending_rollout = False
             self._commit(st)
-            self.ok(self.lib.a0_actor_collect(self.actor, self._qs, self._rs, self.T * self.E, C.addressof(self._nret), st), "a0_actor_collect")
-            self.tr.Qs.extend(np.ctypeslib.as_array(self._qs).tolist())
-            self.tr.Rs.extend(np.ctypeslib.as_array(self._rs)[: self._nret.value].tolist())
+            self._collect_wait(st)
+            self._collect()
 
     def __del__(self):
         try:
@@ -490,10 +484,10 @@ class NativeLoop:
             pass
 
     def close(self):
-        if getattr(self, "actor", None) is None and getattr(self, "rbuf", None) is None and getattr(self, "learner", None) is None:
+        if self.actor is None and self.rbuf is None and self.learner is None:
             return
         torch.cuda.synchronize()
-        for h, fn in ((self.actor, self.lib.a0_actor_destroy), (self.rbuf, self.lib.a0_rbuf_destroy), (getattr(self, "stage", None), self.lib.a0_rbuf_destroy),
+        for h, fn in ((self.actor, self.lib.a0_actor_destroy), (self.rbuf, self.lib.a0_rbuf_destroy), (self.stage, self.lib.a0_rbuf_destroy),
                       (self.learner, self.lib.a0_learner_destroy)):
             if h is not None and h.value:
                 fn(h)

@@ -14,6 +14,8 @@ import logging
 import math
 import os
 import time
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -22,7 +24,7 @@ from . import agent as agents
 from .config import ExpConfig, ReplayEnum, to_dict
 from .replay import ReplayDataset, StageRing
 from agent0_amd.common.atari_wrappers import make_atari
-from agent0_amd.common.utils import set_random_seed
+from agent0_amd.common.utils import pinned_copy, set_random_seed
 
 
 def _git_sha() -> str:
@@ -39,6 +41,44 @@ def epsilon_schedule(cfg: ExpConfig):
             return cfg.actor.min_eps
         return (1.0 - step / cfg.trainer.exploration_steps) + cfg.actor.min_eps
     return fn
+
+
+@dataclass
+class _BlockStats:
+    """What one update block leaves for the host (after the learner's ``_Upd`` and the actor's ``_Roll``).  ``_block`` opens it with the slots the block's statistics
+    will lie in and counts its updates; ``Trainer._stats`` fills the host tensors — page-locked copies in flight, or ``.cpu()`` reads; ``finish`` books them once the
+    host has waited for them.  The slot counts are update counts: a ring's slot is the count modulo its length."""
+    n_upd: int = 0
+    ring0: Optional[int] = None                  # the block's first slot in DeviceLearner.loss_ring; None: a0_mean_rows filled ``loss`` from index 0
+    gn0: Optional[int] = None                    # learner.clip_grad_norm: the block's first slot in DeviceLearner.gnorm_ring; None: off
+    has_frac: bool = False                       # fqf: the block left fraction-loss means
+    state: Optional[torch.Tensor] = None         # the unfused optimizer tail does not advance the slot counter: the status words, [6] = the slot of the block's last norm
+    loss: Optional[torch.Tensor] = None          # the host tensors; absent ones stay None
+    floss: Optional[torch.Tensor] = None
+    gnorm: Optional[torch.Tensor] = None
+    wd_partials: Optional[torch.Tensor] = None
+
+    def finish(self, tr):
+        """Extends ``tr.Ls`` / ``tr.FLs``, sets ``tr.GNs`` (the block's norms, its newest ring-length ones when it is longer than the ring) and ``tr.PN`` (learner.weight_decay:
+        the decay launch leaves one double per workgroup, a0_weight_decay; the norm is finished here — the sum in index order, the square root in double)."""
+        n = self.n_upd
+        if not n:
+            return
+        if self.ring0 is None:
+            tr.Ls.extend(self.loss[:n].tolist())
+        else:
+            tr.Ls.extend(float(self.loss[(self.ring0 + i) % self.loss.numel()]) for i in range(n))
+        if self.floss is not None:
+            tr.FLs.extend(self.floss[:n].tolist())
+        if self.gnorm is not None:
+            cap = self.gnorm.numel()
+            k = min(n, cap)
+            tr.GNs = [float(self.gnorm[(self.gn0 + n - k + i) % cap]) for i in range(k)] if self.state is None else [float(self.gnorm[int(self.state[6]) % cap])]
+        if self.wd_partials is not None:
+            total = 0.0
+            for x in self.wd_partials.tolist():
+                total += x
+            tr.PN = math.sqrt(total)
 
 
 class Trainer:
@@ -82,7 +122,16 @@ class Trainer:
             # either way); with a host env, whose workers wait for every step's actions, 23.5 -> 21.7 ms per iteration (profiles/r04_experiments.md)
             self.actor_stream = torch.cuda.Stream(priority=-1)
             self.overlap = True
-            self._pending = None
+        # what is in flight between two iterations: the launch schedule's rollout (``_pending``), the main schedule's rollout issued ahead (``_prefetched``)
+        self._pending = self._prefetched = None
+        # who runs the loop (``_native_loop``): None = undecided, False = the Python classes (``native_loop_reason`` says why), or the NativeLoop
+        self._nl, self.native_loop_reason = None, None
+        self._resume = None                               # ``load_snapshot``: what the handles take over at the first iteration
+        self.on_snapshot_loaded = None                    # launch.TrainerNode's hook, called at the end of ``load_snapshot``
+        self._stat_host = {}                              # ``_stats``: its page-locked buffers
+        self._updates_done = None                         # the device's update count where the host has read it anyway (``_pipeline_ok``)
+        self.pipelined_blocks = 0
+        self._tstream = self._tev = self._mev = None      # the pipelined block's stream and events, created at first use
         self.epsilon_fn = epsilon_schedule(cfg)
         self.writer = None
         self._wandb = None
@@ -156,10 +205,20 @@ class Trainer:
             self.learner.updates_issued = int(eng.state[6])      # the device's count of loss-ring entries travels with the state block
 
     # ------------------------------------------------------------------ resumable snapshots: the run CONTINUES (deepq/snapshot.py, csrc/snapshot.hip)
+    @property
+    def _device_env(self) -> bool:
+        """The device-resident env: its state can be saved (``Actor.state_dict``)."""
+        return hasattr(self.actors[1].envs, "state_dict")
+
+    @property
+    def _host_env(self) -> bool:
+        """Emulator processes, one pool or groups of them: a rollout occupies the host thread until its last step."""
+        envs = self.actors[1].envs
+        return hasattr(envs, "step_send") or hasattr(envs, "pools")
+
     def _snapshot_geometry(self):
         from . import snapshot as snap
-        env = "device" if hasattr(self.actors[1].envs, "state_dict") else "host"
-        return snap.geometry(to_dict(self.cfg), "launch" if self.use_lp else "main", env)
+        return snap.geometry(to_dict(self.cfg), "launch" if self.use_lp else "main", "device" if self._device_env else "host")
 
     def _snapshot_dir(self, path: str) -> str:
         return os.path.join(path, f"rank{self.rank}") if int(os.environ.get("WORLD_SIZE", "1")) > 1 else path
@@ -176,23 +235,20 @@ class Trainer:
         ``path/rank<k>/``, no collective is added (untested beyond one rank, like everything multi-GPU here)."""
         from . import snapshot as snap
         path = self._snapshot_dir(path)
-        nl = getattr(self, "_nl", None) or None
+        nl = self._nl or None
         actor, rp, eng = self.actors[1], self.replay, self.learner.engine
-        device_env = hasattr(actor.envs, "state_dict")
+        device_env = self._device_env
         # ---- what is in flight
         if not device_env:
             self._book_in_flight()
             pending = None
         elif nl is not None:
             pending = nl.wait_pending()
-        elif self.use_lp:
-            pending = None
-            if self._pending is not None:
-                self._pending[6].synchronize()
-                pending = {"kind": "launch", "start": int(self._pending[4])}
         else:
-            pf = getattr(self, "_prefetched", None)
-            pending = None if pf is None else {"kind": "main", "start": int(pf[4])}
+            pf = self._pending if self.use_lp else self._prefetched
+            if pf is not None and self.use_lp:
+                pf.done_ev.synchronize()
+            pending = None if pf is None else {"kind": "launch" if self.use_lp else "main", "start": int(pf.start)}
         torch.cuda.synchronize()
         # ---- handle / class state
         if nl is not None:
@@ -235,18 +291,16 @@ class Trainer:
 
     def _book_in_flight(self):
         """A rollout issued ahead and never consumed is booked into the replay, a launch-schedule rollout in flight is waited for and dropped (what ``final`` does)."""
-        if self.use_lp and self._pending is not None:
+        if self._pending is not None:
             self.actors[1].sample_finish(self._pending)
             self._pending = None
-        if getattr(self, "_nl", None):
+        if self._nl:
             self._nl.drain_lp() if self.use_lp else self._nl.drain()
-        if getattr(self, "_prefetched", None) is not None:
+        if self._prefetched is not None:
             pending, self._prefetched = self._prefetched, None
             transitions, returns, qmax = self.actors[1].sample_finish(pending)
-            self.replay.extend(transitions)
-            self.frame_count += self.num_transitions
-            self.Qs.extend(qmax)
-            self.Rs.extend(returns)
+            self._book(transitions)
+            self._collect(returns, qmax)
 
     def load_snapshot(self, path: str):
         """The inverse of ``save_snapshot``, into a freshly constructed Trainer of the same configuration (refused, with the differing keys named, when ring
@@ -254,7 +308,7 @@ class Trainer:
         continues the SAVED run.  The first iteration after it hands the loop to the library's handles as a new run would — over the restored buffers, with the
         restored state — or keeps it on the Python classes; a snapshot written under one loads under the other."""
         from . import snapshot as snap
-        if self.frame_count != 0 or self.replay.written != 0 or getattr(self, "_nl", None):
+        if self.frame_count != 0 or self.replay.written != 0 or self._nl:
             raise RuntimeError("load_snapshot needs a freshly constructed Trainer")
         path = snap.resolve_dir(self._snapshot_dir(path))
         st = torch.load(os.path.join(path, "state.pth"), map_location="cpu", weights_only=True)
@@ -300,7 +354,7 @@ class Trainer:
                 ff.read(f, self.stage.frames, [c for c in meta["chunks"] if c["buf"] == "stage"])
         # ---- actor (device env), statistics, what was in flight
         pending = st.get("pending")
-        if st.get("actor") is not None and hasattr(actor.envs, "state_dict"):
+        if st.get("actor") is not None and self._device_env:
             actor.load_state_dict(snap.parse_actor_blob(st["actor"].numpy(), rp.obs_bytes))
             if pending and pending["kind"] == "main":
                 self._prefetched = actor.pending_from(pending["start"])
@@ -312,165 +366,115 @@ class Trainer:
         self._updates_done = None
         self._resume = {"actor": st.get("actor"), "replay": st["replay"], "learner_rng": st["learner_rng"], "pending": pending}
         torch.cuda.synchronize()
-        hook = getattr(self, "on_snapshot_loaded", None)      # launch.TrainerNode: the ranks agree on rank 0's reset seed again (learner.net_reset_freq)
-        if hook is not None:
-            hook()
+        if self.on_snapshot_loaded is not None:      # launch.TrainerNode: the ranks agree on rank 0's reset seed again (learner.net_reset_freq)
+            self.on_snapshot_loaded()
         return path
 
     # ------------------------------------------------------------------ trainer.py:74-119
     def step(self, transitions, returns, qmax):
-        self.Qs.extend(qmax)
-        self.Rs.extend(returns)
+        self._collect(returns, qmax)
         self._step_device(transitions)
         return self._result()
 
-    def _step_device(self, transitions, defer: bool = False):
-        """trainer.py:76-110 without the host-side statistics: commit the rollout, run the update block.  Everything here is enqueued on the
-        stream; nothing waits for the device except the one read of the block's loss means at the end."""
-        cfg = self.cfg
+    # ------------------------------------------------------------------ the stages of one iteration, under the names NativeLoop gives its own: rollout, book, block, stats, collect, close
+    def _book(self, transitions):
+        """A finished (or merely issued: ``Actor.block_of``) rollout's rows become part of the replay and of the frame count."""
         self.replay.extend(transitions)
         self.frame_count += self.num_transitions
-        n_upd = 0
-        has_frac = False
-        self._ring0 = None
-        self._gn0 = self._gnorm_ring_start()
-        self.GNs = []
-        if len(self.replay) > cfg.trainer.training_start_steps and self._pipeline_ok():
-            with self.ops.range("update_block"):
-                n_upd = self._update_block_pipelined()
-        elif len(self.replay) > cfg.trainer.training_start_steps:
-            rp = self.replay
-            if self._loss_means.numel() < cfg.learner.learner_steps:       # learner_steps changed after construction
-                self._loss_means = self.ops.zeros(cfg.learner.learner_steps)
-                self._floss_means = self.ops.zeros(cfg.learner.learner_steps)
-            ring0 = self._loss_ring_start()
-            for i in range(cfg.learner.learner_steps):
-                b = rp.sample()
-                q_loss, f_loss = self.learner.train_batch(rp.frames, b.slot, rp.row_bytes, b.act, b.rew, b.done, b.weights)
-                if cfg.replay.policy == ReplayEnum.prioritize:
-                    rp.update_priority(b.idx, q_loss, state=self.learner.engine.state)
-                B = cfg.learner.batch_size
-                if ring0 is None:
-                    self.ops.mean_rows(q_loss, 1, B, self._loss_means[i:i + 1])      # one launch; read back once per update block
-                if f_loss is not None:
-                    self.ops.mean_rows(f_loss, 1, B, self._floss_means[i:i + 1])
-                    has_frac = True
-                n_upd += 1
+
+    def _collect(self, returns, qmax):
+        self.Qs.extend(qmax)
+        self.Rs.extend(returns)
+
+    def _close(self, tic, sync=None):
+        """The iteration's result dict with its ``fps``; ``sync``: what the host waits for before the clock is read (nothing, when the next rollout has been issued ahead)."""
+        result = self._result()
+        if sync is not None:
+            sync()
+        result.update(fps=self.num_transitions / (time.time() - tic))
+        return result
+
+    def _step_device(self, transitions, defer: bool = False):
+        """trainer.py:76-110 without the host-side statistics: book the rollout, run the update block, send for its statistics.  Everything here is enqueued on the
+        stream; nothing waits for the device except, without ``defer``, the one read of the block's statistics at the end — with it the caller gets the record and
+        calls its ``finish`` once it has waited for an event recorded after this call."""
+        self._book(transitions)
+        blk = self._stats(self._block(), defer)
         if defer:
-            return self._block_stats_async(n_upd, has_frac)
-        if n_upd:
-            self.Ls.extend(self._block_loss_means(n_upd))                   # the one device->host read of the update block
-            if self._gn0 is not None:
-                self.GNs = self._block_grad_norms(self.learner.engine.gnorm_ring.cpu(), n_upd)
-            if getattr(self.learner.engine, "wd_partials", None) is not None:
-                self.PN = self._param_norm(self.learner.engine.wd_partials.cpu())
-            # the device's update count (NaN-skipped steps do not count) for the next block's pipelining decision: read here, where the host has just waited
-            # for the block anyway, so that the next block can be enqueued behind the rollout without a stop
-            self._updates_done = int(self.learner.engine.state[1]) if self._pipeline_candidate() else None
-            if has_frac:
-                self.FLs.extend(self._floss_means[:n_upd].cpu().tolist())
+            return blk
+        blk.finish(self)
         return None
 
-    # ------------------------------------------------------------------ statistics read-back that does not stop the stream (run_iteration(prefetch=True))
-    def _block_stats_async(self, n_upd: int, has_frac: bool):
-        """Enqueue the copies of the block's loss means into page-locked host buffers (stream-ordered behind the block, ahead of whatever is enqueued next);
-        ``_block_stats_finish`` reads them once the caller has waited for an event recorded after this call."""
-        if not n_upd:
-            return (0, None, None, None)
-        host = self.__dict__.setdefault("_stat_host", {})
-        ring0 = getattr(self, "_ring0", None)
-        src = self.learner.engine.loss_ring if ring0 is not None else self._loss_means
-        key = ("ring" if ring0 is not None else "means", src.numel())
-        if key not in host:
-            host[key] = torch.empty(src.numel(), dtype=src.dtype).pin_memory()
-        host[key].copy_(src, non_blocking=True)
-        fl = None
-        if has_frac:
-            fk = ("fmeans", self._floss_means.numel())
-            if fk not in host:
-                host[fk] = torch.empty(self._floss_means.numel(), dtype=self._floss_means.dtype).pin_memory()
-            host[fk].copy_(self._floss_means, non_blocking=True)
-            fl = host[fk]
-        self._updates_done = None
-        gn = None
-        if getattr(self, "_gn0", None) is not None:      # the ring of gradient norms travels with the loss means: one more small copy per block, none per update
-            ring = self.learner.engine.gnorm_ring
-            gk = ("gnorm", ring.numel())
-            if gk not in host:
-                host[gk] = torch.empty(ring.numel(), dtype=ring.dtype).pin_memory()
-            host[gk].copy_(ring, non_blocking=True)
-            gn = host[gk]
-        pn = None
-        part = getattr(self.learner.engine, "wd_partials", None)
-        if part is not None:      # learner.weight_decay: the last update's sums of squares travel with the loss means too
-            pk = ("wd_partials", part.numel())
-            if pk not in host:
-                host[pk] = torch.empty(part.numel(), dtype=part.dtype).pin_memory()
-            host[pk].copy_(part, non_blocking=True)
-            pn = host[pk]
-        return (n_upd, ring0, host[key], fl, gn, pn)
+    def _block_open(self, on_ring: bool) -> _BlockStats:
+        """The record of the block about to be issued.  The Adam launch files every update's loss mean — and with learner.clip_grad_norm on its pre-clip gradient norm — in
+        the slot of the update's count (DeviceLearner.loss_ring / gnorm_ring); ``on_ring`` False: a0_mean_rows per update fills ``_loss_means`` instead."""
+        ln, eng = self.learner, self.learner.engine
+        self.GNs = []
+        return _BlockStats(ring0=ln.updates_issued if on_ring else None, gn0=ln.updates_issued if eng.gnorm_ring is not None else None,
+                           state=None if eng.online.fused else eng.state)
 
-    def _block_stats_finish(self, handle):
-        n_upd, ring0, buf, fl = handle[:4]
-        if not n_upd:
-            return
-        if len(handle) > 4 and handle[4] is not None:
-            self.GNs = self._block_grad_norms(handle[4], n_upd)
-        if len(handle) > 5 and handle[5] is not None:
-            self.PN = self._param_norm(handle[5])
-        if ring0 is None:
-            self.Ls.extend(buf[:n_upd].tolist())
+    def _block(self) -> _BlockStats:
+        """The update block, once the replay holds ``training_start_steps`` rows: pipelined where it may be, else strictly serial."""
+        ln, eng = self.learner, self.learner.engine
+        # the loss means come off the ring when the fused optimizer tail runs, the block fits the ring and ``train_batch`` is the learner's own
+        blk = self._block_open(eng.online.fused and self.cfg.learner.learner_steps <= eng.loss_ring.numel() and "train_batch" not in vars(ln)
+                               and os.environ.get("A0_LOSS_RING", "1") != "0")
+        if len(self.replay) <= self.cfg.trainer.training_start_steps:
+            return blk
+        if self._pipeline_ok():
+            with self.ops.range("update_block"):
+                self._update_block_pipelined(blk)
         else:
-            self.Ls.extend(float(buf[(ring0 + i) % buf.numel()]) for i in range(n_upd))
-        if fl is not None:
-            self.FLs.extend(fl[:n_upd].tolist())
+            self._update_block_serial(blk)
+        return blk
+
+    def _mean_buffers(self, n: int):
+        if self._loss_means.numel() < n or self._floss_means.numel() < n:       # learner_steps changed after construction
+            self._loss_means, self._floss_means = self.ops.zeros(n), self.ops.zeros(n)
+
+    def _update_block_serial(self, blk: _BlockStats):
+        """trainer.py:83-104: sample -> train -> priority update, ``learner_steps`` times on the current stream."""
+        cfg, rp = self.cfg, self.replay
+        B = cfg.learner.batch_size
+        self._mean_buffers(cfg.learner.learner_steps)
+        for i in range(cfg.learner.learner_steps):
+            b = rp.sample()
+            q_loss, f_loss = self.learner.train_batch(rp.frames, b.slot, rp.row_bytes, b.act, b.rew, b.done, b.weights)
+            if cfg.replay.policy == ReplayEnum.prioritize:
+                rp.update_priority(b.idx, q_loss, state=self.learner.engine.state)
+            if blk.ring0 is None:
+                self.ops.mean_rows(q_loss, 1, B, self._loss_means[i:i + 1])      # one launch; read back once per update block
+            if f_loss is not None:
+                self.ops.mean_rows(f_loss, 1, B, self._floss_means[i:i + 1])
+                blk.has_frac = True
+            blk.n_upd += 1
+
+    def _stats(self, blk: _BlockStats, defer: bool) -> _BlockStats:
+        """The block's statistics on their way to the host: read now (the one device->host stop of the update block), or with ``defer`` (``run_iteration(prefetch=True)``,
+        the launch schedule) copied into page-locked buffers, stream-ordered behind the block and ahead of whatever is enqueued next.  The gradient norms and the last
+        update's sums of squares travel with the loss means: one more small copy per block each, none per update."""
+        if not blk.n_upd:
+            return blk
+        eng = self.learner.engine
+        read = (lambda name, src: pinned_copy(self._stat_host, name, src)) if defer else (lambda name, src: src.cpu())
+        blk.loss = read("means", self._loss_means) if blk.ring0 is None else read("ring", eng.loss_ring)
+        if blk.has_frac:
+            blk.floss = read("fmeans", self._floss_means)
+        if blk.gn0 is not None:
+            blk.gnorm = read("gnorm", eng.gnorm_ring)
+        if eng.wd_partials is not None:
+            blk.wd_partials = read("wd_partials", eng.wd_partials)
+        # the device's update count (NaN-skipped steps do not count) for the next block's pipelining decision: read only where the host has just waited for the
+        # block anyway, so that the next block can be enqueued behind the rollout without a stop
+        self._updates_done = int(eng.state[1]) if not defer and self._pipeline_candidate() else None
+        return blk
 
     # ------------------------------------------------------------------ the update block with the target network's passes one update ahead
-    def _loss_ring_start(self):
-        """The per-update loss means come out of the Adam launch (DeviceLearner.loss_ring, slot = update count % ring length) when the fused optimizer tail runs and
-        the block fits the ring; returns the first slot of the block about to be issued, or None (then a0_mean_rows per update fills ``_loss_means``)."""
-        ln = self.learner
-        eng = ln.engine
-        ring = getattr(eng, "loss_ring", None)
-        ok = (ring is not None and eng.online.fused and hasattr(ln, "updates_issued") and self.cfg.learner.learner_steps <= ring.numel()
-              and "train_batch" not in vars(ln) and os.environ.get("A0_LOSS_RING", "1") != "0")
-        self._ring0 = ln.updates_issued if ok else None
-        return self._ring0
-
-    def _gnorm_ring_start(self):
-        """learner.clip_grad_norm: the Adam launch files every update's pre-clip gradient norm in DeviceLearner.gnorm_ring, in the slot of the update's loss mean
-        (update count % ring length).  Returns the first slot of the block about to be issued, or None when the setting is off."""
-        ln = self.learner
-        return int(getattr(ln, "updates_issued", 0)) if getattr(ln.engine, "gnorm_ring", None) is not None else None
-
-    def _block_grad_norms(self, ring, n_upd: int):
-        """The block's norms out of a host copy of the ring (its newest ring-length entries when the block is longer than the ring)."""
-        cap = ring.numel()
-        if not self.learner.engine.online.fused:      # the unfused optimizer tail does not advance the slot counter: the slot holds the block's last update
-            return [float(ring[int(self.learner.engine.state[6]) % cap])]
-        n = min(n_upd, cap)
-        return [float(ring[(self._gn0 + n_upd - n + i) % cap]) for i in range(n)]
-
-    @staticmethod
-    def _param_norm(partials) -> float:
-        """learner.weight_decay: the decay launch leaves the sums of squares of the parameters it read (a0_weight_decay, one double per workgroup); the norm is
-        finished here — the sum in index order, the square root in double."""
-        total = 0.0
-        for x in partials.tolist():
-            total += x
-        return math.sqrt(total)
-
-    def _block_loss_means(self, n_upd: int):
-        if getattr(self, "_ring0", None) is None:
-            return self._loss_means[:n_upd].cpu().tolist()
-        ring = self.learner.engine.loss_ring.cpu()
-        return [float(ring[(self._ring0 + i) % ring.numel()]) for i in range(n_upd)]
-
     def _pipeline_candidate(self) -> bool:
         cfg, ln = self.cfg, self.learner
         # OFF by default: measured slower than the strictly serial block on MI355X (profiles/r04_experiments.md) — kept as a tested option
         return (os.environ.get("A0_PIPELINE_TARGET", "0") == "1" and cfg.replay.policy != ReplayEnum.prioritize and cfg.learner.learner_steps >= 2
-                and bool(getattr(ln.engine, "target_stage_supported", False)) and ln.use_graph)
+                and ln.engine.target_stage_supported and ln.use_graph)
 
     def _pipeline_ok(self) -> bool:
         """Uniform replay (the next batch does not depend on this update's priorities), a learner whose target pass can run as a stage of its own, the
@@ -481,27 +485,25 @@ class Trainer:
             return False
         if "sample" in vars(self.replay) or "train_batch" in vars(ln) or "update_priority" in vars(self.replay):      # instance-level wrappers (tests/test_gpu_trace.py)
             return False
-        if getattr(self, "_updates_done", None) is None:
+        if self._updates_done is None:
             self._updates_done = int(ln.engine.state[1])          # one small read per block; NaN-skipped steps do not count, so the device's number is the one to use
         c0, L, f = self._updates_done, int(cfg.learner.learner_steps), int(cfg.learner.target_update_freq)
         return (c0 + L) // f == c0 // f                           # no multiple of f in (c0, c0 + L]: no sync in this block, however many steps a NaN skips
 
-    def _update_block_pipelined(self) -> int:
+    def _update_block_pipelined(self, blk: _BlockStats):
         """trainer.py:83-104's loop with the same work in the same per-update order, except that batch k + 1 is drawn and pushed through the TARGET network
         (encoder + fc1 GEMM, ~70 us for dqn at B = 512) on a second stream while update k runs: those kernels fill the CUs that update k's latency-bound
         launches (512-row GEMMs, head / loss, reductions, Adam) leave idle.  Two sets of batch and target-stage buffers alternate; update k + 1 waits for its
         stage through an event, the stage of batch k + 2 waits for update k (the last reader of the buffers it overwrites).  Numbers are unchanged."""
         cfg, rp, ln = self.cfg, self.replay, self.learner
         L, B = int(cfg.learner.learner_steps), cfg.learner.batch_size
-        if self._loss_means.numel() < L:
-            self._loss_means = self.ops.zeros(L)
-        if getattr(self, "_tstream", None) is None:
+        self._mean_buffers(L)
+        if self._tstream is None:
             self._tstream = torch.cuda.Stream()
             self._tev = [torch.cuda.Event(), torch.cuda.Event()]
             self._mev = torch.cuda.Event()
-        self.pipelined_blocks = getattr(self, "pipelined_blocks", 0) + 1
+        self.pipelined_blocks += 1
         cur = torch.cuda.current_stream()
-        ring0 = self._loss_ring_start()
         batches = [None, None]
         batches[0] = rp.sample(buf=0)
         ln.target_stage_batch(rp.frames, batches[0].slot, rp.row_bytes, 0)          # the first batch's stage has nothing to hide behind: same stream
@@ -519,9 +521,9 @@ class Trainer:
                 cur.wait_event(self._tev[p])
             b = batches[p]
             q_loss, _ = ln.train_batch(rp.frames, b.slot, rp.row_bytes, b.act, b.rew, b.done, b.weights, tstage=p)
-            if ring0 is None:
+            if blk.ring0 is None:
                 self.ops.mean_rows(q_loss, 1, B, self._loss_means[i:i + 1])
-        return L
+        blk.n_upd = L
 
     def _result(self):
         """The result dict of trainer.py:111-118; with learner.clip_grad_norm on also ``grad_norm``, the mean pre-clip gradient norm over the last block's updates; with
@@ -529,11 +531,11 @@ class Trainer:
         front of the decay of the last block's last update."""
         eng = self.learner.engine
         out = self._result_base()
-        if getattr(eng, "gnorm_ring", None) is not None:
+        if eng.gnorm_ring is not None:
             out["grad_norm"] = np.mean(self.GNs) if len(self.GNs) > 0 else None
-        if getattr(eng, "net_reset_freq", 0) > 0:      # learner.net_reset_freq: the resets so far, from the device's step count (one small read per logged iteration)
+        if eng.net_reset_freq > 0:      # learner.net_reset_freq: the resets so far, from the device's step count (one small read per logged iteration)
             out["net_resets"] = int(eng.state[1]) // eng.net_reset_freq
-        if getattr(eng, "wd_partials", None) is not None:
+        if eng.wd_partials is not None:
             out["param_norm"] = self.PN
         return out
 
@@ -619,18 +621,20 @@ class Trainer:
         except OSError:
             pass
 
-    def _issue_rollout(self):
-        """``actor.futures.sample(eps, state_dict)`` (launch.py:34-36,58-62): snapshot the weights, start the rollout, do not wait."""
-        actor = self.actors[1]
+    # ------------------------------------------------------------------ the launch schedule (launch.py:30-63)
+    def _snapshot_lp(self):
+        """First half of ``actor.futures.sample(eps, state_dict)`` (launch.py:34-36,58-62): epsilon from the frame count as it is now, and the weight snapshot on the
+        learner's stream — ordered after every update enqueued so far and before the next one.  Returns (epsilon, the event the rollout has to wait for)."""
         eps = self.epsilon_fn(self.frame_count)
-        cur = torch.cuda.current_stream()
-        st = self.actor_stream if self.overlap else cur
-        # snapshot on the learner's stream — ordered after every update enqueued so far and before the next one — then let the
-        # actor stream start once the copy has landed
-        actor.model._dev.copy_from(self.learner.model._dev)
-        st.wait_stream(cur)
+        self.actors[1].model._dev.copy_from(self.learner.model._dev)
+        return eps, torch.cuda.current_stream().record_event()
+
+    def _rollout_lp(self, eps, ev):
+        """Second half: the rollout into the free half of the stage, on the actor stream once the snapshot has landed, without waiting for it."""
+        st = self.actor_stream if self.overlap else torch.cuda.current_stream()
+        st.wait_event(ev)
         with torch.cuda.stream(st):
-            pending = actor.sample_async(eps)
+            pending = self.actors[1].sample_async(eps)
         self.stage.written += self.num_transitions  # the next rollout goes to the other half of the stage
         return pending
 
@@ -639,72 +643,63 @@ class Trainer:
         then run the update block on the collected transitions while that rollout is in flight."""
         tic = time.time()
         if self._pending is None:
-            self._pending = self._issue_rollout()   # launch.py:32-37 primes the pipeline before the loop
+            self._pending = self._rollout_lp(*self._snapshot_lp())      # launch.py:32-37 primes the pipeline before the loop
         transitions, returns, qmax = self.actors[1].sample_finish(self._pending)
-        actor = self.actors[1]
-        if self.overlap and (hasattr(actor.envs, "step_send") or hasattr(actor.envs, "pools")):
+        snap = self._snapshot_lp()
+        if self.overlap and self._host_env:
             # a HOST env's rollout occupies this thread until its last step (it waits for the worker processes), so the update block — which needs nothing from the
             # thread once enqueued — goes first and the rollout then runs on the actor stream beside it: launch.py's actor processes stepping their emulators while
             # the learner trains (launch.py:44-63).  Same dependencies as the order below (weights snapshot before the block's first Adam, epsilon from the frame
             # count before the commit, the rollout into the other half of the stage), hence the same numbers (tests/test_gpu_trainer.py).
-            eps = self.epsilon_fn(self.frame_count)
-            cur = torch.cuda.current_stream()
-            actor.model._dev.copy_from(self.learner.model._dev)
-            snap = torch.cuda.Event()
-            snap.record(cur)
-            self.Qs.extend(qmax)
-            self.Rs.extend(returns)
-            stats = self._step_device(transitions, defer=True)
-            self.actor_stream.wait_event(snap)
-            with torch.cuda.stream(self.actor_stream):
-                self._pending = actor.sample_async(eps)
-            self.stage.written += self.num_transitions
+            self._collect(returns, qmax)
+            blk = self._step_device(transitions, defer=True)
+            self._pending = self._rollout_lp(*snap)
             torch.cuda.synchronize()
-            self._block_stats_finish(stats)
-            result = self._result()
-            result.update(fps=self.num_transitions / (time.time() - tic))
-            return result
-        self._pending = self._issue_rollout()
-        result = self.step(transitions, returns, qmax)
-        torch.cuda.synchronize()
-        result.update(fps=self.num_transitions / (time.time() - tic))
-        return result
+            blk.finish(self)
+            return self._close(tic)
+        self._pending = self._rollout_lp(*snap)
+        self._collect(returns, qmax)
+        self._step_device(transitions)
+        return self._close(tic, torch.cuda.synchronize)
 
+    # ------------------------------------------------------------------ who runs the loop
     def _native_loop(self):
         """The library's own handles over this Trainer's buffers (deepq/native_loop.py) when the configuration is one they cover, nothing has wrapped the hot-loop
         methods and no gradient hook is installed; decided at the first iteration, and final from then on (the handles own the actor's and the sampler's state)."""
-        nl = getattr(self, "_nl", None)
-        if nl is False:
+        if self._nl is None:
+            self._decide_native_loop()
+        if not self._nl:
             return None
+        if not self._unwrapped():
+            raise RuntimeError("Trainer: a gradient hook or a method wrapper was installed after the native loop had taken over the run")
+        return self._nl
+
+    def _unwrapped(self) -> bool:
         from . import native_loop
-        ok_now = native_loop.hook_ok(self.learner.engine.grad_hook) and not any(native_loop._wrapped(o) for o in (self, self.replay, self.learner, self.actors[1]))
-        if nl is None:
-            why = native_loop.eligible(self)
-            resume = getattr(self, "_resume", None)        # a loaded snapshot is the second legitimate starting point: the handles take over its state
-            under_way = resume is None and (getattr(self, "_prefetched", None) is not None or self.replay.written != 0 or self.actors[1].steps != 0 or getattr(self, "_pending", None) is not None)
-            self._resume = None
-            if why is not None or not ok_now or under_way:
-                self._nl = False
-                self.native_loop_reason = why or "hot-loop methods wrapped, a gradient hook, or a run already under way"
-                return None
+        return native_loop.hook_ok(self.learner.engine.grad_hook) and not any(native_loop._wrapped(o) for o in (self, self.replay, self.learner, self.actors[1]))
+
+    def _decide_native_loop(self):
+        """Once per Trainer, and with ``final`` (which closes the handles) the only writer of ``_nl`` and ``native_loop_reason``."""
+        from . import native_loop
+        resume, self._resume = self._resume, None          # a loaded snapshot is the second legitimate starting point: the handles take over its state
+        under_way = resume is None and (self._prefetched is not None or self.replay.written != 0 or self.actors[1].steps != 0 or self._pending is not None)
+        why = native_loop.eligible(self)
+        if why is None and (under_way or not self._unwrapped()):
+            why = "hot-loop methods wrapped, a gradient hook, or a run already under way"
+        nl = None
+        if why is None:
             try:
-                nl = self._nl = native_loop.NativeLoop(self)
+                nl = native_loop.NativeLoop(self)
                 if resume is not None:
                     nl.load_state(resume, resume["pending"])
-                    self._prefetched = None                # the handles hold what was in flight
-                    if self.use_lp:
-                        self._pending = None
+                    self._prefetched = self._pending = None      # the handles hold what was in flight
             except RuntimeError as e:            # a create call refused the configuration: NativeLoop has destroyed what it had created; the Python classes run the loop
-                self._nl = False
-                self.native_loop_reason = f"handle creation failed: {e}"
+                nl, why = None, f"handle creation failed: {e}"
                 if self.primary:
-                    self.logger.info("host loop: Python classes (%s)", self.native_loop_reason)
-                return None
-            if self.primary:
-                self.logger.info("host loop: library handles over this Trainer's buffers, device env or one host-env pool (agent0_amd/deepq/native_loop.py); A0_NATIVE_LOOP=0 keeps the Python classes in charge")
-        elif not ok_now:
-            raise RuntimeError("Trainer: a gradient hook or a method wrapper was installed after the native loop had taken over the run")
-        return nl
+                    self.logger.info("host loop: Python classes (%s)", why)
+        self._nl, self.native_loop_reason = (False, why) if nl is None else (nl, None)
+        if nl is not None and self.primary:
+            self.logger.info("host loop: library handles over this Trainer's buffers, device env or one host-env pool (agent0_amd/deepq/native_loop.py); A0_NATIVE_LOOP=0 keeps the Python classes in charge")
 
     def run_iteration(self, prefetch: bool = False):
         """One pass of the loop body of trainer.py:176-182; returns the result dict including fps.
@@ -715,14 +710,10 @@ class Trainer:
         (tests/test_gpu_trainer.py::test_prefetched_rollouts_change_no_number), but the GPU does not idle while Python collects statistics, logs and builds the
         next launch.  A rollout issued ahead is consumed by the next call (whatever its ``prefetch``), or booked into the replay by ``final()``."""
         nl = self._native_loop()
-        if nl is not None:
-            with self.ops.range("iteration"):             # roctx (A0_ROCTX=1): the handles open `rollout`, `sample`, `update`, `exchange` inside it
+        with self.ops.range("iteration"):                 # roctx (A0_ROCTX=1): the handles open `rollout`, `sample`, `update`, `exchange` inside it
+            if nl is not None:
                 return nl.run_iteration_lp() if self.use_lp else nl.run_iteration(prefetch)
-        if self.use_lp:
-            with self.ops.range("iteration"):
-                return self.run_iteration_lp()
-        with self.ops.range("iteration"):
-            return self._run_iteration_py(prefetch)
+            return self.run_iteration_lp() if self.use_lp else self._run_iteration_py(prefetch)
 
     def _run_iteration_py(self, prefetch: bool):
         tic = time.time()
@@ -730,25 +721,19 @@ class Trainer:
         # the host does not stop between them: the rollout's statistics (episode returns, per-step max-Q: one small read-back) are collected
         # after the update block has been enqueued instead of before, so the GPU never waits for Python at the rollout / update boundary.
         actor = self.actors[1]
-        pending, self._prefetched = getattr(self, "_prefetched", None), None
+        pending, self._prefetched = self._prefetched, None
         if pending is None:
             pending = actor.sample_async(self.epsilon_fn(self.frame_count))
+        blk = self._step_device(actor.block_of(pending), defer=prefetch)
         if not prefetch:
-            self._step_device(actor.block_of(pending))
             _, returns, qmax = actor.sample_finish(pending)
         else:
-            blk = self._step_device(actor.block_of(pending), defer=True)
             st = actor.stats_async(pending)                                     # ahead of the next rollout, which overwrites the statistics buffers
             self._prefetched = actor.sample_async(self.epsilon_fn(self.frame_count))
             returns, qmax = actor.stats_finish(st)
-            self._block_stats_finish(blk)
-        self.Qs.extend(qmax)
-        self.Rs.extend(returns)
-        result = self._result()
-        if not prefetch:
-            torch.cuda.synchronize()
-        result.update(fps=self.num_transitions / (time.time() - tic))
-        return result
+            blk.finish(self)
+        self._collect(returns, qmax)
+        return self._close(tic, None if prefetch else torch.cuda.synchronize)
 
     def run(self):
         cfg = self.cfg
@@ -772,18 +757,7 @@ class Trainer:
         self.final()
 
     def final(self, save: bool = True):
-        if self.use_lp and self._pending is not None:
-            self.actors[1].sample_finish(self._pending)      # drain the rollout still in flight
-            self._pending = None
-        if getattr(self, "_nl", None):
-            self._nl.drain_lp() if self.use_lp else self._nl.drain()
-        if getattr(self, "_prefetched", None) is not None:   # a rollout issued ahead by run_iteration(prefetch=True) and never consumed: book it, so that replay and counters agree with the device
-            pending, self._prefetched = self._prefetched, None
-            transitions, returns, qmax = self.actors[1].sample_finish(pending)
-            self.replay.extend(transitions)
-            self.frame_count += self.num_transitions
-            self.Qs.extend(qmax)
-            self.Rs.extend(returns)
+        self._book_in_flight()                                # so that replay and counters agree with the device
         if save and int(self.cfg.trainer.snapshot_freq) > 0:
             try:
                 self.save_snapshot(os.path.join(self.cfg.logdir, "snapshot"))
@@ -798,7 +772,7 @@ class Trainer:
                     self.save_checkpoint(os.path.join(self.cfg.logdir, "final.pth"))
                 except OSError:
                     pass
-        if getattr(self, "_nl", None):
+        if self._nl:
             self._nl.close()
             self._nl = False
         for actor in self.actors:

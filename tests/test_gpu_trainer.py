@@ -1114,3 +1114,67 @@ def test_plain_c_host_runs_baseline_config1(tmp_path, config):
         assert "a0_learner_set_exchange" in dp["gradient_exchange"] and out["gradient_exchange"] == "none"
         for k in ("updates", "episodes", "mean_return", "last_mean_loss", "last_qmax", "finite", "frames"):
             assert dp[k] == out[k], (k, dp[k], out[k])
+
+
+# the sizes tests/test_gpu_trace.py calls SMALL, at batch 16: 8 envs x 10 steps per rollout, a 200-slot ring (wraps in the third rollout), 3 updates per block from the second rollout on
+STAGES_SMALL = {"actor.sample_steps": 10, "replay.size": 200, "learner.batch_size": 16, "learner.learner_steps": 3, "trainer.training_start_steps": 100,
+                "learner.target_update_freq": 4, "trainer.exploration_steps": 100}
+
+
+def _close_trainer(tr):
+    if tr._nl:
+        tr._nl.close()
+        tr._nl = False
+    for actor in tr.actors:
+        if actor is not None:
+            actor.close()
+
+
+def test_launch_node_runs_on_the_library_handles(monkeypatch):
+    """a job started through ``python -m agent0.deepq.launch`` runs the host loop every one-GPU number was measured with.  launch.TrainerNode installs
+    ``on_snapshot_loaded`` on its Trainer — the Trainer's own hook, not a harness around the hot loop (native_loop.NOT_WRAPPERS) — so the handles take the run over."""
+    from agent0_amd.deepq import launch
+    from agent0_amd.deepq.native_loop import NativeLoop
+
+    monkeypatch.setenv("A0_NATIVE_LOOP", "1")
+    node = launch.TrainerNode(make_cfg("dqn", 8, **STAGES_SMALL), rank=0, world=1)
+    tr = node.trainer
+    try:
+        assert tr.use_lp and tr._nl is None and tr.native_loop_reason is None
+        for _ in range(2):
+            tr.run_iteration()
+        assert isinstance(tr._nl, NativeLoop), tr.native_loop_reason
+        assert tr.frame_count == 160 and len(tr.Ls) == 3
+    finally:
+        _close_trainer(tr)
+
+
+@pytest.mark.parametrize("native", ["0", "1"], ids=["python-classes", "library-handles"])
+def test_book_in_flight_books_the_rollout_issued_ahead(native, monkeypatch):
+    """``Trainer._book_in_flight`` (``final``, and ``save_snapshot`` with host environments): a rollout issued ahead by ``run_iteration(prefetch=True)`` and never consumed
+    enters the replay and the counters exactly as the next iteration of the loop that issues nothing ahead would have booked it, and nothing stays in flight."""
+    from agent0_amd.deepq.native_loop import NativeLoop
+    from agent0_amd.deepq.trainer import Trainer
+
+    monkeypatch.setenv("A0_NATIVE_LOOP", native)
+
+    def run(ahead):
+        tr = Trainer(make_cfg("dqn", 8, **STAGES_SMALL))
+        try:
+            for _ in range(3 if ahead else 4):
+                tr.run_iteration(prefetch=ahead)
+            assert isinstance(tr._nl, NativeLoop) if native == "1" else tr._nl is False, tr.native_loop_reason
+            if ahead:
+                assert tr._nl._pending_rollout if native == "1" else tr._prefetched is not None
+                assert tr.replay.written == tr.frame_count == 240
+                tr._book_in_flight()
+                assert tr._prefetched is None and tr._pending is None and not (native == "1" and tr._nl._pending_rollout)
+                tr._book_in_flight()                       # nothing in flight: nothing to book
+            torch.cuda.synchronize()
+            return tr.replay.written, tr.frame_count, len(tr.Qs), len(tr.replay), tr.replay.top
+        finally:
+            _close_trainer(tr)
+
+    a = run(False)
+    b = run(True)
+    assert a == b and a[:3] == (320, 320, 40)
