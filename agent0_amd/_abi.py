@@ -66,6 +66,11 @@ class NetResetSeg(C.Structure):
     _fields_ = [("offset", C.c_longlong), ("count", C.c_longlong), ("kind", C.c_int), ("scale", C.c_float), ("keep", C.c_int)]
 
 
+class RedoBlocks(C.Structure):
+    """a0_redo_blocks: where conv1, conv2, conv3, fc1 and the head start in the flat parameter buffer, conv1's and fc1's row lengths, the head's padded rows."""
+    _fields_ = [("conv1", C.c_longlong), ("conv2", C.c_longlong), ("conv3", C.c_longlong), ("fc1", C.c_longlong), ("head", C.c_longlong), ("K1", C.c_int), ("feat", C.c_int), ("Npad", C.c_int)]
+
+
 class EncoderPass(C.Structure):
     _fields_ = [("wt", C.c_void_p), ("w", C.c_void_p), ("f", C.c_void_p), ("B", C.c_int), ("act1", C.c_void_p), ("act2", C.c_void_p), ("act3", C.c_void_p)]
 

@@ -52,6 +52,7 @@ class DeviceRng:
     STREAM_EGREEDY_U, STREAM_EGREEDY_A, STREAM_TAUS, STREAM_NOISE, STREAM_SUMTREE, STREAM_PERM = 1, 2, 3, 4, 5, 6
     STREAM_AUG = 7      # learner.aug_shift's random shifts (a0_augment_shift): positioned by the device's update count, so it keeps no running offset here
     STREAM_RESET = 8    # learner.net_reset_freq's fresh values (a0_net_reset): positioned by (reset number, flat index), so it keeps no running offset either
+    STREAM_REDO = 9     # learner.redo_freq's fresh values (a0_redo_recycle): positioned by (recycle number, flat index), no running offset
 
     CTRL_INDEX = {3: 5, 4: 6}      # STREAM_TAUS -> A0_CTRL_RNG_TAUS, STREAM_NOISE -> A0_CTRL_RNG_NOISE (include/agent0_hip.h)
 

@@ -38,6 +38,8 @@ struct a0_hip_error : std::runtime_error {
 #define A0_STREAM_AUG 7
 // 8 = the fresh values of learner.net_reset_freq (optim.hip: a0_net_reset), positioned by (reset number, flat index): no running offset either
 #define A0_STREAM_RESET 8
+// 9 = the fresh values of learner.redo_freq (optim.hip: a0_redo_recycle), positioned by (recycle number, flat index): no running offset
+#define A0_STREAM_REDO 9
 // augment.hip: the range checks of a0_augment_shift (A0_EINVAL with a message that starts with `who`)
 int a0_augment_shift_check(const char* who, int C, int H, int W, int pad, long long row_bytes);
 

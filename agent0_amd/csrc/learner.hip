@@ -289,6 +289,7 @@ extern "C" int a0_learner_set_exchange(a0_learner* L, long long comm) {
         A0_HIP_THROW(hipStreamCreateWithFlags(&L->dp_side, hipStreamNonBlocking));
         for (hipEvent_t& e : L->dp_ev) A0_HIP_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
+    if (comm && L->redo_freq > 0) return a0_fail(A0_EINVAL, "a0_learner_set_exchange: not together with a0_learner_set_redo (the ranks would draw different masks)");
     L->dp_comm = comm;
     L->dp_one_rank = false;
     if (comm) {       // a one-rank group (a rehearsal, or a job of one GPU): nothing to overlap, so both all-reduces go on the update's own stream
@@ -411,6 +412,37 @@ extern "C" int a0_learner_net_reset_segs(const a0_learner* L, a0_net_reset_seg* 
     if (n > cap) return a0_fail(A0_EINVAL, "a0_learner_net_reset_segs: cap is smaller than the table (A0_NET_RESET_MAX_SEGS entries always fit)");
     for (int i = 0; i < n; ++i) out[i] = tab[i];
     return n;
+}
+
+extern "C" int a0_learner_set_redo(a0_learner* L, int freq, double tau, int recycle, unsigned long long seed) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_redo: null handle");
+    if (L->updated) return a0_fail(A0_EINVAL, "a0_learner_set_redo: the setting is fixed once the handle has run an update");
+    if (freq < 0) return a0_fail(A0_EINVAL, "a0_learner_set_redo: freq < 0 (0 is off)");
+    if (!(tau >= 0.0) || !(tau < 1.0)) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "a0_learner_set_redo: tau = %g must be a finite number in [0, 1)", tau);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (freq > 0 && recycle && L->d.noisy) return a0_fail(A0_EINVAL, "a0_learner_set_redo: recycle is undefined for NoisyNet's mu / sigma pairs (recycle = 0 measures only)");
+    if (freq > 0 && L->dp_comm) return a0_fail(A0_EINVAL, "a0_learner_set_redo: not on a handle with a data-parallel exchange (the ranks would draw different masks)");
+    L->redo_freq = freq; L->redo_tau = tau; L->redo_recycle = recycle ? 1 : 0; L->redo_seed = seed & 0xFFFFFFFFull;
+    L->n_redo_segs = freq > 0 && recycle ? a0_learner_reset_table(L, L->redo_segs) : 0;
+    if (freq > 0 && !L->redo_partials) {
+        L->redo_partials = L->alloc<double>((long long)A0_REDO_PARTIALS * A0_REDO_NEURONS);
+        L->redo_scores = L->alloc<float>(A0_REDO_NEURONS, true); L->redo_mask = L->alloc<int>(A0_REDO_NEURONS, true); L->redo_counts = L->alloc<int>(8, true);
+        const int never = -1;
+        A0_HIP_THROW(hipMemcpy(L->redo_counts + 5, &never, sizeof never, hipMemcpyHostToDevice));
+    }
+    return A0_OK;
+    A0_CATCH
+}
+
+extern "C" int a0_learner_redo_buffers(const a0_learner* L, float** scores_dev, int** mask_dev, int** counts_dev) {
+    if (!L || !scores_dev || !mask_dev || !counts_dev) return a0_fail(A0_EINVAL, "a0_learner_redo_buffers: null argument");
+    const bool on = L->redo_freq > 0;
+    *scores_dev = on ? L->redo_scores : nullptr; *mask_dev = on ? L->redo_mask : nullptr; *counts_dev = on ? L->redo_counts : nullptr;
+    return A0_OK;
 }
 
 extern "C" int a0_learner_set_aug_shift(a0_learner* L, int pad) {
@@ -817,6 +849,18 @@ static int a0_apply(a0_upd& u, float* loss_out) {
                                       L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, stream));
     }
     if (L->target_tau > 0.0) A0_CHECK(a0_target_blend(tg, on, L->n_pad, L->target_tau, L->state, L->d.target_update_freq, 0, &u.w_tg, L->C, L->wt_tg, stream));
+    // learner.redo_freq: scores, mask and counts from the differentiated pass's activations, then the recycle launch; all three return at once on other updates
+    if (L->redo_freq > 0) {
+        const bool quantile = L->fam == A0_FAM_IQN || L->fam == A0_FAM_FQF;
+        const int H3 = L->feat / 64;      // H3 * W3
+        A0_CHECK(a0_redo_score(L->act1, (long long)B * L->H1 * L->W1, L->act2, (long long)B * L->H2 * L->W2, L->act3_o, (long long)B * H3, quantile ? L->qo.h : L->h, quantile ? L->qo.R : (long long)B,
+                               L->redo_tau, L->state, L->redo_freq, 0, L->redo_partials, L->redo_scores, L->redo_mask, L->redo_counts, stream));
+        if (L->redo_recycle) {
+            const a0_redo_blocks blk{L->conv1.off, L->conv2.off, L->conv3.off, L->fc1.off, L->head.off, L->conv1.K, L->feat, L->Npad};
+            A0_CHECK(a0_redo_recycle(on, L->m, L->v, L->n_adam, L->n_pad, L->redo_segs, L->n_redo_segs, &blk, L->redo_mask, L->redo_seed, L->state, L->redo_freq, 0, 0, &u.w_on, L->C,
+                                     L->wt_on, stream));
+        }
+    }
     return L->reset_freq > 0 ? a0_net_reset(on, tg, L->m, L->v, L->n_adam, L->n_pad, L->reset_segs, L->n_reset_segs, L->reset_shrink, L->reset_seed, L->state, L->reset_freq, 0, 0,
                                             &u.w_on, L->C, L->wt_on, L->wt_tg, stream) : A0_OK;
 }

@@ -85,6 +85,14 @@ struct a0_learner {
     double reset_shrink = 1.0;
     unsigned long long reset_seed = 0;
     a0_net_reset_seg reset_segs[A0_NET_RESET_MAX_SEGS];
+    // ---- dormant-neuron statistic and ReDo recycling (a0_learner_set_redo): off while redo_freq == 0; the buffers exist only while it is on
+    int redo_freq = 0, redo_recycle = 0, n_redo_segs = 0;
+    double redo_tau = 0.1;
+    unsigned long long redo_seed = 0;
+    a0_net_reset_seg redo_segs[A0_NET_RESET_MAX_SEGS];
+    double* redo_partials = nullptr;
+    float* redo_scores = nullptr;
+    int *redo_mask = nullptr, *redo_counts = nullptr;
     // ---- DrQ random shift of the batch (a0_learner_set_aug_shift): off while aug_pad == 0; aug_stage: the dense augmented batch [B][2 * C * H * W], allocated by the first call that switches it on
     int aug_pad = 0;
     uint8_t* aug_stage = nullptr;

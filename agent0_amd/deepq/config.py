@@ -61,6 +61,18 @@ Additions (all default to the reference's behaviour being available):
                    BBF and SR-SPR use 0.1.  c >= 1 is refused, and so is 0 < c < 2^-24, which would move no fp32 value.  Masks that exempt biases or sigmas are
                    not offered.  Adds the statistic ``param_norm``: the L2 norm of everything Adam owns as it stood in front of the decay of the block's last
                    update.  No state of its own, nothing new in a snapshot, and the setting may change across a resume like ``actor.min_eps``.
+  learner.redo_freq  int, default 0 (off; negative values are refused).  N > 0: after every update that was not NaN-skipped and left ``update_steps`` a positive
+                   multiple of N the dormancy score of Sokar et al. 2023 is taken on the device for the 672 hidden neurons (conv1's 32, conv2's 64 and conv3's 64
+                   output channels, fc1's 512 units) from the activations of that update's batch: s_i = mean|h_i| / (the layer's mean of those means), dormant iff
+                   s_i <= ``learner.redo_tau`` (a0_redo_score, two launches behind the update).  With ``learner.redo_recycle`` the dormant neurons are recycled
+                   (ReDo; a0_redo_recycle, a third launch): incoming weights and bias get fresh values of the constructor's scale, outgoing weights become 0, Adam's
+                   moments of both become 0; the rest of the network, the target network and the replay ring are untouched.  The fresh values are a function of
+                   (the learner's seed, the recycle number, the element) on Philox stream 9: no state of its own, a resumed run recycles as the uninterrupted one
+                   does.  Adds the statistics ``dormant_frac`` and ``dormant_frac_conv1|conv2|conv3|fc1`` (NaN until the first evaluation and after a resume).
+                   Refused under the data-parallel path (``A0_DP_FORCE=1`` included): the ranks see different batches and would draw different masks.
+  learner.redo_tau  float in [0, 1), default 0.1 (the paper's recycling threshold; anything else, NaN included, is refused with the number named).  0 counts only
+                   neurons that are exactly silent; the paper's diagnostic uses 0.025.  Without ``learner.redo_freq`` it does nothing.
+  learner.redo_recycle  bool, default true.  false measures only.  true together with ``learner.noisy_net`` is refused: ReDo is undefined for mu / sigma pairs.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -157,6 +169,9 @@ class LearnerConfig:
     net_reset_freq: int = 0
     net_reset_shrink: float = 1.0
     weight_decay: float = 0.0
+    redo_freq: int = 0
+    redo_tau: float = 0.1
+    redo_recycle: bool = True
     learner_steps: int = 20
     double_q: bool = False
     dueling_head: bool = False

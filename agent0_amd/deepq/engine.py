@@ -102,6 +102,31 @@ def net_reset_value(freq, shrink=1.0, pipeline_target: Optional[bool] = None):
     return n, alpha
 
 
+def redo_value(freq, tau=0.1, recycle=True, noisy=False, data_parallel: Optional[bool] = None):
+    """``learner.redo_freq`` / ``learner.redo_tau`` / ``learner.redo_recycle`` as the learner uses them: ``(N, tau, recycle)``, N = 0 (off) for zero or None.
+    Refused: a negative or fractional N, a tau that is not a finite number in [0, 1) (checked whether or not N is on), and with N > 0: recycling together with
+    ``learner.noisy_net`` (``noisy``; measuring only is allowed) and any use under the data-parallel path (``data_parallel``; None reads WORLD_SIZE and
+    ``A0_DP_FORCE``): the ranks see different batches, would draw different masks and would diverge."""
+    if freq is None:
+        freq = 0
+    if isinstance(freq, bool) or int(freq) != freq or freq < 0:
+        raise ValueError(f"learner.redo_freq={freq!r}: must be a whole number of updates >= 0 (0 is off)")
+    t = 0.1 if tau is None else float(tau)
+    if not (0.0 <= t < 1.0):
+        raise ValueError(f"learner.redo_tau={tau!r}: must be a finite number in [0, 1) (0 recycles only neurons that are exactly silent)")
+    n, rec = int(freq), bool(recycle)
+    if n > 0:
+        if rec and noisy:
+            raise ValueError(f"learner.redo_freq={n}: learner.redo_recycle=true is undefined together with learner.noisy_net (mu / sigma pairs); "
+                             "learner.redo_recycle=false measures only")
+        if data_parallel is None:
+            data_parallel = int(os.environ.get("WORLD_SIZE", "1") or 1) > 1 or os.environ.get("A0_DP_FORCE", "0") == "1"
+        if data_parallel:
+            raise ValueError(f"learner.redo_freq={n}: not under the data-parallel path (A0_DP_FORCE=1 included): the ranks see different batches and would draw "
+                             "different dormancy masks")
+    return n, t, rec
+
+
 class Workspace:
     """Activations of one forward pass over ``B`` observations (``n_tau`` quantile samples each for IQN/FQF)."""
 
@@ -397,7 +422,7 @@ class DeviceLearner:
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
                  mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0,
-                 weight_decay=0.0):
+                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -455,6 +480,20 @@ class DeviceLearner:
             if not hasattr(ops, "weight_decay"):
                 raise ValueError(f"learner.weight_decay={weight_decay!r}: needs a backend with weight_decay")
             self.wd_partials = ops.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64)
+        # learner.redo_freq = N > 0: apply() issues two launches more (a0_redo_score) that leave the dormancy scores, the mask and the counts of the 672 hidden neurons
+        # after every N-th successful update, and with learner.redo_recycle a third (a0_redo_recycle) that recycles the dormant ones — between the blend and the
+        # reset launch; all return at once on other updates.  Fresh values: Philox stream 9 of the seed ``reset_seed()`` names.  Off (0): no buffer, no launch.
+        self.redo_freq, self.redo_tau, self.redo_recycle = redo_value(redo_freq, redo_tau, redo_recycle, noisy=L.noisy)
+        self.redo_partials = self.redo_scores = self.redo_mask = self.redo_counts = self.redo_segs = None
+        if self.redo_freq > 0:
+            if not hasattr(ops, "redo_score") or (self.redo_recycle and aug_rng is None):
+                raise ValueError(f"learner.redo_freq={self.redo_freq}: needs a backend with redo_score and, to recycle, the learner's DeviceRng (aug_rng)")
+            self.redo_partials = ops.empty(ops.REDO_PARTIALS * ops.REDO_NEURONS, dtype=torch.float64)
+            self.redo_scores, self.redo_mask = ops.zeros(ops.REDO_NEURONS), ops.zeros(ops.REDO_NEURONS, dtype=torch.int32)
+            self.redo_counts = ops.zeros(8, dtype=torch.int32)
+            self.redo_counts[5] = -1                   # never evaluated
+            if self.redo_recycle:
+                self.redo_segs = L.reset_segments()
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -556,6 +595,24 @@ class DeviceLearner:
         L, on, tg = self.L, self.online, self.target
         self.ops.net_reset(on.flat, tg.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.reset_segs, self.net_reset_shrink, self.reset_seed(), self.state,
                            self.net_reset_freq, force, k_host, *((on.encoder_weights(), L.C, on.wt, tg.wt) if on.fused else ()))
+
+    def _redo(self, force=False, k_host=0):
+        """learner.redo_freq: behind the Adam form and the blend, in front of the reset launch — scores, mask and counts from the activations the differentiated pass
+        has left in ``ws_o`` (for iqn / fqf the fc1 rows are that pass's B * N rows), then the recycle launch; all of them act when this update was not NaN-skipped and
+        left the step count a positive multiple of the period (or ``force``, as recycle number ``k_host``) and return at once otherwise."""
+        if self.redo_freq <= 0:
+            return
+        if self.grad_hook is not None:
+            raise ValueError(f"learner.redo_freq={self.redo_freq}: not with a gradient exchange installed (the data-parallel path): the ranks see different batches and "
+                             "would draw different dormancy masks")
+        L, on, ws = self.L, self.online, self.ws_o
+        B = self.B
+        rows = (B * L.H1 * L.W1, B * L.H2 * L.W2, B * (L.feat // 64), ws.h.numel() // 512)
+        self.ops.redo_score(ws.act1, ws.act2, ws.act3, ws.h, self.redo_tau, self.state, self.redo_freq, force, self.redo_partials, self.redo_scores, self.redo_mask,
+                            self.redo_counts, rows)
+        if self.redo_recycle:
+            self.ops.redo_recycle(on.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.redo_segs, L.redo_blocks(), self.redo_mask, self.reset_seed(), self.state,
+                                  self.redo_freq, force, k_host, *((on.encoder_weights(), L.C, on.wt) if on.fused else ()))
 
     def _grad(self, name: str) -> torch.Tensor:
         L = self.L
@@ -693,7 +750,8 @@ class DeviceLearner:
     def apply(self):
         """Adam on the flat buffer (NaN-skip and step counter on the device), refresh of the fused kernels' weight copies, target sync — with learner.weight_decay on
         behind the decay launch, with learner.target_tau on, the
-        blend of the target (``_blend_target``) behind whichever Adam form ran, and with learner.net_reset_freq on the reset launch (``_reset_net``) behind that."""
+        blend of the target (``_blend_target``) behind whichever Adam form ran, with learner.redo_freq on the dormancy launches (``_redo``) behind that, and with
+        learner.net_reset_freq on the reset launch (``_reset_net``) last."""
         L, ops, on, tg = self.L, self.ops, self.online, self.target
         if L.algo == "fqf":           # unconditional, like the reference's fqf_optimizer.step() in front of the NaN guard (agent.py:139-148)
             blk = L.blocks["frac"]
@@ -718,6 +776,7 @@ class DeviceLearner:
             # fused: two launches — Adam with its bookkeeping and the target copy folded in; the online conv copies, mirrored to the target's on a sync
             (ops.adam_step_sync_wt if on.fused else ops.adam_step_sync)(*adam, *wt)
         self._blend_target()
+        self._redo()
         self._reset_net()
 
     # ------------------------------------------------------------------ the target network's pass as a stage of its own

@@ -184,6 +184,18 @@ class NetLayout:
             add(c.offset + self.feat * self.num_cosines, self.feat, CONST, 0.0, 0)
         return segs
 
+    # ------------------------------------------------------------------ learner.redo_freq: the blocks a recycle walks
+    REDO_LAYERS = (("conv1", 0, 32), ("conv2", 32, 64), ("conv3", 96, 64), ("fc1", 160, 512))      # (block, first neuron, neurons) of the 672 hidden neurons
+
+    def redo_blocks(self) -> Tuple[int, int, int, int, int, int, int, int]:
+        """a0_redo_blocks (include/agent0_hip.h): the offsets of conv1, conv2, conv3, fc1 and the head, conv1's and fc1's row lengths, the head's padded rows.  A
+        dormant neuron's incoming weights are its row (and bias) in its own block; its outgoing weights are the columns ``col % n == i`` of the next block, because
+        every packed matrix keeps the input channel fastest: conv2 (kh, kw, ci), conv3 (kh, kw, ci), fc1 (h, w, c), the head's 512 columns."""
+        if self.noisy:
+            raise ValueError("redo_blocks: ReDo recycling is undefined for NoisyNet's mu / sigma blocks")
+        B = self.blocks
+        return (B["conv1"].offset, B["conv2"].offset, B["conv3"].offset, B["fc1"].offset, B["head"].offset, B["conv1"].K, self.feat, self.Npad)
+
     # ------------------------------------------------------------------ permutations
     def _feat_cols_to_hwc(self, w: torch.Tensor) -> torch.Tensor:
         """[..., 64*H3*W3] with (c,h,w) columns -> (h,w,c) columns."""

@@ -156,7 +156,7 @@ def eligible(tr) -> Optional[str]:
 class NativeLoop:
     def __init__(self, tr):
         self.tr = tr
-        self.learner = self.rbuf = self.actor = self.stage = None        # close() destroys whatever exists, also when a later create call fails
+        self.learner = self.rbuf = self.actor = self.stage = self.redo_views = None        # close() destroys whatever exists, also when a later create call fails
         self.lib, self.ok = _abi.load(), _abi.check
         try:
             self._create(tr)
@@ -211,6 +211,11 @@ class NativeLoop:
             ok(lib.a0_learner_set_weight_decay(self.learner, C.c_double(eng.weight_decay), p(eng.wd_partials)), "a0_learner_set_weight_decay")
         if eng.net_reset_freq > 0:      # learner.net_reset_freq: the handle ends its update with the reset launch, as DeviceLearner.apply does, on the engine's seed
             ok(lib.a0_learner_set_net_reset(self.learner, int(eng.net_reset_freq), C.c_double(eng.net_reset_shrink), C.c_ulonglong(eng.reset_seed())), "a0_learner_set_net_reset")
+        if eng.redo_freq > 0:           # learner.redo_freq: the handle issues the dormancy launches between the blend and the reset, as DeviceLearner.apply does, on the engine's seed
+            ok(lib.a0_learner_set_redo(self.learner, int(eng.redo_freq), C.c_double(eng.redo_tau), int(eng.redo_recycle), C.c_ulonglong(eng.reset_seed() if eng.redo_recycle else 0)),
+               "a0_learner_set_redo")
+            from agent0_amd.ops import redo_buffer_views
+            self.redo_views = redo_buffer_views(lib, self.learner)      # (scores, mask, counts) over the handle's own buffers: what the Trainer's statistics read
         if eng.aug_shift > 0:           # learner.aug_shift: the handle shifts the batch into a stage buffer of its own ahead of its passes, as DeviceLearner.forward_dense does
             ok(lib.a0_learner_set_aug_shift(self.learner, int(eng.aug_shift)), "a0_learner_set_aug_shift")
         if not actor.fc1_planes:        # Actor.fc1_planes = False (comparisons): every step's fc1 on the general GEMM instead of a0_actor_fc1_kernel, as in Actor._rollout
@@ -491,4 +496,4 @@ class NativeLoop:
                       (self.learner, self.lib.a0_learner_destroy)):
             if h is not None and h.value:
                 fn(h)
-        self.actor = self.rbuf = self.learner = self.stage = None
+        self.actor = self.rbuf = self.learner = self.stage = self.redo_views = None      # the views die with the learner handle

@@ -22,6 +22,7 @@ import torch
 
 from . import agent as agents
 from .config import ExpConfig, ReplayEnum, to_dict
+from .layout import NetLayout
 from .replay import ReplayDataset, StageRing
 from agent0_amd.common.atari_wrappers import make_atari
 from agent0_amd.common.utils import pinned_copy, set_random_seed
@@ -33,6 +34,8 @@ def _git_sha() -> str:
 
 
 PROGRESS_COLUMNS = ("frames", "fraction_loss", "loss", "return_train", "return_train_max", "qmax", "fps")      # trainer.py:111-118 + fps (180-181)
+REDO_LAYERS, REDO_NEURONS = NetLayout.REDO_LAYERS, 672      # learner.redo_freq: (block, first neuron, neurons) of the hidden layers
+REDO_COLUMNS = ("dormant_frac",) + tuple(f"dormant_frac_{name}" for name, _, _ in REDO_LAYERS)
 
 
 def epsilon_schedule(cfg: ExpConfig):
@@ -528,7 +531,8 @@ class Trainer:
     def _result(self):
         """The result dict of trainer.py:111-118; with learner.clip_grad_norm on also ``grad_norm``, the mean pre-clip gradient norm over the last block's updates; with
         learner.net_reset_freq on also ``net_resets`` = update_steps // N; with learner.weight_decay on also ``param_norm``, the L2 norm of everything Adam owns in
-        front of the decay of the last block's last update."""
+        front of the decay of the last block's last update; with learner.redo_freq on also ``dormant_frac`` and ``dormant_frac_conv1|conv2|conv3|fc1``, the share of
+        dormant neurons at the newest evaluation, overall and per layer."""
         eng = self.learner.engine
         out = self._result_base()
         if eng.gnorm_ring is not None:
@@ -537,6 +541,12 @@ class Trainer:
             out["net_resets"] = int(eng.state[1]) // eng.net_reset_freq
         if eng.wd_partials is not None:
             out["param_norm"] = self.PN
+        if eng.redo_freq > 0:           # learner.redo_freq: the newest evaluation's dormant counts (one small read more per logged iteration); NaN until there is one
+            c = (self._nl.redo_views[2] if self._nl else eng.redo_counts).tolist()      # the handle evaluates into buffers of its own
+            seen = c[5] >= 0
+            out["dormant_frac"] = c[4] / float(REDO_NEURONS) if seen else float("nan")
+            for (name, _, n), k in zip(REDO_LAYERS, c[:4]):
+                out[f"dormant_frac_{name}"] = k / float(n) if seen else float("nan")
         return out
 
     def _result_base(self):
@@ -598,6 +608,8 @@ class Trainer:
                 self._wandb.log({k: v, "frame": self.frame_count})
             if k == "net_resets":
                 msg += f"{k}: {v} | "
+            elif k.startswith("dormant_frac"):
+                msg += f"{k}: {v:.3f} | "
             elif k in ["frames", "loss", "qmax", "fps", "grad_norm", "param_norm"] or "return" in k:
                 msg += f"{k}: {v:.2f} | "
         self.logger.info(msg)
@@ -615,6 +627,7 @@ class Trainer:
                 cols = PROGRESS_COLUMNS + (("grad_norm",) if "grad_norm" in result else ())      # only with learner.clip_grad_norm on
                 cols = cols + (("net_resets",) if "net_resets" in result else ())               # only with learner.net_reset_freq on
                 cols = cols + (("param_norm",) if "param_norm" in result else ())               # only with learner.weight_decay on
+                cols = cols + tuple(k for k in REDO_COLUMNS if k in result)                      # only with learner.redo_freq on
                 if new:
                     w.writerow(cols)
                 w.writerow(["" if result.get(k) is None else result[k] for k in cols])

@@ -61,6 +61,21 @@ class Net:
             pass
 
 
+def redo_buffer_views(lib, handle):
+    """(scores, mask, counts) of a learner handle's dormant-neuron evaluation as tensors over the handle's own memory — valid while the handle lives
+    (a0_learner_redo_buffers); None while learner.redo_freq is off."""
+    sc, mk, ct = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    check(lib.a0_learner_redo_buffers(handle, C.addressof(sc), C.addressof(mk), C.addressof(ct)), "a0_learner_redo_buffers")
+    if not ct.value:
+        return None
+
+    def view(ptr, n, typestr):
+        v = type("_Redo", (), {"__cuda_array_interface__": {"shape": (n,), "typestr": typestr, "data": (int(ptr.value), False), "version": 3}})()
+        return torch.as_tensor(v, device="cuda")
+
+    return view(sc, HipOps.REDO_NEURONS, "<f4"), view(mk, HipOps.REDO_NEURONS, "<i4"), view(ct, 8, "<i4")
+
+
 class NativeLearner:
     """``a0_learner``: a whole learner (dqn; c51, also with NoisyLinear layers; dueling; double-Q; n-step) behind one handle whose HBM the library owns; ``update`` is BaseLearner.train as ONE
     C call (include/agent0_hip.h).  What a non-Python host binds; here it exists for the parity test against the per-kernel composition of deepq/engine.py."""
@@ -134,6 +149,16 @@ class NativeLearner:
         return [(int(s.offset), int(s.count), int(s.kind), float(s.scale), int(s.keep)) for s in tab[:n]]
 
     NET_RESET_MAX_SEGS = 32
+
+    def set_redo(self, freq, tau, recycle, seed):
+        """learner.redo_freq / redo_tau / redo_recycle through the handle (a0_learner_set_redo): before the first update; freq 0 is off; the low 32 bits of ``seed``
+        position the fresh values."""
+        check(self.lib.a0_learner_set_redo(self.h, int(freq), float(tau), int(bool(recycle)), int(seed) & 0xFFFFFFFFFFFFFFFF), "a0_learner_set_redo")
+
+    def redo_buffers(self):
+        """Copies of the handle's (scores float[672], mask int[672], counts int[8]) (a0_learner_redo_buffers); None while the setting is off."""
+        views = redo_buffer_views(self.lib, self.h)
+        return None if views is None else tuple(v.clone() for v in views)
 
     def set_aug_shift(self, pad):
         """learner.aug_shift through the handle (a0_learner_set_aug_shift): between updates; 0 is off, the kernel's range checks apply to anything else."""
@@ -639,6 +664,36 @@ class HipOps:
                                     _req(exp_avg_sq, torch.float32, n_adam, "exp_avg_sq"), n_adam, n_total, C.addressof(tab), len(segs), float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                     _req(state, torch.int32, 8, "state", optional=bool(force)), int(freq), int(bool(force)), int(k_host), None if ew is None else C.addressof(ew), int(C_),
                                     _req(wt, torch.float32, nw, "wt", optional=True), _req(wt_target, torch.float32, nw, "wt_target", optional=wt is None), _stream()), "a0_net_reset")
+
+    REDO_NEURONS, REDO_PARTIALS = 672, 512      # A0_REDO_NEURONS, A0_REDO_PARTIALS (include/agent0_hip.h)
+
+    def redo_score(self, act1, act2, act3, fc1, tau, state, freq, force, partials, scores, mask, counts, rows=None):
+        """learner.redo_freq: dormancy scores, mask and counts of the 672 hidden neurons from the four activation buffers ([rows][32], [rows][64], [rows][64],
+        [rows][512]; the row counts are ``rows`` or, with None, the tensors' sizes) in two launches that decide for themselves (a0_redo_score): when ``force``, or when ``state[3] == 0`` and
+        ``state[1]`` is a positive multiple of ``freq``."""
+        rows = [int(t.numel()) // w for t, w in ((act1, 32), (act2, 64), (act3, 64), (fc1, 512))] if rows is None else [int(r) for r in rows]
+        n = self.REDO_NEURONS
+        check(self.lib.a0_redo_score(_req(act1, torch.float32, rows[0] * 32, "act1"), rows[0], _req(act2, torch.float32, rows[1] * 64, "act2"), rows[1],
+                                     _req(act3, torch.float32, rows[2] * 64, "act3"), rows[2], _req(fc1, torch.float32, rows[3] * 512, "fc1"), rows[3], float(tau),
+                                     _req(state, torch.int32, 8, "state", optional=bool(force)), int(freq), int(bool(force)),
+                                     _req(partials, torch.float64, self.REDO_PARTIALS * n, "partials"), _req(scores, torch.float32, n, "scores"),
+                                     _req(mask, torch.int32, n, "mask"), _req(counts, torch.int32, 8, "counts"), _stream()), "a0_redo_score")
+
+    def redo_recycle(self, params, exp_avg, exp_avg_sq, n_adam, n_total, segs, blocks, mask, seed, state, freq, force=False, k_host=0, w=None, C_=0, wt=None):
+        """learner.redo_freq: one launch that decides like ``redo_score`` (a0_redo_recycle; recycle number ``k_host`` with ``force``) — the neurons ``mask`` marks get
+        fresh incoming weights and biases by the rule table ``segs`` (Philox stream 9 at ``k * n_total + e``), zero outgoing weights and zero moments; with ``wt`` and
+        the online encoder weights ``w`` the convolution weights written are filed in the fused kernels' copy.  ``blocks``: (conv1, conv2, conv3, fc1, head, K1, feat, Npad)."""
+        if len(segs) > self.NET_RESET_MAX_SEGS:
+            raise A0Error(f"redo_recycle: {len(segs)} segments, at most {self.NET_RESET_MAX_SEGS}")
+        tab = (_abi.NetResetSeg * max(1, len(segs)))()
+        for i, (off, cnt, kind, scale, keep) in enumerate(segs):
+            tab[i] = _abi.NetResetSeg(int(off), int(cnt), int(kind), float(scale), int(keep))
+        blk = _abi.RedoBlocks(*[int(x) for x in blocks])
+        ew = None if wt is None else self._enc_w(w)
+        check(self.lib.a0_redo_recycle(_req(params, torch.float32, n_total, "params"), _req(exp_avg, torch.float32, n_adam, "exp_avg"), _req(exp_avg_sq, torch.float32, n_adam, "exp_avg_sq"),
+                                       n_adam, n_total, C.addressof(tab), len(segs), C.addressof(blk), _req(mask, torch.int32, self.REDO_NEURONS, "mask"), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                       _req(state, torch.int32, 8, "state", optional=bool(force)), int(freq), int(bool(force)), int(k_host), None if ew is None else C.addressof(ew), int(C_),
+                                       _req(wt, torch.float32, self.conv_wt_floats(C_) if wt is not None else 0, "wt", optional=True), _stream()), "a0_redo_recycle")
 
     def noisy_compose(self, mu, sigma, eff, N, K, r0, r1, noise_in, noise_out_w, noise_out_b):
         check(self.lib.a0_noisy_compose(_req(mu, torch.float32, N * K + N, "mu"), _req(sigma, torch.float32, N * K + N, "sigma"), _req(eff, torch.float32, N * K + N, "eff"),

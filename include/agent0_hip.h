@@ -458,6 +458,44 @@ typedef struct a0_net_reset_seg {
 int a0_net_reset(float* params, float* target, float* exp_avg, float* exp_avg_sq, long long n_adam, long long n_total, const a0_net_reset_seg* segs, int n_segs,
                  double alpha, unsigned long long seed, int* state, int freq, int force, long long k_host, const a0_encoder_weights* w, int C, float* wt,
                  float* wt_target, void* stream);
+/* Dormant neurons and ReDo recycling (learner.redo_freq / learner.redo_tau / learner.redo_recycle; Sokar et al. 2023, "The Dormant Neuron Phenomenon in Deep RL").
+ * The 672 hidden neurons of the network, in this order: conv1's 32 output channels [0, 32), conv2's 64 [32, 96), conv3's 64 [96, 160), fc1's 512 units [160, 672).
+ * Both entry points decide for themselves, like a0_net_reset: they act when force != 0, or when state[3] == 0 (the update was not NaN-skipped), freq > 0, state[1] > 0
+ * and state[1] % freq == 0; otherwise every workgroup returns after reading those two words (state may be NULL with force).  Issue them behind an update's Adam form
+ * and behind a0_target_blend, in front of a0_net_reset.
+ *
+ * a0_redo_score (two launches: partial sums, finish): act1 [rows1][32], act2 [rows2][64], act3 [rows3][64], fc1 [rows4][512], fp32, channel-fastest, 16-byte aligned,
+ * rows >= 1 — the activations of the online, differentiated pass (A0_PEEK_ACT1 / 2 / 3 / FC1).  For layer l with n_l neurons: m_i = (1 / rows) sum_r |X[r][i]|,
+ * s_i = m_i / ((1 / n_l) sum_j m_j), a layer whose mean is 0 has s_i = 0; neuron i is dormant iff s_i <= tau (0 <= tau < 1), compared in double.  All sums are
+ * accumulated in double in a fixed order: workgroup g of the (at most A0_REDO_PARTIALS) workgroups a layer's row count names owns a range of rows that depends on that count alone, its lanes' sums are added in
+ * index order into partials[g][672] (plain stores, no atomics), and one workgroup adds the partials of a neuron in index order, in eight slices whose sums it then adds in index order.  partials: A0_REDO_PARTIALS * A0_REDO_NEURONS
+ * doubles of scratch.  Outputs: scores float[672] (the double rounded once), mask int[672] (1 = dormant), counts int[8]: [0..3] dormant per layer, [4] their sum,
+ * [5] state[1] of the evaluation (0 with a NULL state; the caller initialises it to -1 = "never evaluated"), [6], [7] spare and not written.
+ *
+ * a0_redo_recycle (one launch): for every neuron i of layer l with mask != 0,
+ *  - incoming: row i of the layer's W block and bias i get the fresh value the rule table `segs` (a0_net_reset's table; `keep` is ignored: a recycled row is
+ *    replaced, not shrunk) gives element e: kind CONST: `scale`; NORMAL / UNIFORM: what a0_rng_normal / a0_rng_uniform (as scale * (2 u - 1)) write at position
+ *    k * n_total + e of Philox stream 9 of seed & 0xFFFFFFFF, k = state[1] / freq (k_host with force) — a function of (seed, k, e) alone;
+ *  - outgoing: every weight of the next block that reads neuron i becomes 0.0f: conv1 -> conv2 columns with col % 32 == i, conv2 -> conv3 col % 64 == i,
+ *    conv3 -> fc1 col % 64 == i in all 512 rows, fc1 -> head column i in all Npad rows (an element that is both ends at 0); the head's bias, the cosine embedding and
+ *    everything behind n_adam are left alone;
+ *  - exp_avg and exp_avg_sq of every touched element become 0; state is only read (Adam's bias correction is not restarted);
+ *  - with wt (16-byte aligned, a0_net_conv_wt_floats(C) floats) and w, the ONLINE network's convolution weights inside params — the blocks `blocks` names — the lane
+ *    that writes a convolution weight files it in wt: afterwards wt holds the bytes a0_net_conv_wt_refresh builds from the new parameters.
+ * Every other byte is left unread or unwritten; the target network and its weight copy are not arguments.  `blocks`: the offsets of the blocks [W (N x K) | b (N)]
+ * in the flat buffer (agent0_amd/deepq/layout.py), ascending: conv1 32 x K1, conv2 64 x 512, conv3 64 x 576, fc1 512 x feat, head Npad x 512.  Buffers 4-byte
+ * aligned; element by element, stores only where an element is touched; the mask is read into LDS once per workgroup.  No scratch, no atomics. */
+#define A0_REDO_NEURONS 672
+#define A0_REDO_PARTIALS 512
+typedef struct a0_redo_blocks {
+    long long conv1, conv2, conv3, fc1, head; /* first element of each block in the flat parameter buffer */
+    int K1, feat, Npad;                       /* conv1's row length C * 64, fc1's row length 64 * H3 * W3, the head's padded rows */
+} a0_redo_blocks;
+int a0_redo_score(const float* act1, long long rows1, const float* act2, long long rows2, const float* act3, long long rows3, const float* fc1, long long rows4,
+                  double tau, const int* state, int freq, int force, double* partials, float* scores, int* mask, int* counts, void* stream);
+int a0_redo_recycle(float* params, float* exp_avg, float* exp_avg_sq, long long n_adam, long long n_total, const a0_net_reset_seg* segs, int n_segs,
+                    const a0_redo_blocks* blocks, const int* mask, unsigned long long seed, const int* state, int freq, int force, long long k_host,
+                    const a0_encoder_weights* w, int C, float* wt, void* stream);
 /* ---------------------------------------------------------------- a whole learner behind one handle (opaque handles, library-owned HBM)
  * BaseLearner (agent.py:97-169) with DQNLearner.train_step (173-190) for scalar heads on 4 x 84 x 84 observations — BASELINE configs[1]: online + target parameters
  * in the packed layout (agent0_amd/deepq/layout.py: conv1 | conv2 | conv3 | fc1 | head, each [W (N x K) | b (N)], head rows padded to a multiple of 32), gradients,
@@ -548,6 +586,15 @@ int a0_learner_weight_decay_partials(const a0_learner* learner, double** partial
  * the number of entries; a `cap` smaller than that is A0_EINVAL (A0_NET_RESET_MAX_SEGS entries always fit). */
 int a0_learner_set_net_reset(a0_learner* learner, int freq, double shrink, unsigned long long seed);
 int a0_learner_net_reset_segs(const a0_learner* learner, a0_net_reset_seg* out, int cap);
+/* learner.redo_freq / learner.redo_tau / learner.redo_recycle through the handle: with freq > 0 every a0_learner_update issues a0_redo_score on the buffers
+ * A0_PEEK_ACT1 / 2 / 3 / FC1 name and, with recycle != 0, a0_redo_recycle (the handle's rule table and block descriptors, the low 32 bits of `seed`) behind its Adam
+ * form and the blend, in front of a0_net_reset.  freq == 0: off, nothing is allocated and the update issues what it always did.  A0_EINVAL: freq < 0, tau not a
+ * finite number in [0, 1), recycle != 0 on a NoisyNet handle (ReDo is undefined for mu / sigma pairs; measuring is allowed), a handle with a data-parallel exchange
+ * (the ranks see different batches and would draw different masks; a0_learner_set_exchange refuses the other order), a call after the handle's first update.
+ * a0_learner_redo_buffers: the handle's scores float[672], mask int[672], counts int[8] on the device (NULL each while the setting is off); counts[5] is -1 until
+ * the first evaluation.  Descriptor structs are unchanged. */
+int a0_learner_set_redo(a0_learner* learner, int freq, double tau, int recycle, unsigned long long seed);
+int a0_learner_redo_buffers(const a0_learner* learner, float** scores_dev, int** mask_dev, int** counts_dev);
 /* learner.aug_shift through the handle: with pad > 0 every a0_learner_update first issues a0_augment_shift (the caller's frames / slot / row_bytes, the handle's seed
  * and state words, so u = state[6]) into a stage buffer of B * 2 * C * H * W bytes that the handle allocates on the first such call, and then runs every pass — the
  * target and double-Q passes on st_next, the online pass and mdqn's target pass on st, conv1's weight gradient — on that buffer with a NULL slot; the caller's ring is
