@@ -13,6 +13,28 @@
 
 #pragma clang fp contract(off)
 
+// ------------------------------------------------------------------------------------------------ shared by the single-workgroup kernels
+// Launch width for n items: a power of two in [64, 1024] — a0_block_max halves the width, so no other width reaches every lane.
+static int a0_pow2_threads(int n) { int threads = 64; while (threads < n && threads < 1024) threads <<= 1; return threads; }
+
+// max of v over the workgroup, on every lane.  red: blockDim.x floats of LDS; blockDim.x a power of two (a0_pow2_threads).
+A0_D float a0_block_max(float* red, float v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// batch order, a later duplicate wins: is entry i the last of ids[0 .. n) that names ids[i]?
+A0_D bool a0_last_of_id(const long long* ids, int i, int n) {
+    const long long id = ids[i];
+    for (int c = i + 1; c < n; ++c) if (ids[c] == id) return false;
+    return true;
+}
+
 // ------------------------------------------------------------------------------------------------ insert / gather
 // One workgroup column per transition, 16 B per lane.  obs / obs_next: [n][obs_bytes] u8; ring slot (start+i) % cap.
 __global__ __launch_bounds__(256) void a0_replay_insert_kernel(uint8_t* __restrict__ frames, long long cap, int obs_bytes, long long start, int n,
@@ -109,6 +131,12 @@ extern "C" int a0_fill_f32(float* p, long long n, float v, void* stream) {
 // whatever the device's v_sqrt_f32 does
 A0_D float a0_prio_pow(float x, float alpha) { return (alpha == 0.5f) ? (float)sqrt((double)x) : powf(x, alpha); }
 
+// replay.py:55-59 for one entry: the priority (loss + eps)^alpha, and the lane's running max of the raw loss (what max_p tracks)
+A0_D float a0_prio_from_loss(float l, float eps, float alpha, float& mx) {
+    mx = fmaxf(mx, l);
+    return a0_prio_pow(l + eps, alpha);
+}
+
 // priority[ids] = (loss + eps)^alpha in batch order (a later duplicate wins); max_p[0] = max(max_p, max loss)
 // pstate: [0] max_p (float).  Single workgroup so that the duplicate rule is deterministic.
 __global__ __launch_bounds__(1024) void a0_priority_update_kernel(float* __restrict__ priority, const long long* __restrict__ ids,
@@ -118,26 +146,18 @@ __global__ __launch_bounds__(1024) void a0_priority_update_kernel(float* __restr
     __shared__ float red[1024];
     float mx = -INFINITY;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const long long id = ids[b];
-        bool last = true;
-        for (int c = b + 1; c < B; ++c) if (ids[c] == id) { last = false; break; }
-        const float l = loss[b];
-        if (last) priority[id] = a0_prio_pow(l + eps, alpha);
-        mx = fmaxf(mx, l);
+        const bool last = a0_last_of_id(ids, b, B);
+        const float v = a0_prio_from_loss(loss[b], eps, alpha, mx);
+        if (last) priority[ids[b]] = v;
     }
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) pstate[0] = fmaxf(pstate[0], red[0]);
+    mx = a0_block_max(red, mx);
+    if (threadIdx.x == 0) pstate[0] = fmaxf(pstate[0], mx);
 }
 
 extern "C" int a0_priority_update(float* priority, const long long* ids, const float* loss, int B, float eps, float alpha, float* pstate,
                                   const int* state, void* stream) {
     if (!priority || !ids || !loss || !pstate || B < 1) return a0_fail(A0_EINVAL, "a0_priority_update: bad argument");
-    hipLaunchKernelGGL(a0_priority_update_kernel, dim3(1), dim3(B >= 1024 ? 1024 : ((B + 63) / 64) * 64), 0, (hipStream_t)stream, priority, ids, loss, B, eps, alpha, pstate, state);
+    hipLaunchKernelGGL(a0_priority_update_kernel, dim3(1), dim3(a0_pow2_threads(B)), 0, (hipStream_t)stream, priority, ids, loss, B, eps, alpha, pstate, state);
     return a0_fail_hip((int)hipGetLastError(), "a0_priority_update");
 }
 
@@ -182,29 +202,31 @@ extern "C" int a0_sum_f32(const float* x, long long n, float* scratch256, float*
     return a0_fail_hip((int)hipGetLastError(), "a0_sum_f32");
 }
 
-// w = (top * p / sum)^(-beta);  w /= (max w + 1e-8)     (trainer.py:91-94).  Single workgroup.
+// Importance weights, trainer.py:91-94: w = (top * p / total)^(-beta), then w /= (max w + 1e-8) over the batch.  a0_is_weight stores
+// entry b's unnormalised weight and keeps the lane's running max; a0_is_weights_normalise is the second pass (single workgroup).
+A0_D void a0_is_weight(float p, float total, float top, float beta, float* __restrict__ w, int b, float& mx) {
+    const float probs = p / total;
+    const float v = powf(top * probs, -beta);
+    w[b] = v;
+    mx = fmaxf(mx, v);
+}
+A0_D void a0_is_weights_normalise(float* red, float mx, float* __restrict__ w, int B) {
+    const float denom = a0_block_max(red, mx) + 1e-8f;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) w[b] = w[b] / denom;
+}
+
 __global__ __launch_bounds__(1024) void a0_is_weights_kernel(const float* __restrict__ prio, int B, const float* __restrict__ psum, float top, float beta,
                                                               float* __restrict__ w) {
     __shared__ float red[1024];
     const float total = psum[0];
     float mx = 0.f;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const float probs = prio[b] / total;
-        const float v = powf(top * probs, -beta);
-        w[b] = v;
-        mx = fmaxf(mx, v);
-    }
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-    const float denom = red[0] + 1e-8f;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) w[b] = w[b] / denom;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) a0_is_weight(prio[b], total, top, beta, w, b, mx);
+    a0_is_weights_normalise(red, mx, w, B);
 }
 
 extern "C" int a0_is_weights(const float* prio, int B, const float* psum, long long top, float beta, float* w, void* stream) {
     if (!prio || !psum || !w || B < 1 || top < 1) return a0_fail(A0_EINVAL, "a0_is_weights: bad argument");
-    int threads = 64; while (threads < B && threads < 1024) threads <<= 1;
-    hipLaunchKernelGGL(a0_is_weights_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, prio, B, psum, (float)top, beta, w);
+    hipLaunchKernelGGL(a0_is_weights_kernel, dim3(1), dim3(a0_pow2_threads(B)), 0, (hipStream_t)stream, prio, B, psum, (float)top, beta, w);
     return a0_fail_hip((int)hipGetLastError(), "a0_is_weights");
 }
 
@@ -215,13 +237,11 @@ A0_D uint32_t a0_mix32(uint32_t x) {
     return x;
 }
 
-__global__ void a0_perm_kernel(unsigned long long start, int count, unsigned long long n, uint32_t seed, long long* __restrict__ out) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= count) return;
+// element x of the permutation of [0, n) that `seed` names
+A0_D unsigned long long a0_perm_index(unsigned long long x, unsigned long long n, uint32_t seed) {
     uint32_t h = 1;
     while ((1ull << (2 * h)) < n) ++h;
     const uint32_t mask = (uint32_t)((1ull << h) - 1);
-    unsigned long long x = start + (unsigned long long)k;
     do {
         uint32_t l = (uint32_t)(x >> h) & mask, r = (uint32_t)x & mask;
         for (uint32_t round = 0; round < 4; ++round) {
@@ -231,7 +251,28 @@ __global__ void a0_perm_kernel(unsigned long long start, int count, unsigned lon
         }
         x = ((unsigned long long)l << h) | r;
     } while (x >= n);
-    out[k] = (long long)x;
+    return x;
+}
+
+// permutation element x -> logical index li = x % top -> ring slot (head + li) % cap (reference deque(maxlen) semantics) ...
+A0_D long long a0_perm_slot(unsigned long long x, long long top, long long head, long long cap, long long& li) {
+    li = (long long)(x % (unsigned long long)top);
+    return (head + li) % cap;
+}
+// ... -> row o of the batch's metadata (prio: NULL, the flat priority vector's entry, or 1 without one)
+A0_D void a0_perm_row(unsigned long long x, long long top, long long head, long long cap, const int* __restrict__ r_act, const float* __restrict__ r_rew,
+                      const float* __restrict__ r_done, const float* __restrict__ priority, long long o, long long* __restrict__ idx_out, int* __restrict__ slot_out,
+                      int* __restrict__ act, float* __restrict__ rew, float* __restrict__ done, float* __restrict__ prio) {
+    long long li;
+    const long long s = a0_perm_slot(x, top, head, cap, li);
+    idx_out[o] = li; slot_out[o] = (int)s; act[o] = r_act[s]; rew[o] = r_rew[s]; done[o] = r_done[s];
+    if (prio) prio[o] = priority ? priority[li] : 1.f;
+}
+
+__global__ void a0_perm_kernel(unsigned long long start, int count, unsigned long long n, uint32_t seed, long long* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    out[k] = (long long)a0_perm_index(start + (unsigned long long)k, n, seed);
 }
 
 extern "C" int a0_perm_batch(unsigned long long start, int count, unsigned long long n, unsigned int seed, long long* out, void* stream) {
@@ -248,14 +289,35 @@ extern "C" int a0_perm_batch(unsigned long long start, int count, unsigned long 
 // 1 M-leaf tree's twenty levels become LDS work.  Call with level `s0` = min(cap2, A0_ST_TOP) up to date in global memory and a barrier
 // behind its last writes.
 constexpr int A0_ST_TOP = 2048;
-A0_D void a0_sumtree_top(float* __restrict__ tree, long long s0, float* __restrict__ lds) {
+// staging: level s0 loaded into lds[s0 .. 2 * s0), every level above it recomputed there (lds[1] is the root; a barrier behind the last level)
+A0_D void a0_sumtree_top_stage(const float* __restrict__ tree, long long s0, float* __restrict__ lds) {
     for (long long p = threadIdx.x; p < s0; p += blockDim.x) lds[s0 + p] = tree[s0 + p];
     __syncthreads();
     for (long long span = s0 >> 1; span >= 1; span >>= 1) {
         for (long long p = span + threadIdx.x; p < 2 * span; p += blockDim.x) lds[p] = lds[2 * p] + lds[2 * p + 1];
         __syncthreads();
     }
+}
+// write-back of the staged levels above s0
+A0_D void a0_sumtree_top_store(float* __restrict__ tree, long long s0, const float* __restrict__ lds) {
     for (long long p = 1 + threadIdx.x; p < s0; p += blockDim.x) tree[p] = lds[p];
+}
+A0_D void a0_sumtree_top(float* __restrict__ tree, long long s0, float* __restrict__ lds) {
+    a0_sumtree_top_stage(tree, s0, lds);
+    a0_sumtree_top_store(tree, s0, lds);
+}
+
+// One level of the descent (oracle/sumtree.c a0o_sumtree_find): left, unless u lies past the left child's mass and the right child has any.
+A0_D long long a0_sumtree_step(float left, float right, float& u, long long n) {
+    if (u < left || !(right > 0.0f)) return 2 * n;
+    u -= left;
+    return 2 * n + 1;
+}
+// The plain walk from node n down to the level of `stop` nodes, one level per step: the oracle's loop statement for statement, valid for any tree
+// (t: the tree in global memory, or its staged top in LDS).
+A0_D long long a0_sumtree_walk(const float* t, long long stop, float& u, long long n = 1) {
+    while (n < stop) n = a0_sumtree_step(t[2 * n], t[2 * n + 1], u, n);
+    return n;
 }
 
 __global__ __launch_bounds__(1024) void a0_sumtree_set_kernel(float* __restrict__ tree, long long cap2, const long long* __restrict__ idx,
@@ -266,12 +328,7 @@ __global__ __launch_bounds__(1024) void a0_sumtree_set_kernel(float* __restrict_
     __shared__ long long sidx[1024];
     for (int i = threadIdx.x; i < n; i += blockDim.x) sidx[i] = idx[i];
     __syncthreads();
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const long long id = sidx[i];
-        bool last = true;
-        for (int c = i + 1; c < n; ++c) if (sidx[c] == id) { last = false; break; }
-        if (last) tree[cap2 + id] = val[i];
-    }
+    for (int i = threadIdx.x; i < n; i += blockDim.x) if (a0_last_of_id(sidx, i, n)) tree[cap2 + sidx[i]] = val[i];
     __threadfence_block();
     __syncthreads();
     __shared__ float top[2 * A0_ST_TOP];
@@ -335,7 +392,7 @@ template <int M>       // leaves per lane: S = 64 * M
 __global__ __launch_bounds__(64) void a0_sumtree_set_sub_kernel(float* __restrict__ tree, long long cap2, const long long* __restrict__ idx,
                                                                  const float* __restrict__ val, int n, const int* __restrict__ state,
                                                                  const float* __restrict__ loss, float eps, float alpha, float* __restrict__ pstate) {
-    // loss != NULL (round 4, a0_sumtree_set_from_loss): the values are (loss + eps)^alpha, formed here while the batch is staged (== a0_sumtree_prio_kernel:
+    // loss != NULL (a0_sumtree_set_from_loss): the values are (loss + eps)^alpha, formed here while the batch is staged (== a0_sumtree_prio_kernel:
     // one launch less per prioritized update), and workgroup 0 keeps max_p; val is unused then
     if (state && state[3]) return;
     constexpr int S = 64 * M, LS = __builtin_ctz(S);
@@ -346,7 +403,7 @@ __global__ __launch_bounds__(64) void a0_sumtree_set_sub_kernel(float* __restric
     const int lane = threadIdx.x, i = blockIdx.x;
     if (loss) {
         float mx = -INFINITY;
-        for (int j = lane; j < n; j += 64) { const float l = loss[j]; sidx[j] = (int)idx[j]; sval[j] = a0_prio_pow(l + eps, alpha); mx = fmaxf(mx, l); }
+        for (int j = lane; j < n; j += 64) { sidx[j] = (int)idx[j]; sval[j] = a0_prio_from_loss(loss[j], eps, alpha, mx); }
         if (i == 0) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
@@ -413,7 +470,7 @@ static void a0_sumtree_sub_launch(float* tree, long long cap2, const long long* 
     if (!defer_top) hipLaunchKernelGGL(a0_sumtree_top_kernel, dim3(1), dim3(1024), 0, st, tree, state);
 }
 
-// replay.py:55-59 on the sum-tree in TWO launches (was three): leaf[idx] = (loss + eps)^alpha in batch order, max_p = max(max_p, max loss), subtrees, then the top.
+// replay.py:55-59 on the sum-tree in two launches: leaf[idx] = (loss + eps)^alpha in batch order, max_p = max(max_p, max loss), subtrees, then the top.
 // Trees whose subtrees the per-wave kernel does not cover (a0_sumtree_set_from_loss_ok == 0) take a0_priority_from_loss + a0_sumtree_set.
 extern "C" int a0_sumtree_set_from_loss_ok(long long cap2) { return (cap2 >= 1 && !(cap2 & (cap2 - 1)) && a0_sumtree_sub_path(cap2)) ? 1 : 0; }
 
@@ -441,8 +498,7 @@ extern "C" int a0_sumtree_set(float* tree, long long cap2, const long long* idx,
         a0_sumtree_sub_launch(tree, cap2, idx, val, n, state, nullptr, 0.f, 0.f, nullptr, (hipStream_t)stream);
         return a0_fail_hip((int)hipGetLastError(), "a0_sumtree_set");
     }
-    int threads = 64; while (threads < n && threads < 1024) threads <<= 1;
-    hipLaunchKernelGGL(a0_sumtree_set_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, tree, cap2, idx, val, n, state);
+    hipLaunchKernelGGL(a0_sumtree_set_kernel, dim3(1), dim3(a0_pow2_threads(n)), 0, (hipStream_t)stream, tree, cap2, idx, val, n, state);
     return a0_fail_hip((int)hipGetLastError(), "a0_sumtree_set");
 }
 
@@ -452,17 +508,14 @@ __global__ __launch_bounds__(1024) void a0_sumtree_prio_kernel(const float* __re
     if (state && state[3]) return;      // NaN-skipped update: max_p and the staged values stay as they were
     __shared__ float red[1024];
     float mx = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) { const float l = loss[i]; val[i] = a0_prio_pow(l + eps, alpha); mx = fmaxf(mx, l); }
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-    if (threadIdx.x == 0) pstate[0] = fmaxf(pstate[0], red[0]);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) val[i] = a0_prio_from_loss(loss[i], eps, alpha, mx);
+    mx = a0_block_max(red, mx);
+    if (threadIdx.x == 0) pstate[0] = fmaxf(pstate[0], mx);
 }
 
 extern "C" int a0_priority_from_loss(const float* loss, int n, float eps, float alpha, float* val, float* pstate, const int* state, void* stream) {
     if (!loss || !val || !pstate || n < 1) return a0_fail(A0_EINVAL, "a0_priority_from_loss: bad argument");
-    int threads = 64; while (threads < n && threads < 1024) threads <<= 1;
-    hipLaunchKernelGGL(a0_sumtree_prio_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream, loss, n, eps, alpha, val, pstate, state);
+    hipLaunchKernelGGL(a0_sumtree_prio_kernel, dim3(1), dim3(a0_pow2_threads(n)), 0, (hipStream_t)stream, loss, n, eps, alpha, val, pstate, state);
     return a0_fail_hip((int)hipGetLastError(), "a0_priority_from_loss");
 }
 
@@ -489,17 +542,7 @@ __global__ void a0_sumtree_sample_kernel(const float* __restrict__ tree, long lo
     const float total = tree[1];
     const float seg = total / (float)B;
     float u = ((float)k + xi[k]) * seg;
-    long long n = 1;
-    while (n < cap2) {
-        const float left = tree[2 * n];
-        const float right = tree[2 * n + 1];
-        if (u < left || !(right > 0.0f)) {
-            n = 2 * n;
-        } else {
-            u -= left;
-            n = 2 * n + 1;
-        }
-    }
+    const long long n = a0_sumtree_walk(tree, cap2, u);
     out_idx[k] = n - cap2;
     out_p[k] = tree[n];
 }
@@ -510,30 +553,17 @@ extern "C" int a0_sumtree_sample(const float* tree, long long cap2, const float*
     return a0_fail_hip((int)hipGetLastError(), "a0_sumtree_sample");
 }
 
-
-// The descent of a0_sumtree_sample_kernel, two levels per memory round trip: the four grandchildren of node n are the 16 aligned bytes tree[4n .. 4n + 3],
-// and because every internal node IS left + right of its children (the tree is only ever recomputed from children, never updated by delta), the children's
-// values are gc0 + gc1 and gc2 + gc3 bit for bit — so one 16-byte load replaces two dependent 8-byte ones and the comparisons see the same numbers.
+// The same walk, two levels per memory round trip: the four grandchildren of node n are the 16 aligned bytes tree[4n .. 4n + 3], and because every
+// internal node IS left + right of its children (the tree is only ever recomputed from children, never updated by delta), the children's values are
+// gc0 + gc1 and gc2 + gc3 bit for bit — so one 16-byte load replaces two dependent 8-byte ones and the comparisons see the same numbers.
 // A 1 M-leaf tree is 20 dependent L2 round trips deep (~0.8 us each for a lone workgroup); this makes it 10.
 A0_D long long a0_sumtree_descend(const float* __restrict__ tree, long long cap2, float& u, long long n = 1) {
     while (4 * n <= cap2) {              // at least two levels below n
         const a0_f4 g = *(const a0_f4*)(tree + 4 * n);
-        const float left = g.x + g.y, right = g.z + g.w;
-        if (u < left || !(right > 0.0f)) {
-            n = 2 * n;
-            if (u < g.x || !(g.y > 0.0f)) { n = 2 * n; } else { u -= g.x; n = 2 * n + 1; }
-        } else {
-            u -= left;
-            n = 2 * n + 1;
-            if (u < g.z || !(g.w > 0.0f)) { n = 2 * n; } else { u -= g.z; n = 2 * n + 1; }
-        }
+        const long long c = a0_sumtree_step(g.x + g.y, g.z + g.w, u, n);
+        n = (c & 1) ? a0_sumtree_step(g.z, g.w, u, c) : a0_sumtree_step(g.x, g.y, u, c);
     }
-    while (n < cap2) {
-        const float left = tree[2 * n];
-        const float right = tree[2 * n + 1];
-        if (u < left || !(right > 0.0f)) { n = 2 * n; } else { u -= left; n = 2 * n + 1; }
-    }
-    return n;
+    return a0_sumtree_walk(tree, cap2, u, n);      // an odd number of levels left: the last one
 }
 
 // ------------------------------------------------------------------------------------------------ prioritized batch in one launch
@@ -546,46 +576,29 @@ __global__ __launch_bounds__(1024) void a0_sumtree_batch_kernel(unsigned long lo
                                                                  int* __restrict__ slot_out, int* __restrict__ act, float* __restrict__ rew, float* __restrict__ done,
                                                                  float* __restrict__ prio, float* __restrict__ w, int rebuild_top) {
     __shared__ float red[1024];
-    // Round 4: the levels with at most A0_ST_TOP nodes are staged in LDS first — recomputed from level A0_ST_TOP exactly as a0_sumtree_top does (and written back when
-    // `rebuild_top`: the launch a0_sumtree_set_from_loss(defer_top = 1) left out; recomputing a top that is up to date changes no bit) — and the descent walks them
-    // there: eleven of a 1 M-leaf tree's twenty levels cost LDS reads instead of five dependent L2 round trips, and the prioritized update is two launches
-    // (subtrees; top + next batch) instead of three.  Same comparisons on the same node values: every node IS left + right of its children.
+    // The levels with at most A0_ST_TOP nodes are staged in LDS (written back under `rebuild_top`: the launch a0_sumtree_set_from_loss(defer_top = 1) left out;
+    // recomputing a top that is up to date changes no bit) and walked there, the rest two levels per load: eleven of a 1 M-leaf tree's twenty levels cost
+    // LDS reads instead of five dependent L2 round trips.  Same comparisons on the same node values: every node IS left + right of its children.
     __shared__ float top_l[2 * A0_ST_TOP];
     const long long s0 = cap2 < A0_ST_TOP ? cap2 : A0_ST_TOP;
-    for (long long p = threadIdx.x; p < s0; p += blockDim.x) top_l[s0 + p] = tree[s0 + p];
-    __syncthreads();
-    for (long long span = s0 >> 1; span >= 1; span >>= 1) {
-        for (long long p = span + threadIdx.x; p < 2 * span; p += blockDim.x) top_l[p] = top_l[2 * p] + top_l[2 * p + 1];
-        __syncthreads();
-    }
-    if (rebuild_top) for (long long p = 1 + threadIdx.x; p < s0; p += blockDim.x) tree[p] = top_l[p];
+    a0_sumtree_top_stage(tree, s0, top_l);
+    if (rebuild_top) a0_sumtree_top_store(tree, s0, top_l);
     const float total = top_l[1];
     const float seg = total / (float)B;
     float mx = 0.f;
     for (int k = threadIdx.x; k < B; k += blockDim.x) {
         const float xi = (float)(a0_philox_word(seed, stream, offset + (unsigned long long)k) >> 8) * 0x1.0p-24f;
         float u = ((float)k + xi) * seg;
-        long long n = 1;
-        while (n < s0) {
-            const float left = top_l[2 * n], right = top_l[2 * n + 1];
-            if (u < left || !(right > 0.0f)) { n = 2 * n; } else { u -= left; n = 2 * n + 1; }
-        }
-        n = a0_sumtree_descend(tree, cap2, u, n);
+        const long long n0 = a0_sumtree_walk(top_l, s0, u);
+        const long long n = a0_sumtree_descend(tree, cap2, u, n0);
         const long long li = (n - cap2) % cap;          // sum-tree leaves are addressed by ring slot (head = 0): logical index == slot
         const long long sl = li;
         const float p = tree[n];
         idx_out[k] = li; slot_out[k] = (int)sl; act[k] = r_act[sl]; rew[k] = r_rew[sl]; done[k] = r_done[sl];
         prio[k] = p;
-        const float probs = p / total;
-        const float v = powf((float)top * probs, -beta);
-        w[k] = v;
-        mx = fmaxf(mx, v);
+        a0_is_weight(p, total, (float)top, beta, w, k, mx);
     }
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = blockDim.x >> 1; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]); __syncthreads(); }
-    const float denom = red[0] + 1e-8f;
-    for (int k = threadIdx.x; k < B; k += blockDim.x) w[k] = w[k] / denom;
+    a0_is_weights_normalise(red, mx, w, B);
 }
 
 extern "C" int a0_sumtree_sample_batch(unsigned long long seed, unsigned int stream, unsigned long long offset, float* tree, long long cap2, int B, long long top,
@@ -594,8 +607,7 @@ extern "C" int a0_sumtree_sample_batch(unsigned long long seed, unsigned int str
     if (!tree || !r_act || !r_rew || !r_done || !idx_out || !slot_out || !act || !rew || !done || !prio || !w || B < 1 || B > 1024 || top < 1 || cap < top ||
         cap2 < cap || (cap2 & (cap2 - 1)) || cap > 2147483647LL)
         return a0_fail(A0_EINVAL, "a0_sumtree_sample_batch: bad argument");
-    int threads = 64; while (threads < B && threads < 1024) threads <<= 1;
-    hipLaunchKernelGGL(a0_sumtree_batch_kernel, dim3(1), dim3(threads), 0, (hipStream_t)stream_h, seed, stream, offset, tree, cap2, B, top, cap, beta, r_act, r_rew, r_done,
+    hipLaunchKernelGGL(a0_sumtree_batch_kernel, dim3(1), dim3(a0_pow2_threads(B)), 0, (hipStream_t)stream_h, seed, stream, offset, tree, cap2, B, top, cap, beta, r_act, r_rew, r_done,
                        idx_out, slot_out, act, rew, done, prio, w, rebuild_top);
     return a0_fail_hip((int)hipGetLastError(), "a0_sumtree_sample_batch");
 }
@@ -618,32 +630,13 @@ __global__ __launch_bounds__(256) void a0_sample_gather_kernel(int mode, unsigne
         long long li, slot;
         float p = 1.f;
         if (mode == 0) {
-            uint32_t h = 1;
-            while ((1ull << (2 * h)) < n_perm) ++h;
-            const uint32_t mask = (uint32_t)((1ull << h) - 1);
-            unsigned long long x = start + (unsigned long long)b;
-            do {
-                uint32_t l = (uint32_t)(x >> h) & mask, r = (uint32_t)x & mask;
-                for (uint32_t round = 0; round < 4; ++round) {
-                    const uint32_t f = a0_mix32(r ^ (seed + 0x9E3779B9u * (round + 1))) & mask;
-                    const uint32_t nl = r, nr = l ^ f;
-                    l = nl; r = nr;
-                }
-                x = ((unsigned long long)l << h) | r;
-            } while (x >= n_perm);
-            li = (long long)(x % (unsigned long long)top);
-            slot = (head + li) % cap;
+            slot = a0_perm_slot(a0_perm_index(start + (unsigned long long)b, n_perm, seed), top, head, cap, li);
             if (priority) p = priority[li];
         } else {
             const float total = tree[1];
             const float seg = total / (float)B;
             float u = ((float)b + xi[b]) * seg;
-            long long n = 1;
-            while (n < cap2) {
-                const float left = tree[2 * n];
-                const float right = tree[2 * n + 1];
-                if (u < left || !(right > 0.0f)) { n = 2 * n; } else { u -= left; n = 2 * n + 1; }
-            }
+            const long long n = a0_sumtree_walk(tree, cap2, u);
             li = n - cap2;
             slot = li;
             p = tree[n];
@@ -675,23 +668,7 @@ __global__ void a0_sample_slots_kernel(unsigned long long start, unsigned long l
                                        int* __restrict__ act, float* __restrict__ rew, float* __restrict__ done, float* __restrict__ prio) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    uint32_t h = 1;
-    while ((1ull << (2 * h)) < n_perm) ++h;
-    const uint32_t mask = (uint32_t)((1ull << h) - 1);
-    unsigned long long x = start + (unsigned long long)b;
-    do {
-        uint32_t l = (uint32_t)(x >> h) & mask, r = (uint32_t)x & mask;
-        for (uint32_t round = 0; round < 4; ++round) {
-            const uint32_t f = a0_mix32(r ^ (seed + 0x9E3779B9u * (round + 1))) & mask;
-            const uint32_t nl = r, nr = l ^ f;
-            l = nl; r = nr;
-        }
-        x = ((unsigned long long)l << h) | r;
-    } while (x >= n_perm);
-    const long long li = (long long)(x % (unsigned long long)top);
-    const long long s = (head + li) % cap;
-    idx_out[b] = li; slot_out[b] = (int)s; act[b] = r_act[s]; rew[b] = r_rew[s]; done[b] = r_done[s];
-    if (prio) prio[b] = priority ? priority[li] : 1.f;
+    a0_perm_row(a0_perm_index(start + (unsigned long long)b, n_perm, seed), top, head, cap, r_act, r_rew, r_done, priority, b, idx_out, slot_out, act, rew, done, prio);
 }
 
 // n batches of the same epoch structure in ONE launch: batch g = blockIdx.y takes permutation elements start[g] .. start[g] + B - 1 of the epoch (n_perm[g], seed[g]) and
@@ -703,26 +680,8 @@ __global__ void a0_sample_slots_multi_kernel(a0_slots_multi_args S, long long to
                                              float* __restrict__ rew, float* __restrict__ done, float* __restrict__ prio) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y;
     if (b >= B) return;
-    const unsigned long long n_perm = S.n_perm[g];
-    const uint32_t seed = S.seed[g];
-    uint32_t h = 1;
-    while ((1ull << (2 * h)) < n_perm) ++h;
-    const uint32_t mask = (uint32_t)((1ull << h) - 1);
-    unsigned long long x = S.start[g] + (unsigned long long)b;
-    do {
-        uint32_t l = (uint32_t)(x >> h) & mask, r = (uint32_t)x & mask;
-        for (uint32_t round = 0; round < 4; ++round) {
-            const uint32_t f = a0_mix32(r ^ (seed + 0x9E3779B9u * (round + 1))) & mask;
-            const uint32_t nl = r, nr = l ^ f;
-            l = nl; r = nr;
-        }
-        x = ((unsigned long long)l << h) | r;
-    } while (x >= n_perm);
-    const long long li = (long long)(x % (unsigned long long)top);
-    const long long s = (head + li) % cap;
-    const long long o = (long long)g * B + b;
-    idx_out[o] = li; slot_out[o] = (int)s; act[o] = r_act[s]; rew[o] = r_rew[s]; done[o] = r_done[s];
-    if (prio) prio[o] = 1.f;
+    a0_perm_row(a0_perm_index(S.start[g] + (unsigned long long)b, S.n_perm[g], S.seed[g]), top, head, cap, r_act, r_rew, r_done, nullptr, (long long)g * B + b, idx_out, slot_out,
+                act, rew, done, prio);
 }
 
 extern "C" int a0_replay_sample_slots_multi(int n, const unsigned long long* start, const unsigned long long* n_perm, const unsigned int* seed, long long top, long long head,

@@ -66,6 +66,19 @@ struct a0_rbuf {
     // a0_rbuf_sample_block: up to 32 batches' buffers [32][B], allocated on first use
     long long* m_idx = nullptr; int *m_slot = nullptr, *m_act = nullptr; float *m_rew = nullptr, *m_done = nullptr, *m_prio = nullptr;
     long long head() const { return written > size ? written % size : 0; }
+    // beta = beta_schedule(n): the schedule's value BEFORE it advances by n transitions is the one in use (utils.py:25-28)
+    void beta_step(long long n) { beta_use = sched_cur; const double nxt = sched_cur + beta_inc * (double)n; sched_cur = nxt < 1.0 ? nxt : 1.0; }
+    // Uniform replay's next batch: elements [start, start + B) of the epoch's permutation (n_perm, seed) of range(top).  An epoch is opened when the previous one
+    // has no whole batch left BUT ONE: the reference's prefetcher never returns its last batch (utils.py:51-56).  `who`: the entry point, for the error text.
+    int next_batch(const char* who, unsigned long long* start, unsigned long long* n_perm, unsigned* seed) {
+        if (!ep.open || ep.pos + 1 >= ep.nb) {
+            ep.top = top; ep.nb = (top + B - 1) / B; ep.pos = 0; ep.seed = rng.next_seed32(STREAM_PERM); ep.open = true;
+            if (ep.nb < 2) { ep.open = false; return a0_fail(A0_EINVAL, (std::string(who) + ": the ring holds fewer than two batches (the reference's fetcher cannot return one either)").c_str()); }
+        }
+        *start = (unsigned long long)(ep.pos * B); *n_perm = (unsigned long long)ep.top; *seed = ep.seed;
+        ep.pos += 1;
+        return A0_OK;
+    }
 };
 
 extern "C" int a0_rbuf_create(const a0_rbuf_desc* d, a0_rbuf** out) { return a0_rbuf_create_on(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out); }
@@ -160,17 +173,13 @@ extern "C" int a0_rbuf_commit(a0_rbuf* R, long long n, void* stream) {
     if (R->flat) {
         // replay.py:51-52 as written: the roll's result is discarded and the n new priorities max_p^alpha land in the TAIL of the vector (quirk Q1)
         A0_CHECK(a0_priority_tail(R->prio_vec, R->size, n < R->size ? n : R->size, R->pstate, (float)R->d.alpha, stream));
-        R->beta_use = R->sched_cur;
-        const double nxt = R->sched_cur + R->beta_inc * (double)n;
-        R->sched_cur = nxt < 1.0 ? nxt : 1.0;
+        R->beta_step(n);
     } else if (R->prio) {
         hipLaunchKernelGGL(a0_pow_scalar_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, R->pstate, R->d.alpha, R->val);
         const long long k = n < R->size ? n : R->size;
         A0_CHECK(a0_sumtree_set_range(R->tree, R->cap2, (R->written - k) % R->size, k, R->size, R->val, stream));
         R->top_stale = false;
-        R->beta_use = R->sched_cur;                               // beta = beta_schedule(n): the schedule's value BEFORE it advances (utils.py:25-28)
-        const double nxt = R->sched_cur + R->beta_inc * (double)n;
-        R->sched_cur = nxt < 1.0 ? nxt : 1.0;
+        R->beta_step(n);
     }
     return A0_OK;
     A0_CATCH
@@ -213,13 +222,10 @@ extern "C" int a0_rbuf_sample(a0_rbuf* R, a0_batch* out, void* stream) {
         *out = a0_batch{R->b_idx, R->b_slot, R->b_act, R->b_rew, R->b_done, R->b_prio, R->b_w};
         return A0_OK;
     }
-    if (!R->ep.open || R->ep.pos + 1 >= R->ep.nb) {
-        R->ep.top = R->top; R->ep.nb = (R->top + B - 1) / B; R->ep.pos = 0; R->ep.seed = R->rng.next_seed32(STREAM_PERM); R->ep.open = true;
-        if (R->ep.nb < 2) { R->ep.open = false; return a0_fail(A0_EINVAL, "a0_rbuf_sample: the ring holds fewer than two batches (the reference's fetcher cannot return one either)"); }
-    }
-    const long long start = R->ep.pos * B;
-    R->ep.pos += 1;
-    A0_CHECK(a0_replay_sample_slots((unsigned long long)start, (unsigned long long)R->ep.top, R->ep.seed, R->top, R->head(), R->size, R->act, R->rew, R->done, R->flat ? R->prio_vec : nullptr, B,
+    unsigned long long start, n_perm;
+    unsigned seed;
+    A0_CHECK(R->next_batch("a0_rbuf_sample", &start, &n_perm, &seed));
+    A0_CHECK(a0_replay_sample_slots(start, n_perm, seed, R->top, R->head(), R->size, R->act, R->rew, R->done, R->flat ? R->prio_vec : nullptr, B,
                                     R->b_idx, R->b_slot, R->b_act, R->b_rew, R->b_done, R->b_prio, stream));
     if (R->flat) {       // trainer.py:91-94: probs = p / priority.sum() over the WHOLE capacity (quirk Q7), w = (top * probs)^-beta / max
         A0_CHECK(a0_sum_f32(R->prio_vec, R->size, R->sum_scratch, R->psum, stream));
@@ -238,14 +244,8 @@ extern "C" int a0_rbuf_sample_block(a0_rbuf* R, int n, a0_batch* out, void* stre
     const int B = R->B;
     unsigned long long start[32], n_perm[32];
     unsigned int seed[32];
-    for (int g = 0; g < n; ++g) {        // the epoch bookkeeping of n consecutive a0_rbuf_sample calls (the ring does not change inside an update block)
-        if (!R->ep.open || R->ep.pos + 1 >= R->ep.nb) {
-            R->ep.top = R->top; R->ep.nb = (R->top + B - 1) / B; R->ep.pos = 0; R->ep.seed = R->rng.next_seed32(STREAM_PERM); R->ep.open = true;
-            if (R->ep.nb < 2) { R->ep.open = false; return a0_fail(A0_EINVAL, "a0_rbuf_sample_block: the ring holds fewer than two batches"); }
-        }
-        start[g] = (unsigned long long)(R->ep.pos * B); n_perm[g] = (unsigned long long)R->ep.top; seed[g] = R->ep.seed;
-        R->ep.pos += 1;
-    }
+    // the epoch bookkeeping of n consecutive a0_rbuf_sample calls (the ring does not change inside an update block)
+    for (int g = 0; g < n; ++g) A0_CHECK(R->next_batch("a0_rbuf_sample_block", &start[g], &n_perm[g], &seed[g]));
     A0_CHECK(a0_replay_sample_slots_multi(n, start, n_perm, seed, R->top, R->head(), R->size, R->act, R->rew, R->done, B, R->m_idx, R->m_slot, R->m_act, R->m_rew, R->m_done,
                                           R->m_prio, stream));
     for (int g = 0; g < n; ++g) {

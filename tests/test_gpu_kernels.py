@@ -226,27 +226,33 @@ def test_replay_insert_lookup_gather_priorities(hip):
         assert_close(w, want, 2e-6, 1e-7, "importance weights")
 
 
-@pytest.mark.parametrize("prioritize,sumtree", [(False, False), (True, False), (True, True)])
-def test_fused_sample_gather_equals_separate_kernels(prioritize, sumtree):
-    """a0_replay_sample_gather == (a0_perm_batch | a0_sumtree_sample) + a0_replay_lookup + a0_replay_gather, bit for bit."""
+@pytest.mark.parametrize("prioritize,sumtree,size", [pytest.param(False, False, 300, id="False-False"), pytest.param(True, False, 300, id="True-False"),
+                                                     pytest.param(True, True, 300, id="True-True"), pytest.param(True, True, 5000, id="True-True-5000")])
+def test_fused_sample_gather_equals_separate_kernels(prioritize, sumtree, size):
+    """a0_replay_sample_gather == (a0_perm_batch | a0_sumtree_sample) + a0_replay_lookup + a0_replay_gather, bit for bit.  The 5000-entry sum-tree (cap2 = 8192)
+    puts two levels of the walk inside the gather kernel below the 2048-node level, across a run of zero-priority leaves (small rows there: the walk does
+    not depend on the frame size)."""
     from agent0_amd.deepq.config import parse_overrides
     from agent0_amd.deepq.replay import ReplayDataset, TransitionBlock
-    over = ["replay.size=300", "learner.batch_size=64", "wandb=false", "tb=false"]
+    over = [f"replay.size={size}", "learner.batch_size=64", "wandb=false", "tb=false"]
     if prioritize:
         over += ["replay.policy=prioritize", f"replay.sumtree={str(sumtree).lower()}"]
     reps = []
     for _ in range(2):
         cfg = parse_overrides(over)
-        cfg.obs_shape, cfg.action_dim = (4, 84, 84), 4
+        cfg.obs_shape, cfg.action_dim = ((4, 84, 84) if size == 300 else (4, 36, 36)), 4
         rp = ReplayDataset(cfg)
         g = recipe.gen(3)
-        n = 420                        # wraps the ring: head != 0
+        n = size + 120                 # wraps the ring: head != 0
         st = {"obs": torch.from_numpy(g.integers(0, 256, (n, rp.obs_bytes), dtype=np.uint8)).cuda(), "obs_next": torch.from_numpy(g.integers(0, 256, (n, rp.obs_bytes), dtype=np.uint8)).cuda(),
               "act": torch.from_numpy(g.integers(0, 4, n).astype(np.int32)).cuda(), "rew": torch.from_numpy(g.standard_normal(n).astype(np.float32)).cuda(),
               "done": torch.from_numpy((g.random(n) < 0.2).astype(np.float32)).cuda()}
         rp.extend(TransitionBlock(n, staged=st))
         if prioritize:
-            rp.update_priority(torch.from_numpy(g.integers(0, 300, 64)).cuda(), torch.from_numpy(g.uniform(0, 3, 64).astype(np.float32)).cuda())
+            rp.update_priority(torch.from_numpy(g.integers(0, size, 64)).cuda(), torch.from_numpy(g.uniform(0, 3, 64).astype(np.float32)).cuda())
+        if size > 300:                 # (loss + eps)^alpha == 0 exactly for loss = -eps: a dead stretch wider than several of the 64 strata
+            rp.update_priority(torch.arange(1000, 1512).cuda(), torch.full((512,), -np.float32(cfg.replay.eps)).cuda())
+            assert float(rp.tree[rp.cap2 + 1000:rp.cap2 + 1512].abs().max()) == 0.0 and rp.cap2 == 8192
         reps.append(rp)
     a, b = reps
     rows = torch.empty(64 * a.row_bytes, dtype=torch.uint8, device="cuda")
@@ -456,18 +462,21 @@ def test_head_data_and_weight_gradient_side_by_side(hip, R, N):
     assert e0 < 2e-6 and e1 < 2e-6, f"weight gradient {e1} of the scale against fp64 (a0_dense_wgrad: {e0})"
 
 
-def test_sumtree_sample_batch_equals_separate_kernels(hip):
+@pytest.mark.parametrize("size", [24, 1000, 2048, 3000, 100000])
+def test_sumtree_sample_batch_equals_separate_kernels(hip, size):
     """a0_sumtree_sample_batch (draws + descent + lookup + importance weights, one launch) against a0_rng_uniform + a0_sumtree_sample +
-    a0_replay_lookup + a0_is_weights: identical indices, slots, metadata, priorities and weights."""
-    size, B = 100000, 512
+    a0_replay_lookup + a0_is_weights: identical indices, slots, metadata, priorities and weights.  cap2 = 32 and 1024: the whole tree inside the
+    LDS top; 2048: cap2 equal to it; 4096: one level below (no two-level step, only the one-level tail); 2^17: a deep tree."""
+    B = 64 if size < 100000 else 512
     g = recipe.gen(31)
     t = core.SumTree(size)
+    assert t.cap2 == {24: 32, 1000: 1024, 2048: 2048, 3000: 4096, 100000: 1 << 17}[size]
     t.tree[t.cap2:t.cap2 + size] = g.uniform(0.0, 2.0, size).astype(np.float32)
-    t.tree[t.cap2 + 100:t.cap2 + 5000] = 0.0          # a dead stretch the descent must never enter
+    t.tree[t.cap2 + max(3, size // 1000):t.cap2 + max(10, size // 20)] = 0.0          # a dead stretch the descent must never enter (leaves 3 .. 9 of 24)
     t.rebuild()
     tree = D(hip, t.tree)
     r_act = D(hip, g.integers(0, 18, size).astype(np.int32)); r_rew = D(hip, g.standard_normal(size).astype(np.float32)); r_done = D(hip, (g.random(size) < 0.1).astype(np.float32))
-    seed, stream, off, top, beta = 0x1234_0000_002A, 5, 4096, 77777, 0.45
+    seed, stream, off, top, beta = 0x1234_0000_002A, 5, 4096, size * 3 // 4, 0.45
     xi, idx0, p0 = hip.zeros(B), hip.zeros(B, dtype=torch.int64), hip.zeros(B)
     hip.rng_uniform(seed, stream, off, xi, B)
     hip.sumtree_sample(tree, t.cap2, xi, B, idx0, p0)
@@ -582,6 +591,51 @@ def test_priority_update_of_a_batch_larger_than_one_workgroup(hip):
         hip.sumtree_set(rp.tree, rp.cap2, D(hip, ids.astype(np.int64)), D(hip, val), B)
     b = rp.sample()                          # B > 1024 takes the unfused sampling path
     assert int(b.idx.min()) >= 0 and int(b.idx.max()) < size and torch.isfinite(b.weights).all()
+
+
+@pytest.mark.parametrize("B,at", [(64, 7), (192, 2), (320, 4), (448, 2), (512, 100)])
+def test_priority_update_keeps_the_max_loss_at_any_batch_size(hip, B, at):
+    """a0_priority_update on the flat priority vector (replay.sumtree=false) at batch sizes that are no power of two: max_p = max(max_p, max loss) whichever
+    entry holds the largest loss.  The workgroup's max reduction halves its width, so it reaches every lane only from a power-of-two width; a launch of
+    192, 320 or 448 lanes dropped lanes 2, 5, 8, ... / 4, 9, 14, ... / 2, 5, 6, 9, ... — ``at`` is one of them."""
+    g = recipe.gen(B)
+    prio, pstate = hip.zeros(1000), hip.zeros(1)
+    hip.fill_f32(prio, 1000, 1.0); hip.fill_f32(pstate, 1, 1.0)
+    ids = g.permutation(1000)[:B]             # distinct
+    loss = g.uniform(0, 3, B).astype(np.float32)
+    loss[at] = np.float32(7.5)
+    hip.priority_update(prio, D(hip, ids.astype(np.int64)), D(hip, loss), B, 0.01, 0.5, pstate, None)
+    assert float(pstate[0]) == max(np.float32(1.0), loss.max()) == 7.5
+    want = np.ones(1000, np.float32)
+    want[ids] = np.sqrt(loss + np.float32(0.01))          # fp32 add, IEEE sqrt — what a0_prio_pow computes for alpha = 0.5
+    assert np.array_equal(prio.cpu().numpy(), want)
+
+
+def test_sample_slots_multi_equals_the_single_batch_calls(hip):
+    """a0_replay_sample_slots_multi (what a0_rbuf_sample_block launches for an update block): row g of its [n][B] outputs, bit for bit, is
+    a0_replay_sample_slots on (start[g], n_perm[g], seed[g]), its indices a0_perm_batch % top, its priorities 1.  Two consecutive batches of one epoch and
+    one of another; head != 0, so that slot != index."""
+    from agent0_amd._abi import check
+    n, B, cap, head = 3, 64, 300, 120
+    top = cap
+    g = recipe.gen(17)
+    r_act, r_rew, r_done = D(hip, g.integers(0, 18, cap).astype(np.int32)), D(hip, g.standard_normal(cap).astype(np.float32)), D(hip, (g.random(cap) < 0.2).astype(np.float32))
+    start, n_perm, seed = np.array([64, 128, 600], np.uint64), np.array([300, 300, 700], np.uint64), np.array([0x9E3779B1, 0x9E3779B1, 12345], np.uint32)
+    idx, slot, act = hip.zeros(n * B, dtype=torch.int64), hip.zeros(n * B, dtype=torch.int32), hip.zeros(n * B, dtype=torch.int32)
+    rew, done, prio = hip.zeros(n * B), hip.zeros(n * B), hip.zeros(n * B)
+    check(hip.lib.a0_replay_sample_slots_multi(n, start.ctypes.data, n_perm.ctypes.data, seed.ctypes.data, top, head, cap, r_act.data_ptr(), r_rew.data_ptr(), r_done.data_ptr(), B,
+                                               idx.data_ptr(), slot.data_ptr(), act.data_ptr(), rew.data_ptr(), done.data_ptr(), prio.data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream), "a0_replay_sample_slots_multi")
+    assert torch.equal(prio, torch.ones_like(prio))
+    for k in range(n):
+        i1, s1, a1, r1, d1, p1 = hip.zeros(B, dtype=torch.int64), hip.zeros(B, dtype=torch.int32), hip.zeros(B, dtype=torch.int32), hip.zeros(B), hip.zeros(B), hip.zeros(B)
+        hip.replay_sample_slots(int(start[k]), int(n_perm[k]), int(seed[k]), top, head, cap, r_act, r_rew, r_done, None, B, i1, s1, a1, r1, d1, p1)
+        row = slice(k * B, (k + 1) * B)
+        for got, want in ((idx, i1), (slot, s1), (act, a1), (rew, r1), (done, d1)):
+            assert torch.equal(got[row], want), f"batch {k}"
+        perm = hip.zeros(B, dtype=torch.int64)
+        hip.perm_batch(int(start[k]), B, int(n_perm[k]), int(seed[k]), perm)
+        assert torch.equal(idx[row], perm % top) and not torch.equal(idx[row], slot[row].long())
 
 
 @pytest.mark.parametrize("size,prioritize", [(64, False), (40, True)])
