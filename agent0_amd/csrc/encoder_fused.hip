@@ -493,7 +493,21 @@ struct EpiFwdT {            // y = relu(acc + bias[n]) -> fp32 global [m][N] (co
 // each is below 2^-24 of a*b (|a1| <= 2^-8 |a|, |b2| <= 2^-16 |b|), i.e. below the rounding the fp32 chain itself applies to every partial
 // SUM, which for a K-term dot product is ~sqrt(K) times larger.  A third fewer conv2 / conv3 MFMAs shorten the forward kernel by 7-9 % and
 // the data-gradient kernel by 9 % (profiles/r02_encoder_experiments.md).  Both forms are instantiated; the launchers pick one.
-template <int ORD, int N, int WN, int MBT, int R, int LR, class AFX, class EPI, class Between>
+// LIVE: which (row block, k step) pairs the stage issues at all.  a0_live_all (the forward stages): every one, and the k loop is the rolled
+// loop over the ring's depth.  A policy with `all = false` (AFD3X, AFD2X below) names the stage's `steps` k steps and answers live(i, st):
+// does any real row (m < M) of row block i read, under the tap of step st, a pixel that is not structural zero padding?  Where no step
+// of a wave-shared group st = WK * j .. WK * j + WK - 1 is live, the stage issues neither the block's A-fragment reads nor its MFMAs for own
+// step j: products with an exactly zero operand, which leave the fp32 accumulator (never -0: it starts at +0) as it was, so every
+// element keeps its sequence of surviving steps, its product order and its bits.  (What changes: zero padding times a non-finite weight
+// no longer makes a NaN — such a network is already past the loss's NaN skip.)  The answer depends on constants only — the k loop of
+// such a stage is unrolled in full, so every test folds at compile time: no branch, no lane mask, exact wait counts.  The weight ring's
+// fill(u) advances every step all the same: the weights are shared by the live blocks.
+struct a0_live_all {
+    static constexpr bool all = true;
+    static constexpr int steps = 2;          // unused
+    static constexpr bool live(int, int) { return true; }
+};
+template <int ORD, int N, int WN, int MBT, int R, int LR, class LIVE = a0_live_all, class AFX, class EPI, class Between>
 A0_D void a0_conv_stage_x9k(const AFX& af, int M, a0_wring9<N, WN, R, A0_FUSED_WAVES / WN>& ring, const EPI& epi, float* xch0, float* xch1, Between&& between) {
     constexpr int WK = A0_FUSED_WAVES / WN, HB0 = (MBT + 1) / 2, HB1 = MBT / 2;       // row blocks of the two halves of a k step: [0, HB0) and [HB0, MBT)
     static_assert(WK == 2 && N == 16 * WN && HB1 >= 1 && EPI::TR && LR >= 1 && LR <= 16, "tile shape");
@@ -501,7 +515,10 @@ A0_D void a0_conv_stage_x9k(const AFX& af, int M, a0_wring9<N, WN, R, A0_FUSED_W
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave % WN, wk = wave / WN;
     const int q = lane >> 4, r16 = lane & 15;
-    const int MB = (M + 15) >> 4, NSTW = ring.nst;       // NSTW is a multiple of R for every supported shape
+    const int MB = (M + 15) >> 4, NSTW = LIVE::all ? ring.nst : LIVE::steps / WK;       // NSTW is a multiple of R for every supported shape
+    static_assert(LIVE::all || (LIVE::steps % (WK * R)) == 0, "own k steps: a multiple of the ring depth");
+    // own step j = the steps WK * j + wk of the waves that share a column block; past the last step nothing is live
+    auto live = [](int blk, int j) { return j < LIVE::steps / WK && (LIVE::live(blk, WK * j) || LIVE::live(blk, WK * j + 1)); };
     int rows[MBT];
 #pragma unroll
     for (int i = 0; i < MBT; ++i) {
@@ -512,17 +529,22 @@ A0_D void a0_conv_stage_x9k(const AFX& af, int M, a0_wring9<N, WN, R, A0_FUSED_W
 #pragma unroll
     for (int i = 0; i < MBT; ++i) acc[i] = a0_acc4{0.f, 0.f, 0.f, 0.f};
     uint4 a[2][HB0][3];
-    auto fetch = [&](int slot, int h, int off) {
+    auto fetch = [&](int slot, int h, int off, int j) {       // j: the own step the fragments are for
 #pragma unroll
         for (int i = 0; i < HB0; ++i)
             if (h * HB0 + i < MBT) {
+                if constexpr (!LIVE::all) { if (!live(h * HB0 + i, j)) continue; }
 #pragma unroll
                 for (int t = 0; t < 3; ++t) a[slot][i][t] = *(const uint4*)(af.planes + rows[h * HB0 + i] + off + t * AFX::term);
             }
     };
-    fetch(0, 0, af.step_off(wk));
+    fetch(0, 0, af.step_off(wk), 0);
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): see a0_conv_stage
-#pragma unroll 1
+    // a policy's k loop is unrolled in full (its step count is a constant), so every liveness test folds at compile time.  Unrolled, every
+    // step's weight address would be an invariant of the caller's observation loop and be hoisted out of it, two registers per step the kernel
+    // does not have: the ring's pointer is made opaque here, and the addresses are formed step by step as in the rolled loop.
+    if constexpr (!LIVE::all) asm volatile("" : "+v"(ring.p));
+#pragma unroll LIVE::all ? 1 : LIVE::steps / (WK * R)
     for (int tb = 0; tb < NSTW; tb += R) {
 #pragma unroll
         for (int u = 0; u < R; ++u) {
@@ -530,8 +552,8 @@ A0_D void a0_conv_stage_x9k(const AFX& af, int M, a0_wring9<N, WN, R, A0_FUSED_W
             const int off = af.step_off(st), offn = af.step_off(tb + u + 1 < NSTW ? st + WK : st);      // past the end: re-read the last step (never consumed)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                if (h == 0) fetch(1, 1, off);
-                else fetch(0, 0, offn);
+                if (h == 0) fetch(1, 1, off, tb + u);
+                else fetch(0, 0, offn, tb + u + 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int ta = 0; ta < 3; ++ta)
@@ -540,6 +562,7 @@ A0_D void a0_conv_stage_x9k(const AFX& af, int M, a0_wring9<N, WN, R, A0_FUSED_W
 #pragma unroll
                         for (int i = 0; i < HB0; ++i) {
                             if (ta + tw > ORD || h * HB0 + i >= MBT) continue;      // ORD: see above
+                            if constexpr (!LIVE::all) { if (!live(h * HB0 + i, tb + u)) continue; }
                             const a0_u32x4 av = {a[h][i][ta].x, a[h][i][ta].y, a[h][i][ta].z, a[h][i][ta].w};
                             const a0_u32x4 bv = {ring.v[u][0][tw].x, ring.v[u][0][tw].y, ring.v[u][0][tw].z, ring.v[u][0][tw].w};
                             acc[h * HB0 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(a0_bf16x8, bv), __builtin_bit_cast(a0_bf16x8, av), acc[h * HB0 + i], 0, 0, 0);
@@ -1165,18 +1188,58 @@ struct a0_dgrad_args {
 // 9-wide output: +192 bytes -> 4.7 LDS cycles per fragment read instead of 8.0; 2x2 taps, 10-wide output: +96 bytes -> 4.6 instead of 7.4)
 constexpr int A0_RPDA = 11 * A0_P2X + 96, A0_RPDB = 11 * A0_P2X + 48;
 constexpr int A0_DTERMA = 11 * A0_RPDA, A0_DTERMB = 11 * A0_RPDB;      // elements per term plane
+// Does any output position m of row block i (16 i .. 16 i + 15, m < M; OW positions per output row) read, under the tap (dy, dx), a pixel
+// of the padded image inside rows and columns lo .. hi — the part a launch writes?  The border outside it is cleared once per launch and
+// stays zero: a (block, tap) pair that reads nothing else contributes nothing (the LIVE policy of a0_conv_stage_x9k).
+constexpr bool a0_block_reads_interior(int i, int M, int OW, int dy, int dx, int lo, int hi) {
+    for (int m = 16 * i; m < 16 * i + 16 && m < M; ++m) {
+        const int y = m / OW + dy, x = m % OW + dx;
+        if (y >= lo && y <= hi && x >= lo && x <= hi) return true;
+    }
+    return false;
+}
+// ... for every block and tap (ty * TW + tx), evaluated by the compiler: bit `tap` of v[i].  The stages index it with unrolled loop counters.
+template <int MBT, int M, int OW, int TW, int NT, int LO, int HI>
+struct a0_tap_table {
+    uint32_t v[MBT];
+    constexpr a0_tap_table() : v{} {
+        for (int i = 0; i < MBT; ++i)
+            for (int t = 0; t < NT; ++t) v[i] |= a0_block_reads_interior(i, M, OW, t / TW, t % TW, LO, HI) ? 1u << t : 0u;
+    }
+};
+// Of the 81 x 9 (position, tap) pairs of conv3's data gradient 441 touch a d3 pixel, of the 54 (block, tap) pairs 40: dead are block 0
+// (output rows 0 - 1) under the dy = 0 taps, block 4 (rows 7 - 8) under dy = 2, block 5 (the lone position (8, 8)) under every tap but
+// (0, 0).  Of conv2's 28 (block, cell) pairs per stage 26: block 6 (row 9, columns 6 - 9) reads only row 10 under the cy = 1 cells.
+// 16 % of the kernel's MFMAs and fragment reads, -5.3 us of 48.3 per 512 observations (profiles/r30_dgrad_padding.md).
 struct AFD3X {   // 3x3 taps over the d3pad planes; MFMA step = half (32 channels) of tap st >> 1; output 9 wide
     static constexpr int term = A0_DTERMA;
     const uint16_t* planes;
     A0_D int row(int m) const { const int oh = m / 9, ow = m - oh * 9; return oh * A0_RPDA + ow * A0_P2X; }
     A0_D int step_off(int st) const { const int tap = st >> 1; return (tap / 3) * A0_RPDA + (tap % 3) * A0_P2X + 32 * (st & 1); }
+    // LIVE policy: d3 occupies rows / columns 2 .. 8 of the 11 x 11 image
+    static constexpr bool all = false;
+    static constexpr int steps = 18;
+    static constexpr a0_tap_table<6, 81, 9, 3, 9, 2, 8> taps{};
+    static constexpr bool live(int i, int st) { return (taps.v[i] >> (st >> 1)) & 1u; }
 };
 struct AFD2X {   // 2x2 taps over the d2pad planes; output 10 wide
     static constexpr int term = A0_DTERMB;
     const uint16_t* planes;
     A0_D int row(int m) const { const int oh = m / 10, ow = m - oh * 10; return oh * A0_RPDB + ow * A0_P2X; }
     A0_D int step_off(int st) const { const int cell = st >> 1; return (cell >> 1) * A0_RPDB + (cell & 1) * A0_P2X + 32 * (st & 1); }
+    // LIVE policy: d2 occupies rows / columns 1 .. 9
+    static constexpr bool all = false;
+    static constexpr int steps = 8;
+    static constexpr a0_tap_table<7, 100, 10, 2, 4, 1, 9> taps{};
+    static constexpr bool live(int i, int st) { return (taps.v[i] >> (st >> 1)) & 1u; }
 };
+constexpr int a0_live_pairs(bool three) {      // (block, tap / cell) pairs that are live: counted from the predicates, asserted against the figures above
+    int n = 0;
+    for (int i = 0; i < (three ? 6 : 7); ++i)
+        for (int t = 0; t < (three ? 9 : 4); ++t) n += three ? AFD3X::live(i, 2 * t) : AFD2X::live(i, 2 * t);
+    return n;
+}
+static_assert(a0_live_pairs(true) == 40 && a0_live_pairs(false) == 26, "dead (block, tap) pairs of the data-gradient stages");
 struct EpiBwd3X {               // d2 = act2 > 0 ? acc : 0 -> global [81][64] and, split into three bf16 terms, the interior of the d2pad planes; transposed accumulators
     static constexpr bool PER_ELEM = true;
     static constexpr bool ROW4 = false;
@@ -1215,7 +1278,6 @@ __global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_dgrad_fused_x9_ke
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* plA = (uint16_t*)smem;                  // d3, padded by 2: three term planes
     uint16_t* plB = plA + 3 * A0_DTERMA;              // d2, padded by 1 (last row / column unused)
-    for (int i = threadIdx.x; i < 3 * (A0_DTERMA + A0_DTERMB) / 2; i += A0_FUSED_THREADS) ((uint32_t*)smem)[i] = 0u;     // both images; borders stay zero for the whole launch
     // N-stationary stages (a0_conv_stage_x9k): conv3's data gradient as in the forward kernel; conv2's four stride phases share their A operand
     // (the d2pad taps), so two phases at a time form ONE stage of 64 virtual columns — column block wn = phase (wn >> 1) of the pair, channel
     // block wn & 1 — and every weight fragment of the kernel is loaded once per workgroup, every d2pad fragment
@@ -1229,27 +1291,54 @@ __global__ __launch_bounds__(A0_FUSED_THREADS) void a0_encoder_dgrad_fused_x9_ke
     ring3.prologue();
     // phase matrices: 4 x [256 k][32 n] in the N = 32 ring layout (3072 uint4 each, 384 per k step)
     const uint4* const wq = (const uint4*)P.wd2 + (((wn & 1) * 16 + (lane & 15)) * 4 + (lane >> 4)) * 3 + (wn >> 1) * 3072 + wk * 384;
+    // An observation's d3 is 784 sixteen-byte pieces, two per lane (the second for the first 272 lanes): requested into registers, then
+    // split into the interior of the d3pad planes — in full, so nothing of the previous observation survives; the border is never written.
+    static_assert(49 * 16 > A0_FUSED_THREADS && 49 * 16 <= 2 * A0_FUSED_THREADS, "two pieces of d3 per lane");
+    a0_f4 nx[2] = {a0_f4{0.f, 0.f, 0.f, 0.f}, a0_f4{0.f, 0.f, 0.f, 0.f}};
+    auto d3_request = [&](int b) {
+        const a0_f4* src = (const a0_f4*)(P.d3 + (long long)b * 49 * 64);
+        nx[0] = src[threadIdx.x];
+        if (threadIdx.x + A0_FUSED_THREADS < 49 * 16) nx[1] = src[threadIdx.x + A0_FUSED_THREADS];
+    };
+    auto d3_put = [&]() {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int i = threadIdx.x + k * A0_FUSED_THREADS;
+            if (i < 49 * 16) {
+                const int pos = i >> 4, c4 = (i & 15) * 4, h = pos / 7, w = pos - h * 7;
+                const float x[4] = {nx[k].x, nx[k].y, nx[k].z, nx[k].w};
+                uint2 hi, mid, lo;
+                a0_split4(x, hi, mid, lo);
+                uint16_t* d = plA + (h + 2) * A0_RPDA + (w + 2) * A0_P2X + c4;
+                *(uint2*)(d) = hi; *(uint2*)(d + A0_DTERMA) = mid; *(uint2*)(d + 2 * A0_DTERMA) = lo;
+            }
+        }
+    };
+    if ((int)blockIdx.x < P.B) d3_request(blockIdx.x);       // in flight while the images are cleared
+    for (int i = threadIdx.x; i < 3 * (A0_DTERMA + A0_DTERMB) / 2; i += A0_FUSED_THREADS) ((uint32_t*)smem)[i] = 0u;     // both images; borders stay zero for the whole launch
+    __syncthreads();
+    d3_put();
     __syncthreads();
     for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
-        const a0_f4* src = (const a0_f4*)(P.d3 + (long long)b * 49 * 64);
-        for (int i = threadIdx.x; i < 49 * 16; i += A0_FUSED_THREADS) {
-            const a0_f4 v = src[i];
-            const int pos = i >> 4, c4 = (i & 15) * 4, h = pos / 7, w = pos - h * 7;
-            const float x[4] = {v.x, v.y, v.z, v.w};
-            uint2 hi, mid, lo;
-            a0_split4(x, hi, mid, lo);
-            uint16_t* d = plA + (h + 2) * A0_RPDA + (w + 2) * A0_P2X + c4;
-            *(uint2*)(d) = hi; *(uint2*)(d + A0_DTERMA) = mid; *(uint2*)(d + 2 * A0_DTERMA) = lo;
-        }
-        __syncthreads();
+        // The workgroup's next observation, if it has one: its d3 is requested behind conv2's first k loop and written into plA — dead since
+        // the barriers that end conv3's stage — behind the second; the barriers that end that stage order the writes before the next
+        // conv3 reads them.  Only a workgroup's first observation waits for its d3.
+        const int bn = b + gridDim.x;
+        const bool more = bn < P.B;
         const AFD3X f3{plA};
         const AFD2X f2{plB};
         const EpiBwd3X e3{P.act2 + (long long)b * 81 * 64, P.d2 + (long long)b * 81 * 64, plB};
         const EpiBwdPair e2a{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, 0};
         const EpiBwdPair e2b{P.act1 + (long long)b * 400 * 32, P.d1 + (long long)b * 400 * 32, 2};
-        a0_conv_stage_x9k<ORD, 64, 4, 6, 3, 1>(f3, 81, ring3, e3, xch0, xch1, [&] { ringq[0].init_at(wq, 4, 768); ringq[0].prologue(); });
-        a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4>(f2, 100, ringq[0], e2a, xch0, xch1, [&] { ringq[1].init_at(wq + 2 * 3072, 4, 768); ringq[1].prologue(); });
-        a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4>(f2, 100, ringq[1], e2b, xch0, xch1, [&] { ring3.prologue(); });
+        a0_conv_stage_x9k<ORD, 64, 4, 6, 3, 1, AFD3X>(f3, 81, ring3, e3, xch0, xch1, [&] { ringq[0].init_at(wq, 4, 768); ringq[0].prologue(); });
+        a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4, AFD2X>(f2, 100, ringq[0], e2a, xch0, xch1, [&] {
+            ringq[1].init_at(wq + 2 * 3072, 4, 768); ringq[1].prologue();
+            if (more) d3_request(bn);
+        });
+        a0_conv_stage_x9k<ORD, 64, 4, 7, 2, 4, AFD2X>(f2, 100, ringq[1], e2b, xch0, xch1, [&] {
+            ring3.prologue();
+            if (more) d3_put();
+        });
     }
 }
 
@@ -1469,8 +1558,9 @@ extern "C" int a0_net_encoder_dgrad_fused(int C, int H, int W, const float* wt, 
         A0_HIP_THROW(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         configured[six] = true;
     }
-    // at most one workgroup per CU, each looping over its observations (b += gridDim.x): the next observation's masks and the first
-    // stage's weights are prefetched in the last stage's `between` slot instead of at workgroup start (-5 us per 512 observations)
+    // at most one workgroup per CU, each looping over its observations (b += gridDim.x): the first stage's weights are prefetched in the
+    // last stage's `between` slot instead of at workgroup start (-5 us per 512 observations), and the next observation's d3 is requested
+    // behind conv2's first k loop and split into its LDS planes behind the second, so only a workgroup's first observation waits for it
     const int gridx = B > 256 ? 256 : B;
     A0_LAUNCH_PROBED(A0_TAG_ENCODER_DGRAD_FUSED, 2.0 * (81.0 * 64 * 576 + 400.0 * 32 * 256) * B, fn, dim3(gridx), dim3(A0_FUSED_THREADS), lds, (hipStream_t)stream, P);
     A0_HIP_THROW(hipGetLastError());
