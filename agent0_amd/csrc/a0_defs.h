@@ -18,6 +18,30 @@ struct __attribute__((aligned(16))) a0_i4 { int x, y, z, w; };
 
 A0_HD a0_f4 a0_zero4() { a0_f4 v; v.x = 0.f; v.y = 0.f; v.z = 0.f; v.w = 0.f; return v; }
 
+#if defined(__HIPCC__)
+// the product alone, rounded to fp32: never contracted into the subtraction or the multiply-add that consumes it, so that stepping on g * coef gives the bits of
+// a0_adam_step_sync on a gradient buffer multiplied by coef beforehand
+A0_D float a0_mul_rounded(float a, float b) {
+    float r;
+    {
+#pragma clang fp contract(off)
+        r = a * b;
+    }
+    asm volatile("" : "+v"(r));      // the Adam arithmetic behind it sees a plain register value, as it sees a loaded gradient
+    return r;
+}
+// One rounded subtraction and one fused multiply-add per element, kept out of the compiler's contraction choices (see a0_mul_rounded).
+A0_D float a0_blend1(float t, float p, float tau) {
+    float d;
+    {
+#pragma clang fp contract(off)
+        d = p - t;
+    }
+    asm volatile("" : "+v"(d));
+    return __builtin_fmaf(tau, d, t);
+}
+#endif
+
 // status codes returned by every exported function (include/agent0_hip.h)
 enum {
     A0_OK = 0,

@@ -33,12 +33,18 @@ struct a0_hip_error : std::runtime_error {
     catch (const std::exception& e) { return a0_fail(A0_EINVAL, e.what()); } \
     catch (...) { return a0_fail(A0_EINVAL, "unknown C++ exception"); }
 
+// at most 2048 workgroups of 256 lanes, grid-stride behind that
+static inline unsigned a0_grid_256(long long items) { const long long b = (items + 255) / 256; return (unsigned)(b > 2048 ? 2048 : b < 1 ? 1 : b); }
+// every one of these pointers is a multiple of `bytes` (a power of two); a null pointer counts as aligned
+template <class... P>
+static inline bool a0_aligned(unsigned bytes, const P*... p) { return ((((uintptr_t)p) | ... | (uintptr_t)0) & (bytes - 1)) == 0; }
+
 // Philox stream ids (agent0_amd/common/utils.py DeviceRng: 1 / 2 epsilon-greedy, 3 quantile fractions, 4 NoisyNet, 5 sum-tree, 6 permutation seeds); 7 = the
 // random shifts of learner.aug_shift (augment.hip), positioned by the update count alone: no running offset, nothing to snapshot
 #define A0_STREAM_AUG 7
-// 8 = the fresh values of learner.net_reset_freq (optim.hip: a0_net_reset), positioned by (reset number, flat index): no running offset either
+// 8 = the fresh values of learner.net_reset_freq (net_reset.hip: a0_net_reset), positioned by (reset number, flat index): no running offset either
 #define A0_STREAM_RESET 8
-// 9 = the fresh values of learner.redo_freq (optim.hip: a0_redo_recycle), positioned by (recycle number, flat index): no running offset
+// 9 = the fresh values of learner.redo_freq (net_reset.hip: a0_redo_recycle), positioned by (recycle number, flat index): no running offset
 #define A0_STREAM_REDO 9
 // augment.hip: the range checks of a0_augment_shift (A0_EINVAL with a message that starts with `who`)
 int a0_augment_shift_check(const char* who, int C, int H, int W, int pad, long long row_bytes);

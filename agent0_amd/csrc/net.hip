@@ -118,13 +118,6 @@ __global__ __launch_bounds__(256) void a0_reduce_segments_kernel(a0_reduce_multi
     }
 }
 
-static inline int a0_grid_for(long long count, int block = 256, int cap = 2048) {
-    long long g = (count + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // ------------------------------------------------------------------------------------------------ profiler probe
 // bench.py brackets every launch of ONE tagged GEMM with HIP events on the stream the kernel runs on, so that its
 // average duration (and hence achieved FLOP/s against the fp32 MFMA roofline) is measured live inside the timed region.
@@ -311,7 +304,7 @@ struct a0_hip_backend {
             A.vec[k] = 0;
             if (k < nseg) {
                 A.seg[k] = segs[k];
-                A.vec[k] = ((segs[k].count | segs[k].slab_stride) % 4 == 0) && ((((uintptr_t)segs[k].slabs) | ((uintptr_t)segs[k].out)) % 16 == 0);
+                A.vec[k] = ((segs[k].count | segs[k].slab_stride) % 4 == 0) && a0_aligned(16, segs[k].slabs, segs[k].out);
                 blocks += A.vec[k] ? (int)((segs[k].count / 4 + 31) / 32) : (int)((segs[k].count + 31) / 32);
             } else {
                 A.seg[k] = a0_reduce_seg{nullptr, 0, 0, nullptr, 0};
@@ -323,7 +316,7 @@ struct a0_hip_backend {
         A0_HIP_THROW(hipGetLastError());
     }
     void reduce_bias_act(const float* slabs, long long slab_stride, int nslab, const float* bias, float* out, int rows, int N, int relu) {
-        hipLaunchKernelGGL(a0_reduce_bias_act_kernel, dim3(a0_grid_for((long long)rows * N)), dim3(256), 0, st, slabs, slab_stride, nslab, bias, out, rows, N, relu);
+        hipLaunchKernelGGL(a0_reduce_bias_act_kernel, dim3(a0_grid_256((long long)rows * N)), dim3(256), 0, st, slabs, slab_stride, nslab, bias, out, rows, N, relu);
         A0_HIP_THROW(hipGetLastError());
     }
 };
@@ -517,13 +510,13 @@ extern "C" int a0_reduce_bias_act_multi(int n, const float* const* slabs, const 
     int maxrows = 0;
     for (int i = 0; i < n; ++i) {
         if (!slabs[i] || !bias[i] || !out[i] || rows[i] < 1 || nslab[i] < 1 || (slab_stride[i] & 3) || slab_stride[i] < (long long)rows[i] * N ||
-            ((((uintptr_t)slabs[i]) | ((uintptr_t)bias[i]) | ((uintptr_t)out[i])) & 15))
+            !a0_aligned(16, slabs[i], bias[i], out[i]))
             return a0_fail(A0_EINVAL, "a0_reduce_bias_act_multi: bad layer (16-byte aligned buffers, slab stride a multiple of 4 floats)");
         A.seg[i] = a0_rba_seg{slabs[i], slab_stride[i], nslab[i], bias[i], out[i], rows[i]};
         if (rows[i] > maxrows) maxrows = rows[i];
     }
     for (int i = n; i < 4; ++i) A.seg[i] = A.seg[0];
-    hipLaunchKernelGGL(a0_reduce_bias_act_multi_kernel, dim3(a0_grid_for((long long)maxrows * (N >> 2)), n), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(a0_reduce_bias_act_multi_kernel, dim3(a0_grid_256((long long)maxrows * (N >> 2)), n), dim3(256), 0, (hipStream_t)stream, A);
     return a0_fail_hip((int)hipGetLastError(), "a0_reduce_bias_act_multi");
 }
 

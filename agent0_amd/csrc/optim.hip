@@ -3,11 +3,12 @@
 // fraction net), :152-158 (skip the step when any per-sample loss is NaN) and :160-161 (target <- online every
 // target_update_freq successful updates) without the two host syncs per update the reference pays (quirk Q14):
 // the NaN flag, the step counter and the "sync now" decision all live in a small device-side state block.
+// Resets and ReDo recycling of the same buffer: net_reset.hip.  NoisyNet: noisy.hip.
 #include "a0_internal.h"
-#include "rng_elem.h"
 #include "update_tail.h"
 
 #include <algorithm>
+#include <type_traits>
 
 // state block (ints): see a0_learner_state in include/agent0_hip.h
 //   [0] nan_flag      set by the loss kernels (atomicOr) when a per-sample loss is NaN
@@ -57,11 +58,17 @@ A0_D void a0_adam_scalar(float& p, float& m, float& v, float gi, const a0_adam_h
     m = mi; v = vi;
 }
 
-// at most 2048 workgroups of 256 lanes, grid-stride behind that
-static unsigned a0_grid_256(long long items) { const long long b = (items + 255) / 256; return (unsigned)(b > 2048 ? 2048 : b < 1 ? 1 : b); }
 // the 16-byte path of the Adam forms: n, n_total multiples of four and every buffer 16-byte aligned
 static int a0_adam_vec4(const float* params, const float* grads, const float* exp_avg, const float* exp_avg_sq, const float* target, long long n, long long n_total) {
-    return ((n | n_total) % 4 == 0) && ((((uintptr_t)params) | ((uintptr_t)grads) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)target)) % 16 == 0);
+    return ((n | n_total) % 4 == 0) && a0_aligned(16, params, grads, exp_avg, exp_avg_sq, target);
+}
+
+// The sum of 256 lanes' values through LDS: store, then the tree o = 128 ... 1 with a barrier per step; the result is red[0], in the one order every sum here has
+template <class T>
+A0_D void a0_block_sum256(T* red, T v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
 }
 
 __global__ void a0_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -94,7 +101,11 @@ struct a0_adam_fold { double lr, b1, b2; int target_freq; const float* extra_fla
 // partials[b] with a plain store (0 when its range is empty): no atomics, no "last workgroup" counter, and the same bits on every run.  Squares and sums are doubles:
 // the square of a float is exact in double, so the only rounding of the norm that matters is stage 2's final cast.  vec4: g is 16-byte aligned (16-byte loads, a
 // scalar tail); otherwise element by element.
-__global__ __launch_bounds__(256) void a0_grad_sumsq_kernel(const float* __restrict__ g, long long n, long long chunk, int vec4, double* __restrict__ partials) {
+// The walk itself, for every kernel of this shape.  T: float or const float; `each(at, x)` sees every value x the walk has read at `at` (an a0_f4 on the 16-byte
+// path) once its squares are added, and stores there what it likes.
+template <class T, class F>
+A0_D void a0_chunk_sumsq(T* __restrict__ x, long long n, long long chunk, int vec4, double* __restrict__ partials, F each) {
+    using T4 = std::conditional_t<std::is_const_v<T>, const a0_f4, a0_f4>;
     __shared__ double red[256];
     const long long lo = (long long)blockIdx.x * chunk;
     const long long hi = lo + chunk < n ? lo + chunk : n;
@@ -103,38 +114,38 @@ __global__ __launch_bounds__(256) void a0_grad_sumsq_kernel(const float* __restr
         long long done = 0;
         if (vec4) {
             const long long n4 = (hi - lo) >> 2;
-            const a0_f4* g4 = (const a0_f4*)(g + lo);
+            T4* x4 = (T4*)(x + lo);
             for (long long j = threadIdx.x; j < n4; j += 256) {
-                const a0_f4 x = g4[j];
-                s += (double)x.x * (double)x.x; s += (double)x.y * (double)x.y; s += (double)x.z * (double)x.z; s += (double)x.w * (double)x.w;
+                const a0_f4 v = x4[j];
+                s += (double)v.x * (double)v.x; s += (double)v.y * (double)v.y; s += (double)v.z * (double)v.z; s += (double)v.w * (double)v.w;
+                each(x4 + j, v);
             }
             done = n4 << 2;
         }
-        for (long long i = lo + done + threadIdx.x; i < hi; i += 256) s += (double)g[i] * (double)g[i];
+        for (long long i = lo + done + threadIdx.x; i < hi; i += 256) {
+            const float v = x[i];
+            s += (double)v * (double)v;
+            each(x + i, v);
+        }
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    a0_block_sum256(red, s);
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+// ... and its launch: A0_GRAD_NORM_PARTIALS workgroups of 256, chunk from n alone, the 16-byte path for a 16-byte aligned buffer; `rest`: the kernel's own arguments
+template <class K, class T, class... A>
+static void a0_chunk_sumsq_launch(K kernel, T* x, long long n, void* stream, A... rest) {
+    const long long chunk = ((n + A0_GRAD_NORM_PARTIALS - 1) / A0_GRAD_NORM_PARTIALS + 3) / 4 * 4;
+    hipLaunchKernelGGL(kernel, dim3(A0_GRAD_NORM_PARTIALS), dim3(256), 0, (hipStream_t)stream, x, n, chunk, a0_aligned(16, x) ? 1 : 0, rest...);
+}
+
+__global__ __launch_bounds__(256) void a0_grad_sumsq_kernel(const float* __restrict__ g, long long n, long long chunk, int vec4, double* __restrict__ partials) {
+    a0_chunk_sumsq(g, n, chunk, vec4, partials, [](const void*, const auto&) {});      // the sums alone: nothing to store
 }
 
 extern "C" int a0_grad_norm_partials(const float* grads, long long n, double* partials, void* stream) {
-    if (!grads || !partials || n < 1 || (((uintptr_t)grads) & 3) || (((uintptr_t)partials) & 7)) return a0_fail(A0_EINVAL, "a0_grad_norm_partials: bad argument");
-    const long long chunk = ((n + A0_GRAD_NORM_PARTIALS - 1) / A0_GRAD_NORM_PARTIALS + 3) / 4 * 4;
-    hipLaunchKernelGGL(a0_grad_sumsq_kernel, dim3(A0_GRAD_NORM_PARTIALS), dim3(256), 0, (hipStream_t)stream, grads, n, chunk, (((uintptr_t)grads) & 15) == 0 ? 1 : 0, partials);
+    if (!grads || !partials || n < 1 || !a0_aligned(4, grads) || !a0_aligned(8, partials)) return a0_fail(A0_EINVAL, "a0_grad_norm_partials: bad argument");
+    a0_chunk_sumsq_launch(a0_grad_sumsq_kernel, grads, n, stream, partials);
     return a0_fail_hip((int)hipGetLastError(), "a0_grad_norm_partials");
-}
-
-// the product alone, rounded to fp32: never contracted into the subtraction or the multiply-add that consumes it, so that stepping on g * coef gives the bits of
-// a0_adam_step_sync on a gradient buffer multiplied by coef beforehand
-A0_D float a0_mul_rounded(float a, float b) {
-    float r;
-    {
-#pragma clang fp contract(off)
-        r = a * b;
-    }
-    asm volatile("" : "+v"(r));      // the Adam arithmetic behind it sees a plain register value, as it sees a loaded gradient
-    return r;
 }
 
 // Decoupled weight decay (learner.weight_decay; torch.optim.AdamW's p <- p * (1 - lr * lambda) in front of its Adam step), ONE launch in front of the update's Adam
@@ -152,45 +163,25 @@ A0_D float a0_decay1(float p, float c) {
     }
     return r;
 }
+struct a0_decay_each {
+    float c; bool skip;
+    A0_D void operator()(float* at, float x) const { if (!skip) *at = a0_decay1(x, c); }
+    A0_D void operator()(a0_f4* at, a0_f4 x) const {
+        if (!skip) { x.x = a0_decay1(x.x, c); x.y = a0_decay1(x.y, c); x.z = a0_decay1(x.z, c); x.w = a0_decay1(x.w, c); *at = x; }
+    }
+};
 __global__ __launch_bounds__(256) void a0_weight_decay_kernel(float* __restrict__ p, long long n, long long chunk, int vec4, float c, const int* __restrict__ state,
                                                               const float* __restrict__ extra_flag, double* __restrict__ partials) {
-    __shared__ double red[256];
     const bool skip = (state[0] != 0) || (extra_flag && extra_flag[0] != 0.f);
-    const long long lo = (long long)blockIdx.x * chunk;
-    const long long hi = lo + chunk < n ? lo + chunk : n;
-    double s = 0.0;
-    if (lo < hi) {
-        long long done = 0;
-        if (vec4) {
-            const long long n4 = (hi - lo) >> 2;
-            a0_f4* p4 = (a0_f4*)(p + lo);
-            for (long long j = threadIdx.x; j < n4; j += 256) {
-                a0_f4 x = p4[j];
-                s += (double)x.x * (double)x.x; s += (double)x.y * (double)x.y; s += (double)x.z * (double)x.z; s += (double)x.w * (double)x.w;
-                if (!skip) { x.x = a0_decay1(x.x, c); x.y = a0_decay1(x.y, c); x.z = a0_decay1(x.z, c); x.w = a0_decay1(x.w, c); p4[j] = x; }
-            }
-            done = n4 << 2;
-        }
-        for (long long i = lo + done + threadIdx.x; i < hi; i += 256) {
-            const float x = p[i];
-            s += (double)x * (double)x;
-            if (!skip) p[i] = a0_decay1(x, c);
-        }
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+    a0_chunk_sumsq(p, n, chunk, vec4, partials, a0_decay_each{c, skip});
 }
 
 // c: lr * lambda as the caller formed it in double; rounded to fp32 once here.  2^-24 <= fl32(c) < 1: a smaller c moves no fp32 value, c >= 1 is no decay
 extern "C" int a0_weight_decay(float* params, long long n, double c, const int* state, const float* extra_nan_flag, double* partials, void* stream) {
-    if (!params || !state || !partials || n < 1 || (((uintptr_t)params) & 3) || (((uintptr_t)partials) & 7)) return a0_fail(A0_EINVAL, "a0_weight_decay: bad argument");
+    if (!params || !state || !partials || n < 1 || !a0_aligned(4, params) || !a0_aligned(8, partials)) return a0_fail(A0_EINVAL, "a0_weight_decay: bad argument");
     const float c32 = (float)c;
     if (!(c32 >= 0x1p-24f) || !(c32 < 1.f)) return a0_fail(A0_EINVAL, "a0_weight_decay: c = lr * lambda must lie in [2^-24, 1) as an fp32 number");
-    const long long chunk = ((n + A0_GRAD_NORM_PARTIALS - 1) / A0_GRAD_NORM_PARTIALS + 3) / 4 * 4;
-    hipLaunchKernelGGL(a0_weight_decay_kernel, dim3(A0_GRAD_NORM_PARTIALS), dim3(256), 0, (hipStream_t)stream, params, n, chunk, (((uintptr_t)params) & 15) == 0 ? 1 : 0, c32, state,
-                       extra_nan_flag, partials);
+    a0_chunk_sumsq_launch(a0_weight_decay_kernel, params, n, stream, c32, state, extra_nan_flag, partials);
     return a0_fail_hip((int)hipGetLastError(), "a0_weight_decay");
 }
 
@@ -201,9 +192,7 @@ A0_D void a0_loss_mean_to_ring(const float* loss, int loss_n, float* loss_ring, 
     __shared__ float red[256];
     float s = 0.f;
     for (int e = threadIdx.x; e < loss_n; e += 256) s += loss[e];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    a0_block_sum256(red, s);
     if (threadIdx.x == 0) { const int c = state_w[6]; loss_ring[c % ring_cap] = red[0] / (float)loss_n; state_w[6] = c + 1; }
 }
 
@@ -220,9 +209,7 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
         // state[6] % cap — the slot of this update's loss mean, read before workgroup 0 advances the counter below — on skipped (NaN) steps too.
         static_assert(A0_GRAD_NORM_PARTIALS == 256, "one partial per lane of the 256-lane workgroup");
         __shared__ double cred[256];
-        cred[threadIdx.x] = K.partials[threadIdx.x];
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) cred[threadIdx.x] += cred[threadIdx.x + o]; __syncthreads(); }
+        a0_block_sum256(cred, K.partials[threadIdx.x]);
         const float norm = (float)sqrt(cred[0]);
         if (blockIdx.x == 0 && threadIdx.x == 0) K.norm_ring[(FOLD ? F.state_w[6] : state[6]) % K.ring_cap] = norm;
         const float c = K.max_norm / (norm + 1e-6f);
@@ -272,7 +259,7 @@ __global__ void a0_adam_sync_kernel(float* __restrict__ p, const float* __restri
 }
 
 static bool a0_clip_args_ok(const double* partials, float max_norm, const float* norm_ring, int norm_ring_cap) {
-    return partials && (((uintptr_t)partials) & 7) == 0 && max_norm > 0.f && norm_ring && norm_ring_cap >= 1;
+    return partials && a0_aligned(8, partials) && max_norm > 0.f && norm_ring && norm_ring_cap >= 1;
 }
 
 // The one launcher of the four instantiations.  Plain (wt == nullptr): the one-thread prep kernel in front, == a0_adam_step + a0_target_sync.  Folded (the optimizer
@@ -343,26 +330,7 @@ extern "C" int a0_adam_step_sync_wt_clip(float* params, const float* grads, floa
 //     0..7 from zero, writes the gradient and steps its four parameters on it; scalar path: 32 parameters likewise;
 //   * between segments: a0_adam_sync_kernel's body, 1024 parameters per workgroup on the 16-byte path, 256 on the scalar path.
 // The step's decisions were derived one launch earlier (a0_tail_prep_run): state[3], state[4] and the scalars are only read here, so there is nothing to commit and
-// no workgroup waits for another.  The lane that holds a new convolution weight also files it in the fused kernels' copies (the inverse of a0_conv_wt_kernel's gather).
-
-// Where a new convolution weight goes in the fused kernels' copies `wt` (online) / `wt_t` (target): the one description the tail, the blend and the reset share.
-struct a0_wt_sink {
-    long long o1, o2, o3;                       // first weight of conv1 / conv2 / conv3 in the flat buffer
-    int K1, wt4;                                // wt4: o1, o2, o3 multiples of four (four consecutive k of one row per 16-byte lane)
-    float *wt, *wt_t;
-};
-// w: the convolution weights inside base[0, n_total) (`what`: the buffer's name in who's error text); wt may be NULL for a caller that files the target side only
-static int a0_wt_sink_make(a0_wt_sink* S, const char* who, const char* what, const float* base, long long n_total, const a0_encoder_weights* w, int C, float* wt, float* wt_target) {
-    const std::string name(who);
-    if (!w || !w->w1 || !w->w2 || !w->w3 || C < 1 || !wt_target) return a0_fail(A0_EINVAL, (name + ": weight copies need the encoder weights, C >= 1 and the copies' buffers").c_str());
-    if ((((uintptr_t)wt) | ((uintptr_t)wt_target)) & 15) return a0_fail(A0_EINVAL, (name + ": the weight copies must be 16-byte aligned").c_str());
-    *S = a0_wt_sink{w->w1 - base, w->w2 - base, w->w3 - base, C * 64, 0, wt, wt_target};
-    if (S->o1 < 0 || S->o1 + 32LL * S->K1 > n_total || S->o2 < 0 || S->o2 + 64 * 512 > n_total || S->o3 < 0 || S->o3 + 64 * 576 > n_total)
-        return a0_fail(A0_EINVAL, (name + ": the convolution weights must lie inside " + what + "[0, n_total)").c_str());
-    S->wt4 = ((S->o1 | S->o2 | S->o3) % 4 == 0) ? 1 : 0;
-    return A0_OK;
-}
-
+// no workgroup waits for another.  The lane that holds a new convolution weight also files it in the fused kernels' copies (a0_wt_sink and a0_tail_wt*: update_tail.h).
 struct a0_tail_region { long long lo, hi; int first_block, seg, vec, pad_; };      // [lo, hi) of the flat buffer; seg < 0: not a slab segment
 struct a0_tail_args {
     float *p, *g, *m, *v, *target;
@@ -376,82 +344,6 @@ struct a0_tail_args {
     const float* loss; int loss_n; float* loss_ring; int ring_cap; int* state_w;
     a0_wt_sink W;
 };
-
-A0_D void a0_tail_put16(const a0_wt_sink& A, bool to_online, bool to_target, long long u16, uint32_t bits) {
-    if (to_online) ((uint16_t*)A.wt)[u16] = (uint16_t)bits;
-    if (to_target) ((uint16_t*)A.wt_t)[u16] = (uint16_t)bits;
-}
-A0_D void a0_tail_put32(const a0_wt_sink& A, bool to_online, bool to_target, int dw, uint32_t bits) {
-    if (to_online) ((uint32_t*)A.wt)[dw] = bits;
-    if (to_target) ((uint32_t*)A.wt_t)[dw] = bits;
-}
-// dword of term s of weight (n, k) in an a0_wring1 / a0_wring9 segment of N columns: uint4 ((t*N + n)*4 + q)*3 + s holds k = 32t + 8q .. +7; a dword is two consecutive k
-A0_D int a0_tail_term_dword(int N, int n, int k, int s) { return ((((k >> 5) * N + n) * 4 + ((k >> 3) & 3)) * 3 + s) * 4 + ((k >> 1) & 3); }
-// the data-gradient copies of one weight: conv3's flipped taps, conv2's stride phases (see a0_conv_wt_kernel)
-A0_D void a0_tail_wt_dgrad(const a0_wt_sink& A, bool to_online, bool to_target, const a0_wt_layout& T, bool c3, int co, int k, float w) {
-    int base, N, n, kk;
-    if (c3) {              // k = (kh*3 + kw)*64 + ci  ->  n = ci, k' = ((2-kh)*3 + (2-kw))*64 + co
-        const int cell = k >> 6;
-        n = k & 63; kk = (8 - cell) * 64 + co; base = T.dgrad3x(); N = 64;
-    } else {               // k = (kh*4 + kw)*32 + ci  ->  phase (kh & 1, kw & 1), n = ci, k' = ((1 - kh/2)*2 + (1 - kw/2))*64 + co
-        const int tap = k >> 5, kh = tap >> 2, kw = tap & 3;
-        n = k & 31; kk = ((1 - (kh >> 1)) * 2 + (1 - (kw >> 1))) * 64 + co; base = T.dgrad2x() + ((kh & 1) * 2 + (kw & 1)) * T.n_dgrad2x_phase; N = 32;
-    }
-#pragma unroll
-    for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * (base + a0_tail_term_dword(N, n, kk, s)) + (kk & 1), a0_bf16_term(w, s));
-}
-// every copy of the weight at flat index idx (new value w): nothing to do outside the three convolution weight blocks
-A0_D void a0_tail_wt1(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, float w) {
-    const a0_wt_layout T{A.K1 / 64};
-    if (idx >= A.o1 && idx < A.o1 + 32LL * A.K1) {
-        const int e = (int)(idx - A.o1), n = e / A.K1, k = e - n * A.K1;
-        const float x = w / 255.0f;             // conv1 multiplies raw bytes: the reference's /255 is folded in here
-#pragma unroll
-        for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * (T.conv1x() + a0_tail_term_dword(32, n, k, s)) + (k & 1), a0_bf16_term(x, s));
-    } else if ((idx >= A.o2 && idx < A.o2 + 64 * 512) || (idx >= A.o3 && idx < A.o3 + 64 * 576)) {
-        const bool c3 = idx >= A.o3 && idx < A.o3 + 64 * 576;
-        const int K = c3 ? 576 : 512, e = (int)(idx - (c3 ? A.o3 : A.o2)), n = e / K, k = e - n * K;
-        // fp32, a0_wring layout: float ((c*64 + n)*4 + q)*4 + j holds W[n][k = 16c + 4j + q]
-        a0_tail_put32(A, to_online, to_target, (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4 + (k & 3)) * 4 + ((k >> 2) & 3), __float_as_uint(w));
-#pragma unroll
-        for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * ((c3 ? T.conv3x() : T.conv2x()) + a0_tail_term_dword(64, n, k, s)) + (k & 1), a0_bf16_term(w, s));
-        a0_tail_wt_dgrad(A, to_online, to_target, T, c3, n, k, w);
-    }
-}
-// four consecutive weights idx .. idx + 3 of one row (idx a multiple of four floats behind its block's start): the terms of four k are 8 adjacent bytes
-A0_D void a0_tail_wt4(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, const a0_f4& pv) {
-    const a0_wt_layout T{A.K1 / 64};
-    const float w[4] = {pv.x, pv.y, pv.z, pv.w};
-    int base, N, n, k;
-    bool c1 = false, c3 = false;
-    if (idx >= A.o1 && idx < A.o1 + 32LL * A.K1) { const int e = (int)(idx - A.o1); n = e / A.K1; k = e - n * A.K1; base = T.conv1x(); N = 32; c1 = true; }
-    else if (idx >= A.o2 && idx < A.o2 + 64 * 512) { const int e = (int)(idx - A.o2); n = e >> 9; k = e & 511; base = T.conv2x(); N = 64; }
-    else if (idx >= A.o3 && idx < A.o3 + 64 * 576) { const int e = (int)(idx - A.o3); n = e / 576; k = e - n * 576; base = T.conv3x(); N = 64; c3 = true; }
-    else return;
-    float x[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = c1 ? w[e] / 255.0f : w[e];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-        const uint2 t{a0_bf16_term(x[0], s) | (a0_bf16_term(x[1], s) << 16), a0_bf16_term(x[2], s) | (a0_bf16_term(x[3], s) << 16)};
-        const int dw = base + a0_tail_term_dword(N, n, k, s);          // k a multiple of four: an even dword
-        if (to_online) *(uint2*)((uint32_t*)A.wt + dw) = t;
-        if (to_target) *(uint2*)((uint32_t*)A.wt_t + dw) = t;
-    }
-    if (c1) return;
-    const int ring = (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4) * 4 + ((k >> 2) & 3);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        a0_tail_put32(A, to_online, to_target, ring + 4 * e, __float_as_uint(w[e]));
-        a0_tail_wt_dgrad(A, to_online, to_target, T, c3, n, k + e, w[e]);
-    }
-}
-
-// four consecutive weights held by one lane
-A0_D void a0_tail_wt_f4(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, const a0_f4& pv) {
-    if (A.wt4) a0_tail_wt4(A, to_online, to_target, idx, pv);
-    else { a0_tail_wt1(A, to_online, to_target, idx, pv.x); a0_tail_wt1(A, to_online, to_target, idx + 1, pv.y); a0_tail_wt1(A, to_online, to_target, idx + 2, pv.z); a0_tail_wt1(A, to_online, to_target, idx + 3, pv.w); }
-}
 
 // a0_adam_sync_kernel's body for float4 i of the flat buffer; HAVE_G: the gradient is the sum this lane has just formed
 template <bool HAVE_G>
@@ -582,7 +474,7 @@ extern "C" int a0_update_tail(float* params, float* grads, float* exp_avg, float
         const a0_reduce_seg& s = plan->seg[order[j]];
         long long lo = s.out - grads, hi = lo + s.count;
         // a0_reduce_segments_kernel's choice of path
-        const int vec = ((s.count | s.slab_stride) % 4 == 0) && ((((uintptr_t)s.slabs) | ((uintptr_t)s.out)) % 16 == 0);
+        const int vec = ((s.count | s.slab_stride) % 4 == 0) && a0_aligned(16, s.slabs, s.out);
         if (!vec && A.vec4) { lo = lo / 4 * 4; hi = (hi + 3) / 4 * 4; }       // 16-byte Adam: a scalar segment's region grows to whole groups of four (see the kernel)
         if (lo < at) return a0_fail(A0_EINVAL, "a0_update_tail: segments overlap or share a 16-byte group of parameters");
         gap(at, lo);
@@ -628,12 +520,7 @@ __global__ __launch_bounds__(256) void a0_clip_coef_kernel(const float* __restri
     __shared__ float red[256];
     float s = 0.f;
     for (long long i = threadIdx.x; i < n; i += 256) s += g[i] * g[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    a0_block_sum256(red, s);
     if (threadIdx.x == 0) {
         float c = max_norm / (sqrtf(red[0]) + 1e-6f);
         coef[0] = c < 1.f ? c : 1.f;
@@ -650,9 +537,7 @@ extern "C" int a0_rmsprop_step(float* params, const float* grads, float* square_
         hipLaunchKernelGGL(a0_clip_coef_kernel, dim3(1), dim3(256), 0, st, grads, n, (float)max_grad_norm, clip_scratch);
         coef = clip_scratch;
     }
-    long long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(a0_rmsprop_kernel, dim3((unsigned)blocks), dim3(256), 0, st, params, grads, square_avg, n, (float)lr, (float)alpha,
+    hipLaunchKernelGGL(a0_rmsprop_kernel, dim3(a0_grid_256(n)), dim3(256), 0, st, params, grads, square_avg, n, (float)lr, (float)alpha,
                        (float)(1.0 - alpha), (float)eps, coef);
     return a0_fail_hip((int)hipGetLastError(), "a0_rmsprop_step");
 }
@@ -671,11 +556,8 @@ __global__ void a0_target_sync_kernel(float* __restrict__ dst, const float* __re
 
 extern "C" int a0_target_sync(float* target, const float* online, long long n, const int* state, int force, void* stream) {
     if (!target || !online || n < 1 || (!force && !state)) return a0_fail(A0_EINVAL, "a0_target_sync: bad argument");
-    if ((((uintptr_t)target) | ((uintptr_t)online)) & 15) return a0_fail(A0_EINVAL, "a0_target_sync: buffers must be 16-byte aligned");
-    long long blocks = ((n >> 2) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(a0_target_sync_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, target, online, n, state, force);
+    if (!a0_aligned(16, target, online)) return a0_fail(A0_EINVAL, "a0_target_sync: buffers must be 16-byte aligned");
+    hipLaunchKernelGGL(a0_target_sync_kernel, dim3(a0_grid_256(n >> 2)), dim3(256), 0, (hipStream_t)stream, target, online, n, state, force);
     return a0_fail_hip((int)hipGetLastError(), "a0_target_sync");
 }
 
@@ -683,16 +565,7 @@ extern "C" int a0_target_sync(float* target, const float* online, long long n, c
 // learner.target_tau: target <- target + tau * (online - target) over [0, n_total) — the whole module, as the hard copy takes it — at the updates where the hard copy
 // would have happened.  The Adam forms in front are called with a target period of 0 ("never sync"), so this launch decides for itself from the step count they have
 // committed by now: state[1] holds the NEW count behind all three tail forms.  When it does not blend, every workgroup returns at once.
-// One rounded subtraction and one fused multiply-add per element, kept out of the compiler's contraction choices (see a0_mul_rounded).
-A0_D float a0_blend1(float t, float p, float tau) {
-    float d;
-    {
-#pragma clang fp contract(off)
-        d = p - t;
-    }
-    asm volatile("" : "+v"(d));
-    return __builtin_fmaf(tau, d, t);
-}
+// The element: a0_blend1 (a0_defs.h).  The firing rule is on purpose not net_reset.hip's a0_period_fires: no skip test, and at count 0 it blends only under `force`.
 
 // W: the target's fused-kernel weight copies follow.  The lane that holds a blended convolution weight files it through the update tail's helpers, on the target
 // side only — a0_wt_layout stays the only description of the copy layout.
@@ -723,557 +596,15 @@ __global__ __launch_bounds__(256) void a0_target_blend_kernel(float* __restrict_
 
 extern "C" int a0_target_blend(float* target, const float* online, long long n_total, double tau, const int* state, int target_update_freq, int force,
                                const a0_encoder_weights* w_target, int C, float* wt_target, void* stream) {
-    if (!target || !online || n_total < 1 || (!force && !state) || ((((uintptr_t)target) | ((uintptr_t)online)) & 3))
+    if (!target || !online || n_total < 1 || (!force && !state) || !a0_aligned(4, target, online))
         return a0_fail(A0_EINVAL, "a0_target_blend: bad argument");
     const float tau32 = (float)tau;       // rounded to fp32 once
     if (!(tau > 0.0) || !(tau < 1.0) || !(tau32 > 0.f) || !(tau32 < 1.f)) return a0_fail(A0_EINVAL, "a0_target_blend: tau must lie in (0, 1); tau >= 1 is the hard copy (a0_target_sync)");
     a0_wt_sink B{0, 0, 0, 0, 0, nullptr, nullptr};
     if (wt_target)
         if (int e = a0_wt_sink_make(&B, "a0_target_blend", "target", target, n_total, w_target, C, nullptr, wt_target)) return e;
-    const int vec4 = ((((uintptr_t)target) | ((uintptr_t)online)) % 16 == 0) ? 1 : 0;
+    const int vec4 = a0_aligned(16, target, online) ? 1 : 0;
     hipLaunchKernelGGL(wt_target ? a0_target_blend_kernel<true> : a0_target_blend_kernel<false>, dim3(a0_grid_256(vec4 ? (n_total + 3) / 4 : n_total)), dim3(256), 0, (hipStream_t)stream,
                        target, online, n_total, tau32, state, target_update_freq, force, vec4, B);
     return a0_fail_hip((int)hipGetLastError(), "a0_target_blend");
-}
-
-// ------------------------------------------------------------------------------------------------ periodic network resets
-// learner.net_reset_freq = N: after an update that was not NaN-skipped and left update_steps a positive multiple of N, the Q-network is re-initialised in ONE launch
-// behind the update's Adam form (and behind a0_target_blend): the head blocks are replaced by fresh values, the encoder blocks keep the share alpha of theirs
-// (shrink and perturb), Adam's moments are zeroed, its bias correction restarts (state[7] <- state[1]), the target becomes a copy of the online network and the
-// lane that holds a convolution weight files it in both networks' weight copies.  On every other update all workgroups return after reading state[1] and state[3].
-// Fresh values: element i at reset k = update_steps / N draws from Philox stream A0_STREAM_RESET of the seed at position k * n_total + i — a function of
-// (seed, k, i) alone; a normal element is a0_rng_normal's value there, a uniform one bound * (2 u - 1) with u a0_rng_uniform's (rng_elem.h).
-struct a0_reset_table { a0_net_reset_seg s[A0_NET_RESET_MAX_SEGS]; int n; };
-// the rule of one flat index: kind < 0 outside every segment; keep is the share that survives (alpha32 or 0); end: one past the segment's last index
-struct a0_reset_rule { long long end; int kind; float scale, keep; };
-
-// every lane walks the table in the same order (uniform loads of the by-value table, no indexed access to it); outside every segment `end` is where the next one starts
-A0_D a0_reset_rule a0_reset_find(const a0_reset_table& T, float alpha, long long i, long long n_total) {
-    a0_reset_rule R{n_total, -1, 0.f, 1.f};
-#pragma nounroll
-    for (int s = 0; s < T.n; ++s) {
-        const long long lo = T.s[s].offset, hi = lo + T.s[s].count;
-        if (i >= lo && i < hi) { R.end = hi; R.kind = T.s[s].kind; R.scale = T.s[s].scale; R.keep = T.s[s].keep ? alpha : 0.f; }
-        else if (lo > i && lo < R.end && R.kind < 0) R.end = lo;
-    }
-    return R;
-}
-// 2u - 1 is exact in fp32 (u is a multiple of 2^-24 below 1), then one rounded multiply
-A0_D float a0_reset_uniform(float bound, float u) {
-#pragma clang fp contract(off)
-    return bound * (2.0f * u - 1.0f);
-}
-A0_D float a0_reset_fresh1(const a0_reset_rule& R, unsigned long long seed, unsigned long long pos, uint32_t stream = A0_STREAM_RESET) {
-    if (R.kind == A0_NET_RESET_NORMAL) return a0_rng_normal_at(seed, stream, pos, R.scale);
-    if (R.kind == A0_NET_RESET_UNIFORM) return a0_reset_uniform(R.scale, a0_rng_uniform_at(seed, stream, pos));
-    return R.scale;
-}
-// four consecutive positions that share one Philox block (pos0 a multiple of four): one block, two Box-Muller pairs — the words a0_philox_word would pick
-A0_D a0_f4 a0_reset_fresh4(const a0_reset_rule& R, unsigned long long seed, unsigned long long pos0) {
-    a0_f4 f;
-    if (R.kind == A0_NET_RESET_CONST) { f.x = f.y = f.z = f.w = R.scale; return f; }
-    const unsigned long long blk = pos0 >> 2;
-    const a0_u4 o = a0_philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), A0_STREAM_RESET, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    if (R.kind == A0_NET_RESET_NORMAL) {
-        f.x = a0_rng_normal_words(o.x, o.y, false, R.scale); f.y = a0_rng_normal_words(o.x, o.y, true, R.scale);
-        f.z = a0_rng_normal_words(o.z, o.w, false, R.scale); f.w = a0_rng_normal_words(o.z, o.w, true, R.scale);
-    } else {
-        f.x = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.x)); f.y = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.y));
-        f.z = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.z)); f.w = a0_reset_uniform(R.scale, a0_rng_uniform_word(o.w));
-    }
-    return f;
-}
-// keep == 0: the fresh value itself; otherwise fmaf(keep, fl32(p - phi), phi) — a0_blend1's form with the fresh value in the target's place
-A0_D float a0_reset_mix(const a0_reset_rule& R, float p, float phi) { return R.keep == 0.f ? phi : a0_blend1(phi, p, R.keep); }
-
-template <bool W>
-__global__ __launch_bounds__(256) void a0_net_reset_kernel(float* __restrict__ p, float* __restrict__ target, float* __restrict__ m, float* __restrict__ v, long long n_adam,
-                                                           long long n_total, a0_reset_table T, float alpha, unsigned long long seed_arg, int* __restrict__ state, int freq,
-                                                           int force, long long k_host, int vec4, a0_wt_sink B) {
-    long long k = k_host;
-    if (!force) {
-        const int steps = state[1];
-        if (state[3] != 0 || !(freq > 0 && steps > 0 && steps % freq == 0)) return;
-        k = steps / freq;
-    }
-    // a fresh optimizer: a0_step_decide counts t from here (nobody reads state[7] during this launch)
-    if (state && blockIdx.x == 0 && threadIdx.x == 0) state[7] = state[1];
-    // the seed (32 bits) travels in a vector register: Philox's key schedule of a uniform seed would be hoisted into twenty scalar registers for the whole loop
-    uint32_t seed_v = (uint32_t)seed_arg;
-    asm volatile("" : "+v"(seed_v));
-    const unsigned long long seed = seed_v;
-    const unsigned long long base = (unsigned long long)k * (unsigned long long)n_total;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const long long groups = (n_total + 3) >> 2;
-    // a lane owns four consecutive elements.  `wide`: the buffers are 16-byte aligned, the four share a Philox block and, with weight copies, a row of a convolution
-    // matrix; where they also lie inside one segment (or between two) they move as 16 bytes.  Everything else — a segment boundary inside the four (the real / pad
-    // boundary of a noisy bias), the tail of n_total % 4 floats, 4-byte-aligned buffers — goes element by element through the same arithmetic.
-    const bool wide = vec4 && (base & 3) == 0 && (!W || B.wt4);
-    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < groups; j += stride) {
-        const long long e0 = 4 * j;
-        const a0_reset_rule R = a0_reset_find(T, alpha, e0, n_total);
-        if (wide && e0 + 4 <= R.end) {
-            a0_f4 pv = ((a0_f4*)p)[j];
-            if (R.kind >= 0 && R.keep != 1.f) {
-                const a0_f4 f = a0_reset_fresh4(R, seed, base + (unsigned long long)e0);
-                pv.x = a0_reset_mix(R, pv.x, f.x); pv.y = a0_reset_mix(R, pv.y, f.y); pv.z = a0_reset_mix(R, pv.z, f.z); pv.w = a0_reset_mix(R, pv.w, f.w);
-                ((a0_f4*)p)[j] = pv;
-            }
-            ((a0_f4*)target)[j] = pv;
-            if (e0 + 4 <= n_adam) { ((a0_f4*)m)[j] = a0_zero4(); ((a0_f4*)v)[j] = a0_zero4(); }
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (e0 + e < n_adam) { m[e0 + e] = 0.f; v[e0 + e] = 0.f; }
-            }
-            continue;
-        }
-#pragma nounroll
-        for (long long idx = e0; idx < e0 + 4 && idx < n_total; ++idx) {
-            const a0_reset_rule Re = a0_reset_find(T, alpha, idx, n_total);
-            float x = p[idx];
-            if (Re.kind >= 0 && Re.keep != 1.f) { x = a0_reset_mix(Re, x, a0_reset_fresh1(Re, seed, base + (unsigned long long)idx)); p[idx] = x; }
-            target[idx] = x;
-            if (idx < n_adam) { m[idx] = 0.f; v[idx] = 0.f; }
-        }
-    }
-    // the weight copies of BOTH networks (the target is the online network after a reset), in a pass of their own over the convolution blocks: every lane files the
-    // parameters it has just written itself (the same lane-to-element map)
-    if constexpr (W) {
-        const long long c_lo = (B.o1 < B.o2 ? (B.o1 < B.o3 ? B.o1 : B.o3) : (B.o2 < B.o3 ? B.o2 : B.o3)) >> 2;
-        long long c_hi = B.o1 + 32LL * B.K1;
-        if (B.o2 + 64 * 512 > c_hi) c_hi = B.o2 + 64 * 512;
-        if (B.o3 + 64 * 576 > c_hi) c_hi = B.o3 + 64 * 576;
-        c_hi = (c_hi + 3) >> 2;
-        for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < c_hi && j < groups; j += stride) {      // the first pass's groups, lane for lane
-            if (j < c_lo) continue;
-            const long long e0 = 4 * j;
-            if (wide && e0 + 4 <= n_total) a0_tail_wt4(B, true, true, e0, ((const a0_f4*)p)[j]);
-            else {
-#pragma nounroll
-                for (long long idx = e0; idx < e0 + 4 && idx < n_total; ++idx) a0_tail_wt1(B, true, true, idx, p[idx]);
-            }
-        }
-    }
-}
-
-// the by-value table of a launch from the caller's rules, checked (`who`: the entry point's name in the error text)
-static int a0_reset_table_make(a0_reset_table* T, const char* who, const a0_net_reset_seg* segs, int n_segs, long long n_adam) {
-    const std::string name(who);
-    if (n_segs < 0 || n_segs > A0_NET_RESET_MAX_SEGS || (n_segs > 0 && !segs)) return a0_fail(A0_EINVAL, (name + ": between 0 and A0_NET_RESET_MAX_SEGS segments").c_str());
-    T->n = n_segs;
-    long long at = 0;
-    for (int s = 0; s < A0_NET_RESET_MAX_SEGS; ++s) {
-        if (s >= n_segs) { T->s[s] = a0_net_reset_seg{0, 0, A0_NET_RESET_CONST, 0.f, 0}; continue; }
-        const a0_net_reset_seg& g = segs[s];
-        if (g.offset < at || g.count < 1 || g.offset + g.count > n_adam) return a0_fail(A0_EINVAL, (name + ": the segments must be ascending, disjoint and inside [0, n_adam)").c_str());
-        if (g.kind != A0_NET_RESET_CONST && g.kind != A0_NET_RESET_NORMAL && g.kind != A0_NET_RESET_UNIFORM) return a0_fail(A0_EINVAL, (name + ": unknown segment kind").c_str());
-        if (!(g.scale == g.scale) || g.scale - g.scale != 0.f || (g.keep != 0 && g.keep != 1)) return a0_fail(A0_EINVAL, (name + ": a segment's scale must be finite and its keep flag 0 or 1").c_str());
-        at = g.offset + g.count;
-        T->s[s] = g;
-    }
-    return A0_OK;
-}
-
-extern "C" int a0_net_reset(float* params, float* target, float* exp_avg, float* exp_avg_sq, long long n_adam, long long n_total, const a0_net_reset_seg* segs, int n_segs,
-                            double alpha, unsigned long long seed, int* state, int freq, int force, long long k_host, const a0_encoder_weights* w, int C, float* wt,
-                            float* wt_target, void* stream) {
-    if (!params || !target || !exp_avg || !exp_avg_sq || n_adam < 1 || n_total < n_adam || (!force && !state) || freq < 0 || (force && k_host < 0) ||
-        ((((uintptr_t)params) | ((uintptr_t)target) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) & 3))
-        return a0_fail(A0_EINVAL, "a0_net_reset: bad argument");
-    if (!(alpha >= 0.0) || !(alpha <= 1.0)) return a0_fail(A0_EINVAL, "a0_net_reset: alpha must lie in [0, 1]");
-    a0_reset_table T;
-    if (int e = a0_reset_table_make(&T, "a0_net_reset", segs, n_segs, n_adam)) return e;
-    a0_wt_sink B{0, 0, 0, 0, 0, nullptr, nullptr};
-    if (wt || wt_target) {
-        if (!wt) return a0_fail(A0_EINVAL, "a0_net_reset: weight copies need wt and wt_target, both or neither");
-        if (int e = a0_wt_sink_make(&B, "a0_net_reset", "params", params, n_total, w, C, wt, wt_target)) return e;
-    }
-    const int vec4 = ((((uintptr_t)params) | ((uintptr_t)target) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) % 16 == 0) ? 1 : 0;
-    const float alpha32 = (float)alpha;       // rounded to fp32 once
-    const unsigned long long seed32 = seed & 0xFFFFFFFFull;
-    hipLaunchKernelGGL(wt ? a0_net_reset_kernel<true> : a0_net_reset_kernel<false>, dim3(a0_grid_256((n_total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       params, target, exp_avg, exp_avg_sq, n_adam, n_total, T, alpha32, seed32, state, freq, force, k_host, vec4, B);
-    return a0_fail_hip((int)hipGetLastError(), "a0_net_reset");
-}
-
-// ------------------------------------------------------------------------------------------------ dormant neurons and ReDo
-// learner.redo_freq = N (Sokar et al. 2023): after an update that was not NaN-skipped and left update_steps a positive multiple of N, three launches behind the
-// update's Adam form (and a0_target_blend), in front of a0_net_reset: (1) per-workgroup sums of |activation| per neuron over the differentiated pass's four buffers,
-// (2) one workgroup finishes them into the scores s_i = m_i / mean_j(m_j), the mask s_i <= tau and the counts, (3) the dormant neurons are recycled.  On every other
-// update each launch returns after reading state[1] and state[3].  Everything is summed in double in a fixed order (the rows of a workgroup by the geometry alone,
-// the lanes of a channel and the workgroups in index order; no atomics), so a run is reproducible.
-A0_D bool a0_redo_fires(const int* __restrict__ state, int freq, int force) {
-    if (force) return true;
-    const int steps = state[1];
-    return state[3] == 0 && freq > 0 && steps > 0 && steps % freq == 0;
-}
-
-// The workgroups that take part in a layer of `rows` rows when one workgroup step covers `rps` rows: about eight steps each, at most all of them — a function of
-// the row count alone.  A short layer (fc1: B rows of 512) leaves few partials for the finish to read.
-A0_D int a0_redo_groups(long long rows, int rps) {
-    const long long g = ((rows + rps - 1) / rps + 7) / 8;
-    return (int)(g < 1 ? 1 : g > A0_REDO_PARTIALS ? A0_REDO_PARTIALS : g);
-}
-
-// One layer of N channels, channel-fastest: a lane owns four channels (one 16-byte load per row) of every (256 / (N / 4))-th row of its workgroup's rows, four
-// loads in flight; one exchange through LDS per layer, after which lane ch adds its channel's lanes in index order.  out: this workgroup's N partial sums.
-template <int N>
-A0_D void a0_redo_layer_sums(const float* __restrict__ X, long long rows, double* __restrict__ out, double (*sh)[4]) {
-    constexpr int N4 = N / 4, RPS = 256 / N4;
-    const int tid = threadIdx.x, r = tid / N4, c = tid % N4, G = a0_redo_groups(rows, RPS);
-    if ((int)blockIdx.x >= G) return;          // the whole workgroup: nobody waits at the barriers below
-    const long long steps = (rows + RPS - 1) / RPS, per = (steps + G - 1) / G;
-    const long long s0 = (long long)blockIdx.x * per, s1 = s0 + per < steps ? s0 + per : steps;
-    const a0_f4* __restrict__ X4 = (const a0_f4*)X;
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    long long s = s0;
-    for (; s + 4 <= s1; s += 4) {
-        a0_f4 x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const long long row = (s + u) * RPS + r; x[u] = row < rows ? X4[row * N4 + c] : a0_zero4(); }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { a[0] += (double)fabsf(x[u].x); a[1] += (double)fabsf(x[u].y); a[2] += (double)fabsf(x[u].z); a[3] += (double)fabsf(x[u].w); }
-    }
-    for (; s < s1; ++s) {
-        const long long row = s * RPS + r;
-        const a0_f4 x = row < rows ? X4[row * N4 + c] : a0_zero4();
-        a[0] += (double)fabsf(x.x); a[1] += (double)fabsf(x.y); a[2] += (double)fabsf(x.z); a[3] += (double)fabsf(x.w);
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sh[tid][e] = a[e];
-    __syncthreads();
-    for (int ch = tid; ch < N; ch += 256) {
-        double t = 0.0;
-#pragma unroll
-        for (int rr = 0; rr < RPS; ++rr) t += sh[rr * N4 + (ch >> 2)][ch & 3];
-        out[ch] = t;
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void a0_redo_sums_kernel(const float* __restrict__ act1, long long rows1, const float* __restrict__ act2, long long rows2,
-                                                           const float* __restrict__ act3, long long rows3, const float* __restrict__ fc1, long long rows4,
-                                                           const int* __restrict__ state, int freq, int force, double* __restrict__ partials) {
-    if (!a0_redo_fires(state, freq, force)) return;
-    __shared__ double sh[256][4];
-    double* out = partials + (long long)blockIdx.x * A0_REDO_NEURONS;
-    a0_redo_layer_sums<32>(act1, rows1, out, sh);
-    a0_redo_layer_sums<64>(act2, rows2, out + 32, sh);
-    a0_redo_layer_sums<64>(act3, rows3, out + 96, sh);
-    a0_redo_layer_sums<512>(fc1, rows4, out + 160, sh);
-}
-
-// layer of neuron i: 0 conv1 [0, 32), 1 conv2 [32, 96), 2 conv3 [96, 160), 3 fc1 [160, 672)
-A0_D int a0_redo_layer_of(int i) { return i < 32 ? 0 : i < 96 ? 1 : i < 160 ? 2 : 3; }
-
-// One workgroup of 1024 lanes.  The partials of a neuron — those of the workgroups that took part in its layer — are added in index order in two steps, so that
-// up to 512 dependent additions do not wait for as many loads one after the other: lane (slice s, neuron i) adds the s-th eighth of them (independent loads), then
-// lane i adds its eight slice sums in index order.
-__global__ __launch_bounds__(1024) void a0_redo_finish_kernel(const double* __restrict__ partials, long long rows1, long long rows2, long long rows3, long long rows4,
-                                                              double tau, const int* __restrict__ state, int freq, int force, float* __restrict__ scores, int* __restrict__ mask,
-                                                              int* __restrict__ counts) {
-    if (!a0_redo_fires(state, freq, force)) return;
-    constexpr int SLICES = 8;
-    __shared__ double part[SLICES][A0_REDO_NEURONS];
-    __shared__ double m[A0_REDO_NEURONS];
-    __shared__ double mean[4];
-    __shared__ int dorm[A0_REDO_NEURONS];
-    __shared__ int cnt[4];
-    const int i = threadIdx.x, lay = a0_redo_layer_of(i);
-    const int lo = i == 0 ? 0 : i == 1 ? 32 : i == 2 ? 96 : 160, width = i == 0 ? 32 : i == 3 ? 512 : 64;      // of layer i, for the lanes i < 4
-    for (int item = threadIdx.x; item < SLICES * A0_REDO_NEURONS; item += 1024) {
-        const int sl = item / A0_REDO_NEURONS, n = item - sl * A0_REDO_NEURONS, ln = a0_redo_layer_of(n);
-        const int G = ln == 0 ? a0_redo_groups(rows1, 32) : ln == 1 ? a0_redo_groups(rows2, 16) : ln == 2 ? a0_redo_groups(rows3, 16) : a0_redo_groups(rows4, 2);
-        const int per = (G + SLICES - 1) / SLICES, g0 = sl * per, g1 = g0 + per < G ? g0 + per : G;
-        double t = 0.0;
-#pragma unroll 8
-        for (int g = g0; g < g1; ++g) t += partials[(long long)g * A0_REDO_NEURONS + n];
-        part[sl][n] = t;
-    }
-    __syncthreads();
-    if (i < A0_REDO_NEURONS) {
-        const long long rows = lay == 0 ? rows1 : lay == 1 ? rows2 : lay == 2 ? rows3 : rows4;
-        double t = 0.0;
-#pragma unroll
-        for (int sl = 0; sl < SLICES; ++sl) t += part[sl][i];
-        m[i] = t / (double)rows;
-    }
-    __syncthreads();
-    if (i < 4) {
-        double t = 0.0;
-        for (int j = 0; j < width; ++j) t += m[lo + j];
-        mean[i] = t / (double)width;
-    }
-    __syncthreads();
-    if (i < A0_REDO_NEURONS) {
-        const double s = mean[lay] > 0.0 ? m[i] / mean[lay] : 0.0;
-        const int d = s <= tau ? 1 : 0;
-        scores[i] = (float)s; mask[i] = d; dorm[i] = d;
-    }
-    __syncthreads();
-    if (i < 4) {
-        int c = 0;
-        for (int j = 0; j < width; ++j) c += dorm[lo + j];
-        cnt[i] = c; counts[i] = c;
-    }
-    __syncthreads();
-    if (i == 0) { counts[4] = cnt[0] + cnt[1] + cnt[2] + cnt[3]; counts[5] = state ? state[1] : 0; }
-}
-
-extern "C" int a0_redo_score(const float* act1, long long rows1, const float* act2, long long rows2, const float* act3, long long rows3, const float* fc1, long long rows4,
-                             double tau, const int* state, int freq, int force, double* partials, float* scores, int* mask, int* counts, void* stream) {
-    if (!act1 || !act2 || !act3 || !fc1 || !partials || !scores || !mask || !counts || rows1 < 1 || rows2 < 1 || rows3 < 1 || rows4 < 1 || (!force && !state) || freq < 0)
-        return a0_fail(A0_EINVAL, "a0_redo_score: bad argument");
-    if (!(tau >= 0.0) || !(tau < 1.0)) return a0_fail(A0_EINVAL, "a0_redo_score: tau must lie in [0, 1)");
-    if ((((uintptr_t)act1) | ((uintptr_t)act2) | ((uintptr_t)act3) | ((uintptr_t)fc1)) & 15) return a0_fail(A0_EINVAL, "a0_redo_score: the activation buffers must be 16-byte aligned");
-    if ((((uintptr_t)partials) & 7) || ((((uintptr_t)scores) | ((uintptr_t)mask) | ((uintptr_t)counts)) & 3)) return a0_fail(A0_EINVAL, "a0_redo_score: misaligned output");
-    hipLaunchKernelGGL(a0_redo_sums_kernel, dim3(A0_REDO_PARTIALS), dim3(256), 0, (hipStream_t)stream, act1, rows1, act2, rows2, act3, rows3, fc1, rows4, state, freq, force, partials);
-    hipLaunchKernelGGL(a0_redo_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double*)partials, rows1, rows2, rows3, rows4, tau, state, freq, force,
-                       scores, mask, counts);
-    return a0_fail_hip((int)hipGetLastError(), "a0_redo_score");
-}
-
-// The recycle launch.  Blocks in flat order conv1, conv2, conv3, fc1, head; block b is [W (N x K) | bias (N)] at `off`; `in`: where its rows' neurons start in the
-// mask (-1: the head, whose rows are no hidden neurons), `out`: where the neurons its columns read start (-1: conv1 reads pixels), column k reads neuron k % mod.
-struct a0_redo_map { long long off[5]; int N[5], K[5], in[5], out[5], mod[5]; };
-
-template <bool W>
-__global__ __launch_bounds__(256) void a0_redo_recycle_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long n_adam, long long n_total, a0_reset_table T,
-                                                              a0_redo_map D, const int* __restrict__ mask, unsigned long long seed_arg, const int* __restrict__ state, int freq,
-                                                              int force, long long k_host, a0_wt_sink B) {
-    if (!a0_redo_fires(state, freq, force)) return;
-    const long long k = force ? k_host : (long long)(state[1] / freq);
-    __shared__ unsigned char dm[A0_REDO_NEURONS];
-    for (int i = threadIdx.x; i < A0_REDO_NEURONS; i += 256) dm[i] = mask[i] != 0 ? 1 : 0;
-    __syncthreads();
-    // the seed in a vector register, as in a0_net_reset_kernel
-    uint32_t seed_v = (uint32_t)seed_arg;
-    asm volatile("" : "+v"(seed_v));
-    const unsigned long long seed = seed_v;
-    const unsigned long long base = (unsigned long long)k * (unsigned long long)n_total;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n_adam; e += stride) {
-        bool incoming = false, outgoing = false;
-#pragma nounroll
-        for (int b = 0; b < 5; ++b) {      // uniform loads of the by-value map, as a0_reset_find walks its table
-            const long long nw = (long long)D.N[b] * D.K[b], r = e - D.off[b];
-            if (r < 0 || r >= nw + D.N[b]) continue;
-            if (r >= nw) { incoming = D.in[b] >= 0 && dm[D.in[b] + (int)(r - nw)]; continue; }      // a bias: incoming only
-            const int n = (int)((unsigned)r / (unsigned)D.K[b]), kk = (int)r - n * D.K[b];
-            incoming = D.in[b] >= 0 && dm[D.in[b] + n];
-            outgoing = D.out[b] >= 0 && dm[D.out[b] + kk % D.mod[b]];
-        }
-        if (!incoming && !outgoing) continue;
-        // an element that is both (the weight from a dormant neuron into a dormant neuron) ends at zero: the outgoing rule is applied last, as in ReDo's published code
-        float x = 0.f;
-        if (!outgoing) {
-            const a0_reset_rule R = a0_reset_find(T, 0.f, e, n_total);
-            if (R.kind < 0) continue;                  // the table has no rule for it: left alone
-            x = a0_reset_fresh1(R, seed, base + (unsigned long long)e, A0_STREAM_REDO);
-        }
-        p[e] = x; m[e] = 0.f; v[e] = 0.f;
-        if constexpr (W) a0_tail_wt1(B, true, false, e, x);
-    }
-}
-
-extern "C" int a0_redo_recycle(float* params, float* exp_avg, float* exp_avg_sq, long long n_adam, long long n_total, const a0_net_reset_seg* segs, int n_segs,
-                               const a0_redo_blocks* blocks, const int* mask, unsigned long long seed, const int* state, int freq, int force, long long k_host,
-                               const a0_encoder_weights* w, int C, float* wt, void* stream) {
-    if (!params || !exp_avg || !exp_avg_sq || !blocks || !mask || n_adam < 1 || n_total < n_adam || (!force && !state) || freq < 0 || (force && k_host < 0) ||
-        ((((uintptr_t)params) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)mask)) & 3))
-        return a0_fail(A0_EINVAL, "a0_redo_recycle: bad argument");
-    a0_reset_table T;
-    if (int e = a0_reset_table_make(&T, "a0_redo_recycle", segs, n_segs, n_adam)) return e;
-    if (blocks->K1 < 1 || blocks->feat < 64 || blocks->feat % 64 != 0 || blocks->Npad < 1) return a0_fail(A0_EINVAL, "a0_redo_recycle: K1 >= 1, feat a positive multiple of 64, Npad >= 1");
-    a0_redo_map D;
-    const long long off[5] = {blocks->conv1, blocks->conv2, blocks->conv3, blocks->fc1, blocks->head};
-    const int N[5] = {32, 64, 64, 512, blocks->Npad}, K[5] = {blocks->K1, 512, 576, blocks->feat, 512};
-    const int in[5] = {0, 32, 96, 160, -1}, out[5] = {-1, 0, 32, 96, 160}, mod[5] = {1, 32, 64, 64, 512};
-    long long at = 0;
-    for (int b = 0; b < 5; ++b) {
-        if (off[b] < at || off[b] + (long long)N[b] * K[b] + N[b] > n_adam) return a0_fail(A0_EINVAL, "a0_redo_recycle: the blocks conv1, conv2, conv3, fc1, head must be ascending, disjoint and inside [0, n_adam)");
-        at = off[b] + (long long)N[b] * K[b] + N[b];
-        D.off[b] = off[b]; D.N[b] = N[b]; D.K[b] = K[b]; D.in[b] = in[b]; D.out[b] = out[b]; D.mod[b] = mod[b];
-    }
-    a0_wt_sink B{0, 0, 0, 0, 0, nullptr, nullptr};
-    if (wt) {
-        if (int e = a0_wt_sink_make(&B, "a0_redo_recycle", "params", params, n_total, w, C, nullptr, wt)) return e;
-        if (B.o1 != blocks->conv1 || B.o2 != blocks->conv2 || B.o3 != blocks->conv3 || B.K1 != blocks->K1)
-            return a0_fail(A0_EINVAL, "a0_redo_recycle: the encoder weights and the block descriptors name different convolution blocks");
-        B.wt = wt; B.wt_t = nullptr;                   // the online copy alone: the target follows at its next sync or blend
-    }
-    const unsigned long long seed32 = seed & 0xFFFFFFFFull;
-    hipLaunchKernelGGL(wt ? a0_redo_recycle_kernel<true> : a0_redo_recycle_kernel<false>, dim3(a0_grid_256(n_adam)), dim3(256), 0, (hipStream_t)stream, params, exp_avg, exp_avg_sq, n_adam,
-                       n_total, T, D, mask, seed32, state, freq, force, k_host, B);
-    return a0_fail_hip((int)hipGetLastError(), "a0_redo_recycle");
-}
-
-// ------------------------------------------------------------------------------------------------ NoisyNet
-// W = mu + sigma * (f(eps_out) x f(eps_in)),  b = mu_b + sigma_b * f(eps_b),  f(x) = sign(x) sqrt|x|
-// (reference agent0/deepq/model.py:54-62,73-87).  Blocks are [W (N*K) | b (N)]; one call handles the rows [r0, r1) that
-// belong to one NoisyLinear module (q_head and value_head share a packed block but have their own noise vectors).
-A0_D float a0_noise_f(float x) { return (x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f)) * sqrtf(fabsf(x)); }
-
-__global__ void a0_noisy_compose_kernel(const float* __restrict__ mu, const float* __restrict__ sigma, float* __restrict__ eff, int N, int K,
-                                        int r0, int r1, const float* __restrict__ noise_in, const float* __restrict__ noise_out_w,
-                                        const float* __restrict__ noise_out_b) {
-    const long long rows = r1 - r0;
-    const long long total = rows * K + rows;
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        long long off; float e;
-        if (i < rows * K) {
-            const int n = (int)(i / K), k = (int)(i % K);
-            off = (long long)(r0 + n) * K + k;
-            e = a0_noise_f(noise_out_w[n]) * a0_noise_f(noise_in[k]);
-        } else {
-            const int n = (int)(i - rows * K);
-            off = (long long)N * K + r0 + n;
-            e = a0_noise_f(noise_out_b[n]);
-        }
-        eff[off] = mu[off] + sigma[off] * e;
-    }
-}
-
-// gradient fan-out: the weight-gradient kernels write d(eff) into the mu block (d mu = d eff); d sigma = d eff * eps
-__global__ void a0_noisy_grad_sigma_kernel(const float* __restrict__ gmu, float* __restrict__ gsigma, int N, int K, int r0, int r1,
-                                           const float* __restrict__ noise_in, const float* __restrict__ noise_out_w,
-                                           const float* __restrict__ noise_out_b) {
-    const long long rows = r1 - r0;
-    const long long total = rows * K + rows;
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-        long long off; float e;
-        if (i < rows * K) {
-            const int n = (int)(i / K), k = (int)(i % K);
-            off = (long long)(r0 + n) * K + k;
-            e = a0_noise_f(noise_out_w[n]) * a0_noise_f(noise_in[k]);
-        } else {
-            const int n = (int)(i - rows * K);
-            off = (long long)N * K + r0 + n;
-            e = a0_noise_f(noise_out_b[n]);
-        }
-        gsigma[off] = gmu[off] * e;
-    }
-}
-
-// Up to six NoisyLinear modules (first_dense, q_head, value_head of the online AND the target network: round 4) in one launch: workgroups [first_block[m], first_block[m+1]) serve module m.
-struct a0_noisy_mod { const float* mu; const float* sigma; float* out; int N, K, r0, r1; const float* noise_in; const float* noise_out_w; const float* noise_out_b; };
-struct a0_noisy_multi_args { a0_noisy_mod mod[6]; int first_block[7]; };
-
-template <bool GRAD>
-__global__ void a0_noisy_multi_kernel(a0_noisy_multi_args A) {
-    int mi = 0;
-#pragma unroll
-    for (int k = 1; k < 6; ++k) mi += ((int)blockIdx.x >= A.first_block[k]) ? 1 : 0;
-    const a0_noisy_mod M = A.mod[mi];
-    const int nblk = A.first_block[mi + 1] - A.first_block[mi];
-    const long long rows = M.r1 - M.r0;
-    const long long total = rows * M.K + rows;
-    long long i = (long long)((int)blockIdx.x - A.first_block[mi]) * blockDim.x + threadIdx.x;
-    const long long stride = (long long)nblk * blockDim.x;
-    for (; i < total; i += stride) {
-        long long off; float e;
-        if (i < rows * M.K) {
-            const int n = (int)(i / M.K), k = (int)(i % M.K);
-            off = (long long)(M.r0 + n) * M.K + k;
-            e = a0_noise_f(M.noise_out_w[n]) * a0_noise_f(M.noise_in[k]);
-        } else {
-            const int n = (int)(i - rows * M.K);
-            off = (long long)M.N * M.K + M.r0 + n;
-            e = a0_noise_f(M.noise_out_b[n]);
-        }
-        if (GRAD) M.out[off] = M.mu[off] * e;                 // d sigma = d eff * eps (mu = the gradient written into the mu block)
-        else M.out[off] = M.mu[off] + M.sigma[off] * e;       // eff = mu + sigma * eps
-    }
-}
-
-// The same, four k per lane: 16-byte loads and stores, 32-bit index arithmetic (the element-wise kernel spends its time in a 64-bit division per element; this one
-// runs at the HBM rate).  Every element is formed by the same expression as above; needs K % 4 == 0 and 16-byte aligned blocks / noise vectors (the packed layout's).
-template <bool GRAD>
-__global__ __launch_bounds__(256) void a0_noisy_multi_v4_kernel(a0_noisy_multi_args A) {
-    int mi = 0;
-#pragma unroll
-    for (int k = 1; k < 6; ++k) mi += ((int)blockIdx.x >= A.first_block[k]) ? 1 : 0;
-    const a0_noisy_mod M = A.mod[mi];
-    const unsigned nblk = (unsigned)(A.first_block[mi + 1] - A.first_block[mi]);
-    const unsigned rows = (unsigned)(M.r1 - M.r0), K4 = (unsigned)M.K >> 2, nw = rows * K4, total = nw + rows;
-    const unsigned stride = nblk * 256u;
-    for (unsigned i = ((unsigned)blockIdx.x - (unsigned)A.first_block[mi]) * 256u + threadIdx.x; i < total; i += stride) {
-        if (i < nw) {
-            const unsigned n = i / K4, k4 = i - n * K4;
-            const long long off = (long long)(M.r0 + (int)n) * M.K + 4 * k4;
-            const float eo = a0_noise_f(M.noise_out_w[n]);
-            const a0_f4 ni = *(const a0_f4*)(M.noise_in + 4 * k4);
-            const float e0 = eo * a0_noise_f(ni.x), e1 = eo * a0_noise_f(ni.y), e2 = eo * a0_noise_f(ni.z), e3 = eo * a0_noise_f(ni.w);
-            const a0_f4 mu = *(const a0_f4*)(M.mu + off);
-            a0_f4 o;
-            if (GRAD) { o.x = mu.x * e0; o.y = mu.y * e1; o.z = mu.z * e2; o.w = mu.w * e3; }
-            else {
-                const a0_f4 sg = *(const a0_f4*)(M.sigma + off);
-                o.x = mu.x + sg.x * e0; o.y = mu.y + sg.y * e1; o.z = mu.z + sg.z * e2; o.w = mu.w + sg.w * e3;
-            }
-            *(a0_f4*)(M.out + off) = o;
-        } else {
-            const unsigned n = i - nw;
-            const long long off = (long long)M.N * M.K + M.r0 + (int)n;
-            const float e = a0_noise_f(M.noise_out_b[n]);
-            if (GRAD) M.out[off] = M.mu[off] * e;
-            else M.out[off] = M.mu[off] + M.sigma[off] * e;
-        }
-    }
-}
-
-// nmod <= 6 modules; arrays are host arrays.  grad = 0: eff[m] = mu[m] + sigma[m] * eps (a0_noisy_compose per module);
-// grad = 1: gsigma[m] (passed as eff) = gmu[m] (passed as mu) * eps (a0_noisy_grad_sigma per module; sigma unused).
-extern "C" int a0_noisy_multi(int grad, int nmod, const float* const* mu, const float* const* sigma, float* const* eff, const int* N, const int* K, const int* r0,
-                              const int* r1, const float* const* noise_in, const float* const* noise_out_w, const float* const* noise_out_b, void* stream) {
-    if (nmod < 1 || nmod > 6 || !mu || !eff || !N || !K || !r0 || !r1 || !noise_in || !noise_out_w || !noise_out_b || (!grad && !sigma))
-        return a0_fail(A0_EINVAL, "a0_noisy_multi: bad argument");
-    a0_noisy_multi_args A;
-    int blocks = 0;
-    bool v4 = true;      // the four-wide kernel, unless an operand is unaligned or K not a multiple of 4
-    for (int m = 0; m < nmod && v4; ++m)
-        v4 = mu[m] && eff[m] && noise_in[m] && K[m] % 4 == 0 && (long long)N[m] * K[m] < (1LL << 31) &&
-             (((uintptr_t)mu[m] | (uintptr_t)eff[m] | (uintptr_t)noise_in[m] | (grad ? 0 : (uintptr_t)sigma[m])) & 15) == 0;
-    for (int m = 0; m < 6; ++m) {
-        A.first_block[m] = blocks;
-        if (m < nmod) {
-            if (!mu[m] || !eff[m] || (!grad && !sigma[m]) || !noise_in[m] || !noise_out_w[m] || !noise_out_b[m] || N[m] < 1 || K[m] < 1 || r0[m] < 0 || r1[m] <= r0[m] || r1[m] > N[m])
-                return a0_fail(A0_EINVAL, "a0_noisy_multi: bad module");
-            A.mod[m] = a0_noisy_mod{mu[m], grad ? nullptr : sigma[m], eff[m], N[m], K[m], r0[m], r1[m], noise_in[m], noise_out_w[m], noise_out_b[m]};
-            long long b = v4 ? ((long long)(r1[m] - r0[m]) * (K[m] / 4 + 1) + 255) / 256 : ((long long)(r1[m] - r0[m]) * (K[m] + 1) + 255) / 256;
-            if (b > 2048) b = 2048;
-            blocks += (int)b;
-        } else {
-            A.mod[m] = a0_noisy_mod{nullptr, nullptr, nullptr, 1, 1, 0, 0, nullptr, nullptr, nullptr};
-        }
-    }
-    for (int m = nmod + 1; m <= 6; ++m) A.first_block[m] = 0x7fffffff;       // unused modules are never selected
-    A.first_block[nmod] = blocks;                                              // end of the last real module
-    if (v4 && grad) hipLaunchKernelGGL(a0_noisy_multi_v4_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
-    else if (v4) hipLaunchKernelGGL(a0_noisy_multi_v4_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
-    else if (grad) hipLaunchKernelGGL(a0_noisy_multi_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(a0_noisy_multi_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A);
-    return a0_fail_hip((int)hipGetLastError(), "a0_noisy_multi");
-}
-
-extern "C" int a0_noisy_compose(const float* mu, const float* sigma, float* eff, int N, int K, int r0, int r1, const float* noise_in,
-                                const float* noise_out_w, const float* noise_out_b, void* stream) {
-    if (!mu || !sigma || !eff || !noise_in || !noise_out_w || !noise_out_b || N < 1 || K < 1 || r0 < 0 || r1 <= r0 || r1 > N) return a0_fail(A0_EINVAL, "a0_noisy_compose: bad argument");
-    long long total = (long long)(r1 - r0) * (K + 1), blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(a0_noisy_compose_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mu, sigma, eff, N, K, r0, r1, noise_in, noise_out_w, noise_out_b);
-    return a0_fail_hip((int)hipGetLastError(), "a0_noisy_compose");
-}
-
-extern "C" int a0_noisy_grad_sigma(const float* gmu, float* gsigma, int N, int K, int r0, int r1, const float* noise_in,
-                                   const float* noise_out_w, const float* noise_out_b, void* stream) {
-    if (!gmu || !gsigma || !noise_in || !noise_out_w || !noise_out_b || N < 1 || K < 1 || r0 < 0 || r1 <= r0 || r1 > N) return a0_fail(A0_EINVAL, "a0_noisy_grad_sigma: bad argument");
-    long long total = (long long)(r1 - r0) * (K + 1), blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(a0_noisy_grad_sigma_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, gmu, gsigma, N, K, r0, r1, noise_in, noise_out_w, noise_out_b);
-    return a0_fail_hip((int)hipGetLastError(), "a0_noisy_grad_sigma");
 }

@@ -1,5 +1,5 @@
 // One element of the Philox fills (rng.hip), as device functions: what a0_rng_uniform_kernel and a0_rng_normal_kernel write at position `pos` of stream
-// (seed, stream).  rng.hip's kernels and the network reset (optim.hip: a0_net_reset_kernel) both call these, so a reset's fresh values are bit for bit the values
+// (seed, stream).  rng.hip's kernels and the network reset (net_reset.hip: a0_net_reset_kernel) both call these, so a reset's fresh values are bit for bit the values
 // a fill at the same positions gives.  Every product here is rounded on its own (no contraction), as in the kernels these formulas were moved out of.
 #pragma once
 #include "philox.h"

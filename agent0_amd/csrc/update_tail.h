@@ -1,8 +1,9 @@
 // What the one-launch update tail (optim.hip: a0_update_tail_kernel) shares with the kernels it replaces per update: the row-group sums of
 // a0_reduce_segments_kernel (net.hip), the weight-copy layout and the bf16 terms of a0_conv_wt_kernel (encoder_fused.hip), and the one-thread
 // bookkeeping of an optimizer step (a0_step_decide / a0_step_publish), which every Adam form runs and the tail has run in the launch in front of it.
+// The scatter of a new weight into the weight copies is shared further: the soft target update (optim.hip), the reset and the recycle (net_reset.hip) use it too.
 #pragma once
-#include "a0_defs.h"
+#include "a0_internal.h"
 
 #include <cstdint>
 
@@ -57,6 +58,102 @@ A0_HD uint32_t a0_bf16_term(float w, int s) {
     const uint32_t mid = a0_bf16_trunc(r1);
     const float r2 = r1 - a0_bf16_up(mid);            // exact: at most 8 significant bits left
     return s == 0 ? hi : s == 1 ? mid : a0_bf16_trunc(r2);
+}
+
+// ---- the scatter into that layout (the inverse of a0_conv_wt_kernel's gather): the lane that holds a new convolution weight files it in the copies itself.
+// Where a new convolution weight goes in the fused kernels' copies `wt` (online) / `wt_t` (target): the one description the tail, the blend, the reset and the
+// recycle share.
+struct a0_wt_sink {
+    long long o1, o2, o3;                       // first weight of conv1 / conv2 / conv3 in the flat buffer
+    int K1, wt4;                                // wt4: o1, o2, o3 multiples of four (four consecutive k of one row per 16-byte lane)
+    float *wt, *wt_t;
+};
+// w: the convolution weights inside base[0, n_total) (`what`: the buffer's name in who's error text); wt may be NULL for a caller that files the target side only
+static int a0_wt_sink_make(a0_wt_sink* S, const char* who, const char* what, const float* base, long long n_total, const a0_encoder_weights* w, int C, float* wt, float* wt_target) {
+    const std::string name(who);
+    if (!w || !w->w1 || !w->w2 || !w->w3 || C < 1 || !wt_target) return a0_fail(A0_EINVAL, (name + ": weight copies need the encoder weights, C >= 1 and the copies' buffers").c_str());
+    if (!a0_aligned(16, wt, wt_target)) return a0_fail(A0_EINVAL, (name + ": the weight copies must be 16-byte aligned").c_str());
+    *S = a0_wt_sink{w->w1 - base, w->w2 - base, w->w3 - base, C * 64, 0, wt, wt_target};
+    if (S->o1 < 0 || S->o1 + 32LL * S->K1 > n_total || S->o2 < 0 || S->o2 + 64 * 512 > n_total || S->o3 < 0 || S->o3 + 64 * 576 > n_total)
+        return a0_fail(A0_EINVAL, (name + ": the convolution weights must lie inside " + what + "[0, n_total)").c_str());
+    S->wt4 = ((S->o1 | S->o2 | S->o3) % 4 == 0) ? 1 : 0;
+    return A0_OK;
+}
+
+A0_D void a0_tail_put16(const a0_wt_sink& A, bool to_online, bool to_target, long long u16, uint32_t bits) {
+    if (to_online) ((uint16_t*)A.wt)[u16] = (uint16_t)bits;
+    if (to_target) ((uint16_t*)A.wt_t)[u16] = (uint16_t)bits;
+}
+A0_D void a0_tail_put32(const a0_wt_sink& A, bool to_online, bool to_target, int dw, uint32_t bits) {
+    if (to_online) ((uint32_t*)A.wt)[dw] = bits;
+    if (to_target) ((uint32_t*)A.wt_t)[dw] = bits;
+}
+// dword of term s of weight (n, k) in an a0_wring1 / a0_wring9 segment of N columns: uint4 ((t*N + n)*4 + q)*3 + s holds k = 32t + 8q .. +7; a dword is two consecutive k
+A0_D int a0_tail_term_dword(int N, int n, int k, int s) { return ((((k >> 5) * N + n) * 4 + ((k >> 3) & 3)) * 3 + s) * 4 + ((k >> 1) & 3); }
+// the data-gradient copies of one weight: conv3's flipped taps, conv2's stride phases (see a0_conv_wt_kernel)
+A0_D void a0_tail_wt_dgrad(const a0_wt_sink& A, bool to_online, bool to_target, const a0_wt_layout& T, bool c3, int co, int k, float w) {
+    int base, N, n, kk;
+    if (c3) {              // k = (kh*3 + kw)*64 + ci  ->  n = ci, k' = ((2-kh)*3 + (2-kw))*64 + co
+        const int cell = k >> 6;
+        n = k & 63; kk = (8 - cell) * 64 + co; base = T.dgrad3x(); N = 64;
+    } else {               // k = (kh*4 + kw)*32 + ci  ->  phase (kh & 1, kw & 1), n = ci, k' = ((1 - kh/2)*2 + (1 - kw/2))*64 + co
+        const int tap = k >> 5, kh = tap >> 2, kw = tap & 3;
+        n = k & 31; kk = ((1 - (kh >> 1)) * 2 + (1 - (kw >> 1))) * 64 + co; base = T.dgrad2x() + ((kh & 1) * 2 + (kw & 1)) * T.n_dgrad2x_phase; N = 32;
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * (base + a0_tail_term_dword(N, n, kk, s)) + (kk & 1), a0_bf16_term(w, s));
+}
+// every copy of the weight at flat index idx (new value w): nothing to do outside the three convolution weight blocks
+A0_D void a0_tail_wt1(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, float w) {
+    const a0_wt_layout T{A.K1 / 64};
+    if (idx >= A.o1 && idx < A.o1 + 32LL * A.K1) {
+        const int e = (int)(idx - A.o1), n = e / A.K1, k = e - n * A.K1;
+        const float x = w / 255.0f;             // conv1 multiplies raw bytes: the reference's /255 is folded in here
+#pragma unroll
+        for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * (T.conv1x() + a0_tail_term_dword(32, n, k, s)) + (k & 1), a0_bf16_term(x, s));
+    } else if ((idx >= A.o2 && idx < A.o2 + 64 * 512) || (idx >= A.o3 && idx < A.o3 + 64 * 576)) {
+        const bool c3 = idx >= A.o3 && idx < A.o3 + 64 * 576;
+        const int K = c3 ? 576 : 512, e = (int)(idx - (c3 ? A.o3 : A.o2)), n = e / K, k = e - n * K;
+        // fp32, a0_wring layout: float ((c*64 + n)*4 + q)*4 + j holds W[n][k = 16c + 4j + q]
+        a0_tail_put32(A, to_online, to_target, (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4 + (k & 3)) * 4 + ((k >> 2) & 3), __float_as_uint(w));
+#pragma unroll
+        for (int s = 0; s < 3; ++s) a0_tail_put16(A, to_online, to_target, 2LL * ((c3 ? T.conv3x() : T.conv2x()) + a0_tail_term_dword(64, n, k, s)) + (k & 1), a0_bf16_term(w, s));
+        a0_tail_wt_dgrad(A, to_online, to_target, T, c3, n, k, w);
+    }
+}
+// four consecutive weights idx .. idx + 3 of one row (idx a multiple of four floats behind its block's start): the terms of four k are 8 adjacent bytes
+A0_D void a0_tail_wt4(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, const a0_f4& pv) {
+    const a0_wt_layout T{A.K1 / 64};
+    const float w[4] = {pv.x, pv.y, pv.z, pv.w};
+    int base, N, n, k;
+    bool c1 = false, c3 = false;
+    if (idx >= A.o1 && idx < A.o1 + 32LL * A.K1) { const int e = (int)(idx - A.o1); n = e / A.K1; k = e - n * A.K1; base = T.conv1x(); N = 32; c1 = true; }
+    else if (idx >= A.o2 && idx < A.o2 + 64 * 512) { const int e = (int)(idx - A.o2); n = e >> 9; k = e & 511; base = T.conv2x(); N = 64; }
+    else if (idx >= A.o3 && idx < A.o3 + 64 * 576) { const int e = (int)(idx - A.o3); n = e / 576; k = e - n * 576; base = T.conv3x(); N = 64; c3 = true; }
+    else return;
+    float x[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = c1 ? w[e] / 255.0f : w[e];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const uint2 t{a0_bf16_term(x[0], s) | (a0_bf16_term(x[1], s) << 16), a0_bf16_term(x[2], s) | (a0_bf16_term(x[3], s) << 16)};
+        const int dw = base + a0_tail_term_dword(N, n, k, s);          // k a multiple of four: an even dword
+        if (to_online) *(uint2*)((uint32_t*)A.wt + dw) = t;
+        if (to_target) *(uint2*)((uint32_t*)A.wt_t + dw) = t;
+    }
+    if (c1) return;
+    const int ring = (c3 ? T.conv3() : T.conv2()) + (((k >> 4) * 64 + n) * 4) * 4 + ((k >> 2) & 3);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        a0_tail_put32(A, to_online, to_target, ring + 4 * e, __float_as_uint(w[e]));
+        a0_tail_wt_dgrad(A, to_online, to_target, T, c3, n, k + e, w[e]);
+    }
+}
+
+// four consecutive weights held by one lane
+A0_D void a0_tail_wt_f4(const a0_wt_sink& A, bool to_online, bool to_target, long long idx, const a0_f4& pv) {
+    if (A.wt4) a0_tail_wt4(A, to_online, to_target, idx, pv);
+    else { a0_tail_wt1(A, to_online, to_target, idx, pv.x); a0_tail_wt1(A, to_online, to_target, idx + 1, pv.y); a0_tail_wt1(A, to_online, to_target, idx + 2, pv.z); a0_tail_wt1(A, to_online, to_target, idx + 3, pv.w); }
 }
 
 // ---- an optimizer step's bookkeeping, one thread: NaN skip, step count, bias corrections, "sync now".  a0_step_decide is the only place that derives them; it reads

@@ -339,8 +339,9 @@ def test_sumtree_set_range_equals_batch_set(hip, size, start, n):
 
 
 def test_noisy_multi_equals_per_module_kernels(hip):
-    """a0_noisy_multi (all NoisyLinear modules of a network in one launch) against a0_noisy_compose / a0_noisy_grad_sigma per module:
-    bit-identical effective weights and sigma gradients (reference model.py:54-62,78-83)."""
+    """a0_noisy_multi (all NoisyLinear modules of a network in one launch: the four-wide kernel at these shapes) against a0_noisy_compose /
+    a0_noisy_grad_sigma per module (csrc/noisy.hip: always the element-wise kernel): bit-identical effective weights and sigma gradients
+    (reference model.py:54-62,78-83)."""
     g = recipe.gen(21)
     mods_spec = [(512, 3136, 0, 512), (256, 512, 0, 204), (256, 512, 204, 255)]      # fc1; q_head and value_head rows of one packed block
     def blk(N, K):
@@ -363,6 +364,44 @@ def test_noisy_multi_equals_per_module_kernels(hip):
         hip.noisy_grad_sigma(mu, gs_b, N, K, r0, r1, nin, now, nob)
     for (mu, sg, eff_a, eff_b, gs_a, gs_b) in blocks.values():
         assert torch.equal(eff_a, eff_b) and torch.equal(gs_a, gs_b)
+
+
+@pytest.mark.parametrize("N,K,r0,r1", [(8, 6, 2, 7), (8, 8, 0, 8)])
+def test_noisy_multi_against_float64(hip, N, K, r0, r1):
+    """a0_noisy_multi's two kernels on their own, each in a call of its own (one module that is unaligned or has K % 4 != 0 sends the whole call to the
+    element-wise kernel): K = 6 runs a0_noisy_multi_kernel, K = 8 on aligned blocks a0_noisy_multi_v4_kernel.  Compose and grad against float64 of
+    mu + sigma * f(eps_out) * f(eps_in) (bias: f(eps_b)) and gmu * eps on the float32 inputs, f(x) = sign(x) sqrt|x|; every word outside the rows [r0, r1) of the
+    weight block and the bias entries r0 .. r1 - 1 keeps the sentinel it was filled with.
+    Tolerance per element, derived: sqrt is correctly rounded in this build, so eps carries three roundings (two square roots, their product), sigma * eps a
+    fourth and the sum a fifth (none, if fused) of at most 2^-24 relative each; one more unit for second-order terms: 6 * 2^-24 * (|mu| + |sigma * eps|) for
+    compose, 5 * 2^-24 * |gmu * eps| for grad (four roundings)."""
+    g = recipe.gen(100 * K + r0)
+    rows, n = r1 - r0, N * K + N
+    mu, sg = g.standard_normal(n).astype(np.float32), (0.5 * g.standard_normal(n)).astype(np.float32)
+    nin, now, nob = (g.standard_normal(m).astype(np.float32) for m in (K, rows, rows))
+    nin[1] = 0.0                                     # f(0) = 0: a column without noise
+    f = lambda x: np.sign(x.astype(np.float64)) * np.sqrt(np.abs(x.astype(np.float64)))
+    eps = np.zeros(n)
+    inside = np.zeros(n, bool)
+    eps[r0 * K:r1 * K] = np.outer(f(now), f(nin)).reshape(-1)
+    eps[N * K + r0:N * K + r1] = f(nob)
+    inside[r0 * K:r1 * K] = inside[N * K + r0:N * K + r1] = True
+    SENT = np.float32(7.5e33)
+    u = 2.0 ** -24
+    for grad in (False, True):
+        out = D(hip, np.full(n, SENT, np.float32))
+        hip.noisy_multi(grad, [(D(hip, mu), None if grad else D(hip, sg), out, N, K, r0, r1, D(hip, nin), D(hip, now), D(hip, nob))])
+        got = out.cpu().numpy()
+        assert np.array_equal(got[~inside].view(np.int32), np.full(n - int(inside.sum()), SENT, np.float32).view(np.int32)), f"grad={grad}: a word outside the module's rows was written"
+        if grad:
+            want = mu.astype(np.float64) * eps
+            tol = 5 * u * np.abs(want)
+        else:
+            want = mu.astype(np.float64) + sg.astype(np.float64) * eps
+            tol = 6 * u * (np.abs(mu.astype(np.float64)) + np.abs(sg.astype(np.float64) * eps))
+        err = np.abs(got.astype(np.float64) - want)[inside]
+        print(f"noisy_multi N={N} K={K} rows [{r0}, {r1}) grad={grad}: max err / tol = {np.max(err / np.maximum(tol[inside], 1e-300)):.3f}")
+        assert np.all(err <= tol[inside]), f"grad={grad}: {int(np.sum(err > tol[inside]))} elements beyond the bound"
 
 
 @pytest.mark.parametrize("n,R", [(2, 512), (3, 512), (2, 300), (3, 1024)])

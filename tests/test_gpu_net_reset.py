@@ -8,7 +8,7 @@
 7. DeviceLearner and the a0_learner handle: the reset at the right update, a fresh optimizer afterwards; off == the learner without the argument.
 8. the Trainer: handles == Python classes (eager and hipGraph) on main, launch and one-rank data parallelism; snapshots across a reset; the statistic.
 
-Work split of the kernel (csrc/optim.hip): a lane owns four consecutive elements; 16 bytes at once where the buffers are 16-byte aligned and the four lie inside one
+Work split of the kernel (csrc/net_reset.hip): a lane owns four consecutive elements; 16 bytes at once where the buffers are 16-byte aligned and the four lie inside one
 segment (or between two) and the reset's first draw position k * n_total is a multiple of four, element by element otherwise.  Shapes: 5 (one group and a tail of one), 1025 (two workgroups, a tail of one), 77 824 + 37 (C = 4's three
 convolution blocks and a ragged tail: 77 workgroups); every table below has segment boundaries off the 16-byte grid."""
 import csv

@@ -8,7 +8,7 @@ a0_redo_recycle and everything that issues them, against the numpy restatement t
    zero moments exactly where touched, the weight copy == a0_net_conv_wt_refresh of the result; the self-deciding gate of both entry points.
 3. DeviceLearner and the a0_learner handle beside a twin without the setting.   4. the Trainer on both loops, a snapshot across a recycle, every setting at once.
 
-Work split of the kernels (csrc/optim.hip): scoring — a lane owns four channels of every (1024 / n)-th row of its workgroup's rows, four rows in flight; a
+Work split of the kernels (csrc/net_reset.hip): scoring — a lane owns four channels of every (1024 / n)-th row of its workgroup's rows, four rows in flight; a
 layer engages one workgroup per eight workgroup steps (32 / 16 / 2 rows each) of its rows, at most 512, and the finish adds that many partials in eight slices.
 So the row counts below cover one row (one workgroup, one slice), counts below and off a step, 130 rows of 512 (9 workgroups: slices of 2, the last ones
 empty), 567 rows of 64 (5 workgroups) and 2000 rows of 32 (8 workgroups, one per slice); the learner tests add 3200 / 648 / 392 / 128 rows.  Recycling — element
