@@ -40,6 +40,13 @@ A0_D float a0_blend1(float t, float p, float tau) {
     asm volatile("" : "+v"(d));
     return __builtin_fmaf(tau, d, t);
 }
+// "This update fires" for an action of period freq (net_reset.hip, feature_rank.hip): it was not NaN-skipped (state[3]) and left update_steps (state[1]) a positive
+// multiple of freq; or `force`.  On every other update such a kernel returns after reading these two words.
+A0_D bool a0_period_fires(const int* __restrict__ state, int freq, int force) {
+    if (force) return true;
+    const int steps = state[1];
+    return state[3] == 0 && freq > 0 && steps > 0 && steps % freq == 0;
+}
 #endif
 
 // status codes returned by every exported function (include/agent0_hip.h)

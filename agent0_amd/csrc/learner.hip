@@ -445,6 +445,34 @@ extern "C" int a0_learner_redo_buffers(const a0_learner* L, float** scores_dev, 
     return A0_OK;
 }
 
+extern "C" int a0_learner_set_feature_rank(a0_learner* L, int freq, double delta) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_feature_rank: null handle");
+    if (L->updated) return a0_fail(A0_EINVAL, "a0_learner_set_feature_rank: the setting is fixed once the handle has run an update");
+    if (freq < 0) return a0_fail(A0_EINVAL, "a0_learner_set_feature_rank: freq < 0 (0 is off)");
+    if (!(delta > 0.0) || !(delta < 1.0)) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "a0_learner_set_feature_rank: delta = %g must lie in the open interval (0, 1)", delta);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    L->rank_freq = freq; L->rank_delta = delta;
+    if (freq > 0 && !L->rank_gram) {
+        L->rank_gram = L->alloc<double>((long long)A0_RANK_GRAM_DOUBLES);
+        L->rank_spectrum = L->alloc<double>(A0_RANK_FEATURES, true); L->rank_result = L->alloc<int>(8, true);
+        const int never = -1;
+        A0_HIP_THROW(hipMemcpy(L->rank_result + 2, &never, sizeof never, hipMemcpyHostToDevice));
+    }
+    return A0_OK;
+    A0_CATCH
+}
+
+extern "C" int a0_learner_feature_rank_buffers(const a0_learner* L, double** spectrum_dev, int** result_dev) {
+    if (!L || !spectrum_dev || !result_dev) return a0_fail(A0_EINVAL, "a0_learner_feature_rank_buffers: null argument");
+    const bool on = L->rank_freq > 0;
+    *spectrum_dev = on ? L->rank_spectrum : nullptr; *result_dev = on ? L->rank_result : nullptr;
+    return A0_OK;
+}
+
 extern "C" int a0_learner_set_aug_shift(a0_learner* L, int pad) {
     A0_TRY
     if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_aug_shift: null handle");
@@ -849,6 +877,12 @@ static int a0_apply(a0_upd& u, float* loss_out) {
                                       L->wt_on, L->wt_tg, L->loss, B, L->loss_ring, L->loss_ring_cap, stream));
     }
     if (L->target_tau > 0.0) A0_CHECK(a0_target_blend(tg, on, L->n_pad, L->target_tau, L->state, L->d.target_update_freq, 0, &u.w_tg, L->C, L->wt_tg, stream));
+    // learner.rank_freq: the feature rank of the differentiated pass's fc1 activations (the rows a0_redo_score gets); both launches return at once on other updates
+    if (L->rank_freq > 0) {
+        const bool quantile = L->fam == A0_FAM_IQN || L->fam == A0_FAM_FQF;
+        A0_CHECK(a0_feature_rank(quantile ? L->qo.h : L->h, quantile ? L->qo.R : (long long)B, L->rank_delta, L->state, L->rank_freq, 0, L->rank_gram, L->rank_spectrum, L->rank_result,
+                                 stream));
+    }
     // learner.redo_freq: scores, mask and counts from the differentiated pass's activations, then the recycle launch; all three return at once on other updates
     if (L->redo_freq > 0) {
         const bool quantile = L->fam == A0_FAM_IQN || L->fam == A0_FAM_FQF;

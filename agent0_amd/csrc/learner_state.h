@@ -93,6 +93,11 @@ struct a0_learner {
     double* redo_partials = nullptr;
     float* redo_scores = nullptr;
     int *redo_mask = nullptr, *redo_counts = nullptr;
+    // ---- feature rank (a0_learner_set_feature_rank): off while rank_freq == 0; the buffers exist only while it is on
+    int rank_freq = 0;
+    double rank_delta = 0.01;
+    double *rank_gram = nullptr, *rank_spectrum = nullptr;
+    int* rank_result = nullptr;
     // ---- DrQ random shift of the batch (a0_learner_set_aug_shift): off while aug_pad == 0; aug_stage: the dense augmented batch [B][2 * C * H * W], allocated by the first call that switches it on
     int aug_pad = 0;
     uint8_t* aug_stage = nullptr;

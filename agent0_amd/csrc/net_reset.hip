@@ -5,13 +5,7 @@
 #include "rng_elem.h"
 #include "update_tail.h"
 
-// "This update fires" for an action of period freq: it was not NaN-skipped (state[3]) and left update_steps (state[1]) a positive multiple of freq; or `force`.
-// On every other update the kernels below return after reading these two words.
-A0_D bool a0_period_fires(const int* __restrict__ state, int freq, int force) {
-    if (force) return true;
-    const int steps = state[1];
-    return state[3] == 0 && freq > 0 && steps > 0 && steps % freq == 0;
-}
+// a0_period_fires ("this update fires" for an action of period freq): a0_defs.h, shared with feature_rank.hip.
 // ... and which one it is: k = update_steps / freq, or the caller's under `force`.  Fresh values are positioned by (k, flat index).
 A0_D long long a0_period_index(const int* __restrict__ state, int freq, int force, long long k_host) { return force ? k_host : (long long)(state[1] / freq); }
 // the seed (32 bits) travels in a vector register: Philox's key schedule of a uniform seed would be hoisted into twenty scalar registers for the whole loop

@@ -654,7 +654,8 @@ class BaseLearner:
                                     target_update_freq=lc.target_update_freq, vmin=lc.c51.vmin, vmax=lc.c51.vmax, K=lc.iqn.K, N=lc.iqn.N, N_dash=lc.iqn.N_dash,
                                     max_grad_norm=lc.max_grad_norm, mdqn_tau=lc.mdqn.tau, mdqn_lo=lc.mdqn.lo, clip_grad_norm=lc.clip_grad_norm, target_tau=lc.target_tau,
                                     aug_shift=lc.aug_shift, aug_rng=self.rng, net_reset_freq=lc.net_reset_freq, net_reset_shrink=lc.net_reset_shrink,
-                                    weight_decay=lc.weight_decay, redo_freq=lc.redo_freq, redo_tau=lc.redo_tau, redo_recycle=lc.redo_recycle)
+                                    weight_decay=lc.weight_decay, redo_freq=lc.redo_freq, redo_tau=lc.redo_tau, redo_recycle=lc.redo_recycle,
+                                    rank_freq=lc.rank_freq, rank_delta=lc.rank_delta)
         self.model = DeepQNet(cfg, ops=ops, dev_net=self.engine.online, rng=self.rng)
         self.model_target = DeepQNet(cfg, ops=ops, dev_net=self.engine.target, rng=self.rng)
         self.engine.sync_target(force=True)                 # model_target = deepcopy(model), agent.py:100

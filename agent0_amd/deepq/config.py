@@ -73,6 +73,17 @@ Additions (all default to the reference's behaviour being available):
   learner.redo_tau  float in [0, 1), default 0.1 (the paper's recycling threshold; anything else, NaN included, is refused with the number named).  0 counts only
                    neurons that are exactly silent; the paper's diagnostic uses 0.025.  Without ``learner.redo_freq`` it does nothing.
   learner.redo_recycle  bool, default true.  false measures only.  true together with ``learner.noisy_net`` is refused: ReDo is undefined for mu / sigma pairs.
+  learner.rank_freq  int, default 0 (off; negative values are refused).  N > 0: after every update that was not NaN-skipped and left ``update_steps`` a positive
+                   multiple of N the feature rank of Kumar et al. 2021 (srank_delta) is taken on the device from the fc1 activations X [rows][512] of that update's
+                   differentiated pass (rows = the batch; the B * N rows of that pass for iqn / fqf): G = X^T X accumulated in double on the fp64 matrix pipe, its
+                   512 eigenvalues, sigma_i = sqrt(lambda_i) with sigma_i = 0 where lambda_i <= 512 * 2^-52 * lambda_1, and the smallest k whose leading sigmas
+                   reach the share 1 - ``learner.rank_delta`` of their sum (a0_feature_rank, two launches behind the update).  Nothing the update uses is written: a
+                   run with the setting on is bit-identical to the same run with it off, so it is allowed under the data-parallel path (every rank evaluates
+                   its own batch, rank 0's number is logged; verified on one rank only).  Adds the statistic ``feature_rank`` (NaN until the first evaluation and
+                   after a resume, and when an activation was not finite); ``DeviceLearner.feature_spectrum()`` returns the 512 sigmas.  No state of its own,
+                   nothing new in a snapshot, and the setting may change across a resume.
+  learner.rank_delta  float in the open interval (0, 1), default 0.01 (the paper's delta; anything else, NaN included, is refused with the number named).  Without
+                   ``learner.rank_freq`` it does nothing.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -172,6 +183,8 @@ class LearnerConfig:
     redo_freq: int = 0
     redo_tau: float = 0.1
     redo_recycle: bool = True
+    rank_freq: int = 0
+    rank_delta: float = 0.01
     learner_steps: int = 20
     double_q: bool = False
     dueling_head: bool = False

@@ -127,6 +127,20 @@ def redo_value(freq, tau=0.1, recycle=True, noisy=False, data_parallel: Optional
     return n, t, rec
 
 
+def rank_value(freq, delta=0.01):
+    """``learner.rank_freq`` / ``learner.rank_delta`` as the learner uses them: ``(N, delta)``, N = 0 (off) for zero or None.  Refused: a negative or fractional N, a
+    delta that is not a number in the open interval (0, 1) (checked whether or not N is on).  Allowed under the data-parallel path: the evaluation writes nothing
+    the update uses, so the replicas cannot diverge."""
+    if freq is None:
+        freq = 0
+    if isinstance(freq, bool) or int(freq) != freq or freq < 0:
+        raise ValueError(f"learner.rank_freq={freq!r}: must be a whole number of updates >= 0 (0 is off)")
+    d = 0.01 if delta is None else float(delta)
+    if not (0.0 < d < 1.0):
+        raise ValueError(f"learner.rank_delta={delta!r}: must be a number in the open interval (0, 1)")
+    return int(freq), d
+
+
 class Workspace:
     """Activations of one forward pass over ``B`` observations (``n_tau`` quantile samples each for IQN/FQF)."""
 
@@ -422,7 +436,7 @@ class DeviceLearner:
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
                  mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0,
-                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True):
+                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True, rank_freq=0, rank_delta=0.01):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -494,6 +508,19 @@ class DeviceLearner:
             self.redo_counts[5] = -1                   # never evaluated
             if self.redo_recycle:
                 self.redo_segs = L.reset_segments()
+        # learner.rank_freq = N > 0: apply() issues two launches more (a0_feature_rank) that leave the singular values of the fc1 activations and their srank after
+        # every N-th successful update — behind the blend, in front of the dormancy and reset launches; both return at once on other updates and write nothing the
+        # update uses.  Off (0): no buffer, no launch.
+        self.rank_freq, self.rank_delta = rank_value(rank_freq, rank_delta)
+        self.rank_gram = self.rank_spectrum = self.rank_result = None
+        self.rank_views = None          # a learner handle's own (spectrum, result) while NativeLoop drives the updates: what feature_spectrum() then reads
+        if self.rank_freq > 0:
+            if not hasattr(ops, "feature_rank"):
+                raise ValueError(f"learner.rank_freq={self.rank_freq}: needs a backend with feature_rank")
+            self.rank_gram = ops.empty(ops.RANK_GRAM_DOUBLES, dtype=torch.float64)
+            self.rank_spectrum = ops.zeros(ops.RANK_FEATURES, dtype=torch.float64)
+            self.rank_result = ops.zeros(8, dtype=torch.int32)
+            self.rank_result[2] = -1                   # never evaluated
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -595,6 +622,23 @@ class DeviceLearner:
         L, on, tg = self.L, self.online, self.target
         self.ops.net_reset(on.flat, tg.flat, self.adam_m, self.adam_v, L.n_adam, L.n_params_padded, self.reset_segs, self.net_reset_shrink, self.reset_seed(), self.state,
                            self.net_reset_freq, force, k_host, *((on.encoder_weights(), L.C, on.wt, tg.wt) if on.fused else ()))
+
+    def _feature_rank(self, force=False):
+        """learner.rank_freq: behind the Adam form and the blend, in front of the dormancy and reset launches — Gram matrix, spectrum and srank of the fc1 activations
+        the differentiated pass has left in ``ws_o`` (for iqn / fqf that pass's B * N rows, what ``_redo`` scores); the two launches act when this update was not
+        NaN-skipped and left the step count a positive multiple of the period (or ``force``) and return at once otherwise.  They only read the activations."""
+        if self.rank_freq <= 0:
+            return
+        h = self.ws_o.h
+        self.ops.feature_rank(h, h.numel() // self.ops.RANK_FEATURES, self.rank_delta, self.state, self.rank_freq, force, self.rank_gram, self.rank_spectrum, self.rank_result)
+
+    def feature_spectrum(self):
+        """The 512 singular values (descending, zero under the floor) of the fc1 activations at the newest evaluation of learner.rank_freq as a numpy array — what
+        entropy-based or stable rank need; None while the setting is off and before the first evaluation."""
+        if self.rank_freq <= 0:
+            return None
+        spectrum, result = self.rank_views or (self.rank_spectrum, self.rank_result)
+        return spectrum.cpu().numpy() if int(result[2]) >= 0 else None
 
     def _redo(self, force=False, k_host=0):
         """learner.redo_freq: behind the Adam form and the blend, in front of the reset launch — scores, mask and counts from the activations the differentiated pass
@@ -750,7 +794,8 @@ class DeviceLearner:
     def apply(self):
         """Adam on the flat buffer (NaN-skip and step counter on the device), refresh of the fused kernels' weight copies, target sync — with learner.weight_decay on
         behind the decay launch, with learner.target_tau on, the
-        blend of the target (``_blend_target``) behind whichever Adam form ran, with learner.redo_freq on the dormancy launches (``_redo``) behind that, and with
+        blend of the target (``_blend_target``) behind whichever Adam form ran, with learner.rank_freq on the feature-rank launches (``_feature_rank``) and with
+        learner.redo_freq on the dormancy launches (``_redo``) behind that, and with
         learner.net_reset_freq on the reset launch (``_reset_net``) last."""
         L, ops, on, tg = self.L, self.ops, self.online, self.target
         if L.algo == "fqf":           # unconditional, like the reference's fqf_optimizer.step() in front of the NaN guard (agent.py:139-148)
@@ -776,6 +821,7 @@ class DeviceLearner:
             # fused: two launches — Adam with its bookkeeping and the target copy folded in; the online conv copies, mirrored to the target's on a sync
             (ops.adam_step_sync_wt if on.fused else ops.adam_step_sync)(*adam, *wt)
         self._blend_target()
+        self._feature_rank()
         self._redo()
         self._reset_net()
 

@@ -156,7 +156,7 @@ def eligible(tr) -> Optional[str]:
 class NativeLoop:
     def __init__(self, tr):
         self.tr = tr
-        self.learner = self.rbuf = self.actor = self.stage = self.redo_views = None        # close() destroys whatever exists, also when a later create call fails
+        self.learner = self.rbuf = self.actor = self.stage = self.redo_views = self.rank_views = None        # close() destroys whatever exists, also when a later create call fails
         self.lib, self.ok = _abi.load(), _abi.check
         try:
             self._create(tr)
@@ -216,6 +216,10 @@ class NativeLoop:
                "a0_learner_set_redo")
             from agent0_amd.ops import redo_buffer_views
             self.redo_views = redo_buffer_views(lib, self.learner)      # (scores, mask, counts) over the handle's own buffers: what the Trainer's statistics read
+        if eng.rank_freq > 0:           # learner.rank_freq: the handle issues the feature-rank launches behind the blend, in front of the dormancy launches, as DeviceLearner.apply does
+            ok(lib.a0_learner_set_feature_rank(self.learner, int(eng.rank_freq), C.c_double(eng.rank_delta)), "a0_learner_set_feature_rank")
+            from agent0_amd.ops import feature_rank_buffer_views
+            self.rank_views = eng.rank_views = feature_rank_buffer_views(lib, self.learner)      # (spectrum, result) over the handle's own buffers: what the Trainer's statistic reads
         if eng.aug_shift > 0:           # learner.aug_shift: the handle shifts the batch into a stage buffer of its own ahead of its passes, as DeviceLearner.forward_dense does
             ok(lib.a0_learner_set_aug_shift(self.learner, int(eng.aug_shift)), "a0_learner_set_aug_shift")
         if not actor.fc1_planes:        # Actor.fc1_planes = False (comparisons): every step's fc1 on the general GEMM instead of a0_actor_fc1_kernel, as in Actor._rollout
@@ -496,4 +500,5 @@ class NativeLoop:
                       (self.learner, self.lib.a0_learner_destroy)):
             if h is not None and h.value:
                 fn(h)
-        self.actor = self.rbuf = self.learner = self.stage = self.redo_views = None      # the views die with the learner handle
+        self.actor = self.rbuf = self.learner = self.stage = self.redo_views = self.rank_views = None      # the views die with the learner handle
+        self.tr.learner.engine.rank_views = None

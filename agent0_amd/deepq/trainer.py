@@ -532,7 +532,8 @@ class Trainer:
         """The result dict of trainer.py:111-118; with learner.clip_grad_norm on also ``grad_norm``, the mean pre-clip gradient norm over the last block's updates; with
         learner.net_reset_freq on also ``net_resets`` = update_steps // N; with learner.weight_decay on also ``param_norm``, the L2 norm of everything Adam owns in
         front of the decay of the last block's last update; with learner.redo_freq on also ``dormant_frac`` and ``dormant_frac_conv1|conv2|conv3|fc1``, the share of
-        dormant neurons at the newest evaluation, overall and per layer."""
+        dormant neurons at the newest evaluation, overall and per layer; with learner.rank_freq on also ``feature_rank``, srank_delta of the fc1 activations at the
+        newest evaluation."""
         eng = self.learner.engine
         out = self._result_base()
         if eng.gnorm_ring is not None:
@@ -547,6 +548,11 @@ class Trainer:
             out["dormant_frac"] = c[4] / float(REDO_NEURONS) if seen else float("nan")
             for (name, _, n), k in zip(REDO_LAYERS, c[:4]):
                 out[f"dormant_frac_{name}"] = k / float(n) if seen else float("nan")
+        # learner.rank_freq: the newest evaluation's rank (one small read more per logged iteration); NaN until there is one and for -1 (a non-finite activation).
+        # An engine stand-in written before the setting existed has no such field.
+        if getattr(eng, "rank_freq", 0) > 0:
+            r = (self._nl.rank_views[1] if self._nl else eng.rank_result).tolist()      # the handle evaluates into buffers of its own
+            out["feature_rank"] = float(r[0]) if r[2] >= 0 and r[0] >= 0 else float("nan")
         return out
 
     def _result_base(self):
@@ -610,6 +616,8 @@ class Trainer:
                 msg += f"{k}: {v} | "
             elif k.startswith("dormant_frac"):
                 msg += f"{k}: {v:.3f} | "
+            elif k == "feature_rank":
+                msg += f"{k}: {v:.0f} | "
             elif k in ["frames", "loss", "qmax", "fps", "grad_norm", "param_norm"] or "return" in k:
                 msg += f"{k}: {v:.2f} | "
         self.logger.info(msg)
@@ -628,6 +636,7 @@ class Trainer:
                 cols = cols + (("net_resets",) if "net_resets" in result else ())               # only with learner.net_reset_freq on
                 cols = cols + (("param_norm",) if "param_norm" in result else ())               # only with learner.weight_decay on
                 cols = cols + tuple(k for k in REDO_COLUMNS if k in result)                      # only with learner.redo_freq on
+                cols = cols + (("feature_rank",) if "feature_rank" in result else ())           # only with learner.rank_freq on
                 if new:
                     w.writerow(cols)
                 w.writerow(["" if result.get(k) is None else result[k] for k in cols])

@@ -76,6 +76,21 @@ def redo_buffer_views(lib, handle):
     return view(sc, HipOps.REDO_NEURONS, "<f4"), view(mk, HipOps.REDO_NEURONS, "<i4"), view(ct, 8, "<i4")
 
 
+def feature_rank_buffer_views(lib, handle):
+    """(spectrum, result) of a learner handle's feature-rank evaluation as tensors over the handle's own memory — valid while the handle lives
+    (a0_learner_feature_rank_buffers); None while learner.rank_freq is off."""
+    sp, rs = C.c_void_p(), C.c_void_p()
+    check(lib.a0_learner_feature_rank_buffers(handle, C.addressof(sp), C.addressof(rs)), "a0_learner_feature_rank_buffers")
+    if not rs.value:
+        return None
+
+    def view(ptr, n, typestr):
+        v = type("_Rank", (), {"__cuda_array_interface__": {"shape": (n,), "typestr": typestr, "data": (int(ptr.value), False), "version": 3}})()
+        return torch.as_tensor(v, device="cuda")
+
+    return view(sp, HipOps.RANK_FEATURES, "<f8"), view(rs, 8, "<i4")
+
+
 class NativeLearner:
     """``a0_learner``: a whole learner (dqn; c51, also with NoisyLinear layers; dueling; double-Q; n-step) behind one handle whose HBM the library owns; ``update`` is BaseLearner.train as ONE
     C call (include/agent0_hip.h).  What a non-Python host binds; here it exists for the parity test against the per-kernel composition of deepq/engine.py."""
@@ -158,6 +173,15 @@ class NativeLearner:
     def redo_buffers(self):
         """Copies of the handle's (scores float[672], mask int[672], counts int[8]) (a0_learner_redo_buffers); None while the setting is off."""
         views = redo_buffer_views(self.lib, self.h)
+        return None if views is None else tuple(v.clone() for v in views)
+
+    def set_feature_rank(self, freq, delta):
+        """learner.rank_freq / rank_delta through the handle (a0_learner_set_feature_rank): before the first update; freq 0 is off."""
+        check(self.lib.a0_learner_set_feature_rank(self.h, int(freq), float(delta)), "a0_learner_set_feature_rank")
+
+    def feature_rank_buffers(self):
+        """Copies of the handle's (spectrum double[512], result int[8]) (a0_learner_feature_rank_buffers); None while the setting is off."""
+        views = feature_rank_buffer_views(self.lib, self.h)
         return None if views is None else tuple(v.clone() for v in views)
 
     def set_aug_shift(self, pad):
@@ -678,6 +702,17 @@ class HipOps:
                                      _req(state, torch.int32, 8, "state", optional=bool(force)), int(freq), int(bool(force)),
                                      _req(partials, torch.float64, self.REDO_PARTIALS * n, "partials"), _req(scores, torch.float32, n, "scores"),
                                      _req(mask, torch.int32, n, "mask"), _req(counts, torch.int32, 8, "counts"), _stream()), "a0_redo_score")
+
+    RANK_FEATURES, RANK_GRAM_DOUBLES = 512, 2 * 512 * 512      # A0_RANK_FEATURES, A0_RANK_GRAM_DOUBLES (include/agent0_hip.h)
+
+    def feature_rank(self, fc1, rows, delta, state, freq, force, gram, spectrum, result):
+        """learner.rank_freq: srank_delta of the fc1 activations ``fc1`` [rows][512] in two launches that decide for themselves like ``redo_score`` (a0_feature_rank):
+        G = X^T X in double into the first half of ``gram``, the 512 singular values (descending, zero under the floor) into ``spectrum``, ``result`` int[8]:
+        [0] the rank (-1: an activation was not finite), [1] the number of singular values above the floor, [2] ``state[1]`` of the evaluation."""
+        rows, n = int(rows), self.RANK_FEATURES
+        check(self.lib.a0_feature_rank(_req(fc1, torch.float32, max(rows, 0) * n, "fc1"), rows, float(delta), _req(state, torch.int32, 8, "state", optional=bool(force)), int(freq),
+                                       int(bool(force)), _req(gram, torch.float64, self.RANK_GRAM_DOUBLES, "gram"), _req(spectrum, torch.float64, n, "spectrum"),
+                                       _req(result, torch.int32, 8, "result"), _stream()), "a0_feature_rank")
 
     def redo_recycle(self, params, exp_avg, exp_avg_sq, n_adam, n_total, segs, blocks, mask, seed, state, freq, force=False, k_host=0, w=None, C_=0, wt=None):
         """learner.redo_freq: one launch that decides like ``redo_score`` (a0_redo_recycle; recycle number ``k_host`` with ``force``) — the neurons ``mask`` marks get

@@ -496,6 +496,27 @@ int a0_redo_score(const float* act1, long long rows1, const float* act2, long lo
 int a0_redo_recycle(float* params, float* exp_avg, float* exp_avg_sq, long long n_adam, long long n_total, const a0_net_reset_seg* segs, int n_segs,
                     const a0_redo_blocks* blocks, const int* mask, unsigned long long seed, const int* state, int freq, int force, long long k_host,
                     const a0_encoder_weights* w, int C, float* wt, void* stream);
+/* Feature rank (learner.rank_freq / learner.rank_delta): srank_delta of Kumar et al. 2021, "Implicit Under-Parameterization Inhibits Data-Efficient Deep RL", for the
+ * fc1 activations of an update's differentiated pass — fc1 [rows][512], fp32, 16-byte aligned, rows >= 1: the buffer A0_PEEK_FC1 names, exactly what a0_redo_score is
+ * given as its fourth layer.  Two launches that decide for themselves like a0_redo_score: they act when force != 0, or when state[3] == 0, freq > 0, state[1] > 0 and
+ * state[1] % freq == 0; otherwise every workgroup returns after reading those two words (state may be NULL with force).  Issue them behind an update's Adam form and
+ * a0_target_blend, in front of a0_redo_score and a0_net_reset.  The activations are only read.
+ *  1. G = X^T X (512 x 512) on the fp64 matrix pipe: every lane converts its fp32 element to double, so every product is exact and only the additions round; one
+ *     workgroup owns a 64 x 64 tile and walks all rows in order (rows past `rows` count as zeros), an element [i][j], j >= i, is stored at [i][j] and [j][i]: G is
+ *     bitwise symmetric and the same from run to run.  No atomics.
+ *  2. One workgroup: the eigenvalues l_1 >= ... >= l_512 of G in double (Householder tridiagonalisation of a copy, Sturm bisection with LAPACK dstebz's pivot
+ *     safeguard until the interval is two neighbouring doubles); s_i = sqrt(l_i), and s_i = 0 where l_i <= 512 * 2^-52 * l_1 (the floor: the Gram route cannot
+ *     resolve singular values below about 3e-7 * s_1, and tiny negative eigenvalues fall under it too);
+ *     feature_rank = min { k : (s_1 + ... + s_k) / (s_1 + ... + s_512) >= 1 - delta }, the sums taken in index order in double; 0 if every s_i is 0; -1 if a diagonal
+ *     element of G is not finite (the spectrum is then written as zeros).
+ * gram: A0_RANK_GRAM_DOUBLES doubles of work space, 8-byte aligned: [0, 512 * 512) holds G afterwards, the second half is the copy the eigenvalue stage destroys.
+ * Outputs: spectrum double[A0_RANK_FEATURES] (the s_i, descending), result int[8]: [0] feature_rank, [1] the number of s_i > 0, [2] state[1] of the evaluation (0
+ * with a NULL state; the caller initialises it to -1 = "never evaluated"), the rest spare and not written.
+ * A0_EINVAL, each with the argument named: a NULL fc1 / gram / spectrum / result, a NULL state without force, rows < 1, freq < 0, delta not in the open interval
+ * (0, 1) (NaN included; the number is named), misaligned buffers.  No scratch, no allocation, no host sync: capturable in a hipGraph. */
+#define A0_RANK_FEATURES 512
+#define A0_RANK_GRAM_DOUBLES (2 * A0_RANK_FEATURES * A0_RANK_FEATURES)
+int a0_feature_rank(const float* fc1, long long rows, double delta, const int* state, int freq, int force, double* gram, double* spectrum, int* result, void* stream);
 /* ---------------------------------------------------------------- a whole learner behind one handle (opaque handles, library-owned HBM)
  * BaseLearner (agent.py:97-169) with DQNLearner.train_step (173-190) for scalar heads on 4 x 84 x 84 observations — BASELINE configs[1]: online + target parameters
  * in the packed layout (agent0_amd/deepq/layout.py: conv1 | conv2 | conv3 | fc1 | head, each [W (N x K) | b (N)], head rows padded to a multiple of 32), gradients,
@@ -595,6 +616,14 @@ int a0_learner_net_reset_segs(const a0_learner* learner, a0_net_reset_seg* out, 
  * the first evaluation.  Descriptor structs are unchanged. */
 int a0_learner_set_redo(a0_learner* learner, int freq, double tau, int recycle, unsigned long long seed);
 int a0_learner_redo_buffers(const a0_learner* learner, float** scores_dev, int** mask_dev, int** counts_dev);
+/* learner.rank_freq / learner.rank_delta through the handle: with freq > 0 every a0_learner_update issues a0_feature_rank on the buffer A0_PEEK_FC1 names (for iqn /
+ * fqf the B * N rows of the differentiated pass, as a0_redo_score gets them) behind its Adam form and the blend, in front of the ReDo launches and a0_net_reset.
+ * freq == 0: off, nothing is allocated and the update issues what it always did.  A0_EINVAL: freq < 0, delta not in the open interval (0, 1) (the number is named), a
+ * call after the handle's first update.  The launches modify nothing the update uses, so a handle with a data-parallel exchange is allowed: every rank evaluates its
+ * own batch.  a0_learner_feature_rank_buffers: the handle's spectrum double[512] and result int[8] on the device (NULL each while the setting is off); result[2] is
+ * -1 until the first evaluation.  Descriptor structs are unchanged. */
+int a0_learner_set_feature_rank(a0_learner* learner, int freq, double delta);
+int a0_learner_feature_rank_buffers(const a0_learner* learner, double** spectrum_dev, int** result_dev);
 /* learner.aug_shift through the handle: with pad > 0 every a0_learner_update first issues a0_augment_shift (the caller's frames / slot / row_bytes, the handle's seed
  * and state words, so u = state[6]) into a stage buffer of B * 2 * C * H * W bytes that the handle allocates on the first such call, and then runs every pass — the
  * target and double-Q passes on st_next, the online pass and mdqn's target pass on st, conv1's weight gradient — on that buffer with a NULL slot; the caller's ring is
