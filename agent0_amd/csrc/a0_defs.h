@@ -47,6 +47,17 @@ A0_D bool a0_period_fires(const int* __restrict__ state, int freq, int force) {
     const int steps = state[1];
     return state[3] == 0 && freq > 0 && steps > 0 && steps % freq == 0;
 }
+// butterfly reductions over the 64 lanes of a wave: every lane ends with the result
+A0_D float a0_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+A0_D float a0_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 #endif
 
 // status codes returned by every exported function (include/agent0_hip.h)

@@ -169,17 +169,6 @@ A0_D void a0_actor_qhead_env_body(const a0_qenv_args& P, float* __restrict__ raw
 }
 
 // ---- the distributional / quantile counterpart (c51, qr; iqn, fqf): a0_actor_dist_tail_env_kernel's body (actor_tail.hip)
-A0_D float a0_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-A0_D float a0_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 struct a0_dtenv_args {
     const float* slabs; long long slab_stride; int nslab; const float* bias; int ld, A, T, dueling, mode; const float* atoms; int E;
     unsigned long long rng_seed; uint32_t stream_a, stream_u; unsigned long long off_a, off_u; float eps; const long long* ctrl; const float* eps_ptr;

@@ -1,6 +1,6 @@
 """GPU (MI355X): the quantile learners' small kernels and the dueling combine against float64, each on its own, at the edges of its work split.
 
-Kernels (agent0_amd/csrc/quantile.hip and the tail of loss.hip): a0_dueling_fwd / _bwd, a0_quantile_target, a0_loss_quantile_huber (a0_qh_sweep, which the
+Kernels (agent0_amd/csrc/quantile.hip, loss.hip and loss_quantile.hip): a0_dueling_fwd / _bwd, a0_quantile_target, a0_loss_quantile_huber (a0_qh_sweep, which the
 fused QR kernel shares), a0_cos_features, a0_tau_cos_features, a0_fqf_taus, a0_fqf_taus_cos, a0_fqf_inner_taus, a0_hadamard_fwd / _bwd and
 a0_fqf_fraction_loss.  References: tests/quantile_ref.py, held on the CPU to the G5 fixture, the oracle in float64, torch.autograd and a finite difference by
 tests/test_quantile_reference_helpers.py.  The whole-update tests reach these kernels at one geometry only (F = 32, N = N' = 64, A = 4 / 9 / 18) and the

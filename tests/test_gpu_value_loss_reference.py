@@ -1,6 +1,6 @@
 """GPU (MI355X): the value and categorical losses against float64, each on its own, at the edges of its work split.
 
-Kernels (agent0_amd/csrc/loss.hip): a0_loss_dqn, a0_dqn_head_loss, a0_loss_mdqn and a0_loss_c51 — the yardsticks the bit-identity tests of the fused
+Kernels (agent0_amd/csrc/loss_value.hip, loss_c51.hip): a0_loss_dqn, a0_dqn_head_loss, a0_loss_mdqn and a0_loss_c51 — the yardsticks the bit-identity tests of the fused
 a0_dqn_ / a0_mdqn_ / a0_c51_head_loss_slabs kernels compare against (tests/test_gpu_head_loss_chain.py, tests/test_gpu_engine.py), which therefore cannot see
 an error the yardstick shares.  References, bounds and cases: tests/value_loss_ref.py, held on the CPU to the G4 fixture, the oracle in float64,
 F.smooth_l1_loss, torch.autograd, a finite difference, an fp32 restatement and seven wrong computations by tests/test_value_loss_reference_helpers.py.

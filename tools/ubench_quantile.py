@@ -2,7 +2,7 @@
 reference agent.py:110-114,272-293) — the stand-alone a0_quantile_huber_kernel and a0_qr_head_loss_slabs (head slabs -> loss + head gradient), graph replays timed with
 HIP events, against the fp32 vector-unit bound of the pair sweep:
 
-    20.48 M pairs x 8 vector instructions (sub, cmp, cndmask, min, fma, mul, med3, pk_fma: csrc/loss.hip::a0_qh_sweep) / 64 lanes
+    20.48 M pairs x 8 vector instructions (sub, cmp, cndmask, min, fma, mul, med3, pk_fma: csrc/loss_quantile.hip::a0_qh_sweep) / 64 lanes
     = 2.56 M wave-instructions over 1024 SIMDs, one per 2 cycles per SIMD at two or more waves per SIMD (MI355X_MICROARCH.md) at 2.4 GHz  ->  2.1 us;
     thread i owns online quantile i, so 200 of a workgroup's 256 lanes work: 2.7 us.
 """
