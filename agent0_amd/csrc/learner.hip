@@ -188,6 +188,15 @@ static void a0_ws_layerwise(a0_learner* L) {
     if (d->algo == A0_ALGO_QR) { L->y = L->alloc<float>((long long)B * L->T); a0_ws_qr_taus(L); }
 }
 
+// one pass's cosine-embedding head workspace over B * n_tau rows (a0_ws_quantile; a0_learner_set_munchausen for the pass it adds)
+static void a0_qws_buffers(a0_learner* L, a0_learner::QWs& w, int n_tau, float* act3, bool grads) {
+    const int A = L->d.A;
+    w.n_tau = n_tau; w.R = (long long)L->d.B * n_tau; w.act3 = act3;
+    w.h = L->alloc<float>(w.R * 512); w.raw = L->alloc<float>(w.R * L->Npad); w.q = L->alloc<float>(w.R * A);
+    w.cosx = L->alloc<float>(w.R * 64); w.emb = L->alloc<float>(w.R * L->feat); w.x = L->alloc<float>(w.R * L->feat);
+    if (grads) { w.dq = L->alloc<float>(w.R * A, true); w.dx = L->alloc<float>(w.R * L->feat); w.demb = L->alloc<float>(w.R * L->feat); }
+}
+
 // iqn and fqf (K = N = N' = F, and the fraction net's buffers): the cosine-embedding head's workspaces per pass, the fraction draws, the quantile target
 static void a0_ws_quantile(a0_learner* L, const a0_learner_buffers& U) {
     const a0_learner_desc* d = &L->d; const int B = d->B;
@@ -196,10 +205,7 @@ static void a0_ws_quantile(a0_learner* L, const a0_learner_buffers& U) {
     L->a_star = L->alloc<int>(B, true);
     long long sc = 4;
     auto ws = [&](a0_learner::QWs& w, int n_tau, float* act3, bool grads) {
-        w.n_tau = n_tau; w.R = (long long)B * n_tau; w.act3 = act3;
-        w.h = L->alloc<float>(w.R * 512); w.raw = L->alloc<float>(w.R * L->Npad); w.q = L->alloc<float>(w.R * d->A);
-        w.cosx = L->alloc<float>(w.R * 64); w.emb = L->alloc<float>(w.R * L->feat); w.x = L->alloc<float>(w.R * L->feat);
-        if (grads) { w.dq = L->alloc<float>(w.R * d->A, true); w.dx = L->alloc<float>(w.R * L->feat); w.demb = L->alloc<float>(w.R * L->feat); }
+        a0_qws_buffers(L, w, n_tau, act3, grads);
         for (int r : {B * K, B * Nd, B * N, B * (N - 1)}) {
             if (r > w.R || r < 1) continue;
             const long long a = a0_dense_fwd_scratch(r, L->feat, 64), b2 = a0_dense_fwd_scratch(r, 512, L->feat), c = a0_dense_fwd_scratch(r, L->Npad, 512);
@@ -485,6 +491,40 @@ extern "C" int a0_learner_set_aug_shift(a0_learner* L, int pad) {
     A0_CATCH
 }
 
+// learner.iqn.munchausen (DeviceLearner: munchausen_value + the constructor's refusals).  The new pass's rows, B * N', are rows a0_ws_quantile has sized fwd_scratch for (qt has at least as many)
+extern "C" int a0_learner_set_munchausen(a0_learner* L, int on, double tau, double alpha, double lo) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_munchausen: null handle");
+    if (L->updated) return a0_fail(A0_EINVAL, "a0_learner_set_munchausen: the setting is fixed once the handle has run an update");
+    char msg[256];
+    const float t32 = (float)tau, a32 = (float)alpha, l32 = (float)lo;
+    if (!(tau > 0.0) || !(t32 > 0.f) || !(t32 - t32 == 0.f)) {
+        snprintf(msg, sizeof msg, "a0_learner_set_munchausen: learner.mdqn.tau = %g must be a finite number above 0 (as a float too)", tau);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (!(alpha >= 0.0) || !(a32 - a32 == 0.f)) {
+        snprintf(msg, sizeof msg, "a0_learner_set_munchausen: learner.mdqn.alpha = %g must be a finite number >= 0", alpha);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (!(lo <= 0.0) || !(l32 - l32 == 0.f)) {
+        snprintf(msg, sizeof msg, "a0_learner_set_munchausen: learner.mdqn.lo = %g must be a finite number <= 0", lo);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (!on) { L->miqn = false; return A0_OK; }
+    if (L->d.algo != A0_ALGO_IQN) {
+        snprintf(msg, sizeof msg, "a0_learner_set_munchausen: learner.iqn.munchausen is for iqn handles only (this handle's algo is %d)", L->d.algo);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (L->d.double_q) return a0_fail(A0_EINVAL, "a0_learner_set_munchausen: learner.iqn.munchausen not together with double_q = 1 (the target has no argmax to decouple)");
+    if (!L->act3_m) {
+        L->act3_m = L->alloc<float>((long long)L->d.B * L->feat);
+        a0_qws_buffers(L, L->qm, L->d.iqn_N_dash, L->act3_m, false);
+    }
+    L->miqn = true; L->miqn_tau = t32; L->miqn_alpha = a32; L->miqn_lo = l32;
+    return A0_OK;
+    A0_CATCH
+}
+
 extern "C" int a0_learner_set_params(a0_learner* L, const float* online_packed, const float* target_packed, void* stream) {
     A0_TRY
     if (!L || !online_packed) return a0_fail(A0_EINVAL, "a0_learner_set_params: null argument");
@@ -668,13 +708,20 @@ static int a0_fwd_iqn(a0_upd& u) {
     A0_CHECK(a0_rng_uniform(L->rng.seed, STREAM_TAUS, L->rng.reserve(STREAM_TAUS, (long long)B * K), L->t_sel, (long long)B * K, stream));
     A0_CHECK(a0_rng_uniform(L->rng.seed, STREAM_TAUS, L->rng.reserve(STREAM_TAUS, (long long)B * Nd), L->t_tgt, (long long)B * Nd, stream));
     A0_CHECK(a0_rng_uniform(L->rng.seed, STREAM_TAUS, L->rng.reserve(STREAM_TAUS, (long long)B * N), L->t_on, (long long)B * N, stream));
-    A0_CHECK(a0_upd_encode(u, {{true, true, L->act3_t, false}, {false, true, dq ? L->act3_s : nullptr, false}, {false, false, L->act3_o, true}}));
-    // greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
-    a0_learner::QWs& sel = dq ? L->qs : L->qt;
-    A0_CHECK(a0_iqn_head(L, !dq, sel, L->t_sel, K, false, stream));
-    A0_CHECK(a0_select_action(sel.q, (long long)K * A, 1, A, B, A, K, 1, nullptr, L->a_star, nullptr, nullptr, stream));
-    A0_CHECK(a0_iqn_head(L, true, L->qt, L->t_tgt, Nd, false, stream));
-    A0_CHECK(a0_quantile_target(L->qt.q, (long long)Nd * A, A, 1, L->a_star, u.rew, u.done, L->gamma_n, B, Nd, L->y, stream));
+    if (L->miqn) {      // learner.iqn.munchausen: the target network on s' and on s at the same N' fractions; no greedy next action (the K draw above is made and left unused)
+        A0_CHECK(a0_upd_encode(u, {{true, true, L->act3_t, false}, {true, false, L->act3_m, false}, {false, false, L->act3_o, true}}));
+        A0_CHECK(a0_iqn_head(L, true, L->qt, L->t_tgt, Nd, false, stream));
+        A0_CHECK(a0_iqn_head(L, true, L->qm, L->t_tgt, Nd, false, stream));
+        A0_CHECK(a0_miqn_target(L->qt.q, L->qm.q, (long long)Nd * A, A, 1, u.act, u.rew, u.done, L->gamma_n, L->miqn_tau, L->miqn_alpha, L->miqn_lo, B, Nd, A, L->y, stream));
+    } else {
+        A0_CHECK(a0_upd_encode(u, {{true, true, L->act3_t, false}, {false, true, dq ? L->act3_s : nullptr, false}, {false, false, L->act3_o, true}}));
+        // greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
+        a0_learner::QWs& sel = dq ? L->qs : L->qt;
+        A0_CHECK(a0_iqn_head(L, !dq, sel, L->t_sel, K, false, stream));
+        A0_CHECK(a0_select_action(sel.q, (long long)K * A, 1, A, B, A, K, 1, nullptr, L->a_star, nullptr, nullptr, stream));
+        A0_CHECK(a0_iqn_head(L, true, L->qt, L->t_tgt, Nd, false, stream));
+        A0_CHECK(a0_quantile_target(L->qt.q, (long long)Nd * A, A, 1, L->a_star, u.rew, u.done, L->gamma_n, B, Nd, L->y, stream));
+    }
     A0_CHECK(a0_iqn_head(L, false, L->qo, L->t_on, N, true, stream));
     A0_HIP_THROW(hipMemsetAsync(L->qo.dq, 0, (size_t)L->qo.R * A * 4, (hipStream_t)stream));
     return a0_loss_quantile_huber(L->qo.q, (long long)N * A, A, 1, L->y, L->t_on, N, u.act, u.wgt, B, N, Nd, L->loss, L->qo.dq, L->state, stream);

@@ -101,6 +101,12 @@ struct a0_learner {
     // ---- DrQ random shift of the batch (a0_learner_set_aug_shift): off while aug_pad == 0; aug_stage: the dense augmented batch [B][2 * C * H * W], allocated by the first call that switches it on
     int aug_pad = 0;
     uint8_t* aug_stage = nullptr;
+    // ---- Munchausen-IQN targets (a0_learner_set_munchausen): off while miqn is false; act3_m / qm: the target network's features and head workspace (B * N' rows, no
+    // gradients) on the CURRENT observation, allocated by the first call that switches it on; tau, alpha and lo as a0_miqn_target receives them
+    bool miqn = false;
+    float miqn_tau = 0.03f, miqn_alpha = 0.9f, miqn_lo = -1.f;
+    float* act3_m = nullptr;
+    QWs qm;
     // library-owned HBM
     float *online = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *scalars = nullptr, *loss_ring = nullptr;
     float *wt_on = nullptr, *wt_tg = nullptr;

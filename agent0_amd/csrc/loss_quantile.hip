@@ -1,7 +1,8 @@
 // Quantile-Huber loss (QR / IQN / FQF): target quantiles, the pairwise sweep, stand-alone and — QR — fused with the head tail; forward value and gradient w.r.t.
-// the quantiles in one pass.  Restates reference agent0/deepq/agent.py:110-114 (the loss), 273-293 (QRLearner.train_step) and 297-327 (the IQN / FQF targets) with
+// the quantiles in one pass; and the Munchausen-IQN targets (a0_miqn_target), which have no reference counterpart.  Restates reference agent0/deepq/agent.py:110-114 (the loss), 273-293 (QRLearner.train_step) and 297-327 (the IQN / FQF targets) with
 // the dueling arithmetic of agent0/deepq/model.py:163-177, 180-192.
 #include "head_loss.h"
+#include "store_policy.h"
 
 // ------------------------------------------------------------------------------------------------ quantile Huber
 // y[b][j] = r + gamma_n*(1-d) * qn(b, j, a*_b),  qn(b,j,a) = q_next[b*sb + j*sj + a*sa]
@@ -20,6 +21,70 @@ extern "C" int a0_quantile_target(const float* q_next, long long sb, long long s
     long long n = (long long)B * Nd;
     hipLaunchKernelGGL(a0_quantile_target_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q_next, sb, sj, sa, a_star, rew, done, gamma_n, B, Nd, y);
     return a0_fail_hip((int)hipGetLastError(), "a0_quantile_target");
+}
+
+// ------------------------------------------------------------------------------------------------ Munchausen-IQN targets (learner.iqn.munchausen)
+// Vieillard, Pietquin, Geist 2020, section 5 and appendix B; no reference counterpart (the reference has Munchausen targets for its scalar head only).  Per sample b, with
+// z'_j(a) = q_next(b, j, a), z_j(a) = q_cur(b, j, a) — the TARGET network on s' and on s at the same N' fractions —, element (b, j, a) at b*sb + j*sj + a*sa:
+//   Qm'(a) = (sum_j z'_j(a)) / N',  Qm(a) = (sum_j z_j(a)) / N'                       (each sum taken serially in j order by one lane)
+//   lp(x)_a = (x_a - max x) - tau log sum_k exp((x_k - max x) / tau)                   (tau log pi_tau(a): log_softmax_stable at temperature tau)
+//   pi'_a   = exp((Qm'_a - max) / tau) / sum_k exp((Qm'_k - max) / tau)                (the softmax at temperature tau, as in the paper; mdqn's is at temperature 1)
+//   m       = alpha clamp(lp(Qm)_{a_b}, lo, 0)                                         (alpha is the paper's; mdqn multiplies by tau instead, quirk Q17)
+//   y_j     = r + m + gamma_n (1 - d) sum_a pi'_a (z'_j(a) - lp(Qm')_a)
+// One wave per sample.  Lane l < 32 owns action l of the next-state values, lane 32 + l action l of the current-state values: its serial sum over j, then — inside
+// the wave's 32-lane half, by a five-stage butterfly — the maximum, the sum of exponentials and the log-policy.  pi' and lp(Qm') go to LDS, the taken action's
+// log-policy comes from its lane; then lanes stride over j for y_j, the A products added in action order.  No atomics: the bytes are a function of the inputs.
+// A sum that is not finite (a NaN or an infinity among the sample's 2 N' A inputs) makes s - s a NaN in its lane; the wave's sum of those joins every y_j of the
+// sample, so the quantile Huber kernel behind raises the flag and the update is skipped.  The clamp is two comparisons, not fminf / fmaxf, which would drop a NaN.
+// y is read by the next launch alone: written through (store_policy.h), like the GEMMs' slabs.
+using a0_miqn_y_store = a0_st_wt;
+__global__ __launch_bounds__(64) void a0_miqn_target_kernel(const float* __restrict__ q_next, const float* __restrict__ q_cur, long long sb, long long sj, long long sa,
+                                                            const int* __restrict__ act, const float* __restrict__ rew, const float* __restrict__ done, float gamma_n,
+                                                            float tau, float alpha, float lo, int Nd, int A, float* __restrict__ y) {
+    __shared__ float s_pi[32], s_lp[32];
+    const int b = blockIdx.x, lane = threadIdx.x, half = lane >> 5, a = lane & 31;
+    const bool on = a < A;
+    const int act_b = act[b];
+    const float rew_b = rew[b], done_b = done[b];
+    const float* qn_b = q_next + (long long)b * sb;
+    const float* mine = (half ? q_cur + (long long)b * sb : qn_b) + (long long)(on ? a : 0) * sa;
+    float s = 0.f;
+#pragma unroll 8
+    for (int j = 0; j < Nd; ++j) s += mine[(long long)j * sj];
+    const float x = s / (float)Nd;
+    const float poison = a0_wave_sum(on ? s - s : 0.f);      // +0, or NaN when an input of the sample is not finite
+    float mx = on ? x : -INFINITY;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    const float z = x - mx;
+    const float e = on ? expf(z / tau) : 0.f;
+    float se = e;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+    const float lp = z - tau * logf(se);
+    if (!half && on) { s_pi[a] = e / se; s_lp[a] = lp; }
+    float bonus = __shfl(lp, 32 + (act_b & 31), 64);
+    bonus = bonus < lo ? lo : bonus;
+    bonus = bonus > 0.f ? 0.f : bonus;
+    const float head = rew_b + alpha * bonus + poison;
+    const float g = gamma_n * (1.f - done_b);
+    __syncthreads();
+    for (int j = lane; j < Nd; j += 64) {
+        const float* p = qn_b + (long long)j * sj;
+        float acc = 0.f;
+        for (int k = 0; k < A; ++k) acc += s_pi[k] * (p[(long long)k * sa] - s_lp[k]);
+        a0_put_f32<a0_miqn_y_store>(y + (long long)b * Nd + j, head + g * acc);
+    }
+}
+
+extern "C" int a0_miqn_target(const float* q_next, const float* q_cur, long long sb, long long sj, long long sa, const int* act, const float* rew, const float* done,
+                              float gamma_n, float tau, float alpha, float lo, int B, int Nd, int A, float* y, void* stream) {
+    if (!q_next || !q_cur || !act || !rew || !done || !y || B < 1 || Nd < 1 || Nd > 8192 || A < 1 || A > 32)
+        return a0_fail(A0_EINVAL, "a0_miqn_target: bad argument (null pointer, or outside B >= 1, 1 <= Nd <= 8192, 1 <= A <= 32)");
+    if (!(tau > 0.f) || !(alpha >= 0.f) || !(lo <= 0.f) || !(tau - tau == 0.f) || !(alpha - alpha == 0.f) || !(lo - lo == 0.f))
+        return a0_fail(A0_EINVAL, "a0_miqn_target: tau > 0, alpha >= 0 and lo <= 0, all finite");
+    hipLaunchKernelGGL(a0_miqn_target_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, q_next, q_cur, sb, sj, sa, act, rew, done, gamma_n, tau, alpha, lo, Nd, A, y);
+    return a0_fail_hip((int)hipGetLastError(), "a0_miqn_target");
 }
 
 // One online quantile q_i against the N' targets held in LDS (16-byte aligned), in target order: al = sum_j huber(q_i - T_j) |tau_i - 1{T_j < q_i}| and

@@ -84,6 +84,15 @@ Additions (all default to the reference's behaviour being available):
                    nothing new in a snapshot, and the setting may change across a resume.
   learner.rank_delta  float in the open interval (0, 1), default 0.01 (the paper's delta; anything else, NaN included, is refused with the number named).  Without
                    ``learner.rank_freq`` it does nothing.
+  learner.iqn.munchausen  bool, default false.  true (``learner.algo=iqn`` only): Munchausen-IQN (Vieillard, Pietquin, Geist 2020, section 5 and appendix B).  The
+                   quantile targets become y_j = r + alpha * clamp(tau log pi(a|s), lo, 0) + gamma^n (1 - d) sum_a' pi(a'|s') (z'_j(a') - tau log pi(a'|s')), pi the softmax at
+                   temperature tau of the TARGET network's mean over the N' target fractions, on s' and — one encoder pass and one N'-row head pass more — on s, at the
+                   same fractions; there is no greedy next action, so the K-row selection pass is not run (its K fractions are still drawn: the Philox position is a
+                   plain iqn run's).  It reads ``learner.mdqn.tau`` (0.03), ``learner.mdqn.alpha`` (0.9) and ``learner.mdqn.lo`` (-1): ``learner.mdqn.alpha`` is honoured
+                   here and still unused by ``learner.algo=mdqn``, which keeps the reference's quirks — tau in alpha's place (Q17) and the temperature-1 softmax — and does
+                   not change by a bit.  This follows the paper, not those quirks.  Acting is unchanged (epsilon-greedy on the K-sample mean).  Refused: any other algo
+                   (fqf included), ``learner.double_q`` (no argmax to decouple), tau <= 0, alpha < 0, lo > 0 or any of them NaN or infinite, ``A0_PIPELINE_TARGET=1``.
+                   No state of its own, nothing new in a snapshot, no new statistic, and the setting may change across a resume.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -156,6 +165,7 @@ class IQNConfig:
     N_dash: int = 64
     num_cosines: int = 64
     F: int = 32
+    munchausen: bool = False
 
 
 @dataclass

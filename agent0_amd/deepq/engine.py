@@ -82,6 +82,32 @@ def aug_shift_value(value, obs_shape, pipeline_target: Optional[bool] = None) ->
     return p
 
 
+def munchausen_value(value, tau=0.03, alpha=0.9, lo=-1.0, algo: str = "iqn", double_q: bool = False, pipeline_target: Optional[bool] = None):
+    """``learner.iqn.munchausen`` with ``learner.mdqn.tau`` / ``alpha`` / ``lo`` as the learner uses them: ``(on, tau, alpha, lo)``, the three numbers as Python floats.
+    Refused, whether or not the setting is on: a tau that is not a finite number above 0 (as an fp32 number too — the kernel gets fp32), an alpha that is not a finite
+    number >= 0, a lo that is not a finite number <= 0.  Refused with the setting on: any ``algo`` but iqn (fqf included), ``learner.double_q`` (the Munchausen target has
+    no argmax to decouple), and ``A0_PIPELINE_TARGET=1`` (``pipeline_target``; None reads the environment): the update has two target passes and none of them is staged."""
+    on = bool(value) if value is not None else False
+    t, a, l = (float("nan") if x is None else float(x) for x in (tau, alpha, lo))
+    f32 = lambda x: float(torch.tensor(x, dtype=torch.float64).to(torch.float32))
+    if not (t > 0 and math.isfinite(t) and f32(t) > 0 and math.isfinite(f32(t))):
+        raise ValueError(f"learner.iqn.munchausen: learner.mdqn.tau={tau!r} must be a finite number above 0")
+    if not (a >= 0 and math.isfinite(a) and math.isfinite(f32(a))):
+        raise ValueError(f"learner.iqn.munchausen: learner.mdqn.alpha={alpha!r} must be a finite number >= 0")
+    if not (l <= 0 and math.isfinite(l) and math.isfinite(f32(l))):
+        raise ValueError(f"learner.iqn.munchausen: learner.mdqn.lo={lo!r} must be a finite number <= 0")
+    if on:
+        if algo != "iqn":
+            raise ValueError(f"learner.iqn.munchausen=true: for learner.algo=iqn only, not learner.algo={algo} (mdqn is the scalar head's Munchausen learner)")
+        if double_q:
+            raise ValueError("learner.iqn.munchausen=true: not together with learner.double_q=true (the Munchausen target has no argmax to decouple)")
+        if pipeline_target is None:
+            pipeline_target = os.environ.get("A0_PIPELINE_TARGET", "0") == "1"
+        if pipeline_target:
+            raise ValueError("learner.iqn.munchausen=true: not together with A0_PIPELINE_TARGET=1 (the update has two target passes and neither is staged separately)")
+    return on, t, a, l
+
+
 def net_reset_value(freq, shrink=1.0, pipeline_target: Optional[bool] = None):
     """``learner.net_reset_freq`` / ``learner.net_reset_shrink`` as the learner uses them: ``(N, alpha)``, N = 0 (off) for zero or None.  Refused: a negative or
     fractional N, an alpha outside [0, 1] (NaN included; checked whether or not N is on), and N > 0 together with ``A0_PIPELINE_TARGET=1`` (``pipeline_target``; None
@@ -436,7 +462,7 @@ class DeviceLearner:
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
                  mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0,
-                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True, rank_freq=0, rank_delta=0.01):
+                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True, rank_freq=0, rank_delta=0.01, munchausen=False, mdqn_alpha=0.9):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -521,6 +547,14 @@ class DeviceLearner:
             self.rank_spectrum = ops.zeros(ops.RANK_FEATURES, dtype=torch.float64)
             self.rank_result = ops.zeros(8, dtype=torch.int32)
             self.rank_result[2] = -1                   # never evaluated
+        # learner.iqn.munchausen: _fwd_iqn builds the quantile targets with miqn_target from the target network's passes on s' and on s (``ws_m``, B * N' rows) instead of
+        # the greedy quantile_target; tau, alpha, lo are learner.mdqn's (alpha is honoured here; mdqn leaves it unused, quirk Q17).  Off: no buffer, and _fwd_iqn issues
+        # what it always did.  (For mdqn the numbers were never checked here and still are not.)
+        self.munchausen, self.mdqn_alpha = False, float(mdqn_alpha)
+        if munchausen:
+            self.munchausen, _, self.mdqn_alpha, _ = munchausen_value(munchausen, mdqn_tau, mdqn_alpha, mdqn_lo, algo=L.algo, double_q=double_q)
+            if not hasattr(ops, "miqn_target"):
+                raise ValueError("learner.iqn.munchausen=true: needs a backend with miqn_target")
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -539,6 +573,8 @@ class DeviceLearner:
             self.ws_o = Workspace(ops, L, B, n_on, grads=True)
             self.ws_t = Workspace(ops, L, B, max(n_tg, n_sel))
             self.ws_s = Workspace(ops, L, B, n_sel) if double_q else None
+            if self.munchausen:
+                self.ws_m = Workspace(ops, L, B, n_tg)      # the target network on the CURRENT observation at the N' target fractions
             if L.algo == "fqf":
                 self.ws_f = Workspace(ops, L, B, L.F)        # q at taus[1:-1] for the fraction loss (F-1 used)
                 self.rms_sq = ops.zeros(L.blocks["frac"].size)
@@ -892,6 +928,8 @@ class DeviceLearner:
             raise ValueError("tstage: this learner's target pass cannot run as a separate stage")
         if self.net_reset_freq > 0 and u.tstage is not None:
             raise ValueError("tstage: not together with learner.net_reset_freq (the separately staged target pass has read a target the reset rewrites)")
+        if self.munchausen and u.tstage is not None:
+            raise ValueError("tstage: not together with learner.iqn.munchausen (the update has two target passes and neither is staged separately)")
         if self.aug_shift > 0:
             if u.tstage is not None:
                 raise ValueError("tstage: not together with learner.aug_shift (the separately staged target pass has read the unshifted ring)")
@@ -1032,12 +1070,21 @@ class DeviceLearner:
         L, ops, B, on, tg = self.L, self.ops, self.B, self.online, self.target
         wo, wt, wsel = self.ws_o, self.ws_t, self.ws_s
         (t_sel, t_tgt, t_on), (K, Nd, N) = u.rand, (self.K, self.N_dash, self.N)
-        sel, ws_sel = (on, wsel) if self.double_q else (tg, wt)      # greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
-        self._upd_encode(u, (tg, wt, True, False), (on, wsel, True, False) if self.double_q else None, (on, wo, False, True))
-        sel.head(ws_sel, B, t_sel, K)
-        sel.select(ws_sel, B, K, self.a_star)
-        tg.head(wt, B, t_tgt, Nd)
-        ops.quantile_target(wt.q, Nd * L.A, L.A, 1, self.a_star, u.rew, u.done, self.gamma_n, B, Nd, self.y)
+        if self.munchausen:
+            # learner.iqn.munchausen (a0_fwd_iqn's branch, step for step): the target network on s' and on s at the same N' fractions; no greedy next action, so the
+            # selection pass is not run and t_sel — drawn so that the stream position stays a plain iqn run's — is left unused
+            wm = self.ws_m
+            self._upd_encode(u, (tg, wt, True, False), (tg, wm, False, False), (on, wo, False, True))
+            tg.head(wt, B, t_tgt, Nd)
+            tg.head(wm, B, t_tgt, Nd)
+            ops.miqn_target(wt.q, wm.q, Nd * L.A, L.A, 1, u.act, u.rew, u.done, self.gamma_n, self.mdqn_tau, self.mdqn_alpha, self.mdqn_lo, B, Nd, L.A, self.y)
+        else:
+            sel, ws_sel = (on, wsel) if self.double_q else (tg, wt)      # greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
+            self._upd_encode(u, (tg, wt, True, False), (on, wsel, True, False) if self.double_q else None, (on, wo, False, True))
+            sel.head(ws_sel, B, t_sel, K)
+            sel.select(ws_sel, B, K, self.a_star)
+            tg.head(wt, B, t_tgt, Nd)
+            ops.quantile_target(wt.q, Nd * L.A, L.A, 1, self.a_star, u.rew, u.done, self.gamma_n, B, Nd, self.y)
         on.head(wo, B, t_on, N)
         wo.dq.zero_()
         ops.loss_quantile_huber(wo.q, N * L.A, L.A, 1, self.y, t_on, N, u.act, u.wgt, B, N, Nd, self.loss, wo.dq, self.state)

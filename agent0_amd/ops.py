@@ -188,6 +188,11 @@ class NativeLearner:
         """learner.aug_shift through the handle (a0_learner_set_aug_shift): between updates; 0 is off, the kernel's range checks apply to anything else."""
         check(self.lib.a0_learner_set_aug_shift(self.h, int(pad)), "a0_learner_set_aug_shift")
 
+    def set_munchausen(self, on, tau=0.03, alpha=0.9, lo=-1.0):
+        """learner.iqn.munchausen through the handle (a0_learner_set_munchausen): before the first update, on an iqn handle without double-Q; tau, alpha and lo are
+        learner.mdqn's."""
+        check(self.lib.a0_learner_set_munchausen(self.h, int(bool(on)), float(tau), float(alpha), float(lo)), "a0_learner_set_munchausen")
+
     def grad_norm_ring(self):
         """A copy of the ring of pre-clip gradient norms (A0_PEEK_GRAD_NORM_RING)."""
         ptr, cnt = C.c_void_p(), C.c_longlong()
@@ -548,6 +553,14 @@ class HipOps:
         check(self.lib.a0_quantile_target(_req(q_next, torch.float32, (B - 1) * sb + (Nd - 1) * sj + 1, "q_next"), sb, sj, sa, _req(a_star, torch.int32, B, "a_star"),
                                           _req(rew, torch.float32, B, "rew"), _req(done, torch.float32, B, "done"), gamma_n, B, Nd,
                                           _req(y, torch.float32, B * Nd, "y"), _stream()), "a0_quantile_target")
+
+    def miqn_target(self, q_next, q_cur, sb, sj, sa, act, rew, done, gamma_n, tau, alpha, lo, B, Nd, A, y):
+        """learner.iqn.munchausen: the Munchausen-IQN quantile targets ``y`` [B][Nd] from the target network's quantiles on s' (``q_next``) and on s (``q_cur``) at the
+        same Nd fractions, element (b, j, a) at b*sb + j*sj + a*sa of either, in one launch (a0_miqn_target)."""
+        span = (B - 1) * sb + (Nd - 1) * sj + (A - 1) * sa + 1
+        check(self.lib.a0_miqn_target(_req(q_next, torch.float32, span, "q_next"), _req(q_cur, torch.float32, span, "q_cur"), sb, sj, sa, _req(act, torch.int32, B, "act"),
+                                      _req(rew, torch.float32, B, "rew"), _req(done, torch.float32, B, "done"), gamma_n, tau, alpha, lo, B, Nd, A,
+                                      _req(y, torch.float32, B * Nd, "y"), _stream()), "a0_miqn_target")
 
     def loss_quantile_huber(self, q, sb, si, sa, y, taus, tb, act, wgt, B, N, Nd, loss, dq, state):
         span = (B - 1) * sb + (N - 1) * si + 1

@@ -338,6 +338,16 @@ int a0_quantile_target(const float* q_next, long long sb, long long sj, long lon
 int a0_loss_quantile_huber(const float* q, long long sb, long long si, long long sa, const float* y, const float* taus,
                            long long tb, const int* act, const float* wgt, int B, int N, int Nd, float* loss, float* dq,
                            int* nan_flag, void* stream);
+/* learner.iqn.munchausen: the Munchausen-IQN quantile targets (Vieillard, Pietquin, Geist 2020, section 5 and appendix B) in one launch.  q_next / q_cur: the TARGET
+ * network's quantiles on s' / on s at the same Nd fractions, element (b, j, a) at b*sb + j*sj + a*sa of either (the strides of a0_quantile_target).  Per sample, with
+ * Qm' / Qm the means over j (summed in j order), lp(x)_a = (x_a - max x) - tau log sum_k exp((x_k - max x) / tau) and pi' = softmax(Qm' / tau):
+ *   y[b][j] = rew + alpha clamp(lp(Qm)[act], lo, 0) + gamma_n (1 - done) sum_a pi'_a (q_next(b, j, a) - lp(Qm')_a),  j < Nd.
+ * The softmax is at temperature tau and the bonus is scaled by alpha, as in the paper: a0_loss_mdqn's temperature-1 softmax and its tau in alpha's place (quirk
+ * Q17) are the reference's and stay that entry point's own.  No atomics: equal inputs give equal bytes.  A NaN or an infinity among a sample's inputs makes all Nd
+ * targets of that sample NaN and no other's.  A0_EINVAL: a null pointer, B < 1, Nd outside [1, 8192], A outside [1, 32], tau <= 0, alpha < 0, lo > 0, or one of
+ * the three not finite. */
+int a0_miqn_target(const float* q_next, const float* q_cur, long long sb, long long sj, long long sa, const int* act, const float* rew, const float* done,
+                   float gamma_n, float tau, float alpha, float lo, int B, int Nd, int A, float* y, void* stream);
 
 /* IQN / FQF head pieces (model.py:235-251, 268-278; agent.py:371-387) */
 int a0_cos_features(const float* taus, float* out, long long R, int D, void* stream);
@@ -631,6 +641,14 @@ int a0_learner_feature_rank_buffers(const a0_learner* learner, double** spectrum
  * (A0_EINVAL); with the setting on, a0_learner_update refuses a row_bytes other than 2 * C * H * W.  Call it between updates, not while one is being captured;
  * descriptor structs are unchanged, and nothing is added to a snapshot: the update count travels in the state words. */
 int a0_learner_set_aug_shift(a0_learner* learner, int pad);
+/* learner.iqn.munchausen through the handle (iqn handles only): with on != 0 every a0_learner_update builds its quantile targets with a0_miqn_target instead of the
+ * greedy a0_quantile_target.  The three fraction draws stay as they are (the K draw is made and left unused, so the Philox position is a plain iqn handle's); the
+ * encoder launch gets the passes {target, s'}, {target, s}, {online, s}; the target head runs on both target passes at the N' target fractions; the selection pass
+ * and a0_select_action are not run.  The first call that switches it on allocates the second target pass's buffers (features of B observations, a head workspace of
+ * B * N' rows without gradients).  on == 0: off again, the update issues what it always did (tau, alpha and lo are still checked).  A0_EINVAL, each with the setting
+ * and the number named: a handle of another algo, a double-Q handle (there is no argmax to decouple), tau <= 0, alpha < 0, lo > 0, one of the three NaN or
+ * infinite (as given or once rounded to float), a call after the handle's first update.  Descriptor structs are unchanged and nothing is added to a snapshot. */
+int a0_learner_set_munchausen(a0_learner* learner, int on, double tau, double alpha, double lo);
 /* parameters in the packed layout (device pointers, a0_learner_param_floats floats each); target_packed = NULL: target = copy of online (agent.py:100) */
 int a0_learner_set_params(a0_learner* learner, const float* online_packed, const float* target_packed, void* stream);
 /* copies of what the handle holds (any pointer may be NULL): parameters, target parameters, Adam moments (param_floats each), the eight status words */
