@@ -1,7 +1,7 @@
 // What the head epilogues and TD losses of loss.hip, loss_value.hip, loss_c51.hip and loss_quantile.hip share, each piece stated once: the first-maximum rule, the
 // smooth-L1 tail and the one-hot dueling backward of the scalar heads, the ordered slab sum and the per-column dueling combine of the C51 / QR slab kernels, the C51
-// projection's bin position and cross entropy, and on the host the dynamic-LDS limit and the descriptor of the kernels that work from the head GEMMs' slabs.  The
-// fused kernels are held bit for bit to the launches they replace (tests/test_gpu_head_loss_chain.py, tests/test_gpu_engine.py): the arithmetic here is that of
+// projection's bin position and cross entropy, the HL-Gauss histogram that may stand in the projection's place, and on the host the dynamic-LDS limit and the
+// descriptor of the kernels that work from the head GEMMs' slabs.  The fused kernels are held bit for bit to the launches they replace (tests/test_gpu_head_loss_chain.py, tests/test_gpu_engine.py): the arithmetic here is that of
 // those launches, statement for statement.  What stays written out in its kernels and why: profiles/r33_loss_split.md.
 #pragma once
 #include "a0_internal.h"
@@ -102,8 +102,43 @@ A0_D void a0_c51_xent(float xo, float m, bool on, float w, int lane, float* loss
     }
     if (on) store_g(w * ((eo / so) * msum - m));
 }
+// HL-Gauss (learner.c51.hl_gauss; Farebrother et al. 2024): the mass of bin t — lane t's — of the Gaussian histogram of the clamped scalar target, from the target
+// net's logit xt of atom t at the greedy next action (-inf past the last atom) and the atom itself, the bin's centre.  All 64 lanes call.  fp32, in the order of the
+// selection step and of a0_c51_bin: v' = (sum e z) / (sum e) by a0_wave_sum, y = rew + (gamma_n (1 - done)) v', clamped by comparisons (a NaN reward stays NaN).
+// Then in double: the edges e_k = vmin - delta / 2 + k delta, erf((e - y) / sigma / sqrt 2) at the lane's own two edges and at the two outer ones — the halves and
+// the ones of Phi cancel in the quotient — and one rounding to fp32.  delta and sigma are doubles formed on the host.  Equal inputs give equal bytes.
+A0_D float a0_hl_gauss_mass(float xt, bool on, float atom, float rew, float done, float gamma_n, float vmin, float vmax, double delta, double sigma, int T, int t) {
+    const float mx = a0_wave_max(xt);
+    float se = 0.f, sz = 0.f;
+    if (on) {
+        const float ex = expf(xt - mx);
+        se += ex;
+        sz += ex * atom;
+    }
+    se = a0_wave_sum(se);
+    sz = a0_wave_sum(sz);
+    float y = rew + (gamma_n * (1.f - done)) * (sz / se);
+    y = y < vmin ? vmin : y;
+    y = y > vmax ? vmax : y;
+    const double yd = (double)y, e0 = (double)vmin - 0.5 * delta;
+    auto erf_at = [&](int k) { return erf((e0 + (double)k * delta - yd) / sigma * 0.70710678118654752440); };
+    const double q = (erf_at(t + 1) - erf_at(t)) / (erf_at(T) - erf_at(0));
+    return on ? (float)q : 0.f;
+}
 
 // ------------------------------------------------------------------------------------------------ host pieces
+// What the two HL-Gauss entry points and a0_learner_set_hl_gauss refuse of sigma = rho * delta (delta > 0 the double bin width, T bins): NaN, infinite, <= 0, not a
+// normal fp32 number once rounded, above T * delta (rho > num_atoms: a sanity limit).  Returns A0_OK or the recorded error with the numbers named.
+static int a0_hl_gauss_check(const char* who, double sigma, double delta, int T) {
+    const float s32 = (float)sigma;
+    const bool ok = sigma > 0.0 && sigma - sigma == 0.0 && s32 - s32 == 0.f && s32 >= 1.17549435e-38f && delta > 0.0 && sigma <= (double)T * delta;
+    if (ok) return A0_OK;
+    char msg[320];
+    snprintf(msg, sizeof msg, "%s: learner.c51.hl_gauss: sigma = %g (ratio sigma / Delta = %g, Delta = %g) must be a normal fp32 number above 0 and at most "
+                              "num_atoms * Delta = %g (ratio <= num_atoms = %d)", who, sigma, sigma / delta, delta, (double)T * delta, T);
+    return a0_fail(A0_EINVAL, msg);
+}
+
 // Raises Kernel's dynamic-LDS limit to `lds` bytes where it is above what the kernel was last granted (one high-water mark per kernel); false: HIP refused.
 template <auto Kernel>
 static bool a0_grant_dynamic_lds(size_t lds) {

@@ -13,6 +13,7 @@
 //
 // The update's stages are named after the methods of engine.py::DeviceLearner they mirror; the family (a0_family, learner_state.h) is decided once, in a0_learner_layout.
 #include "learner_state.h"
+#include "head_loss.h"      // a0_hl_gauss_check
 
 extern "C" int a0_learner_create(const a0_learner_desc* d, a0_learner** out) { return a0_learner_create_on(d, nullptr, out); }
 
@@ -525,6 +526,27 @@ extern "C" int a0_learner_set_munchausen(a0_learner* L, int on, double tau, doub
     A0_CATCH
 }
 
+// learner.c51.hl_gauss (DeviceLearner: hl_gauss_value).  sigma from the fp32 vmin and vmax the loss kernels receive, in double
+extern "C" int a0_learner_set_hl_gauss(a0_learner* L, double ratio) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_hl_gauss: null handle");
+    char msg[256];
+    if (!(ratio - ratio == 0.0)) {
+        snprintf(msg, sizeof msg, "a0_learner_set_hl_gauss: learner.c51.hl_gauss = %g must be a finite number (<= 0 is off)", ratio);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (!(ratio > 0.0)) { L->hlg_sigma = 0.0; return A0_OK; }
+    if (L->d.algo != A0_ALGO_C51) {
+        snprintf(msg, sizeof msg, "a0_learner_set_hl_gauss: learner.c51.hl_gauss = %g is for c51 handles only (this handle's algo is %d)", ratio, L->d.algo);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    const double delta = ((double)(float)L->d.vmax - (double)(float)L->d.vmin) / (double)(L->T - 1), sigma = ratio * delta;
+    A0_CHECK(a0_hl_gauss_check("a0_learner_set_hl_gauss", sigma, delta, L->T));
+    L->hlg_sigma = sigma;
+    return A0_OK;
+    A0_CATCH
+}
+
 extern "C" int a0_learner_set_params(a0_learner* L, const float* online_packed, const float* target_packed, void* stream) {
     A0_TRY
     if (!L || !online_packed) return a0_fail(A0_EINVAL, "a0_learner_set_params: null argument");
@@ -770,6 +792,10 @@ static int a0_fwd_dist(a0_upd& u) {
         return a0_qr_head_loss_slabs(L->hs_on, (long long)L->R_on * L->Npad, nh_on, L->R_on, L->hs_tg, (long long)B * L->Npad, nh_tg, dq ? B : -1, L->bh(false), L->bh(true),
                                      L->Npad, A, L->T, L->d.dueling ? 1 : 0, u.act, u.rew, u.done, u.wgt, L->qr_taus, L->gamma_n, B, L->loss, L->draw, L->q_o, L->q_t, L->a_star,
                                      L->state, stream);
+    if (L->hlg_sigma > 0.0)      // learner.c51.hl_gauss: the same launch with the Gaussian histogram of the scalar target in the projection's place
+        return a0_c51_hl_gauss_head_loss_slabs(L->hs_on, (long long)L->R_on * L->Npad, nh_on, L->R_on, L->hs_tg, (long long)B * L->Npad, nh_tg, dq ? B : -1, L->bh(false),
+                                               L->bh(true), L->Npad, A, L->T, L->d.dueling ? 1 : 0, u.act, u.rew, u.done, u.wgt, L->atoms, L->gamma_n, (float)L->d.vmin,
+                                               (float)L->d.vmax, L->hlg_sigma, B, L->loss, L->draw, L->q_o, L->q_t, L->m_proj, L->a_star, L->state, stream);
     return a0_c51_head_loss_slabs(L->hs_on, (long long)L->R_on * L->Npad, nh_on, L->R_on, L->hs_tg, (long long)B * L->Npad, nh_tg, dq ? B : -1, L->bh(false), L->bh(true),
                                   L->Npad, A, L->T, L->d.dueling ? 1 : 0, u.act, u.rew, u.done, u.wgt, L->atoms, L->gamma_n, (float)L->d.vmin, (float)L->d.vmax, B, L->loss, L->draw,
                                   L->q_o, L->q_t, L->m_proj, L->a_star, L->state, stream);

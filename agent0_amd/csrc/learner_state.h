@@ -107,6 +107,8 @@ struct a0_learner {
     float miqn_tau = 0.03f, miqn_alpha = 0.9f, miqn_lo = -1.f;
     float* act3_m = nullptr;
     QWs qm;
+    // ---- HL-Gauss target of the c51 handle (a0_learner_set_hl_gauss): off while hlg_sigma == 0; sigma = ratio * Delta as a0_c51_hl_gauss_head_loss_slabs receives it
+    double hlg_sigma = 0.0;
     // library-owned HBM
     float *online = nullptr, *target = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *scalars = nullptr, *loss_ring = nullptr;
     float *wt_on = nullptr, *wt_tg = nullptr;

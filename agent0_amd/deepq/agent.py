@@ -655,7 +655,8 @@ class BaseLearner:
                                     max_grad_norm=lc.max_grad_norm, mdqn_tau=lc.mdqn.tau, mdqn_lo=lc.mdqn.lo, clip_grad_norm=lc.clip_grad_norm, target_tau=lc.target_tau,
                                     aug_shift=lc.aug_shift, aug_rng=self.rng, net_reset_freq=lc.net_reset_freq, net_reset_shrink=lc.net_reset_shrink,
                                     weight_decay=lc.weight_decay, redo_freq=lc.redo_freq, redo_tau=lc.redo_tau, redo_recycle=lc.redo_recycle,
-                                    rank_freq=lc.rank_freq, rank_delta=lc.rank_delta, munchausen=lc.iqn.munchausen, mdqn_alpha=lc.mdqn.alpha)
+                                    rank_freq=lc.rank_freq, rank_delta=lc.rank_delta, munchausen=lc.iqn.munchausen, mdqn_alpha=lc.mdqn.alpha,
+                                    hl_gauss=lc.c51.hl_gauss)
         self.model = DeepQNet(cfg, ops=ops, dev_net=self.engine.online, rng=self.rng)
         self.model_target = DeepQNet(cfg, ops=ops, dev_net=self.engine.target, rng=self.rng)
         self.engine.sync_target(force=True)                 # model_target = deepcopy(model), agent.py:100

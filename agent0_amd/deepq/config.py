@@ -93,6 +93,15 @@ Additions (all default to the reference's behaviour being available):
                    not change by a bit.  This follows the paper, not those quirks.  Acting is unchanged (epsilon-greedy on the K-sample mean).  Refused: any other algo
                    (fqf included), ``learner.double_q`` (no argmax to decouple), tau <= 0, alpha < 0, lo > 0 or any of them NaN or infinite, ``A0_PIPELINE_TARGET=1``.
                    No state of its own, nothing new in a snapshot, no new statistic, and the setting may change across a resume.
+  learner.c51.hl_gauss  float, default 0.0 = off (any value <= 0 is off).  rho > 0 (``learner.algo=c51`` only): the HL-Gauss classification target of Farebrother et
+                   al. 2024 ("Stop Regressing", ICML 2024) in the place of C51's projected target distribution.  Network, support, acting rule and cross entropy stay;
+                   the atoms z_t = vmin + t Delta, Delta = (vmax - vmin) / (num_atoms - 1), become bin CENTRES with edges e_k = vmin - Delta / 2 + k Delta, and the
+                   scalar target y = clamp(r + gamma^n (1 - d) E[Z(s', a*)], vmin, vmax) — a* chosen as before, the expectation under the TARGET network's softmax —
+                   is spread over the bins as m_t = [Phi((e_{t+1} - y) / sigma) - Phi((e_t - y) / sigma)] / [Phi((e_T - y) / sigma) - Phi((e_0 - y) / sigma)] with
+                   sigma = rho Delta (rho is the paper's sigma / Delta; its value is 0.75).  y is formed in fp32, the Gaussian mass in double on the device and rounded
+                   to fp32 once.  Refused: NaN or infinite, rho > num_atoms (a sanity limit: sigma beyond the whole support), a sigma that is not a normal fp32
+                   number, any other algo.  ``A0_PIPELINE_TARGET=1`` is allowed: c51's staged target pass ends at the fc1 slabs and the loss kernel reads them as
+                   before.  No state of its own, nothing new in a snapshot, no new statistic, no Philox draw, and the setting may change across a resume.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -149,6 +158,7 @@ class C51Config:
     num_atoms: int = 51
     vmax: float = 10
     vmin: float = -10
+    hl_gauss: float = 0.0
 
 
 @dataclass

@@ -108,6 +108,35 @@ def munchausen_value(value, tau=0.03, alpha=0.9, lo=-1.0, algo: str = "iqn", dou
     return on, t, a, l
 
 
+def hl_gauss_value(value, vmin=-10.0, vmax=10.0, num_atoms=51, algo: str = "c51", pipeline_target: Optional[bool] = None):
+    """``learner.c51.hl_gauss`` as the learner uses it: ``(rho, sigma)`` as Python floats, sigma = rho * Delta with Delta = (vmax - vmin) / (num_atoms - 1) formed in
+    double — the number the kernels receive, as a double — and ``(0.0, 0.0)`` (off) for zero, a negative number or None.  Refused: a rho that is NaN or infinite;
+    with the setting on: rho > num_atoms (sigma would exceed the whole support and the histogram is flat: a sanity limit, not a numerical one), a sigma that is
+    not a normal fp32 number (a degenerate support included), and any ``algo`` but c51.  ``A0_PIPELINE_TARGET=1`` (``pipeline_target``) is ALLOWED and the
+    argument is only accepted for symmetry with the other settings: c51's separately staged target pass ends at the target's fc1 slabs, which the loss kernel reads
+    as it does without the stage, and nothing this setting changes is read or written by that stage."""
+    if value is None:
+        return 0.0, 0.0
+    rho = float(value)
+    if not math.isfinite(rho):
+        raise ValueError(f"learner.c51.hl_gauss={value!r}: must be a finite number (0.0 or any value <= 0 is off; the paper's sigma / Delta is 0.75)")
+    if not rho > 0:
+        return 0.0, 0.0
+    if algo != "c51":
+        raise ValueError(f"learner.c51.hl_gauss={rho!r}: for learner.algo=c51 only, not learner.algo={algo}")
+    T = int(num_atoms)
+    if rho > T:
+        raise ValueError(f"learner.c51.hl_gauss={rho!r}: must be at most learner.c51.num_atoms = {T} (sigma = rho * Delta would exceed the whole support)")
+    f32 = lambda x: float(torch.tensor(float(x), dtype=torch.float64).to(torch.float32))
+    delta = (f32(vmax) - f32(vmin)) / (T - 1) if T > 1 else float("nan")      # of vmin and vmax as the kernels receive them (fp32), as a0_learner_set_hl_gauss forms it
+    sigma = rho * delta
+    s32 = f32(sigma)
+    if not (math.isfinite(s32) and s32 >= 2.0 ** -126):
+        raise ValueError(f"learner.c51.hl_gauss={rho!r}: sigma = rho * (vmax - vmin) / (num_atoms - 1) = {rho!r} * ({float(vmax)!r} - {float(vmin)!r}) / {T - 1} = {sigma!r} "
+                         "is not a normal fp32 number")
+    return rho, sigma
+
+
 def net_reset_value(freq, shrink=1.0, pipeline_target: Optional[bool] = None):
     """``learner.net_reset_freq`` / ``learner.net_reset_shrink`` as the learner uses them: ``(N, alpha)``, N = 0 (off) for zero or None.  Refused: a negative or
     fractional N, an alpha outside [0, 1] (NaN included; checked whether or not N is on), and N > 0 together with ``A0_PIPELINE_TARGET=1`` (``pipeline_target``; None
@@ -462,7 +491,7 @@ class DeviceLearner:
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
                  mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0,
-                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True, rank_freq=0, rank_delta=0.01, munchausen=False, mdqn_alpha=0.9):
+                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True, rank_freq=0, rank_delta=0.01, munchausen=False, mdqn_alpha=0.9, hl_gauss=0.0):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -555,6 +584,12 @@ class DeviceLearner:
             self.munchausen, _, self.mdqn_alpha, _ = munchausen_value(munchausen, mdqn_tau, mdqn_alpha, mdqn_lo, algo=L.algo, double_q=double_q)
             if not hasattr(ops, "miqn_target"):
                 raise ValueError("learner.iqn.munchausen=true: needs a backend with miqn_target")
+        # learner.c51.hl_gauss = rho > 0: _fwd_dist ends with c51_hl_gauss_head_loss_slabs — the Gaussian histogram of the scalar TD target in the projected
+        # distribution's place — instead of c51_head_loss_slabs; hl_gauss_sigma = rho * Delta is the double the kernel receives.  A staged target pass (tstage) is
+        # allowed: it ends at the fc1 slabs.  Off (0.0): _fwd_dist issues what it always did.
+        self.hl_gauss, self.hl_gauss_sigma = hl_gauss_value(hl_gauss, vmin, vmax, L.T, algo=L.algo) if hl_gauss else (0.0, 0.0)
+        if self.hl_gauss > 0 and not hasattr(ops, "c51_hl_gauss_head_loss_slabs"):
+            raise ValueError(f"learner.c51.hl_gauss={self.hl_gauss!r}: needs a backend with c51_hl_gauss_head_loss_slabs")
         self.discount, self.n_step, self.double_q = discount, n_step, double_q
         self.gamma_n = float(discount ** n_step)
         self.lr, self.target_update_freq = lr, target_update_freq
@@ -1032,7 +1067,10 @@ class DeviceLearner:
             nh_on = ops.dense_fwd_partial(buf["h_on"], 512, Wh_o, R_on, L.Npad, 512, buf["hs_on"])
             nh_tg = ops.dense_fwd_partial(wt.h, 512, Wh_t, B, L.Npad, 512, buf["hs_tg"])
         head = (buf["hs_on"], nh_on, R_on, buf["hs_tg"], nh_tg, B if dq_ else -1, bh_o, bh_t, L.Npad, L.A, L.T, L.dueling, u.act, u.rew, u.done, u.wgt)
-        if L.algo == "c51":
+        if L.algo == "c51" and self.hl_gauss > 0:      # learner.c51.hl_gauss (a0_fwd_dist's branch): the same launch with the Gaussian histogram in the projection's place
+            ops.c51_hl_gauss_head_loss_slabs(*head, self.atoms, self.gamma_n, self.vmin, self.vmax, self.hl_gauss_sigma, B, self.loss, wo.draw, self.state, q_on=wo.q,
+                                             q_tg=wt.q, m_out=self.m_proj, a_star=self.a_star)
+        elif L.algo == "c51":
             ops.c51_head_loss_slabs(*head, self.atoms, self.gamma_n, self.vmin, self.vmax, B, self.loss, wo.draw, self.state, q_on=wo.q, q_tg=wt.q, m_out=self.m_proj,
                                     a_star=self.a_star)
         else:

@@ -193,6 +193,10 @@ class NativeLearner:
         learner.mdqn's."""
         check(self.lib.a0_learner_set_munchausen(self.h, int(bool(on)), float(tau), float(alpha), float(lo)), "a0_learner_set_munchausen")
 
+    def set_hl_gauss(self, ratio):
+        """learner.c51.hl_gauss through the handle (a0_learner_set_hl_gauss): between updates, on a c51 handle; ``ratio`` = sigma / Delta, <= 0 is off."""
+        check(self.lib.a0_learner_set_hl_gauss(self.h, float(ratio)), "a0_learner_set_hl_gauss")
+
     def grad_norm_ring(self):
         """A copy of the ring of pre-clip gradient norms (A0_PEEK_GRAD_NORM_RING)."""
         ptr, cnt = C.c_void_p(), C.c_longlong()
@@ -548,6 +552,16 @@ class HipOps:
                                    _req(done, torch.float32, B, "done"), _req(wgt, torch.float32, B, "wgt"), _req(atoms, torch.float32, T, "atoms"),
                                    gamma_n, vmin, vmax, B, _req(loss, torch.float32, B, "loss"), _req(dlogits, torch.float32, B * A * T, "dlogits"),
                                    _req(m_out, torch.float32, B * T, "m_out", optional=True), _req(state, torch.int32, 8, "state"), _stream()), "a0_loss_c51")
+
+    def loss_c51_hl_gauss(self, logits, tgt_logits, A, T, act, a_star, rew, done, wgt, atoms, gamma_n, vmin, vmax, sigma, B, loss, dlogits, m_out, state):
+        """learner.c51.hl_gauss, stand-alone (a0_loss_c51_hl_gauss): ``loss_c51``'s arguments plus ``sigma`` = rho * Delta (a double); ``m_out`` receives the Gaussian
+        histogram of the clamped scalar target."""
+        check(self.lib.a0_loss_c51_hl_gauss(_req(logits, torch.float32, B * A * T, "logits"), _req(tgt_logits, torch.float32, B * A * T, "tgt_logits"), A, T,
+                                            _req(act, torch.int32, B, "act"), _req(a_star, torch.int32, B, "a_star"), _req(rew, torch.float32, B, "rew"),
+                                            _req(done, torch.float32, B, "done"), _req(wgt, torch.float32, B, "wgt"), _req(atoms, torch.float32, T, "atoms"),
+                                            gamma_n, vmin, vmax, float(sigma), B, _req(loss, torch.float32, B, "loss"), _req(dlogits, torch.float32, B * A * T, "dlogits"),
+                                            _req(m_out, torch.float32, B * T, "m_out", optional=True), _req(state, torch.int32, 8, "state"), _stream()),
+              "a0_loss_c51_hl_gauss")
 
     def quantile_target(self, q_next, sb, sj, sa, a_star, rew, done, gamma_n, B, Nd, y):
         check(self.lib.a0_quantile_target(_req(q_next, torch.float32, (B - 1) * sb + (Nd - 1) * sj + 1, "q_next"), sb, sj, sa, _req(a_star, torch.int32, B, "a_star"),
@@ -908,6 +922,21 @@ class HipOps:
                                               _req(q_on, torch.float32, B * A * T, "q_on", optional=True), _req(q_tg, torch.float32, B * A * T, "q_tg", optional=True),
                                               _req(m_out, torch.float32, B * T, "m_out", optional=True), _req(a_star, torch.int32, B, "a_star", optional=True),
                                               _req(state, torch.int32, 4, "state"), _stream()), "a0_c51_head_loss_slabs")
+
+    def c51_hl_gauss_head_loss_slabs(self, s_on, nslab_on, rows_on, s_tg, nslab_tg, sel_off, bias_on, bias_tg, ld, A, T, dueling, act, rew, done, wgt, atoms, gamma_n, vmin,
+                                     vmax, sigma, B, loss, draw, state, q_on=None, q_tg=None, m_out=None, a_star=None):
+        """learner.c51.hl_gauss from the head GEMMs' slabs on (a0_c51_hl_gauss_head_loss_slabs): ``c51_head_loss_slabs``'s arguments and slab layout plus ``sigma`` =
+        rho * Delta (a double); the Gaussian histogram of the clamped scalar target stands in the projected distribution's place (``m_out`` receives it)."""
+        nb = ld
+        check(self.lib.a0_c51_hl_gauss_head_loss_slabs(_req(s_on, torch.float32, nslab_on * rows_on * ld, "slabs_on"), rows_on * ld, nslab_on, rows_on,
+                                                       _req(s_tg, torch.float32, nslab_tg * B * ld, "slabs_tg"), B * ld, nslab_tg, int(sel_off),
+                                                       _req(bias_on, torch.float32, nb, "bias_on"), _req(bias_tg, torch.float32, nb, "bias_tg"), ld, A, T, int(dueling),
+                                                       _req(act, torch.int32, B, "act"), _req(rew, torch.float32, B, "rew"), _req(done, torch.float32, B, "done"),
+                                                       _req(wgt, torch.float32, B, "wgt"), _req(atoms, torch.float32, T, "atoms"), float(gamma_n), float(vmin), float(vmax),
+                                                       float(sigma), B, _req(loss, torch.float32, B, "loss"), _req(draw, torch.float32, B * ld, "draw"),
+                                                       _req(q_on, torch.float32, B * A * T, "q_on", optional=True), _req(q_tg, torch.float32, B * A * T, "q_tg", optional=True),
+                                                       _req(m_out, torch.float32, B * T, "m_out", optional=True), _req(a_star, torch.int32, B, "a_star", optional=True),
+                                                       _req(state, torch.int32, 4, "state"), _stream()), "a0_c51_hl_gauss_head_loss_slabs")
 
     def actor_dist_tail(self, slabs, nslab, bias, ld, A, T, dueling, mode, atoms, E, seed, stream_a, stream_u, off_a, off_u, eps, action, qmax, ctrl=None, eps_ptr=None):
         check(self.lib.a0_actor_dist_tail(_req(slabs, torch.float32, nslab * E * ld, "slabs"), E * ld, nslab, _req(bias, torch.float32, ld, "bias"), ld, A, T, int(dueling),

@@ -331,6 +331,27 @@ int a0_qr_head_loss_slabs(const float* slabs_on, long long stride_on, int nslab_
 int a0_loss_c51(const float* logits, const float* tgt_logits, int A, int T, const int* act, const int* a_star,
                 const float* rew, const float* done, const float* wgt, const float* atoms, float gamma_n,
                 float vmin, float vmax, int B, float* loss, float* dlogits, float* m_out, int* nan_flag, void* stream);
+/* learner.c51.hl_gauss: the HL-Gauss classification target (Farebrother et al. 2024, "Stop Regressing: Training Value Functions via Classification for Scalable
+ * Deep RL") in the projected distribution's place — a0_loss_c51's arguments plus sigma, one wave per sample, one lane per bin.  The atoms z_t = vmin + t Delta,
+ * Delta = (vmax - vmin) / (T - 1), are bin CENTRES; the T + 1 edges are e_k = vmin - Delta / 2 + k Delta.  Per sample, in fp32 and in this order:
+ * p' = softmax(tgt_logits at a_star), v' = (sum_t e'_t z_t) / (sum_t e'_t) with the wave sums of a0_select_action's mode 2, y = rew + (gamma_n (1 - done)) v',
+ * y clamped to [vmin, vmax] by comparisons (a NaN reward stays NaN and reaches the loss and the flag).  Then in DOUBLE on the device, rounded to fp32 once:
+ *   m_t = [Phi((e_{t+1} - y) / sigma) - Phi((e_t - y) / sigma)] / [Phi((e_T - y) / sigma) - Phi((e_0 - y) / sigma)],  Phi(u) = (1 + erf(u / sqrt 2)) / 2,
+ * each lane evaluating its own two edges and the two outer ones (equal inputs give equal bytes), Delta the double quotient of the fp32 vmin and vmax.  sigma =
+ * rho * Delta is handed over AS A DOUBLE and used as one; it must still be a normal fp32 number once rounded.  Loss and dlogits are a0_loss_c51's cross
+ * entropy against m unchanged; m_out (optional) receives m.  A0_EINVAL, with the number named: a0_loss_c51's conditions, a sigma that is NaN, infinite, <= 0,
+ * not a normal fp32 number, or above T * Delta (rho > num_atoms). */
+int a0_loss_c51_hl_gauss(const float* logits, const float* tgt_logits, int A, int T, const int* act, const int* a_star,
+                         const float* rew, const float* done, const float* wgt, const float* atoms, float gamma_n,
+                         float vmin, float vmax, double sigma, int B, float* loss, float* dlogits, float* m_out, int* nan_flag, void* stream);
+/* learner.c51.hl_gauss from the head GEMMs' split-K slabs on, one launch: a0_c51_head_loss_slabs with the Gaussian histogram of a0_loss_c51_hl_gauss in the
+ * projection's place (no gather tables) — same slab layout, same meaning of rows_on / sel_off, same optional outputs; m_out receives the histogram.  The
+ * expectation v' at a* is taken from the TARGET's logits also under double-Q, where a* is the online network's choice.  Given the q values it writes, loss, m_out
+ * and a_star equal a0_loss_c51_hl_gauss and draw equals a0_dueling_bwd of its dlogits, bit for bit.  sigma and its refusals as there. */
+int a0_c51_hl_gauss_head_loss_slabs(const float* slabs_on, long long stride_on, int nslab_on, int rows_on, const float* slabs_tg, long long stride_tg, int nslab_tg,
+                                    int sel_off, const float* bias_on, const float* bias_tg, int ld, int A, int T, int dueling, const int* act, const float* rew,
+                                    const float* done, const float* wgt, const float* atoms, float gamma_n, float vmin, float vmax, double sigma, int B, float* loss,
+                                    float* draw, float* q_on_out, float* q_tg_out, float* m_out, int* a_star_out, int* nan_flag, void* stream);
 /* quantile target r + gamma^n (1-d) q_next[a*] (agent.py:281-286,313-318,358-364) and BaseLearner.huber_qr_loss
  * (agent.py:110-114) with its gradient; strides let QR ([B][A][N]) and IQN/FQF ([B][N][A]) share the kernels. */
 int a0_quantile_target(const float* q_next, long long sb, long long sj, long long sa, const int* a_star, const float* rew,
@@ -649,6 +670,12 @@ int a0_learner_set_aug_shift(a0_learner* learner, int pad);
  * and the number named: a handle of another algo, a double-Q handle (there is no argmax to decouple), tau <= 0, alpha < 0, lo > 0, one of the three NaN or
  * infinite (as given or once rounded to float), a call after the handle's first update.  Descriptor structs are unchanged and nothing is added to a snapshot. */
 int a0_learner_set_munchausen(a0_learner* learner, int on, double tau, double alpha, double lo);
+/* learner.c51.hl_gauss through the handle (c51 handles only): with ratio > 0 every a0_learner_update ends its forward half with a0_c51_hl_gauss_head_loss_slabs
+ * instead of a0_c51_head_loss_slabs, sigma = ratio * Delta formed in double from the handle's fp32 vmin and vmax, Delta = (vmax - vmin) / (num_atoms - 1).
+ * ratio <= 0: off again, the update issues what it always did (on a handle of any algo).  A0_EINVAL, each with the setting and the number named: a ratio that is
+ * NaN or infinite, and with ratio > 0 a handle of another algo, ratio > num_atoms, a sigma that is not a normal fp32 number.  Call it between updates, not while
+ * one is being captured; nothing is allocated, descriptor structs are unchanged, and nothing is added to a snapshot. */
+int a0_learner_set_hl_gauss(a0_learner* learner, double ratio);
 /* parameters in the packed layout (device pointers, a0_learner_param_floats floats each); target_packed = NULL: target = copy of online (agent.py:100) */
 int a0_learner_set_params(a0_learner* learner, const float* online_packed, const float* target_packed, void* stream);
 /* copies of what the handle holds (any pointer may be NULL): parameters, target parameters, Adam moments (param_floats each), the eight status words */
