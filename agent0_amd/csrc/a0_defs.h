@@ -69,6 +69,12 @@ enum {
     A0_ESTATE = -4,   // call not valid in the current state
 };
 
+// launch families of the profiler probe (probe.hip; ops.py's PROBE_TAGS and bench.py's roofline use the numbers).  1 - 11: set on the backend before each GEMM of net_impl.h;
+// 12 - 14: the fused kernels (14: the actor step's tail + env step + next observation's encoder in one kernel, a family of its own: the encoder's roofline keeps the pure launches)
+enum { A0_TAG_NONE = 0, A0_TAG_CONV1_FWD = 1, A0_TAG_CONV2_FWD = 2, A0_TAG_CONV3_FWD = 3, A0_TAG_DENSE_FWD = 4, A0_TAG_DENSE_DGRAD = 5,
+       A0_TAG_DENSE_WGRAD = 6, A0_TAG_CONV3_WGRAD = 7, A0_TAG_CONV3_DGRAD = 8, A0_TAG_CONV2_WGRAD = 9, A0_TAG_CONV2_DGRAD = 10, A0_TAG_CONV1_WGRAD = 11,
+       A0_TAG_ENCODER_FUSED = 12, A0_TAG_ENCODER_DGRAD_FUSED = 13, A0_TAG_ACTOR_STEP_ENC = 14 };
+
 // Geometry of a "virtual convolution": row m = (b, oh, ow) reads
 //   in[b][oh*stride - pad + kh][ow*stride - pad + kw][c]
 // Used for forward im2col (pad = 0) and for gather-form data gradients (stride = 1, pad > 0).

@@ -193,7 +193,7 @@ extern "C" int a0_actor_fc1_ok(int R, int N, int K) {
 extern "C" int a0_actor_fc1_n(const float* X, int ldx, const unsigned int* planes, int R, int N, int K, int splits, float* slabs, void* stream) {
     if (!X || !planes || !slabs || (ldx & 3) || ldx < K || !a0_actor_fc1_ok(R, N, K) || ((((uintptr_t)X) | ((uintptr_t)planes)) & 15))
         return a0_fail(A0_EINVAL, "a0_actor_fc1_n: shapes a0_actor_fc1_ok accepts (16-byte aligned rows)");
-    if (splits < 1 || splits > 64 || splits > (K + 31) / 32) return a0_fail(A0_EINVAL, "a0_actor_fc1_n: splits must lie in [1, min(64, ceil(K / 32))]");
+    if (const int rc = a0_splits_check("a0_actor_fc1_n", splits, K)) return rc;
     const int ktiles = K / 32;
     const int kchunk = ((ktiles + splits - 1) / splits) * 32;         // a0_igemm_x9_launch's
     const int gx = (R + 63) / 64, gy = N / 64;

@@ -1,4 +1,4 @@
-// The scalar-head actor tail + the synthetic env's step as DEVICE functions, shared by the kernel that runs them alone (a0_actor_qhead_env_kernel, net.hip) and the
+// The scalar-head actor tail + the synthetic env's step as DEVICE functions, shared by the kernel that runs them alone (a0_actor_qhead_env_kernel, actor_tail.hip) and the
 // kernel that goes on to encode the NEXT observation in the same launch (a0_actor_step_enc2_kernel, encoder_fused.hip: round 5).
 #pragma once
 #include "synth_env.h"
@@ -333,7 +333,7 @@ A0_D void a0_actor_dist_tail_env_body(const a0_dtenv_args& P, float* __restrict_
     asm volatile("" : "+v"(e_v));
     const a0_u4 x = a0_philox4x32_10(e_v, g, 0u, 0x454E56u, (uint32_t)P.env_seed, (uint32_t)(P.env_seed >> 32) ^ P.rank);
     const bool term = (x.y % 500u) == 0u;
-    // A0_ENV_TASK_CHASE: the frame waves wait at a workgroup barrier for wave 0's action and read the block's new cell from LDS (a0_actor_qhead_env_kernel, net.hip)
+    // A0_ENV_TASK_CHASE: the frame waves wait at a workgroup barrier for wave 0's action and read the block's new cell from LDS (a0_actor_qhead_env_kernel, actor_tail.hip)
     const bool chase = P.task == A0_ENV_TASK_CHASE;
     if (wave != 0) {
         int cell = -1;

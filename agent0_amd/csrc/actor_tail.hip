@@ -1,6 +1,6 @@
-// The actor tails over the head GEMM's split-K slabs — c51 / qr (one row per env) and iqn / fqf (a row per env and fraction) — alone and merged with the synthetic
-// env's step, and their launchers.  The scalar heads' counterparts live in net.hip beside the fc1 GEMM they start with.  No file-scope contraction pragma here: the
-// tails' multiply-adds fuse as the compiler's default has them.
+// Every actor tail, alone and merged with the synthetic env's step, and their launchers: the scalar heads' (dqn / mdqn), which start with their fc1 (a0_actor_fc1_slabs,
+// dense.hip), and those over the head GEMM's split-K slabs — c51 / qr (one row per env) and iqn / fqf (a row per env and fraction).  No file-scope contraction pragma
+// here: the tails' multiply-adds fuse as the compiler's default has them.
 #include "a0_internal.h"
 #include "actor_step.h"
 #include "actor_tail.h"      // a0_wave_sum / a0_wave_max, the actor tails' device functions
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void a0_actor_dist_tail_kernel(const float* __
 }
 
 // ---- the same tail AND the synthetic env's step in one launch, a workgroup per env (the distributional counterpart of
-// a0_actor_qhead_env_kernel, net.hip): all four waves sum the head's slabs into LDS (one column per thread: the same slab-order additions),
+// a0_actor_qhead_env_kernel, below): all four waves sum the head's slabs into LDS (one column per thread: the same slab-order additions),
 // then wave 0 alone applies the dueling combine, takes the expectation and the first maximum, draws the action and does the env's scalar work
 // with it, while waves 1-3 already write the new frame, the shifted stack and the replay row.  Same bytes as a0_actor_dist_tail +
 // a0_env_synth_step_commit.
@@ -258,4 +258,129 @@ extern "C" int a0_actor_dist_tail(const float* slabs, long long slab_stride, int
     const a0_slab_head head{slabs, slab_stride, nslab, bias, ld, A, T, dueling, mode, atoms, nullptr, 0};
     const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
     return a0_actor_slab_tail_launch(head, E, draw, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------ fused actor tail (dqn / mdqn)
+// Everything between the conv features and the chosen action of Actor.act (reference agent.py:25-39 with model.py:108-131 behind it), for scalar-valued heads: fc1 runs as
+// the usual split-K implicit GEMM (a0_actor_fc1_slabs), but its slabs are consumed directly by ONE kernel that finishes fc1 (slab sum + bias + ReLU), evaluates the q head (A or
+// A+1 rows of 512), applies the dueling combine, takes the first maximum and makes the epsilon-greedy draw from the actor's Philox streams.  One wave per environment; replaces
+// six launches (reduce, head GEMM, reduce, dueling, select, egreedy) on the actor's critical path.
+__global__ __launch_bounds__(256) void a0_actor_qhead_kernel(const float* __restrict__ slabs, long long slab_stride, int nslab, const float* __restrict__ b1,
+                                                             const float* __restrict__ W2, const float* __restrict__ b2, int A, int dueling, int E,
+                                                             unsigned long long seed, uint32_t stream_a, uint32_t stream_u, unsigned long long off_a,
+                                                             unsigned long long off_u, float eps, const long long* __restrict__ ctrl,
+                                                             const float* __restrict__ eps_ptr, int* __restrict__ action, float* __restrict__ qmax) {
+    __shared__ float raw[4][64];
+    extern __shared__ float w2s[];                       // the head's A(+1) rows of 512, staged once per workgroup
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int e = blockIdx.x * 4 + wave;
+    const int NQ = A + (dueling ? 1 : 0);
+    for (int i = threadIdx.x; i < NQ * 128; i += 256) ((a0_f4*)w2s)[i] = ((const a0_f4*)W2)[i];
+    __syncthreads();
+    if (e >= E) return;
+    if (ctrl) { off_a += (unsigned long long)ctrl[A0_CTRL_RNG_ACTION]; off_u += (unsigned long long)ctrl[A0_CTRL_RNG_UNIFORM]; }
+    eps = a0_env_eps(eps, eps_ptr, (uint32_t)__builtin_amdgcn_readfirstlane(e));      // one env per wave
+    int act = 0; float best = 0.f;
+    a0_qhead_wave(slabs, slab_stride, nslab, b1, w2s, b2, A, dueling, e, lane, raw[wave], seed, stream_a, stream_u, off_a, off_u, eps, act, best);
+    if (lane == 0) { action[e] = act; qmax[e] = best; }
+}
+
+__global__ __launch_bounds__(512) void a0_actor_qhead_env_kernel(a0_qenv_args P) {
+    __shared__ float raw[64];
+    __shared__ int s_chase_cell;
+    extern __shared__ float w2s[];
+    a0_actor_qhead_env_body(P, raw, w2s, &s_chase_cell);
+}
+
+// (the fc1's own split count: a0_dense_fwd_partial's at N = 512)
+extern "C" long long a0_actor_qhead_scratch(int E, int K) { return (long long)a0_dense_fwd_partial_slabs(E, 512, K) * E * 512; }
+
+extern "C" int a0_actor_qhead_n(const float* feat, int E, int K, int splits, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
+    A0_TRY
+    if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !action || !qmax || E < 1 || K < 4 || (K & 3) || A < 1 || A + (dueling ? 1 : 0) > 24)
+        return a0_fail(A0_EINVAL, "a0_actor_qhead: bad argument (A + dueling <= 24: the head rows are staged in 48 KB of LDS)");
+    if (const int rc = a0_splits_check("a0_actor_qhead_n", splits, K)) return rc;
+    if (const int rc = a0_actor_fc1_slabs(feat, K, W1, nullptr, E, splits, scratch, (hipStream_t)stream)) return rc;
+    hipLaunchKernelGGL(a0_actor_qhead_kernel, dim3((E + 3) / 4), dim3(256), (size_t)(A + (dueling ? 1 : 0)) * 512 * sizeof(float), (hipStream_t)stream, scratch, (long long)E * 512, splits, b1, W2, b2, A, dueling, E,
+                       seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax);
+    A0_HIP_THROW(hipGetLastError());
+    return A0_OK;
+    A0_CATCH
+}
+
+extern "C" int a0_actor_qhead(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                              float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                              unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax, void* stream) {
+    return a0_actor_qhead_n(feat, E, K, a0_dense_fwd_partial_slabs(E, 512, K), W1, b1, W2, b2, A, dueling, scratch, seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action,
+                            qmax, stream);
+}
+
+// a0_actor_qhead + a0_env_synth_step_commit: fc1 GEMM over `feat` (this step's features), then ONE launch per env for tail + env step — with `next`, the launch goes on
+// to encode the env's NEW observation (round 5, a0_actor_step_enc2_kernel in encoder_fused.hip) into next->act3_next, which may be `feat` itself: the GEMM has read it
+int a0_actor_qhead_env_launch(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling, float* scratch,
+                              const a0_step_draw& draw, const a0_env_commit& env, const a0_next_enc* next, const unsigned int* w1_planes, hipStream_t st) {
+    A0_TRY
+    if (!feat || !W1 || !b1 || !W2 || !b2 || !scratch || !draw.action || !draw.qmax || E < 1 || (next ? K != 3136 : (K < 4 || (K & 3))) || A < 1 || A + (dueling ? 1 : 0) > 24)
+        return a0_fail(A0_EINVAL, next ? "a0_actor_qhead_env_step_enc: bad argument (4 x 84 x 84 observations, A + dueling <= 24)"
+                                       : "a0_actor_qhead_env_step: bad argument (A + dueling <= 24: the head rows are staged in 48 KB of LDS)");
+    { const int rc = a0_env_commit_check(env, E, A, next ? "a0_actor_qhead_env_step_enc" : "a0_actor_qhead_env_step"); if (rc != A0_OK) return rc; }
+    const int splits = a0_dense_fwd_partial_slabs(E, 512, K);
+    { const int rc = a0_actor_fc1_slabs(feat, K, W1, w1_planes, E, splits, scratch, st); if (rc != A0_OK) return rc; }
+    a0_qenv_args P;
+    P.slabs = scratch; P.slab_stride = (long long)E * 512; P.nslab = splits; P.b1 = b1; P.W2 = W2; P.b2 = b2; P.A = A; P.dueling = dueling; P.E = E;
+    a0_step_fill(P, draw, env);
+    if (next) return a0_actor_step_enc_launch(P, next->wt, next->w, next->act3_next, st);
+    hipLaunchKernelGGL(a0_actor_qhead_env_kernel, dim3(E), dim3(512), (size_t)(A + (dueling ? 1 : 0)) * 512 * sizeof(float), st, P);
+    A0_HIP_THROW(hipGetLastError());
+    return A0_OK;
+    A0_CATCH
+}
+
+// (w1_planes: a0_actor_fc1_planes of W1 — fc1 then runs as a0_actor_fc1_kernel where a0_actor_fc1_ok accepts the step; the plain forms pass none)
+extern "C" int a0_actor_qhead_env_step_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                       float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                       unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                                       unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                                       float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                                       const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, const unsigned int* w1_planes, void* stream) {
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, nullptr, w1_planes, (hipStream_t)stream);
+}
+extern "C" int a0_actor_qhead_env_step(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                       float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                       unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                                       unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                                       float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                                       const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task, void* stream) {
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int a0_actor_qhead_env_step_enc_wp(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                           float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                           unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                                           unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                                           float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                                           const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
+                                           const float* wt, const a0_encoder_weights* w, float* act3_next, const unsigned int* w1_planes, void* stream) {
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    const a0_next_enc next{wt, w, act3_next};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, &next, w1_planes, (hipStream_t)stream);
+}
+extern "C" int a0_actor_qhead_env_step_enc(const float* feat, int E, int K, const float* W1, const float* b1, const float* W2, const float* b2, int A, int dueling,
+                                           float* scratch, unsigned long long seed, unsigned int stream_a, unsigned int stream_u, unsigned long long off_a,
+                                           unsigned long long off_u, float eps, const long long* ctrl, const float* eps_ptr, int* action, float* qmax,
+                                           unsigned long long env_seed, unsigned int rank, unsigned int g, const uint8_t* obs_in, uint8_t* obs_out, float* ep_ret,
+                                           float* final_mask, float* final_ret, int n, long long steps, double gamma, int* ring_act, float* ring_rew, float* ring_done,
+                                           const uint8_t* obs0, uint8_t* frames, long long cap, long long start_slot, int* r_act, float* r_rew, float* r_done, int task,
+                                           const float* wt, const a0_encoder_weights* w, float* act3_next, void* stream) {
+    const a0_step_draw draw{seed, stream_a, stream_u, off_a, off_u, eps, ctrl, eps_ptr, action, qmax};
+    const a0_env_commit env{env_seed, rank, g, obs_in, obs_out, ep_ret, final_mask, final_ret, n, steps, gamma, ring_act, ring_rew, ring_done, obs0, frames, cap, start_slot, r_act, r_rew, r_done, task};
+    const a0_next_enc next{wt, w, act3_next};
+    return a0_actor_qhead_env_launch(feat, E, K, W1, b1, W2, b2, A, dueling, scratch, draw, env, &next, nullptr, (hipStream_t)stream);
 }

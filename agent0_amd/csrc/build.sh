@@ -7,7 +7,7 @@ mkdir -p "${OUT}" "${HERE}/_obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(-O3 --offload-arch=gfx950 -fPIC -std=c++17 -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function -I"${HERE}/../../include")
 # (one line: tools/build_variant.sh reads the list from here)
-SRCS=(core net actor_fc1 encoder_fused conv1_wgrad conv23_wgrad actor_tail loss loss_value loss_c51 loss_quantile quantile optim net_reset feature_rank noisy replay rng augment synth_env actor host_step dp learner runtime snapshot)
+SRCS=(core probe net dense reduce actor_fc1 encoder_fused conv1_wgrad conv23_wgrad actor_tail loss loss_value loss_c51 loss_quantile quantile optim net_reset feature_rank noisy replay rng augment synth_env actor host_step dp learner runtime snapshot)
 pids=()
 for s in "${SRCS[@]}"; do
   src="${HERE}/${s}.hip"; obj="${HERE}/_obj/${s}.o"

@@ -1,4 +1,4 @@
-// Error plumbing and device queries for the C-ABI.
+// Error plumbing, device queries and the process-wide GEMM switches for the C-ABI.
 #include "a0_internal.h"
 
 #include <cstdio>
@@ -41,6 +41,23 @@ extern "C" int a0_device_info(int* cu_count, long long* hbm_bytes, char* arch_na
     if (hbm_bytes) *hbm_bytes = (long long)p.totalGlobalMem;
     if (arch_name64) { std::strncpy(arch_name64, p.gcnArchName, 63); arch_name64[63] = 0; }
     return A0_OK;
+}
+
+// ---- GEMM switches: fp32 operands run on the split-operand kernels of the bf16 matrix pipe (igemm_x9.h); A0_GEMM=fp32 keeps the fmaf-chain kernel.  mode < 0 only reads.
+static int g_gemm_x9 = (getenv("A0_GEMM") && std::string(getenv("A0_GEMM")) == "fp32") ? 0 : 1;
+extern "C" int a0_gemm_mode(int mode) {
+    const int prev = g_gemm_x9;
+    if (mode >= 0) g_gemm_x9 = mode ? 1 : 0;
+    return prev;
+}
+
+// Cross products of the split-operand kernels (igemm_x9.h, encoder_fused.hip): 6 (default) or 9 (strict: every partial product of the fp32 chain)
+static int g_x9_products = (getenv("A0_X9_PRODUCTS") && atoi(getenv("A0_X9_PRODUCTS")) == 9) ? 9 : 6;
+int a0_x9_products_now() { return g_x9_products; }
+extern "C" int a0_x9_products(int n) {
+    const int prev = g_x9_products;
+    if (n == 6 || n == 9) g_x9_products = n;
+    return prev;
 }
 
 // ------------------------------------------------------------------------------------------------ roctx ranges (SURVEY.md §5 tracing; the reference times wall clock only, trainer.py:176-180)

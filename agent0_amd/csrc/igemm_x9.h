@@ -161,7 +161,7 @@ template <class OP, int BX, int NTH, int KS> struct a0_x9_stager<OP, BX, NTH, KS
 };
 
 // ---- an operand that is ALREADY split (round 6): the three bf16 term planes of a weight matrix W [N][K], written once per optimizer step by a0_split_planes_kernel
-// (net.hip) and reused by every GEMM until the weights change — the actor's fc1 runs 80 steps on one W, a learner pass has rows in the tens of thousands — so that
+// (dense.hip) and reused by every GEMM until the weights change — the actor's fc1 runs 80 steps on one W, a learner pass has rows in the tens of thousands — so that
 // this operand's tiles go from global memory to the LDS term planes without a vector instruction.  Layout: per row n and group g of four consecutive k six dwords
 // { hi(k0,k1) hi(k2,k3) | mid .. | lo .. } = the three 8-byte LDS stores of a piece, 24 bytes apart.  K % 4 == 0; rows beyond Y and the k range past the split's end
 // are NOT zero-filled (callers guarantee whole k tiles; rows past the edge only feed outputs that are never stored).
@@ -629,7 +629,7 @@ static inline hipError_t a0_igemm_x9_launch(hipStream_t st, const typename OA::P
     const int ktiles = (K + BK - 1) / BK;
     const int kchunk = ((ktiles + splits - 1) / splits) * BK;
     const int gx = (X + G::BX - 1) / G::BX, gy = (Y + G::BY - 1) / G::BY;
-    // ev0 / ev1 (the profiler probe, net.hip): the launch carries the event pair — the dispatch's own begin / end timestamps
+    // ev0 / ev1 (the profiler probe, probe.hip): the launch carries the event pair — the dispatch's own begin / end timestamps
     if (ev0) hipExtLaunchKernelGGL(kern, dim3((unsigned)(gx * gy * splits)), dim3(WM * WN * 64), (uint32_t)G::LDS_BYTES, st, ev0, ev1, 0, pa, pb, pe, X, Y, K, kchunk, gx, gy);
     else hipLaunchKernelGGL(kern, dim3((unsigned)(gx * gy * splits)), dim3(WM * WN * 64), G::LDS_BYTES, st, pa, pb, pe, X, Y, K, kchunk, gx, gy);
     return hipGetLastError();

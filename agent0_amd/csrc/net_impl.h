@@ -1,7 +1,8 @@
 // Layer orchestration of the Nature CNN, written once against a "backend" that knows how to run one implicit GEMM
-// and three small reductions.  net.hip instantiates it with the HIP backend (real kernels); tests/host_emul.cpp
-// instantiates it with a CPU backend that evaluates the very same operand/epilogue policies in plain loops, so every
-// table, stride and geometry decision below is exercised by the CPU test-suite before it ever reaches a GPU.
+// and three small reductions.  net.hip (encoder) and dense.hip (dense layers) instantiate it with the HIP backend
+// (hip_backend.h: real kernels); tests/host_emul.cpp instantiates it with a CPU backend that evaluates the very same
+// operand/epilogue policies in plain loops, so every table, stride and geometry decision below is exercised by the CPU
+// test-suite before it ever reaches a GPU.
 //
 // Backend concept:
 //   template <class OA, class OB, class EP, int WM, int WN, int MT, int NT>
@@ -15,9 +16,7 @@
 #include "operands.h"
 #include "../../include/agent0_hip.h"
 
-// layer tags: set on the backend before each GEMM so a profiler probe can single out one kernel (bench.py roofline)
-enum { A0_TAG_NONE = 0, A0_TAG_CONV1_FWD = 1, A0_TAG_CONV2_FWD = 2, A0_TAG_CONV3_FWD = 3, A0_TAG_DENSE_FWD = 4, A0_TAG_DENSE_DGRAD = 5,
-       A0_TAG_DENSE_WGRAD = 6, A0_TAG_CONV3_WGRAD = 7, A0_TAG_CONV3_DGRAD = 8, A0_TAG_CONV2_WGRAD = 9, A0_TAG_CONV2_DGRAD = 10, A0_TAG_CONV1_WGRAD = 11 };
+// layer tags (A0_TAG_*, a0_defs.h): set on the backend before each GEMM so a profiler probe can single out one kernel (bench.py roofline)
 
 // one slab reduction: out[i] = sum_z slabs[z * slab_stride + i], i < count
 // a0_reduce_seg, a0_pending_reduce: include/agent0_hip.h
@@ -114,8 +113,9 @@ static inline int a0_conv_wgrad_splits(int K, int M) {
 
 static inline int a0_chunk_rows(int R, int splits) { return (((R + 31) / 32 + splits - 1) / splits) * 32; }
 
+static inline int a0_dense_fwd_splits_impl(int R, int N, int K) { return a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K); }      // a dense forward layer: 128 x 64 tiles
 static inline long long a0_dense_fwd_scratch_impl(int R, int N, int K) {
-    int s = a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K);
+    int s = a0_dense_fwd_splits_impl(R, N, K);
     return s > 1 ? (long long)s * R * N : 0;
 }
 
@@ -227,9 +227,8 @@ static void a0_dense_fwd_impl(BK& bk, const float* X, int ldx, const float* W, c
     if (splits_in <= 1 && a0_short_k_shape(R, N, K, ldx)) { bk.short_k_fwd(X, ldx, W, b, nullptr, 1, Y, nullptr, R, N, relu); return; }
     a0_mat_src a{X, ldx};
     a0_mat_src bw{W, K};
-    const int splits = splits_in > 0 ? splits_in : a0_fwd_splits((R + 127) / 128, (N + 63) / 64, K);
+    const int splits = splits_in > 0 ? splits_in : a0_dense_fwd_splits_impl(R, N, K);
     const bool narrow = (N <= 32);
-    bk.tag = A0_TAG_DENSE_FWD;
     if (splits == 1) {
         EpiBiasAct::Params e{Y, b, N, relu};
         if (narrow) bk.template igemm<OpMatKC, OpMatKC, EpiBiasAct, 4, 1, 1, 1>(a, bw, e, R, N, K, 1);

@@ -1,5 +1,5 @@
-// Device functions of the synthetic vector env that more than one translation unit needs (synth_env.hip: the env's own kernels; net.hip: the
-// actor tail that also performs the env step).  Byte-exact twin of oracle/synth_env.c.
+// Device functions of the synthetic vector env that more than one translation unit needs (synth_env.hip: the env's own kernels; actor_tail.hip: the
+// actor tails that also performs the env step).  Byte-exact twin of oracle/synth_env.c.
 #pragma once
 #include "a0_defs.h"
 #include "philox.h"

@@ -1,5 +1,5 @@
 // What the one-launch update tail (optim.hip: a0_update_tail_kernel) shares with the kernels it replaces per update: the row-group sums of
-// a0_reduce_segments_kernel (net.hip), the weight-copy layout and the bf16 terms of a0_conv_wt_kernel (encoder_fused.hip), and the one-thread
+// a0_reduce_segments_kernel (reduce.hip), the weight-copy layout and the bf16 terms of a0_conv_wt_kernel (encoder_fused.hip), and the one-thread
 // bookkeeping of an optimizer step (a0_step_decide / a0_step_publish), which every Adam form runs and the tail has run in the launch in front of it.
 // The scatter of a new weight into the weight copies is shared further: the soft target update (optim.hip), the reset and the recycle (net_reset.hip) use it too.
 #pragma once
