@@ -48,6 +48,8 @@ static inline bool a0_aligned(unsigned bytes, const P*... p) { return ((((uintpt
 #define A0_STREAM_REDO 9
 // augment.hip: the range checks of a0_augment_shift (A0_EINVAL with a message that starts with `who`)
 int a0_augment_shift_check(const char* who, int C, int H, int W, int pad, long long row_bytes);
+// quantile.hip: learner.iqn.risk's (kind, eta) as every entry point and both handles' setters check them (A0_EINVAL with a message that starts with `who`)
+int a0_risk_check(const char* who, int kind, double eta);
 
 // roctx ranges (core.hip): no-ops unless A0_ROCTX=1
 void a0_trace_push_internal(const char* name);

@@ -517,11 +517,31 @@ extern "C" int a0_learner_set_munchausen(a0_learner* L, int on, double tau, doub
         return a0_fail(A0_EINVAL, msg);
     }
     if (L->d.double_q) return a0_fail(A0_EINVAL, "a0_learner_set_munchausen: learner.iqn.munchausen not together with double_q = 1 (the target has no argmax to decouple)");
+    if (L->risk_kind != A0_RISK_NEUTRAL) return a0_fail(A0_EINVAL, "a0_learner_set_munchausen: learner.iqn.munchausen not together with learner.iqn.risk (a0_learner_set_risk: the target's policy is the softmax of the risk-neutral mean)");
     if (!L->act3_m) {
         L->act3_m = L->alloc<float>((long long)L->d.B * L->feat);
         a0_qws_buffers(L, L->qm, L->d.iqn_N_dash, L->act3_m, false);
     }
     L->miqn = true; L->miqn_tau = t32; L->miqn_alpha = a32; L->miqn_lo = l32;
+    return A0_OK;
+    A0_CATCH
+}
+
+// learner.iqn.risk (DeviceLearner: risk_value + the constructor's refusals)
+extern "C" int a0_learner_set_risk(a0_learner* L, int kind, double eta) {
+    A0_TRY
+    if (!L) return a0_fail(A0_EINVAL, "a0_learner_set_risk: null handle");
+    if (L->updated) return a0_fail(A0_EINVAL, "a0_learner_set_risk: learner.iqn.risk is fixed once the handle has run an update");
+    A0_CHECK(a0_risk_check("a0_learner_set_risk", kind, eta));
+    if (kind == A0_RISK_NEUTRAL) { L->risk_kind = A0_RISK_NEUTRAL; L->risk_eta = 0.0; return A0_OK; }
+    if (L->d.algo != A0_ALGO_IQN) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "a0_learner_set_risk: learner.iqn.risk = %d is for iqn handles only (this handle's algo is %d; fqf proposes its fractions, it does not draw them)", kind, L->d.algo);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (L->miqn) return a0_fail(A0_EINVAL, "a0_learner_set_risk: learner.iqn.risk not together with learner.iqn.munchausen (its target's policy is the softmax of the risk-neutral mean)");
+    if (!L->t_risk) L->t_risk = L->alloc<float>(ceil_to((long long)L->d.B * L->d.iqn_K, 4));
+    L->risk_kind = kind; L->risk_eta = eta;
     return A0_OK;
     A0_CATCH
 }
@@ -739,7 +759,12 @@ static int a0_fwd_iqn(a0_upd& u) {
         A0_CHECK(a0_upd_encode(u, {{true, true, L->act3_t, false}, {false, true, dq ? L->act3_s : nullptr, false}, {false, false, L->act3_o, true}}));
         // greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
         a0_learner::QWs& sel = dq ? L->qs : L->qt;
-        A0_CHECK(a0_iqn_head(L, !dq, sel, L->t_sel, K, false, stream));
+        const float* t_sel = L->t_sel;
+        if (L->risk_kind != A0_RISK_NEUTRAL) {      // learner.iqn.risk: the policy's K fractions distorted into the handle's own buffer; the draws stay what they are
+            A0_CHECK(a0_risk_distort(L->t_sel, L->t_risk, (long long)B * K, L->risk_kind, L->risk_eta, stream));
+            t_sel = L->t_risk;
+        }
+        A0_CHECK(a0_iqn_head(L, !dq, sel, t_sel, K, false, stream));
         A0_CHECK(a0_select_action(sel.q, (long long)K * A, 1, A, B, A, K, 1, nullptr, L->a_star, nullptr, nullptr, stream));
         A0_CHECK(a0_iqn_head(L, true, L->qt, L->t_tgt, Nd, false, stream));
         A0_CHECK(a0_quantile_target(L->qt.q, (long long)Nd * A, A, 1, L->a_star, u.rew, u.done, L->gamma_n, B, Nd, L->y, stream));

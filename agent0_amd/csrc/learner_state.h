@@ -107,6 +107,11 @@ struct a0_learner {
     float miqn_tau = 0.03f, miqn_alpha = 0.9f, miqn_lo = -1.f;
     float* act3_m = nullptr;
     QWs qm;
+    // ---- risk-sensitive IQN policy (a0_learner_set_risk): off while risk_kind is A0_RISK_NEUTRAL; t_risk: the K selection fractions distorted (B * K floats, the
+    // handle's own, allocated by the first call that switches it on) — t_sel keeps the uniform draws
+    int risk_kind = A0_RISK_NEUTRAL;
+    double risk_eta = 0.0;
+    float* t_risk = nullptr;
     // ---- HL-Gauss target of the c51 handle (a0_learner_set_hl_gauss): off while hlg_sigma == 0; sigma = ratio * Delta as a0_c51_hl_gauss_head_loss_slabs receives it
     double hlg_sigma = 0.0;
     // library-owned HBM

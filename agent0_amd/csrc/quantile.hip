@@ -4,6 +4,10 @@
 // agent0/deepq/agent.py:371-387 (fraction loss).
 #include "a0_internal.h"
 #include "philox.h"
+#include "rng_elem.h"
+
+#include <cmath>
+#include <cstdio>
 
 // cosx[r][i] = cos((pi * (i+1)) * tau_r), i < D   — pi*(i+1) rounded to fp32 first, as `np.pi * torch.arange(1, D+1)` is
 __global__ void a0_cos_features_kernel(const float* __restrict__ taus, float* __restrict__ out, long long R, int D) {
@@ -43,6 +47,127 @@ extern "C" int a0_tau_cos_features(unsigned long long seed, unsigned int stream,
     const long long n = R * D;
     hipLaunchKernelGGL(a0_tau_cos_features_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_h, seed, stream, offset, ctrl, ctrl_idx, taus, out, R, D);
     return a0_fail_hip((int)hipGetLastError(), "a0_tau_cos_features");
+}
+
+// ---- learner.iqn.risk: the distortion beta of a risk-sensitive IQN policy (Dabney et al. 2018, section 4), applied where the policy's fractions are drawn.
+// The formula is stated ONCE, here; a0_risk_distort_kernel and a0_tau_cos_features_risk_kernel both call it.  tau is the fp32 draw k * 2^-24.  cvar: one fp32
+// multiply by eta rounded to fp32 (numpy float32 gives the same bits).  pow, cpw, wang: formed in double from (double)tau and the double eta and rounded to fp32
+// once; Phi(u) = erfc(-u / sqrt 2) / 2, never 1 + erf: the lower tail is where a risk-averse wang lives.  tau == 0 gives 0 for every kind; a result above 1
+// becomes 1 by a comparison, so a NaN stays a NaN.
+A0_D float a0_risk_beta(float tau, int kind, double eta) {
+#pragma clang fp contract(off)
+    if (kind == A0_RISK_NEUTRAL) return tau;
+    float f;
+    if (kind == A0_RISK_CVAR) {
+        f = (float)eta * tau;
+    } else {
+        if (tau == 0.f) return 0.f;
+        const double t = (double)tau;
+        double r;
+        if (kind == A0_RISK_POW) {
+            const double e = 1.0 / (1.0 + fabs(eta));
+            r = eta >= 0.0 ? pow(t, e) : 1.0 - pow(1.0 - t, e);
+        } else if (kind == A0_RISK_CPW) {
+            const double a = pow(t, eta), b = pow(1.0 - t, eta);
+            r = a / pow(a + b, 1.0 / eta);
+        } else {
+            r = 0.5 * erfc(-(normcdfinv(t) + eta) * 0.70710678118654752440);
+        }
+        f = (float)r;
+    }
+    if (f > 1.f) f = 1.f;
+    return f;
+}
+
+// the ranges of learner.iqn.risk_eta per kind (config.py), checked by every entry point that takes (kind, eta): A0_OK, or A0_EINVAL behind a message that starts with `who`
+int a0_risk_check(const char* who, int kind, double eta) {
+    char msg[256];
+    if (kind < A0_RISK_NEUTRAL || kind > A0_RISK_WANG) {
+        snprintf(msg, sizeof msg, "%s: learner.iqn.risk = %d is not one of neutral (0), cvar (1), pow (2), cpw (3), wang (4)", who, kind);
+        return a0_fail(A0_EINVAL, msg);
+    }
+    if (kind == A0_RISK_NEUTRAL) return A0_OK;
+    static const char* const names[] = {"neutral", "cvar", "pow", "cpw", "wang"};
+    static const char* const range[] = {"", "0 < eta <= 1 (the paper: 0.25, 0.1)", "a finite |eta| <= 64 (the paper: -2)", "0 < eta <= 1 (the paper: 0.71)", "a finite |eta| <= 8 (the paper: 0.75, -0.75)"};
+    const bool unit = kind == A0_RISK_CVAR || kind == A0_RISK_CPW;
+    const bool ok = unit ? (eta > 0.0 && eta <= 1.0 && (kind == A0_RISK_CPW || (float)eta > 0.f)) : fabs(eta) <= (kind == A0_RISK_POW ? 64.0 : 8.0);      // (a NaN fails every comparison)
+    if (ok) return A0_OK;
+    snprintf(msg, sizeof msg, "%s: learner.iqn.risk_eta = %g is outside the range of learner.iqn.risk = %s: %s", who, eta, names[kind], range[kind]);
+    return a0_fail(A0_EINVAL, msg);
+}
+
+// out[i] = beta(taus[i]), i < n; out may be taus.  A workgroup owns the 256 elements [256 b, 256 b + 256) and every lane evaluates ONE of them (a lane that
+// walked the four components of its own 16 bytes would carry four copies of the double-precision chain, or a loop around one whose constants the compiler
+// hoists into 256 registers).  Where both pointers are 16-byte aligned and the chunk is whole, the chunk travels 16 bytes wide: the first wave loads it into LDS,
+// every lane takes its element from there and puts the result back, the first wave stores it.  A ragged last chunk, or unaligned buffers, go element by element.
+// In place: a workgroup has read its chunk (a lane its element) before it writes it, and no other workgroup touches it.
+__global__ __launch_bounds__(256) void a0_risk_distort_kernel(const float* taus, float* out, long long n, int kind, double eta, int vec) {
+    __shared__ __attribute__((aligned(16))) float s[256];
+    const int t = threadIdx.x;
+    const long long base = (long long)blockIdx.x * 256, e = base + t;
+    const bool whole = vec && base + 256 <= n;      // the same for every lane of the workgroup
+    float x = 0.f;
+    if (whole) {
+        if (t < 64) ((a0_f4*)s)[t] = ((const a0_f4*)(taus + base))[t];
+        __syncthreads();
+        x = s[t];
+    } else if (e < n) {
+        x = taus[e];
+    }
+    const float y = a0_risk_beta(x, kind, eta);
+    if (whole) {
+        s[t] = y;
+        __syncthreads();
+        if (t < 64) ((a0_f4*)(out + base))[t] = ((const a0_f4*)s)[t];
+    } else if (e < n) {
+        out[e] = y;
+    }
+}
+
+extern "C" int a0_risk_distort(const float* taus, float* out, long long n, int kind, double eta, void* stream) {
+    if (!taus || !out || n < 1) return a0_fail(A0_EINVAL, "a0_risk_distort: bad argument (null pointer or n < 1)");
+    if (a0_risk_check("a0_risk_distort", kind, eta) != A0_OK) return A0_EINVAL;
+    const int vec = a0_aligned(16, taus, out) ? 1 : 0;
+    const long long blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return a0_fail(A0_EINVAL, "a0_risk_distort: n too large for one launch");
+    hipLaunchKernelGGL(a0_risk_distort_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, taus, out, n, kind, eta, vec);
+    return a0_fail_hip((int)hipGetLastError(), "a0_risk_distort");
+}
+
+// a0_tau_cos_features with the distortion between the draw and the features, still ONE launch: the bytes of a0_rng_uniform(_ctrl) -> a0_risk_distort ->
+// a0_cos_features.  A workgroup owns 256 consecutive (fraction, cosine) pairs, i.e. the fractions [r0, r1] (four of them at D = 64): lane k < r1 - r0 + 1 draws
+// fraction r0 + k, distorts it — the double-precision chain runs once per fraction, in one wave of the workgroup, not once per pair — stores it (the workgroup that
+// owns a fraction's pair d = 0 does) and leaves it in LDS; behind the barrier every lane takes the cosine of its own pair.
+__global__ __launch_bounds__(256) void a0_tau_cos_features_risk_kernel(unsigned long long seed, uint32_t stream, unsigned long long offset, const long long* __restrict__ ctrl,
+                                                                       int ctrl_idx, float* __restrict__ taus, float* __restrict__ out, long long R, int D, int kind, double eta) {
+    __shared__ float beta[256];
+    const long long i0 = (long long)blockIdx.x * 256, total = R * D;
+    const long long ilast = (i0 + 255 < total ? i0 + 255 : total - 1), r0 = i0 / D, r1 = ilast / D;
+    if (ctrl) offset += (unsigned long long)ctrl[ctrl_idx];
+    const long long rk = r0 + threadIdx.x;
+    if (rk <= r1) {
+        const float b = a0_risk_beta(a0_rng_uniform_at(seed, stream, offset + (unsigned long long)rk), kind, eta);
+        beta[threadIdx.x] = b;
+        if (rk * D >= i0) taus[rk] = b;
+    }
+    __syncthreads();
+    const long long i = i0 + threadIdx.x;
+    if (i >= total) return;
+    const long long r = i / D;
+    const int d = (int)(i % D);
+    const float ipi = 3.14159274101257324f * (float)(d + 1);
+    out[i] = cosf(ipi * beta[r - r0]);
+}
+
+extern "C" int a0_tau_cos_features_risk(unsigned long long seed, unsigned int stream, unsigned long long offset, const long long* ctrl, int ctrl_idx, float* taus, float* out,
+                                        long long R, int D, int kind, double eta, void* stream_h) {
+    if (!taus || !out || R < 1 || D < 1 || (ctrl && (ctrl_idx < 0 || ctrl_idx >= A0_CTRL_WORDS))) return a0_fail(A0_EINVAL, "a0_tau_cos_features_risk: bad argument");
+    if (a0_risk_check("a0_tau_cos_features_risk", kind, eta) != A0_OK) return A0_EINVAL;
+    const long long n = R * D;
+    if ((n + 255) / 256 > 0x7fffffffLL) return a0_fail(A0_EINVAL, "a0_tau_cos_features_risk: R * D too large for one launch");
+    hipLaunchKernelGGL(a0_tau_cos_features_risk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_h, seed, stream, offset, ctrl, ctrl_idx, taus, out, R, D,
+                       kind, eta);
+    return a0_fail_hip((int)hipGetLastError(), "a0_tau_cos_features_risk");
 }
 
 // x[(b,n)][d] = emb[(b,n)][d] * feat[b][d]       (16 B per lane; D % 4 == 0)

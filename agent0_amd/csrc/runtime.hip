@@ -318,6 +318,10 @@ struct a0_actor {
     float ladder_alpha = 0.f;
     long long ladder_i0 = 0, ladder_n = 1;
     float* eps_vec = nullptr;
+    // learner.iqn.risk (a0_actor_set_risk): off while risk_kind is A0_RISK_NEUTRAL; rolled: a rollout has been issued, the setting is fixed from then on
+    int risk_kind = A0_RISK_NEUTRAL;
+    double risk_eta = 0.0;
+    bool rolled = false;
 };
 
 // the network an actor acts with: the learner's online network, or the actor's own snapshot of it
@@ -478,6 +482,21 @@ extern "C" int a0_actor_set_eps_ladder(a0_actor* a, float alpha, long long i0, l
     A0_CATCH
 }
 
+// learner.iqn.risk (Actor: risk_value).  The algo is the learner's: a0_roll_begin refuses a learner that is not iqn
+extern "C" int a0_actor_set_risk(a0_actor* a, int kind, double eta) {
+    if (!a) return a0_fail(A0_EINVAL, "a0_actor_set_risk: null handle");
+    if (a->rolled) return a0_fail(A0_EINVAL, "a0_actor_set_risk: learner.iqn.risk is fixed once the handle has run a rollout");
+    A0_CHECK(a0_risk_check("a0_actor_set_risk", kind, eta));
+    a->risk_kind = kind; a->risk_eta = kind == A0_RISK_NEUTRAL ? 0.0 : eta;
+    return A0_OK;
+}
+
+extern "C" int a0_actor_fractions(const a0_actor* a, float** taus_dev) {
+    if (!a || !taus_dev) return a0_fail(A0_EINVAL, "a0_actor_fractions: null argument");
+    *taus_dev = a->q_taus;
+    return A0_OK;
+}
+
 extern "C" int a0_actor_detach_pool(a0_actor* a) {
     if (!a) return a0_fail(A0_EINVAL, "a0_actor_detach_pool: null handle");
     a->pool_on = false;
@@ -544,6 +563,8 @@ static int a0_roll_begin(a0_roll& r, a0_actor* a, a0_learner* L, a0_rbuf* R, flo
         return a0_fail(A0_EINVAL, "a0_actor_rollout: actor, learner and replay were created for different shapes");
     r.a = a; r.L = L; r.R = R; r.stream = stream;
     r.E = a->E; r.H = a0_actor_head_of(a, L);
+    if (a->risk_kind != A0_RISK_NEUTRAL && L->d.algo != A0_ALGO_IQN)
+        return a0_fail(A0_EINVAL, "a0_actor_rollout: learner.iqn.risk (a0_actor_set_risk) is for iqn learners only (fqf proposes its fractions, it does not draw them)");
     r.freq = a->d.reset_noise_freq > 0 ? a->d.reset_noise_freq : 4;
     if (r.H.kind == A0_ACT_SCALAR && a->d.A + (a->d.dueling ? 1 : 0) > 24) return a0_fail(A0_EINVAL, "a0_actor_rollout: scalar heads with A + dueling <= 24 actions");
     // (over a pool the tail's own launcher refuses the same width, under its own name)
@@ -616,6 +637,8 @@ static int a0_roll_head(a0_roll& r, a0_slab_head* head) {
         if (fqf) {
             A0_CHECK(a0_dense_fwd(a->act3, L->feat, on + L->frac.w(), on + L->frac.b(), a->f_logits, E, 32, L->feat, 0, a->fwd_scratch, stream));
             A0_CHECK(a0_fqf_taus_cos(a->f_logits, 32, a->f_tau_all, a->q_taus, a->q_cosx, 64, E, nt, stream));
+        } else if (a->risk_kind != A0_RISK_NEUTRAL) {      // learner.iqn.risk: the same draws, distorted in the same launch; q_taus receives tau'
+            A0_CHECK(a0_tau_cos_features_risk(a->rng.seed, STREAM_TAUS, a->rng.reserve(STREAM_TAUS, rows), nullptr, 0, a->q_taus, a->q_cosx, rows, 64, a->risk_kind, a->risk_eta, stream));
         } else {
             A0_CHECK(a0_tau_cos_features(a->rng.seed, STREAM_TAUS, a->rng.reserve(STREAM_TAUS, rows), nullptr, 0, a->q_taus, a->q_cosx, rows, 64, stream));
         }
@@ -716,6 +739,7 @@ extern "C" int a0_actor_rollout(a0_actor* a, a0_learner* L, a0_rbuf* R, float ep
     a0_trace_scope range("rollout");
     a0_roll r;
     A0_CHECK(a0_roll_begin(r, a, L, R, epsilon, stream));
+    a->rolled = true;
     A0_CHECK(a->pool_on ? a0_roll_pool(r) : a0_roll_device(r));
     return a0_mean_rows(a->qmax_all, a->T, r.E, a->qs, stream);
     A0_CATCH

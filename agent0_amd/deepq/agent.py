@@ -24,7 +24,7 @@ from agent0_amd.common.atari_wrappers import make_atari
 from agent0_amd.common.utils import DeviceRng, pinned_copy
 from .config import AlgoEnum, ExpConfig
 from .dist import eps_ladder_span, graph_capture_kwargs
-from .engine import DeviceLearner, Workspace
+from .engine import DeviceLearner, Workspace, risk_value
 from .model import DeepQNet, layout_from_cfg
 from .replay import ReplayDataset, StageRing, TransitionBlock
 
@@ -100,6 +100,11 @@ class Actor:
         self.obs_bytes = self.L.C * self.L.H * self.L.W
         n_tau = self.n_tau = self.L.F if self.L.algo == "fqf" else (cfg.learner.iqn.K if self.L.algo == "iqn" else 1)
         self.taus = ops.empty(E * n_tau) if self.L.algo == "iqn" else None
+        # learner.iqn.risk: every evaluation of the policy — training and test rollouts, ``act`` — takes its fractions through the distortion, in the launch that draws
+        # them (``_roll_head``) or right behind the draw (``_act_device``); neutral (0): both call what they always called
+        self.risk_kind, self.risk_eta = risk_value(cfg.learner.iqn.risk, cfg.learner.iqn.risk_eta, algo=self.L.algo, munchausen=cfg.learner.iqn.munchausen)
+        if self.risk_kind and not hasattr(ops, "tau_cos_features_risk"):
+            raise ValueError(f"learner.iqn.risk={cfg.learner.iqn.risk}: needs a backend with tau_cos_features_risk")
         self.greedy, self.qmax = ops.zeros(E, dtype=torch.int32), ops.zeros(E)
         T = int(cfg.actor.sample_steps)
         self.qs = ops.zeros(T)
@@ -272,7 +277,11 @@ class Actor:
             taus, aux, mode = ws.tau_hat, ws.tau_all, 3
         else:
             # env e's n_tau fractions are draws [base + e n_tau, base + (e + 1) n_tau) whatever part it is in; a captured rollout adds ctrl[A0_CTRL_RNG_TAUS]
-            ops.tau_cos_features(rng.seed, rng.STREAM_TAUS, draw[5] + part.off * nt, ws.taus, ws.cosx, k * nt, L.num_cosines, ctrl=rng.ctrl, ctrl_idx=rng.CTRL_INDEX[rng.STREAM_TAUS])
+            if self.risk_kind:      # learner.iqn.risk: the same draws, distorted in the same launch; ws.taus receives tau'
+                ops.tau_cos_features_risk(rng.seed, rng.STREAM_TAUS, draw[5] + part.off * nt, ws.taus, ws.cosx, k * nt, L.num_cosines, self.risk_kind, self.risk_eta,
+                                          ctrl=rng.ctrl, ctrl_idx=rng.CTRL_INDEX[rng.STREAM_TAUS])
+            else:
+                ops.tau_cos_features(rng.seed, rng.STREAM_TAUS, draw[5] + part.off * nt, ws.taus, ws.cosx, k * nt, L.num_cosines, ctrl=rng.ctrl, ctrl_idx=rng.CTRL_INDEX[rng.STREAM_TAUS])
             taus, aux, mode = ws.taus, None, 1
         ns = dev.head_slabs(ws, k, taus, nt, part.slabs, cos_ready=True, w_planes=roll.planes, splits=roll.splits)
         _, bh = dev.wb("head")
@@ -305,6 +314,8 @@ class Actor:
             dev.head(ws, E, ws.tau_hat, L.F)
         elif L.algo == "iqn":
             self.rng.uniform(self.rng.STREAM_TAUS, self.taus, E * self.n_tau)
+            if self.risk_kind:      # learner.iqn.risk: in place, behind the draw
+                ops.risk_distort(self.taus, self.taus, E * self.n_tau, self.risk_kind, self.risk_eta)
             dev.head(ws, E, self.taus, self.n_tau)
         else:
             dev.head(ws, E)
@@ -656,7 +667,7 @@ class BaseLearner:
                                     aug_shift=lc.aug_shift, aug_rng=self.rng, net_reset_freq=lc.net_reset_freq, net_reset_shrink=lc.net_reset_shrink,
                                     weight_decay=lc.weight_decay, redo_freq=lc.redo_freq, redo_tau=lc.redo_tau, redo_recycle=lc.redo_recycle,
                                     rank_freq=lc.rank_freq, rank_delta=lc.rank_delta, munchausen=lc.iqn.munchausen, mdqn_alpha=lc.mdqn.alpha,
-                                    hl_gauss=lc.c51.hl_gauss)
+                                    hl_gauss=lc.c51.hl_gauss, risk=lc.iqn.risk, risk_eta=lc.iqn.risk_eta)
         self.model = DeepQNet(cfg, ops=ops, dev_net=self.engine.online, rng=self.rng)
         self.model_target = DeepQNet(cfg, ops=ops, dev_net=self.engine.target, rng=self.rng)
         self.engine.sync_target(force=True)                 # model_target = deepcopy(model), agent.py:100

@@ -102,6 +102,20 @@ Additions (all default to the reference's behaviour being available):
                    to fp32 once.  Refused: NaN or infinite, rho > num_atoms (a sanity limit: sigma beyond the whole support), a sigma that is not a normal fp32
                    number, any other algo.  ``A0_PIPELINE_TARGET=1`` is allowed: c51's staged target pass ends at the fc1 slabs and the loss kernel reads them as
                    before.  No state of its own, nothing new in a snapshot, no new statistic, no Philox draw, and the setting may change across a resume.
+  learner.iqn.risk  string, default ``neutral``; one of ``neutral | cvar | pow | cpw | wang``, case-insensitive (``learner.algo=iqn`` only): a risk-sensitive policy
+                   (Dabney et al. 2018, section 4).  With tau the uniform fraction, the policy argmax_a (1/K) sum_k Q_{beta(tau_k)}(x, a) evaluates the network at
+                   tau' = beta(tau): cvar eta tau; pow tau^(1/(1+|eta|)) for eta >= 0 and 1 - (1-tau)^(1/(1+|eta|)) for eta < 0; cpw tau^eta / (tau^eta + (1-tau)^eta)^(1/eta);
+                   wang Phi(Phi^-1(tau) + eta).  It applies wherever the policy is evaluated: every actor evaluation (training and test rollouts, ``mode=play``,
+                   ``Actor.act``; device env, host envs, ``actor.env_groups``, the attached pool) and, in the update, the K selection fractions of the greedy next
+                   action only (the target network's, or the online network's under ``learner.double_q``).  The N' target and N online fractions stay uniform; loss,
+                   priorities, NaN skip, Adam and target sync are untouched.  The distortion draws nothing: every Philox position is a neutral run's.  The paper's Norm
+                   distortion is left out (it changes the number of draws).  Refused: an unknown name, any other algo (fqf included: its fractions are proposed, not
+                   drawn), ``learner.iqn.munchausen`` (its target's policy is the softmax of the risk-neutral mean).  ``A0_PIPELINE_TARGET=1`` is allowed (the staged
+                   target pass ends at the fc1 slabs and reads no fraction; iqn has no such stage anyway).  No state of its own, nothing new in a snapshot, no
+                   new statistic, and the setting may change across a resume.
+  learner.iqn.risk_eta  float, default 0.0: the distortion's parameter.  cvar and cpw: 0 < eta <= 1 (the paper: cvar 0.25 and 0.1, cpw 0.71); pow: finite, |eta| <= 64
+                   (the paper: -2; eta < 0 is risk-averse); wang: finite, |eta| <= 8 (the paper: +-0.75; eta < 0 is risk-averse).  ``neutral`` ignores it.  Anything
+                   else, NaN included, is refused with the setting and the number named.
   device           ``cuda`` is the only supported device: this build has no CPU path (it raises instead).
   checkpoint       path of a checkpoint written by ``Trainer.save_checkpoint``; read when ``mode`` is ``finetune`` (resume training)
                    or ``play`` (evaluate only) — the reference declares those modes (config.py:26-29) but never implements them.
@@ -176,6 +190,8 @@ class IQNConfig:
     num_cosines: int = 64
     F: int = 32
     munchausen: bool = False
+    risk: str = "neutral"
+    risk_eta: float = 0.0
 
 
 @dataclass

@@ -108,6 +108,41 @@ def munchausen_value(value, tau=0.03, alpha=0.9, lo=-1.0, algo: str = "iqn", dou
     return on, t, a, l
 
 
+RISK_PAPER_ETA = {"cvar": "0.25 or 0.1", "pow": "-2", "cpw": "0.71", "wang": "0.75 or -0.75"}      # Dabney et al. 2018, section 4
+
+
+def risk_value(risk, eta=0.0, algo: str = "iqn", munchausen: bool = False):
+    """``learner.iqn.risk`` / ``learner.iqn.risk_eta`` as the actor and the learner use them: ``(kind, eta)``, kind the A0_RISK_* number (0: neutral) and eta a Python
+    float (0.0 for neutral, which ignores it).  Refused, each with the setting and the number named: a name that is none of neutral | cvar | pow | cpw | wang (any
+    letter case; None is neutral), an eta outside the kind's range — cvar and cpw 0 < eta <= 1 (cvar: as an fp32 number too, the kernel multiplies by that), pow
+    finite |eta| <= 64, wang finite |eta| <= 8 —, NaN or infinite; and with a kind other than neutral: any ``algo`` but iqn (fqf included: its fractions are
+    proposed, not drawn) and ``learner.iqn.munchausen`` (its target's policy is the softmax of the risk-neutral mean).  ``A0_PIPELINE_TARGET=1`` / ``tstage`` need no
+    refusal of their own: the staged target pass (``target_stage``) ends at the fc1 slabs and reads no fraction, and an iqn learner has no such stage to begin with."""
+    from agent0_amd.ops import RISK_KINDS
+    name = "neutral" if risk is None else str(risk).strip().lower()
+    if name not in RISK_KINDS:
+        raise ValueError(f"learner.iqn.risk={risk!r} is not one of {' | '.join(RISK_KINDS)}")
+    kind = RISK_KINDS[name]
+    if kind == 0:
+        return 0, 0.0
+    e = float("nan") if eta is None else float(eta)
+    if name in ("cvar", "cpw"):
+        ok = 0.0 < e <= 1.0 and (name == "cpw" or float(torch.tensor(e, dtype=torch.float64).to(torch.float32)) > 0.0)
+        want = "0 < eta <= 1"
+    else:
+        lim = 64.0 if name == "pow" else 8.0
+        ok, want = abs(e) <= lim, f"a finite number with |eta| <= {lim:g}"
+    if not ok:
+        hint = f" (the default 0 is not a {name} parameter; the paper uses {RISK_PAPER_ETA[name]})" if e == 0.0 else f" (the paper uses {RISK_PAPER_ETA[name]})"
+        raise ValueError(f"learner.iqn.risk={name}: learner.iqn.risk_eta={eta!r} must be {want}{hint}")
+    if algo != "iqn":
+        raise ValueError(f"learner.iqn.risk={name}: for learner.algo=iqn only, not learner.algo={algo} (fqf proposes its fractions, it does not draw them)")
+    if munchausen:
+        raise ValueError(f"learner.iqn.risk={name}: not together with learner.iqn.munchausen=true (its target's policy is the softmax of the risk-neutral mean; "
+                         "acting on a distorted one is a different agent)")
+    return kind, e
+
+
 def hl_gauss_value(value, vmin=-10.0, vmax=10.0, num_atoms=51, algo: str = "c51", pipeline_target: Optional[bool] = None):
     """``learner.c51.hl_gauss`` as the learner uses it: ``(rho, sigma)`` as Python floats, sigma = rho * Delta with Delta = (vmax - vmin) / (num_atoms - 1) formed in
     double — the number the kernels receive, as a double — and ``(0.0, 0.0)`` (off) for zero, a negative number or None.  Refused: a rho that is NaN or infinite;
@@ -491,7 +526,8 @@ class DeviceLearner:
     def __init__(self, ops, L: NetLayout, batch_size: int, *, discount=0.99, n_step=1, double_q=False, lr=5e-4,
                  target_update_freq=500, vmin=-10.0, vmax=10.0, K=32, N=64, N_dash=64, max_grad_norm=-1.0, adam_eps=None,
                  mdqn_tau=0.03, mdqn_lo=-1.0, clip_grad_norm=-1.0, target_tau=0.0, aug_shift=0, aug_rng=None, net_reset_freq=0, net_reset_shrink=1.0,
-                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True, rank_freq=0, rank_delta=0.01, munchausen=False, mdqn_alpha=0.9, hl_gauss=0.0):
+                 weight_decay=0.0, redo_freq=0, redo_tau=0.1, redo_recycle=True, rank_freq=0, rank_delta=0.01, munchausen=False, mdqn_alpha=0.9, hl_gauss=0.0,
+                 risk="neutral", risk_eta=0.0):
         self.ops, self.L, self.B = ops, L, batch_size
         self.net = ops.net(L.C, L.H, L.W)
         self.online = DeviceNet(ops, L, self.net)
@@ -584,6 +620,11 @@ class DeviceLearner:
             self.munchausen, _, self.mdqn_alpha, _ = munchausen_value(munchausen, mdqn_tau, mdqn_alpha, mdqn_lo, algo=L.algo, double_q=double_q)
             if not hasattr(ops, "miqn_target"):
                 raise ValueError("learner.iqn.munchausen=true: needs a backend with miqn_target")
+        # learner.iqn.risk: _fwd_iqn distorts the K selection fractions of the greedy next action into ``t_risk`` (B * K floats, the engine's own: ``u.rand`` is only
+        # read) with one risk_distort launch, and the selection pass reads that.  Off (neutral): no buffer, and _fwd_iqn issues what it always did.  The setting is
+        # fixed once an update has been issued (``set_risk``).
+        self.risk_kind, self.risk_eta, self.t_risk, self._risk_fixed = 0, 0.0, None, False
+        self.set_risk(risk, risk_eta, K=K)
         # learner.c51.hl_gauss = rho > 0: _fwd_dist ends with c51_hl_gauss_head_loss_slabs — the Gaussian histogram of the scalar TD target in the projected
         # distribution's place — instead of c51_head_loss_slabs; hl_gauss_sigma = rho * Delta is the double the kernel receives.  A staged target pass (tstage) is
         # allowed: it ends at the fc1 slabs.  Off (0.0): _fwd_dist issues what it always did.
@@ -896,6 +937,17 @@ class DeviceLearner:
         self._redo()
         self._reset_net()
 
+    def set_risk(self, risk, eta=0.0, K=None):
+        """``learner.iqn.risk`` / ``risk_eta`` (``risk_value``); refused once an update has been issued, like the handle's a0_learner_set_risk."""
+        if self._risk_fixed:
+            raise ValueError("learner.iqn.risk: the setting is fixed once the learner has run an update")
+        kind, eta = risk_value(risk, eta, algo=self.L.algo, munchausen=self.munchausen)
+        if kind and not hasattr(self.ops, "risk_distort"):
+            raise ValueError(f"learner.iqn.risk={risk}: needs a backend with risk_distort")
+        if kind and self.t_risk is None:
+            self.t_risk = self.ops.empty(self.B * int(self.K if K is None else K))
+        self.risk_kind, self.risk_eta = kind, eta
+
     # ------------------------------------------------------------------ the target network's pass as a stage of its own
     @property
     def target_stage_supported(self) -> bool:
@@ -1119,6 +1171,9 @@ class DeviceLearner:
         else:
             sel, ws_sel = (on, wsel) if self.double_q else (tg, wt)      # greedy next action from the K-sample mean, of the online network under double-Q (agent.py:303-306)
             self._upd_encode(u, (tg, wt, True, False), (on, wsel, True, False) if self.double_q else None, (on, wo, False, True))
+            if self.risk_kind:      # learner.iqn.risk (a0_fwd_iqn's branch): the policy's K fractions, distorted into the engine's own buffer
+                ops.risk_distort(t_sel, self.t_risk, B * K, self.risk_kind, self.risk_eta)
+                t_sel = self.t_risk
             sel.head(ws_sel, B, t_sel, K)
             sel.select(ws_sel, B, K, self.a_star)
             tg.head(wt, B, t_tgt, Nd)
@@ -1170,6 +1225,7 @@ class DeviceLearner:
         Returns the per-sample loss tensor (device) — and for FQF also the fraction loss.
         """
         u = self._upd = _Upd(frames, slot, sample_stride, act, rew, done, wgt, rand, tstage)
+        self._risk_fixed = True
         self._upd_prepare(u)
         {"scalar": self._fwd_scalar, "dist": self._fwd_dist, "layerwise": self._fwd_layerwise, "iqn": self._fwd_iqn, "fqf": self._fwd_fqf}[self.family](u)
         self._backward_dense(self.ws_o, self.B, u.have_draw, u.have_dh)

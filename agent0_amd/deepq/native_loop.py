@@ -224,6 +224,9 @@ class NativeLoop:
             ok(lib.a0_learner_set_aug_shift(self.learner, int(eng.aug_shift)), "a0_learner_set_aug_shift")
         if eng.munchausen:              # learner.iqn.munchausen: the handle builds its quantile targets from two target passes, as DeviceLearner._fwd_iqn does
             ok(lib.a0_learner_set_munchausen(self.learner, 1, C.c_double(eng.mdqn_tau), C.c_double(eng.mdqn_alpha), C.c_double(eng.mdqn_lo)), "a0_learner_set_munchausen")
+        if eng.risk_kind:               # learner.iqn.risk: both handles distort the policy's fractions, as DeviceLearner._fwd_iqn and Actor._roll_head do
+            ok(lib.a0_learner_set_risk(self.learner, int(eng.risk_kind), C.c_double(eng.risk_eta)), "a0_learner_set_risk")
+            ok(lib.a0_actor_set_risk(self.actor, int(actor.risk_kind), C.c_double(actor.risk_eta)), "a0_actor_set_risk")
         if eng.hl_gauss > 0:            # learner.c51.hl_gauss: the handle's fused head-and-loss launch spreads the scalar target as a Gaussian histogram, as DeviceLearner._fwd_dist does
             ok(lib.a0_learner_set_hl_gauss(self.learner, C.c_double(eng.hl_gauss)), "a0_learner_set_hl_gauss")
         if not actor.fc1_planes:        # Actor.fc1_planes = False (comparisons): every step's fc1 on the general GEMM instead of a0_actor_fc1_kernel, as in Actor._rollout

@@ -193,6 +193,11 @@ class NativeLearner:
         learner.mdqn's."""
         check(self.lib.a0_learner_set_munchausen(self.h, int(bool(on)), float(tau), float(alpha), float(lo)), "a0_learner_set_munchausen")
 
+    def set_risk(self, kind, eta=0.0):
+        """learner.iqn.risk through the handle (a0_learner_set_risk): before the first update, on an iqn handle without learner.iqn.munchausen; ``kind`` a RISK_KINDS
+        name or number."""
+        check(self.lib.a0_learner_set_risk(self.h, RISK_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind), float(eta)), "a0_learner_set_risk")
+
     def set_hl_gauss(self, ratio):
         """learner.c51.hl_gauss through the handle (a0_learner_set_hl_gauss): between updates, on a c51 handle; ``ratio`` = sigma / Delta, <= 0 is off."""
         check(self.lib.a0_learner_set_hl_gauss(self.h, float(ratio)), "a0_learner_set_hl_gauss")
@@ -245,6 +250,7 @@ class _NoRange:
 _NO_RANGE = _NoRange()
 
 
+RISK_KINDS = {"neutral": 0, "cvar": 1, "pow": 2, "cpw": 3, "wang": 4}      # A0_RISK_* (include/agent0_hip.h): the distortions of learner.iqn.risk
 EPS_PER_ENV = -1.0      # A0_EPS_PER_ENV (include/agent0_hip.h): with ``eps_ptr`` given, env e of the launch acts with its own eps_ptr[e]
 
 
@@ -575,6 +581,15 @@ class HipOps:
         check(self.lib.a0_miqn_target(_req(q_next, torch.float32, span, "q_next"), _req(q_cur, torch.float32, span, "q_cur"), sb, sj, sa, _req(act, torch.int32, B, "act"),
                                       _req(rew, torch.float32, B, "rew"), _req(done, torch.float32, B, "done"), gamma_n, tau, alpha, lo, B, Nd, A,
                                       _req(y, torch.float32, B * Nd, "y"), _stream()), "a0_miqn_target")
+
+    def risk_distort(self, taus, out, n, kind, eta):
+        """learner.iqn.risk: ``out[i] = beta(taus[i])``, i < n, for the distortion ``kind`` (RISK_KINDS) with parameter ``eta``; ``out`` may be ``taus`` (a0_risk_distort)."""
+        check(self.lib.a0_risk_distort(_req(taus, torch.float32, n, "taus"), _req(out, torch.float32, n, "out"), int(n), int(kind), float(eta), _stream()), "a0_risk_distort")
+
+    def tau_cos_features_risk(self, seed, stream_id, offset, taus, out, R, D, kind, eta, ctrl=None, ctrl_idx=0):
+        """``tau_cos_features`` with the draws distorted in the same launch: taus = beta(draws), out = cos_features(taus) (a0_tau_cos_features_risk)."""
+        check(self.lib.a0_tau_cos_features_risk(seed, stream_id, offset, _req(ctrl, torch.int64, 8, "ctrl", optional=True), int(ctrl_idx), _req(taus, torch.float32, R, "taus"),
+                                                _req(out, torch.float32, R * D, "out"), R, D, int(kind), float(eta), _stream()), "a0_tau_cos_features_risk")
 
     def loss_quantile_huber(self, q, sb, si, sa, y, taus, tb, act, wgt, B, N, Nd, loss, dq, state):
         span = (B - 1) * sb + (N - 1) * si + 1
@@ -1144,6 +1159,19 @@ class HipOps:
     def actor_set_eps_ladder(self, actor, alpha, i0, n_total):
         """actor.eps_ladder for an ``a0_actor`` handle (a0_actor_set_eps_ladder): its rollouts act with one epsilon per env; ``alpha <= 0`` switches it off."""
         check(self.lib.a0_actor_set_eps_ladder(actor, float(alpha), int(i0), int(n_total)), "a0_actor_set_eps_ladder")
+
+    def actor_set_risk(self, actor, kind, eta=0.0):
+        """learner.iqn.risk for an ``a0_actor`` handle (a0_actor_set_risk): its iqn rollouts draw distorted fractions; before the first rollout."""
+        check(self.lib.a0_actor_set_risk(actor, int(kind), float(eta)), "a0_actor_set_risk")
+
+    def actor_fractions(self, actor, n):
+        """The ``n`` fractions the last step of an ``a0_actor`` handle's rollout left on the device (a0_actor_fractions), as a tensor over the handle's own buffer."""
+        p = C.c_void_p()
+        check(self.lib.a0_actor_fractions(actor, C.addressof(p)), "a0_actor_fractions")
+        if not p.value:
+            raise RuntimeError("a0_actor_fractions: the actor is not bound to a quantile learner")
+        v = type("_Fractions", (), {"__cuda_array_interface__": {"shape": (int(n),), "typestr": "<f4", "data": (int(p.value), False), "version": 3}})()
+        return torch.as_tensor(v, device="cuda")
 
     def actor_nstep(self, E, n, steps, gamma, action, reward, terminal, truncated, life_loss, ring_act, ring_rew, ring_done, out_act, out_rew, out_done, ctrl=None):
         check(self.lib.a0_actor_nstep(E, n, steps, gamma, _req(action, torch.int32, E, "action"), _req(reward, torch.float32, E, "reward"),

@@ -376,6 +376,30 @@ int a0_cos_features(const float* taus, float* out, long long R, int D, void* str
  * ctrl[ctrl_idx] to the offset) and out = a0_cos_features(taus) in ONE launch; the same bits as the two calls (model.py:238-241) */
 int a0_tau_cos_features(unsigned long long seed, unsigned int stream, unsigned long long offset, const long long* ctrl, int ctrl_idx, float* taus, float* out,
                         long long R, int D, void* stream_h);
+/* learner.iqn.risk: risk-sensitive IQN policies (Dabney et al. 2018, section 4).  The policy evaluates the network at tau' = beta(tau) instead of the uniform draw tau:
+ *   A0_RISK_CVAR   eta tau                                                                  0 < eta <= 1          (the paper: 0.25, 0.1)
+ *   A0_RISK_POW    eta >= 0: tau^(1 / (1 + |eta|)); eta < 0: 1 - (1 - tau)^(1 / (1 + |eta|))    finite, |eta| <= 64   (the paper: -2)
+ *   A0_RISK_CPW    tau^eta / (tau^eta + (1 - tau)^eta)^(1 / eta)                            0 < eta <= 1          (the paper: 0.71)
+ *   A0_RISK_WANG   Phi(Phi^-1(tau) + eta), beta(0) = 0                                      finite, |eta| <= 8    (the paper: 0.75, -0.75)
+ * A0_RISK_NEUTRAL is the identity and ignores eta.  Arithmetic: tau is the fp32 draw k * 2^-24; cvar is ONE fp32 multiply by eta rounded to fp32 (numpy float32's
+ * bits); the other three are formed in double from (double)tau and the double eta — pow(), normcdfinv(), Phi(u) = erfc(-u / sqrt 2) / 2 — and rounded to fp32 once,
+ * so they lie within one fp32 spacing of the exact value.  tau = 0 gives 0 for every kind; a result above 1 becomes 1; a NaN stays a NaN.  One device function
+ * states the formula for both entry points below.
+ * a0_risk_distort: out[i] = beta(taus[i]), i < n, elementwise; out may equal taus; 16-byte loads and stores where both pointers are 16-byte aligned (the ragged
+ * last chunk of n % 256 elements and unaligned buffers go element by element); neutral copies.  Equal inputs give equal bytes.
+ * a0_tau_cos_features_risk: a0_tau_cos_features's arguments (the ctrl word included, so a captured rollout works) plus (kind, eta); draw, distortion and the D cosine
+ * features stay ONE launch, taus receives tau', and the bytes are those of a0_rng_uniform(_ctrl) -> a0_risk_distort -> a0_cos_features.  The double-precision chain
+ * runs once per fraction (one lane draws and distorts it and leaves it in LDS for the fraction's D cosine lanes), not once per (fraction, cosine) pair.
+ * A0_EINVAL, under the entry point's name with the setting and the number named: a null pointer, n < 1 (R < 1, D < 1, a ctrl index outside the control block), a kind
+ * that is none of the five, an eta outside the kind's range, NaN or infinite. */
+#define A0_RISK_NEUTRAL 0
+#define A0_RISK_CVAR 1
+#define A0_RISK_POW 2
+#define A0_RISK_CPW 3
+#define A0_RISK_WANG 4
+int a0_risk_distort(const float* taus, float* out, long long n, int kind, double eta, void* stream);
+int a0_tau_cos_features_risk(unsigned long long seed, unsigned int stream, unsigned long long offset, const long long* ctrl, int ctrl_idx, float* taus, float* out,
+                             long long R, int D, int kind, double eta, void* stream_h);
 int a0_hadamard_fwd(const float* emb, const float* feat, float* x, int B, int n, int D, void* stream);
 int a0_hadamard_bwd(const float* dx, const float* emb, const float* feat, float* demb, float* d3, int B, int n, int D, void* stream);
 /* (round 6) a0_dense_dgrad(dY [R][N], W [N][K], no mask) + a0_hadamard_bwd in one launch for R = B * n rows, n = 32 or 64: dx = dY W is consumed in the GEMM's epilogue and never
@@ -670,6 +694,14 @@ int a0_learner_set_aug_shift(a0_learner* learner, int pad);
  * and the number named: a handle of another algo, a double-Q handle (there is no argmax to decouple), tau <= 0, alpha < 0, lo > 0, one of the three NaN or
  * infinite (as given or once rounded to float), a call after the handle's first update.  Descriptor structs are unchanged and nothing is added to a snapshot. */
 int a0_learner_set_munchausen(a0_learner* learner, int on, double tau, double alpha, double lo);
+/* learner.iqn.risk through the learner handle (iqn handles only): with a kind other than A0_RISK_NEUTRAL every a0_learner_update distorts the K SELECTION fractions —
+ * those of the greedy next action, of the target network or, under double-Q, of the online network — with one a0_risk_distort launch behind the three draws, into
+ * a buffer of B * K floats that the first such call allocates; the selection pass reads that buffer.  The draws, the N' target fractions, the N online fractions,
+ * the loss and everything behind it are a neutral handle's, and so is the Philox position: the distortion draws nothing.  A0_RISK_NEUTRAL: off again, the update
+ * issues what it always did (eta is ignored).  A0_EINVAL, with the setting and the number named: a kind or an eta a0_risk_distort refuses, a handle of another algo
+ * (fqf included: its fractions are proposed, not drawn), a handle with learner.iqn.munchausen on (its target's policy is the softmax of the risk-neutral mean), a
+ * call after the handle's first update.  Descriptor structs are unchanged and nothing is added to a snapshot. */
+int a0_learner_set_risk(a0_learner* learner, int kind, double eta);
 /* learner.c51.hl_gauss through the handle (c51 handles only): with ratio > 0 every a0_learner_update ends its forward half with a0_c51_hl_gauss_head_loss_slabs
  * instead of a0_c51_head_loss_slabs, sigma = ratio * Delta formed in double from the handle's fp32 vmin and vmax, Delta = (vmax - vmin) / (num_atoms - 1).
  * ratio <= 0: off again, the update issues what it always did (on a handle of any algo).  A0_EINVAL, each with the setting and the number named: a ratio that is
@@ -765,6 +797,14 @@ int a0_actor_rollout(a0_actor* actor, a0_learner* learner, a0_rbuf* replay, floa
  * attached pool and the launch schedule's actor stream alike.  alpha <= 0 switches it off again: the rollout's launches and their arguments are those of a handle
  * that never heard of it.  Derived from `epsilon` every rollout, so no part of a0_actor_state_save. */
 int a0_actor_set_eps_ladder(a0_actor* actor, float alpha, long long i0, long long n_total);
+/* learner.iqn.risk for the actor handle: with a kind other than A0_RISK_NEUTRAL every step of a0_actor_rollout with an iqn learner draws its E * K fractions with
+ * a0_tau_cos_features_risk(kind, eta) in a0_tau_cos_features's place — one launch, as before; the tail kernels and their arguments are untouched — device env and
+ * attached pool alike.  A0_RISK_NEUTRAL: the rollout calls what it always called.  No state of its own: nothing in a0_actor_state_save.  A0_EINVAL: a kind or an
+ * eta a0_risk_distort refuses, a call after the handle's first rollout; a0_actor_rollout then refuses, before anything is launched, a learner of any algo but iqn. */
+int a0_actor_set_risk(a0_actor* actor, int kind, double eta);
+/* where a quantile actor's steps leave their E * nt fractions on the device (iqn: the draws, distorted under learner.iqn.risk; fqf: the tau-hats): the handle's own
+ * buffer, overwritten by every step; NULL until the actor is bound to a quantile learner.  For inspection (tests); nothing reads it between steps. */
+int a0_actor_fractions(const a0_actor* actor, float** taus_dev);
 /* Scalar heads and c51 / qr: a0_actor_rollout over the device env lays fc1's weights out once per rollout (and after every noise reset) with a0_actor_fc1_planes and runs the steps'
  * fc1 through a0_actor_fc1 where a0_actor_fc1_ok accepts the shape.  on = 0: the handle keeps the general GEMM in every step — the same bytes (for comparisons). */
 int a0_actor_set_fc1_planes(a0_actor* actor, int on);
